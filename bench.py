@@ -30,6 +30,17 @@ qEHVI (ModelListGP(3) on DTLZ2, n = 2048, q = 8, S = 128, 128 restarts; the
 box decomposition replicated); both shard their restarts exactly as qEI does.
 At N > 1 the default qEI line also carries both as ``sharded_other_acqs``.
 
+A plain run (``--gpus N --steps K --warmup W``) sets up, warms up, times the K
+steps and prints the headline line (``value``, ``ms_per_step``, config).
+``--dump-outputs DIR`` also writes what the last timed step returned (the
+acquisition values and their maximum, fp64) as ``DIR/<name>.npy``; the inputs
+are seeded, so two builds can be compared value for value.  ``--full`` adds
+everything else to the line: the posterior launch's event timing and roofline,
+the fp64 MFMA ceiling, forward + backward, the strong-scaling projection, the
+standalone Cholesky, the GP fit, the other section-8 configurations, the oracle
+checks and the CPU baseline (and at N > 1 the weak line and the sharded qNEI /
+qEHVI); the ``--no-*`` options trim that set.
+
 Prints ONE JSON line (rank 0).
 """
 from __future__ import annotations
@@ -837,6 +848,15 @@ def timed_steps(step, steps, warmup, dist, sync, dev=None):
     return elapsed
 
 
+def dump_outputs(path, arrays):
+    """``--dump-outputs``: each tensor of ``arrays`` as ``path/<name>.npy``
+    (fp64, whole: a step returns one value per restart, a few KB)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().cpu().numpy().astype(np.float64))
+
+
 def rehearse_cpu(args, ws, rank):
     """BO_BENCH_REHEARSE=cpu: the multi-rank launch, the restart split, the
     collectives and rank 0's report over gloo on the CPU, with a stub in place
@@ -851,20 +871,23 @@ def rehearse_cpu(args, ws, rank):
     strong = ws > 1 and not args.weak
     r0, r1 = shard_range(RESTARTS, ws, rank) if strong else (0, RESTARTS)
     best = torch.empty(1, dtype=torch.float64)
+    last = {}
 
     def step():
         acq = torch.zeros(r1 - r0, dtype=torch.float64)   # stub of acqf(X[r0:r1])
         if strong:
-            torch.amax(allgather_rows(acq, RESTARTS), dim=0, keepdim=True, out=best)
-        else:
-            torch.amax(acq, dim=0, keepdim=True, out=best)
-            if dist is not None:
-                dist.all_reduce(best, op=dist.ReduceOp.MAX)
+            acq = allgather_rows(acq, RESTARTS)
+        torch.amax(acq, dim=0, keepdim=True, out=best)
+        if dist is not None and not strong:
+            dist.all_reduce(best, op=dist.ReduceOp.MAX)
+        last["acq"] = acq
 
     elapsed = timed_steps(step, args.steps, args.warmup, dist, lambda: None)
     if dist is not None:
         assert dist.get_world_size() == args.gpus
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"acq": last["acq"], "best": best})
         print(json.dumps({"metric": "acq-evals/sec (q x restarts x MC), qEI forward",
                           "value": None, "unit": "acq-evals/s", "n_gpus": ws,
                           "steps": args.steps, "warmup": args.warmup,
@@ -1155,7 +1178,14 @@ def main():
                     help="number of GPUs (ranks); without torchrun's env, N > 1 launches them")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: launch timing and roofline, MFMA ceiling, forward+"
+                         "backward, Cholesky, GP fit, the other configurations, oracle checks and "
+                         "the CPU baseline (the --no-* options below trim this set)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's values (acq, best; fp64) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the oracle checks and the CPU baselines")
     ap.add_argument("--no-fit", action="store_true", help="skip the GP-fit half of the metric")
     ap.add_argument("--no-bwd", action="store_true", help="skip the forward+backward timing")
     ap.add_argument("--weak", action="store_true",
@@ -1210,24 +1240,25 @@ def main():
     Xd = Xc.to(dev)
     Xtr, Ytr = w.Xtr, w.Ytr
 
-    # HIP events around every post_partials launch of the timed steps, on the
-    # stream it is launched on: recorded by the native operator (qEI,
+    # --full: HIP events around every post_partials launch of the timed steps,
+    # on the stream it is launched on: recorded by the native operator (qEI,
     # bo::post_timing) or by kernels.post_partials's hook (qNEI / qEHVI)
     native = _lib.torch_ops()
     hook = HookTimer(dev)
-    kernels.TIMING_HOOK = hook
+    if args.full:
+        kernels.TIMING_HOOK = hook
     best = torch.empty(1, dtype=torch.float64, device=dev)
+    last = {}  # the values the latest step returned (--dump-outputs)
 
     def step():
         with torch.no_grad():
             acq = acqf(Xd)
         if strong:
-            allv = allgather_rows(acq, R)   # every rank: all the step's values
-            torch.amax(allv, dim=0, keepdim=True, out=best)
-            return allv
+            acq = allgather_rows(acq, R)   # every rank: all the step's values
         torch.amax(acq, dim=0, keepdim=True, out=best)
-        if dist is not None:
+        if dist is not None and not strong:
             dist.all_reduce(best, op=dist.ReduceOp.MAX)
+        last["acq"] = acq
         return acq
 
     sync = lambda: torch.cuda.synchronize(dev)  # noqa: E731
@@ -1235,20 +1266,55 @@ def main():
     for _ in range(args.warmup):
         step()
     sync()
-    native.post_timing_read()  # drop anything recorded before
-    hook.read()
-    native.post_timing(True)
-    hook.on = True
+    if args.full:
+        native.post_timing_read()  # drop anything recorded before
+        hook.read()
+        native.post_timing(True)
+        hook.on = True
     elapsed = timed_steps(step, args.steps, 0, dist, sync, dev)
+    ms_step = 1e3 * elapsed / args.steps
+    evals_per_step = w.q * R * w.S * (1 if strong else ws)
+    value = evals_per_step * args.steps / elapsed
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"acq": last["acq"], "best": best})
+    head = {
+        "metric": f"acq-evals/sec (q x restarts x MC), {w.name} forward",
+        "value": value,
+        "unit": "acq-evals/s",
+        "n_gpus": ws,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_step,
+        "higher_is_better": True,
+        "scaling": "single" if ws == 1 else ("strong" if strong else "weak"),
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": ("synthetic: Hartmann6 on Sobol(seed 0) training inputs, " if w.acq != "qehvi"
+                 else "synthetic: DTLZ2 on torch.rand(seed 0) training inputs, ")
+                + ("Sobol(seed 1) candidates, rank slice" if strong
+                   else ("Sobol(seed 1+rank) candidates" if w.acq == "qei"
+                         else "Sobol(seed 1) candidates")),
+        "config": {"workload": w.workload + ", "
+                               + (f"{R} restarts sharded over the GPUs" if strong
+                                  else f"{R} restarts/GPU") + ", " + w.tail,
+                   "n": w.n, "d": D, "q": w.q, "restarts_per_gpu": r1 - r0, "mc": w.S,
+                   "parallelism": f"restart-sharded x{ws}"},
+    }
+    if w.acq == "qnei":
+        head["config"].update(r=w.r, init_ms=w.init_ms)
+    if not args.full:  # the plain run ends here: the headline alone
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     native.post_timing(False)
     hook.on = False
     kern_ms = native.post_timing_read().tolist() + hook.read()
     if not kern_ms or len(kern_ms) % args.steps:
         raise SystemExit(f"bench: {len(kern_ms)} timed posterior launches for {args.steps} steps")
     launches = len(kern_ms) // args.steps  # qEHVI: one batched launch for its three members
-    ms_step = 1e3 * elapsed / args.steps
-    evals_per_step = w.q * R * w.S * (1 if strong else ws)
-    value = evals_per_step * args.steps / elapsed
 
     kern_avg_ms = sum(kern_ms) / len(kern_ms)
     fl = w.flops_launch(r1 - r0) * w.launches / launches  # the step's posterior flops per launch
@@ -1332,27 +1398,7 @@ def main():
                 if ws == 1:
                     cpu = cpu_baseline_other(w, acqf)
         line = {
-            "metric": f"acq-evals/sec (q x restarts x MC), {w.name} forward",
-            "value": value,
-            "unit": "acq-evals/s",
-            "n_gpus": ws,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_step,
-            "higher_is_better": True,
-            "scaling": "single" if ws == 1 else ("strong" if strong else "weak"),
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": ("synthetic: Hartmann6 on Sobol(seed 0) training inputs, " if w.acq != "qehvi"
-                     else "synthetic: DTLZ2 on torch.rand(seed 0) training inputs, ")
-                    + ("Sobol(seed 1) candidates, rank slice" if strong
-                       else ("Sobol(seed 1+rank) candidates" if w.acq == "qei"
-                             else "Sobol(seed 1) candidates")),
-            "config": {"workload": w.workload + ", "
-                                   + (f"{R} restarts sharded over the GPUs" if strong
-                                      else f"{R} restarts/GPU") + ", " + w.tail,
-                       "n": w.n, "d": D, "q": w.q, "restarts_per_gpu": r1 - r0, "mc": w.S,
-                       "parallelism": f"restart-sharded x{ws}"},
+            **head,
             "roofline": {"bound": "mfma", "kernel": "post_partials_kernel",
                          "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
                          "frac": achieved / peak, "peak_measured": peak_box,
@@ -1374,8 +1420,6 @@ def main():
             "gp_fit": gp_fit,
             "other_configs": extra,
         }
-        if w.acq == "qnei":
-            line["config"].update(r=w.r, init_ms=w.init_ms)
         if cpu:
             line["speedup_vs_cpu"] = value / cpu["value"]
         print(json.dumps(line), flush=True)

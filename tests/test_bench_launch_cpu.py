@@ -41,6 +41,20 @@ def test_bench_gpus_2_weak_option():
     assert line["config"]["restarts_per_gpu"] == 512
 
 
+def test_bench_dump_outputs_writes_last_step(tmp_path):
+    """--dump-outputs: the last timed step's values (here the stub's zeros,
+    gathered over the two ranks) and their maximum as fp64 .npy, by rank 0;
+    the plain line carries steps and ms_per_step and nothing of --full."""
+    import numpy as np
+    line = _run(["--gpus", "2", "--steps", "2", "--warmup", "0", "--dump-outputs", str(tmp_path / "d")])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    assert "roofline" not in line and "cpu_baseline" not in line
+    acq, best = np.load(tmp_path / "d" / "acq.npy"), np.load(tmp_path / "d" / "best.npy")
+    assert acq.dtype == np.float64 and acq.shape == (512,) and not acq.any()
+    assert best.dtype == np.float64 and best.shape == (1,) and best[0] == 0.0
+    assert sorted(p.name for p in (tmp_path / "d").iterdir()) == ["acq.npy", "best.npy"]
+
+
 def test_bench_world_size_mismatch_fails():
     env = {k: v for k, v in os.environ.items()}
     env.update(BO_BENCH_REHEARSE="cpu", WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")

@@ -3,7 +3,7 @@
 # ms per step, the posterior GEMM's event-timed ms, its fraction of spec, the
 # oracle check's max relative error.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-python3 bench.py --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline --no-extra --no-bwd --no-fit > /tmp/c3_ms.json || exit 1
+python3 bench.py --full --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline --no-extra --no-bwd --no-fit > /tmp/c3_ms.json || exit 1
 python3 - <<'PY'
 import json
 d = json.loads(open("/tmp/c3_ms.json").read().strip().splitlines()[-1])

@@ -32,8 +32,8 @@ timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c4 
 timeout -k 10 300 python3 tools/c4_times.py 20 > $O/c4_times.log 2>&1 || exit $?
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/fit -o run -- python3 tools/fit_only.py 1 > $O/fit.log 2>&1 || exit $?
 timeout -k 10 300 python3 tools/fit_breakdown.py one > $O/fit_breakdown.log 2>&1 || exit $?
-timeout -k 10 200 python3 bench.py --acq qnei --steps 10 --warmup 2 --no-extra --no-fit > $O/bench_qnei.log 2>&1 || exit $?
-timeout -k 10 200 python3 bench.py --acq qehvi --steps 20 --warmup 3 --no-extra --no-fit > $O/bench_qehvi.log 2>&1 || exit $?
+timeout -k 10 200 python3 bench.py --full --acq qnei --steps 10 --warmup 2 --no-extra --no-fit > $O/bench_qnei.log 2>&1 || exit $?
+timeout -k 10 200 python3 bench.py --full --acq qehvi --steps 20 --warmup 3 --no-extra --no-fit > $O/bench_qehvi.log 2>&1 || exit $?
 BO_LBFGSB_JOINT_W=0 timeout -k 10 300 python3 tools/prof_lbfgsb_joint.py > $O/lbfgsb_joint.log 2>&1 || exit $?
 timeout -k 10 300 python3 tools/host_c2_breakdown.py > $O/host_c2.log 2>&1 || exit $?
 find $O -name '*_trace.csv' -size +2M -delete
