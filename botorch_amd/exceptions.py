@@ -17,6 +17,11 @@ class InputDataError(BotorchError):
     pass
 
 
+class BotorchTensorDimensionError(BotorchError, ValueError):
+    """botorch/exceptions/errors.py BotorchTensorDimensionError (also a
+    ValueError here: the shape checks of this package raise ValueError)."""
+
+
 class NotPSDError(RuntimeError):
     """[G] linear_operator NotPSDError: Cholesky failed after the jitter ladder."""
 

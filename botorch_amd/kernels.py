@@ -249,6 +249,105 @@ def build_gp_cache(Xt, y, lengthscale, noise, constant, kind=_lib.RBF, outputsca
                    float(constant), L, Linv, U, beta, alpha, jit.value)
 
 
+# condition_on_observations: at most this many new points take the bordered
+# update (bo_gp_cache_extend); more rebuild the caches.  The k at which the two
+# curves measured by tools/bench_condition.py meet at n = 4096, rounded down to
+# a multiple of 16 (profiles/condition/bench.json).
+EXTEND_MAX_K = 464
+
+
+def extend_gp_cache_enqueue(kind, Xt_scaled, L, Linv, beta, alpha, lengthscale, outputscale,
+                            noise, constant, X_new, y_new, noise_vec=None):
+    """bo_gp_cache_extend on raw tensors, enqueued without a read-back: returns
+    (L', Linv', U', beta', alpha', Xt_scaled', info) at the padded order of
+    n + k; info (device int) is nonzero when the k x k border was not p.d. and
+    the outputs are invalid."""
+    dev = _dev(Xt_scaled, L, Linv, beta, alpha, lengthscale, X_new, y_new, noise_vec)
+    n = Xt_scaled.shape[0]
+    k, d = X_new.shape
+    if k < 1 or n < 1:
+        raise ValueError(f"gp_cache_extend: {k} new points for {n} old ones (both at least 1)")
+    if y_new.numel() != k or (noise_vec is not None and noise_vec.numel() != k):
+        raise ValueError(f"gp_cache_extend: targets / noise do not match the {k} new points")
+    if not (L.is_contiguous() and Linv.is_contiguous() and L.shape == Linv.shape):
+        raise ValueError("gp_cache_extend: L and Linv must be contiguous and of one shape")
+    npo = padded_order(n + k)
+    f64 = dict(dtype=torch.float64, device=dev)
+    Lo = torch.empty(npo, npo, **f64)
+    Linvo = torch.empty(npo, npo, **f64)
+    Uo = torch.empty(npo, npo, **f64)
+    betao = torch.empty(n + k, **f64)
+    alphao = torch.empty(n + k, **f64)
+    Xso = torch.empty(n + k, DP, **f64)
+    we = ctypes.c_int64()
+    check(lib().bo_gp_cache_extend_work(n, k, ctypes.byref(we)), "gp_cache_extend_work")
+    work = torch.empty(we.value, **f64)
+    info = torch.zeros(1, dtype=torch.int32, device=dev)
+    nv = None if noise_vec is None else noise_vec.detach().reshape(-1).contiguous()
+    check(lib().bo_gp_cache_extend(
+        int(kind), _p(Xt_scaled.contiguous()), _p(L), _p(Linv), _p(beta.contiguous()),
+        _p(alpha.contiguous()), L.shape[1], n, d, _p(lengthscale.detach().reshape(-1).contiguous()),
+        float(outputscale), float(constant), _p(X_new.contiguous()),
+        _p(y_new.reshape(-1).contiguous()), k, float(noise), _p(nv), _p(Xso), _p(Lo), _p(Linvo),
+        _p(Uo), _p(betao), _p(alphao), npo, _p(work), _p(info), _stream(dev)), "gp_cache_extend")
+    return Lo, Linvo, Uo, betao, alphao, Xso, info
+
+
+def extend_gp_cache(cache: GPCache, X_new, y_new, noise_new=None, y_old=None, noise_old=None,
+                    jitter_dev=None) -> GPCache:
+    """The cache of the model conditioned on k more points (X_new k x d, y_new k
+    standardised targets, noise_new: their k observed variances under a
+    fixed-noise likelihood) by the bordered update bo_gp_cache_extend; ``cache``
+    is only read.  One device-to-host sync: the border's status.
+
+    Fallback: when the old cache was built with jitter (``cache.jitter`` > 0, or
+    the device scalar ``jitter_dev`` of a cache whose jitter was not read back)
+    or the k x k border is not p.d., the cache of the concatenated data is
+    built by build_gp_cache (the reference's ladder from zero, with its
+    NumericalWarning).  That needs the old targets ``y_old`` (default:
+    constant + L beta) and, under a fixed-noise likelihood, the old variances
+    ``noise_old``.  ``jitter`` carries over; ``Ainv`` is not carried."""
+    X_new = X_new.detach().to(torch.float64).contiguous()
+    y_new = y_new.detach().to(torch.float64).reshape(-1).contiguous()
+    n, k = cache.n, X_new.shape[0]
+    fixed = noise_new is not None
+    if fixed:
+        noise_new = noise_new.detach().to(torch.float64).reshape(-1).contiguous()
+        if noise_old is None:
+            raise ValueError("extend_gp_cache: a fixed-noise cache needs noise_old for the "
+                             "new model's likelihood and the rebuild route")
+    Xt = torch.cat([cache.Xt, X_new])
+    noise_mean = float(cache.noise)
+    if fixed:
+        noise_all = torch.cat([noise_old.detach().reshape(-1), noise_new])
+        noise_mean = float((cache.noise * n + float(noise_new.sum())) / (n + k))
+
+    def rebuild():
+        yo = y_old
+        if yo is None:
+            yo = cache.constant + torch.tril(cache.L[:n, :n]) @ cache.beta
+        return build_gp_cache(Xt, torch.cat([yo.detach().reshape(-1), y_new]), cache.lengthscale,
+                              noise_all if fixed else cache.noise, cache.constant,
+                              kind=cache.kind, outputscale=cache.outputscale)
+
+    if cache.jitter > 0 or cache.d > DP:
+        return rebuild()
+    L, Linv, U, beta, alpha, Xs, info = extend_gp_cache_enqueue(
+        cache.kind, cache.Xt_scaled, cache.L, cache.Linv, cache.beta, cache.alpha,
+        cache.lengthscale, cache.outputscale, cache.noise, cache.constant, X_new, y_new,
+        noise_new)
+    if jitter_dev is not None:  # one transfer for both
+        st = torch.cat([info.to(torch.float64), jitter_dev.reshape(-1)[:1]]).cpu()
+        bad = float(st[0]) != 0 or float(st[1]) > 0
+    else:
+        bad = int(info.item()) != 0
+    if bad:
+        return rebuild()
+    return GPCache(cache.kind, n + k, cache.d, U.shape[0], Xt, Xs, cache.lengthscale,
+                   cache.outputscale, noise_mean, cache.constant, L, Linv, U, beta, alpha,
+                   cache.jitter)
+
+
 def cholesky_inverse_batched(As: torch.Tensor):
     """L = chol(A_m), Linv = L^{-1} of nb SPD matrices (nb x n x n) in ONE
     persistent DAG launch (bo_cholesky_inverse_batched; bit-identical to nb

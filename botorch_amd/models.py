@@ -272,6 +272,11 @@ class Model(_TrackedModule):
     def posterior(self, X, output_indices=None, observation_noise=False, posterior_transform=None):
         raise NotImplementedError
 
+    def condition_on_observations(self, X, Y, **kwargs):
+        """models/model.py:149."""
+        raise NotImplementedError(
+            f"`condition_on_observations` not implemented for {type(self).__name__}")
+
     def outcome_stats(self):
         """(mean, std) of the Standardize transform as host floats, read back once
         per change of the buffers (not per acquisition call: each read is a
@@ -424,6 +429,7 @@ class SingleTaskGP(Model):
         if mode:
             self._cache = None
             self._cache_key = None
+            self._cache_jit = None
         return super().train(mode)
 
     @property
@@ -468,6 +474,7 @@ class SingleTaskGP(Model):
                                           float(os_), float(noise), float(c), L, Linv, U, beta,
                                           alpha, 0.0)
             self._cache_key = key
+            self._cache_jit = jit  # device scalar, not read back here
         return self._cache
 
     def posterior(self, X: torch.Tensor, output_indices=None, observation_noise=False,
@@ -491,6 +498,141 @@ class SingleTaskGP(Model):
         if posterior_transform is not None:
             return posterior_transform(post)
         return post
+
+    # -- conditioning on new observations ------------------------------------------
+    def _blank_copy(self, train_X):
+        """A SingleTaskGP shell with the new inputs and no modules yet (the
+        constructor's checks and statistics do not apply to a conditioned model)."""
+        new = SingleTaskGP.__new__(SingleTaskGP)
+        Model.__init__(new)
+        new.train_inputs = (train_X,)
+        new._cache = None
+        new._cache_key = None
+        new._cache_jit = None
+        return new
+
+    def condition_on_observations(self, X: torch.Tensor, Y: torch.Tensor,
+                                  noise: Optional[torch.Tensor] = None, **kwargs):
+        """botorch/models/gpytorch.py:468-531 (model.py:149): a new eval-mode
+        SingleTaskGP on cat(train_X, X) with the same hyperparameters; the source
+        model and its caches are untouched.  X: k x d, Y: k x m in the original
+        outcome space (it goes through the outcome transform with its fitted
+        statistics, which are not refitted); ``noise`` (k x m, a fixed-noise
+        likelihood's observed variances) is taken as already transformed.
+
+        When this model holds a valid prediction cache and k is at most
+        kernels.EXTEND_MAX_K, the new model's cache is the bordered update of
+        it (kernels.extend_gp_cache, O(n^2 k)); otherwise the new model builds
+        its cache on its first posterior as any model does.  Both give the same
+        model.  The new model carries no gradient to X or Y."""
+        from . import kernels
+        from .exceptions import InputDataError
+        from .settings import propagate_grads
+        if kwargs:
+            raise UnsupportedError("condition_on_observations: unsupported arguments "
+                                   f"{sorted(kwargs)}")
+        if X.dim() > 2 or Y.dim() > 2 or (noise is not None and noise.dim() > 2):
+            raise UnsupportedError("condition_on_observations takes X k x d and Y k x m here: "
+                                   "batched fantasy models are not on the accelerated path")
+        train_X = self.train_inputs[0]
+        if X.dim() != 2 or Y.dim() != 2:
+            raise ValueError("condition_on_observations: expected X k x d and Y k x m")
+        if X.shape[-1] != train_X.shape[-1]:
+            raise ValueError(f"condition_on_observations: X has {X.shape[-1]} features, the model "
+                             f"{train_X.shape[-1]}")
+        if Y.shape[-1] != self._num_outputs:
+            raise ValueError(f"condition_on_observations: Y has {Y.shape[-1]} outputs, the model "
+                             f"{self._num_outputs}")
+        if X.shape[0] != Y.shape[0]:
+            raise ValueError(f"condition_on_observations: {X.shape[0]} points but {Y.shape[0]} "
+                             "observations")
+        if noise is not None and noise.shape != Y.shape:
+            raise ValueError(f"condition_on_observations: noise of shape {tuple(noise.shape)} does "
+                             f"not match Y of shape {tuple(Y.shape)}")
+        if propagate_grads.on() and (X.requires_grad or Y.requires_grad):
+            raise UnsupportedError(
+                "settings.propagate_grads: posterior gradients to the training data are not "
+                "supported (the prediction caches are built without a backward to them)")
+        X = X.detach().to(train_X)
+        Y = Y.detach().to(train_X)
+        if noise is not None:
+            noise = noise.detach().to(train_X)
+        if torch.isnan(X).any() or torch.isnan(Y).any() or (
+                noise is not None and torch.isnan(noise).any()):
+            raise InputDataError("Input data contains NaN values.")
+        if self._is_multi_output:
+            return self._condition_multi_output(X, Y, noise)
+        import copy
+        fixed = isinstance(self.likelihood, FixedNoiseGaussianLikelihood)
+        if fixed and noise is None:
+            raise RuntimeError("FixedNoiseGaussianLikelihood.fantasize requires a `noise` kwarg")
+        if not fixed and noise is not None:
+            raise UnsupportedError("condition_on_observations: `noise` needs a fixed-noise "
+                                   "likelihood (a SingleTaskGP built with train_Yvar)")
+        ot = self._modules.get("outcome_transform")
+        if ot is not None:
+            was_training = ot.training
+            ot.eval()  # the fitted statistics, never refitted here
+            try:
+                Y_tf, _ = ot(Y)
+            finally:
+                ot.train(was_training)
+        else:
+            Y_tf = Y
+        y_new = Y_tf.squeeze(-1)
+        k = X.shape[0]
+        new = self._blank_copy(torch.cat([train_X, X]))
+        new.train_targets = torch.cat([self.train_targets.detach(), y_new])
+        new._raw_train_Y = torch.cat([self._raw_train_Y.detach().to(Y), Y])
+        if ot is not None:
+            new.outcome_transform = copy.deepcopy(ot)
+        if fixed:
+            new.likelihood = FixedNoiseGaussianLikelihood(
+                torch.cat([self.likelihood.noise, noise.reshape(-1)]))
+        else:
+            new.likelihood = copy.deepcopy(self.likelihood)
+        new.mean_module = copy.deepcopy(self.mean_module)
+        new.covar_module = copy.deepcopy(self.covar_module)
+        new.eval()
+        cache = self._cache
+        if (not self.training and cache is not None and self._cache_key == self._key()
+                and k <= kernels.EXTEND_MAX_K):
+            if k > 0:
+                cache = kernels.extend_gp_cache(
+                    cache, X, y_new, noise_new=noise.reshape(-1) if fixed else None,
+                    y_old=self.train_targets, noise_old=self.likelihood.noise if fixed else None,
+                    jitter_dev=self.__dict__.get("_cache_jit"))
+                cache.Xt = new.train_inputs[0]
+            else:
+                new._cache_jit = self.__dict__.get("_cache_jit")
+            new._cache = cache
+            new._cache_key = new._key()
+        return new
+
+    def _condition_multi_output(self, X, Y, noise):
+        """m > 1: each output's member is conditioned on its column; the parent's
+        m x (n + k) targets and stacked views are rebuilt."""
+        import copy
+        members = [mm.condition_on_observations(
+            X, Y[:, t:t + 1], None if noise is None else noise[:, t:t + 1])
+            for t, mm in enumerate(self.models)]
+        shared = members[0].train_inputs[0]
+        for mm in members[1:]:  # the members share train_X, as the constructor's do
+            mm.train_inputs = (shared,)
+            if mm._cache is not None:
+                mm._cache.Xt = shared
+                mm._cache_key = mm._key()
+        new = self._blank_copy(shared)
+        ot = self._modules.get("outcome_transform")
+        if ot is not None:
+            new.outcome_transform = copy.deepcopy(ot)
+        new.models = nn.ModuleList(members)
+        new._num_outputs = self._num_outputs
+        for name in ("likelihood", "covar_module", "mean_module"):
+            setattr(new, name, _StackedView(members, name))
+        new.train_targets = torch.stack([mm.train_targets for mm in members])  # m x (n + k)
+        new.eval()
+        return new
 
 
 def prime_prediction_caches(models):
@@ -538,6 +680,7 @@ def prime_prediction_caches(models):
     for (mm, key), cache in zip(stale, kernels.build_gp_caches(specs)):
         mm._cache = cache
         mm._cache_key = key
+        mm._cache_jit = None  # cache.jitter is exact here
     return keys
 
 
@@ -558,6 +701,43 @@ class ModelListGP(Model):
         if posterior_transform is not None:
             return posterior_transform(post)
         return post
+
+    def condition_on_observations(self, X: List[torch.Tensor], Y: torch.Tensor,
+                                  noise: Optional[torch.Tensor] = None, **kwargs):
+        """botorch/models/model_list_gp_regression.py:58-129: X is a list with one
+        k x d tensor per output, Y k x m; each member is conditioned on its own
+        inputs and its slice of Y.  ``noise`` (k x m, original outcome space)
+        goes through each member's outcome transform with Y, as there."""
+        from .exceptions import BotorchTensorDimensionError
+        if Y.shape[-1] != self.num_outputs:
+            raise BotorchTensorDimensionError(
+                "Incorrect number of outputs for observations. Received "
+                f"{Y.shape[-1]} observation outputs, but model has {self.num_outputs} outputs.")
+        if len(X) != self.num_outputs:
+            raise BotorchTensorDimensionError(
+                "Incorrect number of inputs for observations. Received "
+                f"{len(X)} observation inputs, but model has {self.num_outputs} outputs.")
+        if noise is not None and noise.shape != Y.shape[-noise.dim():]:
+            raise BotorchTensorDimensionError(
+                "The shape of observation noise does not agree with the outcomes. "
+                f"Received {tuple(noise.shape)} noise with {tuple(Y.shape)} outcomes.")
+        if Y.dim() > 2 or any(x.dim() > 2 for x in X):
+            raise UnsupportedError("condition_on_observations takes X k x d and Y k x m here: "
+                                   "batched fantasy models are not on the accelerated path")
+        members, i = [], 0
+        for model in self.models:
+            j = i + model.num_outputs
+            noise_i = None
+            if noise is not None:
+                noise_i = noise[..., i:j]
+                ot = model._modules.get("outcome_transform")
+                if ot is not None:
+                    noise_i = noise_i.to(ot.stdvs) / ot.stdvs.pow(2)
+            # (a multi-output member takes the inputs of its first output)
+            members.append(model.condition_on_observations(X[i], Y[..., i:j], noise=noise_i,
+                                                           **kwargs))
+            i = j
+        return ModelListGP(*members)
 
     def train(self, mode: bool = True):
         for m in self.models:
@@ -670,6 +850,11 @@ class SaasFullyBayesianSingleTaskGP(Model):
             members.append(mdl.eval())
         self._members = nn.ModuleList(members)
         self._ens = None
+
+    def condition_on_observations(self, X, Y, **kwargs):
+        raise UnsupportedError("condition_on_observations of a fully Bayesian model (a batch "
+                               "of fantasy models over the MCMC samples) is not on the "
+                               "accelerated path")
 
     @property
     def num_mcmc_samples(self) -> int:

@@ -12,6 +12,8 @@ Ops (reference computation each replaces):
   bo::sobol_normal    SobolEngine + NormalQMCEngine draw        (sampling/qmc.py:60-98)
   bo::gp_cache        L, L^{-1}, L^{-T}, beta, alpha (+ jitter)  ([G] prediction caches,
                                                                  models/gpytorch.py:446)
+  bo::gp_cache_extend the caches after k more observations, by the bordered
+                      update of the old ones                    (models/gpytorch.py:468-531)
   bo::chol_jitter     psd_safe_cholesky of a batch (+ autograd)  ([G] psd_safe_cholesky)
   bo::post_partials   column-tile partials of R R^T and R beta  ([G] exact_predictive_covar)
   bo::qmc_finalize    posterior moments / q x q root / MC reduction
@@ -106,6 +108,31 @@ def _(Xt, y, lengthscale, outputscale, noise, constant, kind, noise_vec=None):
     np_ = _padded(n)
     mk = lambda *s: Xt.new_empty(*s, dtype=F64)  # noqa: E731
     return mk(np_, np_), mk(np_, np_), mk(np_, np_), mk(n), mk(n), mk(n, kernels.DP), mk(1)
+
+
+# ---- bo::gp_cache_extend -------------------------------------------------------------------
+@torch.library.custom_op("bo::gp_cache_extend", mutates_args=(), device_types="cuda")
+def gp_cache_extend(Xt_scaled: Tensor, L: Tensor, Linv: Tensor, beta: Tensor, alpha: Tensor,
+                    lengthscale: Tensor, X_new: Tensor, y_new: Tensor, outputscale: float,
+                    noise: float, constant: float, kind: int, noise_vec: Optional[Tensor] = None
+                    ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """The caches of the model conditioned on X_new (k x d), y_new (k) by the
+    bordered update of the old ones (condition_on_observations,
+    models/gpytorch.py:468-531): (L', L'^{-1}, U': np' x np' at the padded order
+    of n + k; beta', alpha': n + k; Xt_scaled': (n + k) x 8; info: 1, nonzero when
+    the k x k border was not p.d.).  The inputs are only read."""
+    return kernels.extend_gp_cache_enqueue(kind, Xt_scaled, L, Linv, beta, alpha, lengthscale,
+                                           outputscale, noise, constant, X_new, y_new, noise_vec)
+
+
+@gp_cache_extend.register_fake
+def _(Xt_scaled, L, Linv, beta, alpha, lengthscale, X_new, y_new, outputscale, noise, constant,
+      kind, noise_vec=None):
+    m = Xt_scaled.shape[0] + X_new.shape[0]
+    np_ = _padded(m)
+    mk = lambda *s: L.new_empty(*s, dtype=F64)  # noqa: E731
+    return (mk(np_, np_), mk(np_, np_), mk(np_, np_), mk(m), mk(m), mk(m, kernels.DP),
+            L.new_empty(1, dtype=torch.int32))
 
 
 # ---- bo::chol_jitter -------------------------------------------------------------------------
@@ -488,6 +515,6 @@ def _(Xt, y, lengthscale, noise, constant, outputscale, kind, noise_vec=None):
     return Xt.new_empty(1, dtype=F64), Xt.new_empty(d + 3, dtype=F64)
 
 
-OPS: List[str] = ["sobol_normal", "gp_cache", "chol_jitter", "chol_backward", "post_partials",
-                  "qmc_finalize", "gp_posterior", "gp_posterior_backward", "qmc_acq",
-                  "qmc_acq_backward", "qehvi", "qehvi_backward", "mll"]
+OPS: List[str] = ["sobol_normal", "gp_cache", "gp_cache_extend", "chol_jitter", "chol_backward",
+                  "post_partials", "qmc_finalize", "gp_posterior", "gp_posterior_backward",
+                  "qmc_acq", "qmc_acq_backward", "qehvi", "qehvi_backward", "mll"]

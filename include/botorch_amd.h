@@ -255,6 +255,40 @@ int bo_gp_cache_build_fixed(int kind, const double* Xt, int64_t n, int d,
                             double* Linv, double* U, double* beta, double* alpha, int max_tries,
                             double jitter0, double* jitter_used, int* info_dev, void* stream);
 
+/* The caches of the n + k point model from those of the n point model, for
+ * Model.condition_on_observations (botorch/models/gpytorch.py:468-531,
+ * botorch/models/model.py:149 -> [G] ExactGP.get_fantasy_model), without
+ * refactoring: the new factor is the old one with a k-row border,
+ *   B = K(X2, X1) L^{-T},  S = K(X2, X2) + noise - B B^T,  L22 = chol(S),
+ *   C = -L22^{-1} B L^{-1},
+ *   L' = [[L, 0], [B, L22]],  Linv' = [[Linv, 0], [C, L22^{-1}]],  U' = Linv'^T,
+ *   beta' = [beta; b2],  b2 = L22^{-1}(y2 - constant - B beta),
+ *   alpha' = [alpha + C^T b2; L22^{-T} b2],
+ * applied in blocks of <= 16 rows (O(n^2 k) flops, a few streaming passes over
+ * L^{-1}).  The old caches (Xt_scaled: n x 8; L, Linv: leading dimension ld;
+ * beta, alpha: n) are only read.  X_new: k x d (d <= 8, original scale), y_new:
+ * k standardised targets, noise: the likelihood's variance, or noise_vec (k
+ * observed variances, may be NULL) under a fixed-noise likelihood.  Outputs at
+ * the new padded order np' = bo_padded_order(n + k), leading dimension ld_out
+ * >= np': Xt_scaled_out (n + k) x 8, L_out / Linv_out / U_out np' rows, beta_out
+ * / alpha_out n + k; every element of the np' x np' blocks is written, with
+ * the identity pad and zero opposite triangle bo_gp_cache_build leaves.  work:
+ * bo_gp_cache_extend_work(n, k) doubles.  info: device int the caller zeroes;
+ * a non-positive pivot of S leaves its 1-based index there (no jitter ladder:
+ * the caller then rebuilds with bo_gp_cache_build, and also when the old
+ * caches were built with jitter).  Enqueue only.  L, Linv, their outputs,
+ * U_out and work 16-B aligned, ld and ld_out even.  BO_ERR_ARG (nothing
+ * launched) on k < 1, ld_out < np', a NULL or misaligned buffer, d > 8.
+ * A pure addition to the ABI: BO_ABI_VERSION stays 11. */
+int bo_gp_cache_extend_work(int64_t n, int k, int64_t* work_elems);
+int bo_gp_cache_extend(int kind, const double* Xt_scaled, const double* L, const double* Linv,
+                       const double* beta, const double* alpha, int64_t ld, int64_t n, int d,
+                       const double* lengthscale, double outputscale, double constant,
+                       const double* X_new, const double* y_new, int k, double noise,
+                       const double* noise_vec, double* Xt_scaled_out, double* L_out,
+                       double* Linv_out, double* U_out, double* beta_out, double* alpha_out,
+                       int64_t ld_out, double* work, int* info, void* stream);
+
 /* Geometry of the fused posterior kernels for B t-batches of q points (1 <= q
  * <= 16) over n training points: Qp = q rounded up to a power of two,
  * nrows_pad = roundup(B*Qp, 128) test rows, nC = ceil(n/128) column tiles.
