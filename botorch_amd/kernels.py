@@ -1077,7 +1077,8 @@ def qmc_backward(mode: int, mean: torch.Tensor, L: torch.Tensor, Z: torch.Tensor
     fat, tau_relu, tau_max = log_params if log_params is not None else (1, 1.0, 1.0)
     if acq_fwd is not None:
         acq_fwd = acq_fwd.contiguous()
-    a = _lib.QmcBackwardArgs(mode=mode, B=B, q=q, S=S, mean=mean, Lq=L,
+    # row-major operands: torch.linalg.cholesky, for one, returns column-major factors
+    a = _lib.QmcBackwardArgs(mode=mode, B=B, q=q, S=S, mean=mean.contiguous(), Lq=L.contiguous(),
                              Z=Z.reshape(S, q).contiguous(), best_f=float(best_f),
                              best_f_s=best_f_s, F=F, ldF=F.shape[1] if F is not None else 0,
                              dacq=dacq.contiguous(), dmean=dmean, dcov=dcov, dF=dF,
