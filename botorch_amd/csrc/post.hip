@@ -176,6 +176,9 @@ struct PostMembers {
 #ifndef BO_USTORE_ALWAYS
 #define BO_USTORE_ALWAYS 1
 #endif
+#ifndef BO_POST_RING
+#define BO_POST_RING 1  // 0: the two-stage loop for the K*x^T-reading kernels too (A/B)
+#endif
 template <int KIND, int ND, bool SPLIT, bool CROSS, bool PRE = false, bool LOWERK = false,
           bool FUSEDX = false>
 __global__ __launch_bounds__(256, 2) void post_partials_kernel(
@@ -190,7 +193,19 @@ __global__ __launch_bounds__(256, 2) void post_partials_kernel(
   // are in flight to registers and this thread evaluates its 8 kernel values
   // of step t+1 between the MFMAs (VALU work hidden under the matrix pipe);
   // one barrier per k-step.
-  __shared__ __attribute__((aligned(16))) double Us[2][PK][PLD];
+  // PRE (RING, the K*x^T-reading kernels): a ring of three U stages with the
+  // step's one barrier in its middle.  In step t the waves multiply the first
+  // k-slices from stage t % 3, write U(t+1) -- loaded a whole step earlier --
+  // into stage (t+1) % 3, meet at the barrier, issue the loads of U(t+2) and
+  // multiply the remaining slices; the first slice of step t+1 is read before
+  // the step ends.  The stage written was last read in step t-2, which every
+  // wave had finished before the barrier of step t-1, so one barrier per step
+  // is enough, and the step edge carries no store, drain or barrier (with two
+  // stages the edge was: last MFMA, LDS store, vmcnt(0), barrier, addresses,
+  // loads, LDS read, first MFMA -- about 700 idle cycles of the matrix pipe
+  // per wave and step at C3, 14.4 % -> 11.2 % idle with the ring).
+  constexpr bool RING = PRE && BO_POST_RING;
+  __shared__ __attribute__((aligned(16))) double Us[RING ? 3 : 2][PK][PLD];
   __shared__ __attribute__((aligned(16))) double Ks[2][PK][PLD];
 
   const int bid = blockIdx.x;
@@ -404,49 +419,116 @@ __global__ __launch_bounds__(256, 2) void post_partials_kernel(
     _Pragma("unroll") for (int ks = 0; ks < 4; ++ks)                              \
       DST[it][ks] = FUSEDX ? ktb[((int64_t)((K0) >> 4) * (nI * (PI / 16)) + it) * 256 + ks * 64] \
                            : ktw[(int64_t)((K0) + 4 * ks) * (nI * PI) + it * 16];
-  BO_LOAD_U(kfirst);
-  if (PRE) {
-    BO_LOAD_B(kfirst, bc);
-  } else {
-#pragma unroll
-    for (int kk = 0; kk < 8; ++kk)
-      kv[kk] = BO_KVAL(kfirst + kh * 8 + kk);
+  // RING: the operand pointers advance by one constant stride per k-step (the
+  // walk's last steps re-read the last rows: harmless duplicates).
+  const int64_t ustep = (int64_t)kdir * ldu, bstep = (int64_t)kdir * (nI * PI);
+  const double* up = U + (int64_t)(kfirst + urow) * ldu + ucol;
+  const double* bp = FUSEDX ? ktb + (int64_t)(kfirst >> 4) * (nI * (PI / 16)) * 256
+                            : (PRE ? ktw + (int64_t)kfirst * (nI * PI) : nullptr);
+#define BO_LOAD_UP()                                                              \
+  {                                                                               \
+    const double2 v0 = *reinterpret_cast<const double2*>(up);                     \
+    const double2 v1 = *reinterpret_cast<const double2*>(up + 4 * ldu);           \
+    const double2 v2 = *reinterpret_cast<const double2*>(up + 8 * ldu);           \
+    const double2 v3 = *reinterpret_cast<const double2*>(up + 12 * ldu);          \
+    u0x = v0.x; u0y = v0.y; u1x = v1.x; u1y = v1.y;                               \
+    u2x = v2.x; u2y = v2.y; u3x = v3.x; u3y = v3.y;                               \
   }
-  BO_STORE(0);
-  __syncthreads();
+#define BO_LOAD_BP(DST)                                                            \
+  _Pragma("unroll") for (int it = 0; it < 2; ++it)                                 \
+    _Pragma("unroll") for (int ks = 0; ks < 4; ++ks)                              \
+      DST[it][ks] = FUSEDX ? bp[it * 256 + ks * 64]                                \
+                           : bp[(int64_t)(4 * ks) * (nI * PI) + it * 16];
+  double an[8];  // RING: the next step's first k-slice of U fragments
+  int stage = 0;
+  if (RING) {
+    BO_LOAD_UP();
+    BO_LOAD_BP(bc);
+    BO_STORE(0);
+    if (nsteps > 1) { up += ustep; bp += bstep; }
+    BO_LOAD_UP();  // U(1) in flight over the barrier
+    __syncthreads();
+#pragma unroll
+    for (int ct = 0; ct < 8; ++ct) an[ct] = Us[0][lane >> 4][ct * 16 + (lane & 15)];
+  } else {
+    BO_LOAD_U(kfirst);
+    if (PRE) {
+      BO_LOAD_B(kfirst, bc);
+    } else {
+#pragma unroll
+      for (int kk = 0; kk < 8; ++kk)
+        kv[kk] = BO_KVAL(kfirst + kh * 8 + kk);
+    }
+    BO_STORE(0);
+    __syncthreads();
+  }
   // One k-step; XMFMA = the cross-term MFMAs (cross workgroups only: a
   // separate copy of the loop keeps the common loop free of branches, which
   // would split its MFMA / kernel-evaluation interleaving).
-#define BO_KSTEP(XLOAD, XMFMA)                                                       \
+  //
+  // DIAG: the U operand is triangular, so in the column tile's diagonal
+  // 128-block the 16-column sub-tiles ct on the far side of the k-step hold
+  // only zeros (upper U: every column of ct below k0; LOWERK, U = L^-1: every
+  // column of ct above k0 + 15).  Their MFMAs are skipped behind a
+  // workgroup-uniform (scalar) branch: ctb is the first sub-tile that is
+  // multiplied (the last one, LOWERK).  The skipped products are exact zeros,
+  // so the sums are unchanged bit for bit; the skipped 16 x 16 blocks of U are
+  // staged through LDS but never multiplied.  DIAG = 0 is the plain step of
+  // the k-steps outside the diagonal block.
+#define BO_KSTEP(XLOAD, XMFMA, DIAG)                                                 \
   {                                                                                  \
-    const int cur = t & 1;                                                           \
+    const int cur = RING ? stage : (t & 1);                                          \
+    const int nxt = RING ? (stage == 2 ? 0 : stage + 1) : (cur ^ 1);                 \
     const bool more = t + 1 < nsteps;                                                \
     const int knext = kfirst + (more ? t + 1 : t) * kdir;                            \
+    const int kd = kfirst + t * kdir - c0;                                           \
+    const int ctb = (DIAG) ? __builtin_amdgcn_readfirstlane(                         \
+                                 LOWERK ? (kd + PK - 1) >> 4 : max(kd, 0) >> 4)      \
+                           : 0;                                                      \
     XLOAD                                                                            \
-    BO_LOAD_U(knext);                                                                \
-    if (PRE) { BO_LOAD_B(knext, bn); }                                               \
+    if (RING) {                                                                      \
+      BO_LOAD_BP(bn);  /* bp is at step t + 1 (or the last step) */                  \
+    } else {                                                                         \
+      BO_LOAD_U(knext);                                                              \
+      if (PRE) { BO_LOAD_B(knext, bn); }                                             \
+    }                                                                                \
     _Pragma("unroll") for (int ks = 0; ks < PK / 4; ++ks) {                         \
+      if (RING && ks == PK / 8) {                                                    \
+        BO_STORE(nxt);  /* U(t + 1), loaded after the previous step's barrier */     \
+        __syncthreads();                                                             \
+        if (t + 2 < nsteps) { up += ustep; bp += bstep; }                            \
+        BO_LOAD_UP();   /* U(t + 2), or the last step's rows again */                \
+      }                                                                              \
       const int kr = ks * 4 + (lane >> 4);                                           \
       double a[8], b[2];                                                             \
-      _Pragma("unroll") for (int ct = 0; ct < 8; ++ct) a[ct] = Us[cur][kr][ct * 16 + (lane & 15)]; \
+      _Pragma("unroll") for (int ct = 0; ct < 8; ++ct)                              \
+        a[ct] = (RING && ks == 0) ? an[ct] : Us[cur][kr][ct * 16 + (lane & 15)];     \
       _Pragma("unroll") for (int it = 0; it < 2; ++it)                              \
         b[it] = PRE ? bc[it][ks] : Ks[cur][kr][wave * 32 + it * 16 + (lane & 15)];   \
       _Pragma("unroll") for (int ct = 0; ct < 8; ++ct)                              \
-        _Pragma("unroll") for (int it = 0; it < 2; ++it)                            \
-          acc[ct][it] = FUSEDX ? mfma_f64(b[it], a[ct], acc[ct][it])                \
-                               : mfma_f64(a[ct], b[it], acc[ct][it]);                \
+        if (!(DIAG) || (LOWERK ? ct <= ctb : ct >= ctb)) {                           \
+          _Pragma("unroll") for (int it = 0; it < 2; ++it)                          \
+            acc[ct][it] = FUSEDX ? mfma_f64(b[it], a[ct], acc[ct][it])              \
+                                 : mfma_f64(a[ct], b[it], acc[ct][it]);              \
+        }                                                                            \
       XMFMA                                                                          \
       if (!PRE) {                                                                    \
         kv[2 * ks] = BO_KVAL(knext + kh * 8 + 2 * ks);                              \
         kv[2 * ks + 1] = BO_KVAL(knext + kh * 8 + 2 * ks + 1);                      \
       }                                                                              \
     }                                                                                \
-    if (BO_USTORE_ALWAYS || more) BO_STORE(cur ^ 1);                                 \
+    if (RING) {                                                                      \
+      _Pragma("unroll") for (int ct = 0; ct < 8; ++ct)                              \
+        an[ct] = Us[nxt][lane >> 4][ct * 16 + (lane & 15)];                          \
+      stage = nxt;                                                                   \
+    } else if (BO_USTORE_ALWAYS || more) {                                           \
+      BO_STORE(cur ^ 1);                                                             \
+    }                                                                                \
     if (PRE) {                                                                       \
       _Pragma("unroll") for (int it = 0; it < 2; ++it)                              \
         _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) bc[it][ks] = bn[it][ks];   \
     }                                                                                \
-    __syncthreads();                                                                 \
+    if (!RING) __syncthreads();                                                      \
   }
   int t = 0;
   if (cross) {
@@ -454,16 +536,31 @@ __global__ __launch_bounds__(256, 2) void post_partials_kernel(
     // the first ones on a reversed walk
     const int tc = min(nsteps, c0 / PK);
     const int t0 = rev ? 0 : tc, t1 = rev ? nsteps - tc : nsteps;
-    for (; t < t0; ++t) BO_KSTEP(, )
+    // (they contain the diagonal block's skipping steps, k >= c0 + 16)
+    for (; t < t0; ++t) BO_KSTEP(, , 0)
     for (; t < t1; ++t)
       BO_KSTEP(BO_LOAD_Q(kfirst + t * kdir),
                accx[0] = mfma_f64(qa[ks], b[0], accx[0]);
-               accx[1] = mfma_f64(qa[ks], b[1], accx[1]);)
-    for (; t < nsteps; ++t) BO_KSTEP(, )
+               accx[1] = mfma_f64(qa[ks], b[1], accx[1]);, 1)
+    for (; t < nsteps; ++t) BO_KSTEP(, , 0)
   } else {
-    for (; t < nsteps; ++t) BO_KSTEP(, )
+    // The skipping steps are those at k0 = kbeg + 16 s with k0 >= c0 + 16
+    // (LOWERK: k0 + 15 < c0 + 112): a run [a0, a1) of s at one end of the
+    // segment (possibly empty: split segments), so the walk is at most one run
+    // of plain steps and one of skipping steps, in either order.
+    const int a0 = LOWERK ? 0 : min(nsteps, max(0, (c0 + PK - kbeg + PK - 1) / PK));
+    const int a1 = LOWERK ? min(nsteps, max(0, (c0 + PC - 2 * PK + 1 - kbeg + PK - 1) / PK)) : nsteps;
+    const int d0 = rev ? nsteps - a1 : a0, d1 = rev ? nsteps - a0 : a1;
+    for (; t < d0; ++t) BO_KSTEP(, , 0)
+    for (; t < d1; ++t) BO_KSTEP(, , 1)
+    for (; t < nsteps; ++t) BO_KSTEP(, , 0)
   }
+  // RING: the last step's readers are done before the next segment's prologue
+  // (or the FUSEDX epilogue) rewrites the stages
+  if (RING) __syncthreads();
 #undef BO_KSTEP
+#undef BO_LOAD_UP
+#undef BO_LOAD_BP
 #undef BO_KVAL
 #undef BO_LOAD_U
 #undef BO_STORE

@@ -316,7 +316,19 @@ int bo_prepare_rows(const double* X, int B, int q, int d, const double* lengthsc
  * Cx[ci] (nC x rq x nrows_pad; sum over ci = Qc K*x^T) -- the
  * qNEI cross-covariance P_b R^T = Q_b K*x^T, Q_b = P_b U^T
  * (acquisition/cached_cholesky.py:94-120), without storing R.
- * Kt (nullable): K*x^T from bo_post_kxt (read instead of evaluated). */
+ * Kt (nullable): K*x^T from bo_post_kxt (read instead of evaluated).
+ *
+ * The triangular operand (every entry point on the posterior kernel's 128 x
+ * 128 tiles: bo_post_partials*, bo_post_partials_members with U = L^{-T}
+ * upper; bo_post_w*, bo_post_w_dx, bo_ainv with L^{-1} lower).  Column tile c
+ * reads rows [0, 128 c + 128) of U (rows [128 c, n) of L^{-1}) and nothing
+ * beyond.  Inside the tile's diagonal 128 x 128 block it multiplies only the
+ * 16 x 16 blocks on or above the block diagonal (on or below, L^{-1}): the
+ * 16 x 16 blocks on the zero side are loaded but never multiplied, so their
+ * contents do not reach the result.  What the caller owes: the zero triangle
+ * INSIDE the 16 x 16 diagonal blocks holds exact zeros, and rows / columns
+ * >= n hold the identity pad.  bo_gp_cache_build*, bo_cholesky_inverse* and
+ * bo_gp_cache_extend leave the whole opposite triangle zero. */
 int bo_post_partials(int kind, const double* Xq, int B, int q, int d,
                      const double* Xt_scaled, int64_t n, const double* U, int64_t ldu, const double* beta,
                      double outputscale, double* Spart, double* mpart, double* Rt,
