@@ -224,6 +224,11 @@ class QehviArgs(_Args):
                        ("work_elems", c_int64)]
 
 
+class QehviFeasArgs(_Args):
+    _fields_ = QehviArgs._fields_ + [("feas", _D), ("dfeas", _D), ("Mt", c_int32), ("zm", c_int32),
+                                     ("zld", c_int64), ("out_idx", c_int32 * 4)]
+
+
 class LbfgsStepArgs(_Args):
     _fields_ = _HDR + [("B", c_int32), ("n", c_int32), ("m", c_int32), ("_pad", c_int32),
                        ("x", _D), ("f", _D), ("g", _D), ("xt", _D), ("ft", _D), ("gt", _D),
@@ -244,13 +249,15 @@ class LbfgsbArgs(_Args):
 for _name, _cls in (("bo_post_partials_v", PostPartialsArgs), ("bo_qmc_finalize_v", QmcFinalizeArgs),
                     ("bo_qmc_backward_v", QmcBackwardArgs), ("bo_post_backward_v", PostBackwardArgs),
                     ("bo_qehvi_v", QehviArgs), ("bo_qehvi_backward_v", QehviArgs),
+                    ("bo_qehvi_feas_v", QehviFeasArgs), ("bo_qehvi_feas_backward_v", QehviFeasArgs),
                     ("bo_lbfgs_step_v", LbfgsStepArgs), ("bo_lbfgsb_step_v", LbfgsbArgs)):
     _SIGNATURES[_name] = (c_int, [POINTER(_cls), _P])
 _SIGNATURES["bo_struct_size"] = (c_int64, [ctypes.c_char_p])
 _SIGNATURES["bo_post_backward_jobs"] = (c_int, [c_int, POINTER(POINTER(PostBackwardArgs)), _P, _P])
 ARG_RECORDS = {"BoPostPartialsArgs": PostPartialsArgs, "BoQmcFinalizeArgs": QmcFinalizeArgs,
                "BoQmcBackwardArgs": QmcBackwardArgs, "BoPostBackwardArgs": PostBackwardArgs,
-               "BoQehviArgs": QehviArgs, "BoLbfgsStepArgs": LbfgsStepArgs,
+               "BoQehviArgs": QehviArgs, "BoQehviFeasArgs": QehviFeasArgs,
+               "BoLbfgsStepArgs": LbfgsStepArgs,
                "BoLbfgsbArgs": LbfgsbArgs}
 
 _lib = None

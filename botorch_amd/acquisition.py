@@ -24,12 +24,13 @@ import torch
 from torch import nn
 
 from . import _lib, kernels
-from .exceptions import BotorchError, BotorchWarning, NanError, NotPSDError, UnsupportedError
+from .exceptions import (BotorchError, BotorchTensorDimensionError, BotorchWarning, NanError,
+                         NotPSDError, UnsupportedError)
 from .safe_math import TAU_MAX, TAU_RELU, fatmax, log_improvement, logmeanexp, smooth_amax
 from .objective import (ConstrainedMCObjective, GenericMCObjective, IdentityMCObjective,
                         MCAcquisitionObjective, MCObjective, compute_best_feasible_objective,
                         compute_feasibility_indicator, compute_smoothed_feasibility_indicator,
-                        repeat_to_match_aug_dim)
+                        repeat_to_match_aug_dim, _as_etas)
 from .models import prime_prediction_caches
 from .posteriors import FUSED_QMAX
 from .sampling import MCSampler, ShapeOnlyPosterior, SobolQMCNormalSampler, get_sampler
@@ -1020,7 +1021,13 @@ class _FusedQEHVI(torch.autograd.Function):
         lo, hi = acqf._cells(X3.device)
         # the kernel itself (as the backward below): this Function already is
         # the autograd node, the registered op's wrapper would only add host time
-        acq = kernels.qehvi(mean, L, Z, lo, hi)
+        feas = None
+        if acqf._weighted:
+            # outcome constraints: the weighted kernel on the objective members
+            feas = _feas_weights(acqf, mean, L, Z, None, 0, need_grad)
+            acq = kernels.qehvi_feas(mean, L, Z, lo, hi, feas[0].detach(), acqf._out_idx)
+        else:
+            acq = kernels.qehvi(mean, L, Z, lo, hi)
         # the members' ladders checked once, behind the qEHVI launch (one host
         # read per forward instead of one per member, each of which drained
         # the queue: ~40 us of idle device between members at C4)
@@ -1034,12 +1041,18 @@ class _FusedQEHVI(torch.autograd.Function):
             kernels.raise_not_psd_many(status, "qEHVI posterior root")
         if need_grad:
             ctx.saved, ctx.mean, ctx.L, ctx.Z, ctx.cells = saved, mean, L, Z, (lo, hi)
+            ctx.feas, ctx.out_idx = feas, acqf._out_idx
         return acq
 
     @staticmethod
     def backward(ctx, dacq):
         lo, hi = ctx.cells
-        dmean, dL = kernels.qehvi_backward(ctx.mean, ctx.L, ctx.Z, lo, hi, dacq)
+        if ctx.feas is not None:
+            dmean, dL, dfeas = kernels.qehvi_feas_backward(ctx.mean, ctx.L, ctx.Z, lo, hi,
+                                                           ctx.feas[0].detach(), ctx.out_idx, dacq)
+            _feas_backward(ctx.feas, dfeas, dmean, dL, None)
+        else:
+            dmean, dL = kernels.qehvi_backward(ctx.mean, ctx.L, ctx.Z, lo, hi, dacq)
         dX = None
         sv = ctx.saved
         if (_PB_JOBS and 1 < len(sv) <= 16 and all(
@@ -1069,10 +1082,96 @@ def _settle_ladder(ctx) -> None:
 
 
 class IdentityMCMultiOutputObjective(MCObjective):
-    """acquisition/multi_objective/objective.py (identity over outputs)."""
+    """acquisition/multi_objective/objective.py:65-101: the samples, or their
+    ``outcomes`` columns (the objective members of a model list that also has
+    constraint members; negative indices count from ``num_outcomes``)."""
+
+    def __init__(self, outcomes: Optional[List[int]] = None, num_outcomes: Optional[int] = None):
+        super().__init__()
+        if outcomes is not None:
+            outcomes = [int(i) for i in outcomes]
+            if len(outcomes) < 2:
+                raise BotorchTensorDimensionError("Must specify at least two outcomes for MOO.")
+            if any(i < 0 for i in outcomes):
+                if num_outcomes is None:
+                    raise BotorchError("num_outcomes is required if any outcomes are less than 0.")
+                if any(not -num_outcomes <= i < num_outcomes for i in outcomes):
+                    raise ValueError(f"outcomes {outcomes} out of range for {num_outcomes} outcomes")
+                outcomes = [i % num_outcomes for i in outcomes]
+            self.register_buffer("outcomes", torch.tensor(outcomes, dtype=torch.long))
 
     def forward(self, samples, X=None):
+        if hasattr(self, "outcomes"):
+            return samples.index_select(-1, self.outcomes.to(device=samples.device))
         return samples
+
+
+def _init_outcome_constraints(acqf, num_members: int, objective, constraints, eta, fat,
+                              num_ref: int) -> None:
+    """The constraint options of qEHVI / qNEHVI (monte_carlo.py:105-130),
+    checked before any device work: sets ``constraints``, ``eta``, ``fat``, the
+    objective members ``_out_idx`` and ``_weighted`` (whether forward takes the
+    feasibility-weighted kernels: constraints, or an objective that selects
+    outcomes)."""
+    acqf.constraints = list(constraints) if constraints else None
+    acqf.fat = fat
+    acqf.eta = None
+    if acqf.constraints is not None:
+        if objective is not None and type(objective) is not IdentityMCMultiOutputObjective:
+            raise UnsupportedError("outcome constraints with a non-identity multi-output objective "
+                                   "are not on the accelerated path")
+        acqf.eta = _as_etas(eta, len(acqf.constraints)).to(torch.float64)
+    outcomes = (getattr(objective, "outcomes", None)
+                if type(objective) is IdentityMCMultiOutputObjective else None)
+    if outcomes is not None:
+        out_idx = [int(i) for i in outcomes.tolist()]
+        if any(not 0 <= i < num_members for i in out_idx) or len(set(out_idx)) != len(out_idx):
+            raise ValueError(f"objective outcomes {out_idx} must be distinct members of the "
+                             f"{num_members}-member model list")
+    else:
+        out_idx = list(range(num_members))
+    acqf._out_idx = out_idx
+    acqf._weighted = acqf.constraints is not None or outcomes is not None
+    if acqf._weighted:
+        if num_ref != len(out_idx):
+            raise ValueError("The length of the reference point must match the number of outcomes. "
+                             f"Got ref_point with {num_ref} elements, but expected {len(out_idx)}.")
+        if not 2 <= len(out_idx) <= 4:
+            raise UnsupportedError("the feasibility-weighted kernels support 2 to 4 objectives")
+
+
+def _feas_weights(acqf, mean, L, Z, F, Qp: int, need_grad: bool):
+    """The smoothed feasibility weights w (S x B x q) of the samples
+    f = mean + L z (+ F) of ALL members (S x B x q x Mt; the constraint
+    callables may read any output), as a differentiable function of detached
+    leaf copies of mean, L (and F): -> (w, leaves).  Plain torch: the tensor is
+    tiny next to the posterior.  Without constraints (an objective that only
+    selects outcomes) every weight is 1."""
+    Mt, B, q = mean.shape
+    S = Z.shape[0]
+    if acqf.constraints is None:
+        return torch.ones(S, B, q, dtype=torch.float64, device=mean.device), None
+    leaves = [t.detach().requires_grad_(need_grad) for t in ((mean, L) if F is None else (mean, L, F))]
+    with torch.enable_grad() if need_grad else torch.no_grad():
+        f = leaves[0].permute(1, 2, 0).unsqueeze(0) + torch.einsum(
+            "tbpj,sjt->sbpt", leaves[1].tril(), Z.reshape(S, q, Mt))
+        if F is not None:
+            f = f + leaves[2][:, :, : B * Qp].reshape(Mt, S, B, Qp)[..., :q].permute(1, 2, 3, 0)
+        w = compute_smoothed_feasibility_indicator(acqf.constraints, f, acqf.eta.to(f),
+                                                   fat=acqf.fat)
+    return w.to(torch.float64).contiguous(), leaves
+
+
+def _feas_backward(feas, dfeas, dmean, dL, dF) -> None:
+    """The constraint path's cotangents added to the kernel's: one
+    autograd.grad of w w.r.t. the leaves of _feas_weights, for all members."""
+    w, leaves = feas
+    if leaves is None or not w.requires_grad:
+        return
+    grads = torch.autograd.grad(w, leaves, dfeas, allow_unused=True)
+    for out, g in zip((dmean, dL, dF), grads):
+        if g is not None:
+            out.add_(g)
 
 
 class qExpectedHypervolumeImprovement(MCAcquisitionFunction):
@@ -1083,7 +1182,15 @@ class qExpectedHypervolumeImprovement(MCAcquisitionFunction):
     the exact posterior of the B t-batches (post_partials + the per-t-batch
     jittered Cholesky, qmc_finalize in CHOL mode), then one bo_qehvi launch that
     draws the non-interleaved Sobol samples and evaluates the inclusion-exclusion
-    hypervolume improvement over (sample, hypercell) pairs."""
+    hypervolume improvement over (sample, hypercell) pairs.
+
+    Outcome constraints (monte_carlo.py:245-251, 303-309): the model list holds
+    objective and constraint members, ``objective =
+    IdentityMCMultiOutputObjective(outcomes=[...])`` picks the objectives, and
+    every subset term is weighted by the smoothed feasibility of its points
+    (``constraints``: callables on the S x B x q x Mt samples, <= 0 feasible;
+    ``eta``, ``fat``): bo_qehvi_feas / bo_qehvi_feas_backward, the constraint
+    path's gradient through torch autograd on the small sample tensor."""
 
     _default_sample_shape = torch.Size([128])
 
@@ -1094,9 +1201,9 @@ class qExpectedHypervolumeImprovement(MCAcquisitionFunction):
                 "The length of the reference point must match the number of outcomes. "
                 f"Got ref_point with {len(ref_point)} elements, but expected "
                 f"{partitioning.num_outcomes}.")
-        if constraints is not None:
-            raise UnsupportedError("outcome constraints are not on the accelerated path")
         AcquisitionFunction.__init__(self, model)
+        _init_outcome_constraints(self, len(getattr(model, "models", None) or ()), objective,
+                                  constraints, eta, fat, len(ref_point))
         self.sampler = sampler
         self.objective = objective if objective is not None else IdentityMCMultiOutputObjective()
         self.posterior_transform = None
@@ -1127,7 +1234,8 @@ class qExpectedHypervolumeImprovement(MCAcquisitionFunction):
         if q > 12 or d > kernels.DP:
             raise UnsupportedError("fused qEHVI supports q <= 12 and d <= 8")
         acq = None
-        if not (torch.is_grad_enabled() and X3.requires_grad) and X3.dtype == torch.float64:
+        if (not self._weighted and not (torch.is_grad_enabled() and X3.requires_grad)
+                and X3.dtype == torch.float64):
             acq = _qehvi_members_eager(self, X3)
         if acq is None:
             acq = _FusedQEHVI.apply(X3, self)
@@ -1138,18 +1246,17 @@ class qExpectedHypervolumeImprovement(MCAcquisitionFunction):
 def prune_inferior_points_multi_objective(model, X, ref_point, objective=None, constraints=None,
                                           num_samples: int = 2048, max_frac: float = 1.0,
                                           marginalize_dim=None, chunk: int = 64):
-    """acquisition/multi_objective/utils.py:77-161 (unconstrained, identity
-    objective): keep the points with a positive probability of being
-    Pareto-optimal and better than ref_point under ``num_samples`` joint
-    posterior samples (drawn on the device; Pareto masks in sample chunks)."""
+    """acquisition/multi_objective/utils.py:77-161: keep the points with a
+    positive probability of being feasible, Pareto-optimal and better than
+    ref_point under ``num_samples`` joint posterior samples (drawn on the
+    device; Pareto masks in sample chunks).  ``constraints`` read the samples
+    of all outputs, ``objective`` selects / maps the objectives' columns."""
     from .multi_objective import is_non_dominated
     if X.ndim > 2:
         raise UnsupportedError("Batched inputs `X` are currently unsupported by "
                                "prune_inferior_points_multi_objective")
     if max_frac <= 0 or max_frac > 1.0:
         raise ValueError(f"max_frac must take values in (0, 1], is {max_frac}")
-    if constraints is not None:
-        raise UnsupportedError("constraints are not on the accelerated path")
     max_points = math.ceil(max_frac * X.size(-2))
     ref = torch.as_tensor(ref_point, dtype=torch.float64, device=X.device)
     models = getattr(model, "models", [model])
@@ -1171,9 +1278,13 @@ def prune_inferior_points_multi_objective(model, X, ref_point, objective=None, c
             L, _, _ = kernels.cholesky_with_inverse(post.distribution.covariance_matrix.reshape(n, n))
             cols.append(kernels.sample_mvn(mean, L.unsqueeze(0).contiguous(),
                                            Z[:, :, t].contiguous()).reshape(num_samples, n))
-        obj = torch.stack(cols, dim=-1)  # S x n x m
-        if objective is not None:
-            obj = objective(obj, X=X)
+        samples = torch.stack(cols, dim=-1)  # S x n x m
+        obj = samples if objective is None else objective(samples, X=X)
+        if constraints:
+            # infeasible samples never count as Pareto-optimal (utils.py:144-150)
+            infeas = ~compute_feasibility_indicator(constraints, samples,
+                                                    marginalize_dim=marginalize_dim)
+            obj = obj.masked_fill(infeas.unsqueeze(-1), float("-inf"))
         hits = torch.zeros(n, dtype=torch.float64, device=X.device)
         # one device launch for all samples (bo_pareto_mask); host tensors chunked
         step = obj.shape[0] if obj.is_cuda else chunk
@@ -1278,7 +1389,13 @@ class _FusedQNEHVI(torch.autograd.Function):
                 status.append((out["info"], out["jitter"]))
         Zq = acqf._base_samples_q(q, X3.device)
         lo, hi = acqf._cells
-        acq = kernels.qehvi(mean, L, Zq, lo, hi, F=F, Qp=pp.Qp)
+        feas = None
+        if acqf._weighted:
+            feas = _feas_weights(acqf, mean, L, Zq, F, pp.Qp, need_grad)
+            acq = kernels.qehvi_feas(mean, L, Zq, lo, hi, feas[0].detach(), acqf._out_idx, F=F,
+                                     Qp=pp.Qp)
+        else:
+            acq = kernels.qehvi(mean, L, Zq, lo, hi, F=F, Qp=pp.Qp)
         ctx.ladder = None
         if defer:
             kernels.raise_not_psd_deferred(torch.cat([i_.reshape(-1) for i_, _ in status]),
@@ -1295,13 +1412,20 @@ class _FusedQNEHVI(torch.autograd.Function):
             ctx.acqf, ctx.saved, ctx.mean, ctx.L, ctx.F, ctx.Zq, ctx.Qp = (
                 acqf, saved, mean, L, F, Zq, pp.Qp)
             ctx.batched = batched
+            ctx.feas = feas
         return acq
 
     @staticmethod
     def backward(ctx, dacq):
         lo, hi = ctx.acqf._cells
-        dmean, dL, dF = kernels.qehvi_backward(ctx.mean, ctx.L, ctx.Zq, lo, hi, dacq, F=ctx.F,
-                                               Qp=ctx.Qp)
+        if ctx.feas is not None:
+            dmean, dL, dF, dfeas = kernels.qehvi_feas_backward(
+                ctx.mean, ctx.L, ctx.Zq, lo, hi, ctx.feas[0].detach(), ctx.acqf._out_idx, dacq,
+                F=ctx.F, Qp=ctx.Qp)
+            _feas_backward(ctx.feas, dfeas, dmean, dL, dF)
+        else:
+            dmean, dL, dF = kernels.qehvi_backward(ctx.mean, ctx.L, ctx.Zq, lo, hi, dacq, F=ctx.F,
+                                                   Qp=ctx.Qp)
         dX = None
         if ctx.batched and _BWD_BATCHED:
             dX = _roots_backward_batched(ctx, dmean, dL, dF)
@@ -1435,6 +1559,27 @@ class _QEHVIFromRoots(torch.autograd.Function):
         return dmean, dL, dF, None, None, None, None
 
 
+class _QEHVIFeasFromRoots(torch.autograd.Function):
+    """_QEHVIFromRoots with feasibility weights (bo_qehvi_feas): a
+    differentiable function of (mean, L, F, w) over all Mt members; the caller
+    forms w from the same (mean, L, F) in torch, so autograd adds the
+    constraint path through dfeas."""
+
+    @staticmethod
+    def forward(ctx, mean, L, F, w, Zq, lo, hi, q, out_idx):
+        acq = kernels.qehvi_feas(mean, L, Zq, lo, hi, w, out_idx, F=F, Qp=q)
+        ctx.save_for_backward(mean, L, F, w, Zq, lo, hi)
+        ctx.q, ctx.out_idx = q, out_idx
+        return acq
+
+    @staticmethod
+    def backward(ctx, dacq):
+        mean, L, F, w, Zq, lo, hi = ctx.saved_tensors
+        dmean, dL, dF, dfeas = kernels.qehvi_feas_backward(mean, L, Zq, lo, hi, w, ctx.out_idx,
+                                                           dacq.contiguous(), F=F, Qp=ctx.q)
+        return dmean, dL, dF, dfeas, None, None, None, None, None
+
+
 class qNoisyExpectedHypervolumeImprovement(qExpectedHypervolumeImprovement):
     """MC q-noisy expected hypervolume improvement (acquisition/multi_objective/
     monte_carlo.py:325-468; NoisyExpectedHypervolumeMixin,
@@ -1463,7 +1608,12 @@ class qNoisyExpectedHypervolumeImprovement(qExpectedHypervolumeImprovement):
     (without incremental_nehvi, the hypervolume they add to every sample's
     front, mean_s (HV_s - HV0_s)+, is carried in prev_nehvi); up to max_iep, or
     all of them without cache_pending, are appended to every forward's q-batch
-    (concatenate_pending_points)."""
+    (concatenate_pending_points).
+
+    Outcome constraints (hypervolume.py:725-767): roots and base samples cover
+    all Mt members; every sample's decomposition is built from its strictly
+    feasible baseline points in objective space (pending points that join the
+    baseline included), the new points are weighted softly as in qEHVI."""
 
     _default_sample_shape = torch.Size([128])
 
@@ -1477,21 +1627,20 @@ class qNoisyExpectedHypervolumeImprovement(qExpectedHypervolumeImprovement):
         if X_baseline.ndim > 2:
             raise UnsupportedError("NoisyExpectedHypervolumeMixin does not support batched "
                                    f"X_baseline. Expected 2 dims, got {X_baseline.ndim}.")
-        if constraints is not None:
-            raise UnsupportedError("outcome constraints are not on the accelerated path")
         models = getattr(model, "models", None)
         if models is None or not all(hasattr(mm, "prediction_cache") for mm in models):
             raise UnsupportedError("qNEHVI here runs on a ModelListGP of SingleTaskGPs")
-        if len(models) != len(ref_point):
-            raise ValueError("The length of the reference point must match the number of outcomes.")
         AcquisitionFunction.__init__(self, model)
+        _init_outcome_constraints(self, len(models), objective, constraints, eta, fat,
+                                  len(ref_point))
+        if len(self._out_idx) != len(ref_point):
+            raise ValueError("The length of the reference point must match the number of outcomes.")
         self.sampler = sampler
         self.objective = objective if objective is not None else IdentityMCMultiOutputObjective()
         if not isinstance(self.objective, IdentityMCMultiOutputObjective):
             raise UnsupportedError("only the identity multi-output objective is accelerated")
         self.posterior_transform = None
         self.ref_point = torch.as_tensor(ref_point, dtype=torch.float64, device=X_baseline.device)
-        self.fat = fat
         self.alpha = alpha
         self.cache_pending = bool(cache_pending)
         self._max_iep = int(max_iep)
@@ -1499,7 +1648,10 @@ class qNoisyExpectedHypervolumeImprovement(qExpectedHypervolumeImprovement):
         self._cache_root = bool(cache_root)
         self.X_pending = None
         if prune_baseline:
-            X_baseline = prune_inferior_points_multi_objective(model, X_baseline, self.ref_point)
+            X_baseline = prune_inferior_points_multi_objective(
+                model, X_baseline, self.ref_point,
+                objective=self.objective if self._weighted else None,
+                constraints=self.constraints, marginalize_dim=marginalize_dim)
         self._X_baseline = X_baseline
         self._X_baseline_and_pending = X_baseline
         self._partitioned = False
@@ -1572,6 +1724,21 @@ class qNoisyExpectedHypervolumeImprovement(qExpectedHypervolumeImprovement):
         if not all(rt.fused_ready for rt in self._roots):
             raise UnsupportedError(f"qNEHVI here needs d <= {kernels.DP}")
         Y = torch.stack([rt.samples for rt in self._roots], dim=-1).cpu()  # S x r x m
+        self.baseline_samples = Y
+        if self._weighted:
+            # hypervolume.py:725-767: every sample's decomposition is built from
+            # its feasible baseline points (the hard, strict indicator of the
+            # samples of all members) in objective space.  The host
+            # decomposition keeps only the points strictly above the reference
+            # point, so an infeasible row overwritten with the reference point
+            # is dropped: exactly the cells of the filtered set.
+            obj = Y[..., self._out_idx].clone()
+            if self.constraints is not None:
+                feas = compute_feasibility_indicator(self.constraints, Y)     # S x r
+                obj[~feas] = self.ref_point.cpu()
+            Y = obj
+            m = Y.shape[-1]
+        self._baseline_obj = Y
         if self.alpha > 0 and m > 2:  # NondominatedPartitioning(alpha); m = 2 is exact there
             lo, hi = kernels.nd_partition_host(Y, self.ref_point.cpu(), alpha=self.alpha)
         else:
@@ -1579,9 +1746,9 @@ class qNoisyExpectedHypervolumeImprovement(qExpectedHypervolumeImprovement):
         self.cell_lower_bounds = lo.to(Xb.device)
         self.cell_upper_bounds = hi.to(Xb.device)
         self._cells = (self.cell_lower_bounds, self.cell_upper_bounds)
-        self.baseline_samples = Y
         self._zq = {}
         if not self._partitioned and not self.incremental_nehvi:
+            # _compute_initial_hvs (:654-678): the feasible points' hypervolume
             self._initial_hvs = dominated_hypervolume(Y, self.ref_point.cpu()).to(self.ref_point)
         self._partitioned = True
 
@@ -1589,7 +1756,7 @@ class qNoisyExpectedHypervolumeImprovement(qExpectedHypervolumeImprovement):
     def _hypervolumes(self) -> torch.Tensor:
         """hypervolume.py:824-835: every sample's hypervolume over the current
         baseline, from its cells (non_dominated.py:445-457)."""
-        return cells_hypervolume(self.baseline_samples, self.ref_point.cpu(),
+        return cells_hypervolume(self._baseline_obj, self.ref_point.cpu(),
                                  self.cell_lower_bounds.cpu(),
                                  self.cell_upper_bounds.cpu()).to(self.ref_point)
 
@@ -1642,6 +1809,19 @@ class qNoisyExpectedHypervolumeImprovement(qExpectedHypervolumeImprovement):
             Fs.append(F.reshape(Zb.shape[0], B * q))
         Zq = self._base_samples_q(q, X3.device)
         lo, hi = self._cells
+        if self._weighted:
+            mean, L, F = torch.stack(means), torch.stack(Ls), torch.stack(Fs)
+            S, Mt = Zq.shape[0], len(means)
+            if self.constraints is None:
+                w = torch.ones(S, B, q, dtype=torch.float64, device=X3.device)
+            else:
+                f = (mean.permute(1, 2, 0).unsqueeze(0)
+                     + torch.einsum("tbpj,sjt->sbpt", L, Zq.reshape(S, q, Mt))
+                     + F.reshape(Mt, S, B, q).permute(1, 2, 3, 0))
+                w = compute_smoothed_feasibility_indicator(self.constraints, f, self.eta.to(f),
+                                                           fat=self.fat).to(torch.float64)
+            return _QEHVIFeasFromRoots.apply(mean, L, F, w.contiguous(), Zq, lo, hi, q,
+                                             tuple(self._out_idx))
         return _QEHVIFromRoots.apply(torch.stack(means), torch.stack(Ls), torch.stack(Fs), Zq,
                                      lo, hi, q)
 

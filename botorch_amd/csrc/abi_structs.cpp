@@ -58,6 +58,10 @@ int bo_qehvi_backward_ext(int B, int q, int m, const double* mean, const double*
                           const double* dacq, double* dmean, double* dL, double* dF, double* work,
                           int64_t work_elems, void* stream);
 
+// the weighted qEHVI launches (qehvi.hip)
+int bo_qehvi_feas_impl(const BoQehviFeasArgs* a, void* stream);
+int bo_qehvi_feas_backward_impl(const BoQehviFeasArgs* a, void* stream);
+
 int bo_post_partials_v(const BoPostPartialsArgs* a, void* stream) {
   if (!header_ok(a, "bo_post_partials_v")) return BO_ERR_ARG;
   return bo_post_partials_layout(a->kind, a->Xq, a->B, a->q, a->d, a->Xt_scaled, a->n, a->U,
@@ -104,6 +108,16 @@ int bo_qehvi_backward_v(const BoQehviArgs* a, void* stream) {
                                a->dacq, a->dmean, a->dL, a->dF, a->work, a->work_elems, stream);
 }
 
+int bo_qehvi_feas_v(const BoQehviFeasArgs* a, void* stream) {
+  if (!header_ok(a, "bo_qehvi_feas_v")) return BO_ERR_ARG;
+  return bo_qehvi_feas_impl(a, stream);
+}
+
+int bo_qehvi_feas_backward_v(const BoQehviFeasArgs* a, void* stream) {
+  if (!header_ok(a, "bo_qehvi_feas_backward_v")) return BO_ERR_ARG;
+  return bo_qehvi_feas_backward_impl(a, stream);
+}
+
 int bo_lbfgs_step_v(const BoLbfgsStepArgs* a, void* stream) {
   if (!header_ok(a, "bo_lbfgs_step_v")) return BO_ERR_ARG;
   return bo_lbfgs_step(a->B, a->n, a->m, a->x, a->f, a->g, a->xt, a->ft, a->gt, a->d, a->alpha,
@@ -128,6 +142,7 @@ extern "C" int64_t bo_struct_size(const char* name) {
   if (s == "BoQmcBackwardArgs") return sizeof(BoQmcBackwardArgs);
   if (s == "BoPostBackwardArgs") return sizeof(BoPostBackwardArgs);
   if (s == "BoQehviArgs") return sizeof(BoQehviArgs);
+  if (s == "BoQehviFeasArgs") return sizeof(BoQehviFeasArgs);
   if (s == "BoLbfgsStepArgs") return sizeof(BoLbfgsStepArgs);
   if (s == "BoLbfgsbArgs") return sizeof(BoLbfgsbArgs);
   return -1;

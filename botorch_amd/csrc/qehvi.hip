@@ -25,6 +25,7 @@
 #include <cstdlib>
 
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
@@ -47,6 +48,44 @@ struct QehviExt {
   int Qp;
 };
 
+// FEAS (the feasibility-weighted variant, outcome constraints: reference
+// monte_carlo.py:245-251, 303-309): every subset term carries the product of
+// its points' weights feas[s][b][p] (S x B x q).  The model list has Mt >= M
+// members; objective t is member oi(t) of the stacked mean / L / F, and reads
+// column j zm + oi(t) of a base-sample row zld doubles wide, so the
+// constrained callers gather nothing.  The unweighted instantiations take
+// QehviExt and compile to what they were before the variant existed.
+struct QehviExtFeas : QehviExt {
+  const double* feas;
+  double* dfeas;
+  int zm, zld;
+  unsigned oi;  // member of objective t in bits [8 t, 8 t + 8)
+};
+
+template <bool FEAS>
+using QehviExtOf = std::conditional_t<FEAS, QehviExtFeas, QehviExt>;
+
+template <bool FEAS, class E>
+__device__ __forceinline__ int member_of(const E& ex, int t) {
+  if constexpr (FEAS) return (int)((ex.oi >> (8 * t)) & 0xffu);
+  else return t;
+}
+
+template <int M>
+__device__ __forceinline__ double sample_value_feas(int B, int b, int q, int p, int t, int s,
+                                                    const double* __restrict__ mean,
+                                                    const double* __restrict__ L,
+                                                    const double* __restrict__ Z,
+                                                    const QehviExtFeas& ex) {
+  const int mt = member_of<true>(ex, t);
+  const double* Lt = L + (((int64_t)mt * B + b) * q + p) * q;
+  const double* zs = Z + (int64_t)s * ex.zld + mt;
+  double v = mean[((int64_t)mt * B + b) * q + p];
+  if (ex.F) v += ex.F[mt * ex.sF + (int64_t)s * ex.ldF + (int64_t)b * ex.Qp + p];
+  for (int j = 0; j <= p; ++j) v = fma(Lt[j], zs[j * ex.zm], v);
+  return v;
+}
+
 template <int M>
 __device__ __forceinline__ double sample_value(int B, int b, int q, int p, int t, int s,
                                                const double* __restrict__ mean,
@@ -66,11 +105,11 @@ constexpr int LDS_CELL_DOUBLES = 2048;  // K * M <= 1024 (C4: 294 x 3)
 
 // QB: the q bucket (4, 8 or QMAX) the per-point arrays are sized for -- the
 // backward's a / gacc arrays at QMAX spilled to scratch (300-400 B per lane).
-template <int M, int NT = FWD_THREADS, bool CELLS_LDS = false, int QB = QMAX>
+template <int M, int NT = FWD_THREADS, bool CELLS_LDS = false, int QB = QMAX, bool FEAS = false>
 __global__ __launch_bounds__(NT) void qehvi_kernel(
     int B, int q, const double* __restrict__ mean, const double* __restrict__ L,
     const double* __restrict__ Z, int S, const double* __restrict__ lo,
-    const double* __restrict__ hi, int K, QehviExt ex, double* __restrict__ acq, int H = 1,
+    const double* __restrict__ hi, int K, QehviExtOf<FEAS> ex, double* __restrict__ acq, int H = 1,
     double* __restrict__ part = nullptr) {
   // H > 1: the t-batch's samples are split over H workgroups (C4's 128
   // t-batches would leave half the CUs idle); workgroup h sums the samples
@@ -85,8 +124,10 @@ __global__ __launch_bounds__(NT) void qehvi_kernel(
   const int tid = threadIdx.x;
   const int per_sample = q * M;
   // a chunk's samples, then their per-objective maxima over the points
-  const int chunk = LDS_SAMPLES_DOUBLES / (per_sample + M);
+  // (FEAS: then the points' weights)
+  const int chunk = LDS_SAMPLES_DOUBLES / (per_sample + M + (FEAS ? q : 0));
   double* const fmx = f + chunk * per_sample;
+  double* const wq = fmx + chunk * M;
   if constexpr (CELLS_LDS) {
     for (int e = tid; e < K * M; e += NT) {
       cells[e] = lo[e];
@@ -99,7 +140,12 @@ __global__ __launch_bounds__(NT) void qehvi_kernel(
     __syncthreads();
     for (int e = tid; e < ns * per_sample; e += NT) {
       const int s = e / per_sample;
-      f[e] = sample_value<M>(B, b, q, (e / M) % q, e % M, s0 + s, mean, L, Z, ex);
+      if constexpr (FEAS) f[e] = sample_value_feas<M>(B, b, q, (e / M) % q, e % M, s0 + s, mean, L, Z, ex);
+      else f[e] = sample_value<M>(B, b, q, (e / M) % q, e % M, s0 + s, mean, L, Z, ex);
+    }
+    if constexpr (FEAS) {
+      for (int e = tid; e < ns * q; e += NT)
+        wq[e] = ex.feas[((int64_t)(s0 + e / q) * B + b) * q + e % q];
     }
     __syncthreads();
     for (int e = tid; e < ns * M; e += NT) {
@@ -142,16 +188,19 @@ __global__ __launch_bounds__(NT) void qehvi_kernel(
         if (ok) act |= 1u << p;
       }
       double cell = 0.0;
+      const double* ws = wq + s * q;
       for (unsigned sub = act; sub; sub = (sub - 1) & act) {
         double mn[M];
+        double vol = 1.0;  // FEAS: the subset's weight product first
 #pragma unroll
         for (int t = 0; t < M; ++t) mn[t] = INFINITY;
 #pragma unroll
         for (int p = 0; p < QB; ++p)
-          if (sub & (1u << p))
+          if (sub & (1u << p)) {
 #pragma unroll
             for (int t = 0; t < M; ++t) mn[t] = fmin(mn[t], a[p][t]);
-        double vol = 1.0;
+            if constexpr (FEAS) vol *= ws[p];
+          }
 #pragma unroll
         for (int t = 0; t < M; ++t) vol *= mn[t];
         cell += (__popc(sub) & 1) ? vol : -vol;
@@ -190,11 +239,17 @@ __global__ __launch_bounds__(64) void qehvi_part_reduce_kernel(const double* __r
 // CELLS_LDS (shared cells, K m <= LDS_CELL_DOUBLES / 2): the cells staged in
 // LDS once; the chunk's base samples are staged in LDS always (read by the
 // sample values and again by the dmean / dL sums).
-template <int M, int NT = BWD_THREADS, int QB = QMAX, bool CELLS_LDS = false>
+// FEAS: the df terms carry the subset's weight product, and
+//   dfeas[s][b][p] = dacq_b / S sum_k sum_{T containing p} sign vol_T prod_{p' in T, p' != p} w_p'
+// with that product formed from the prefix and suffix products over the subset
+// (no division: exact where a weight is 0 or 1), summed over the cells by the
+// same fixed 16-lane butterfly.  dmean / dL / dF are written at the objective
+// members' slices only.
+template <int M, int NT = BWD_THREADS, int QB = QMAX, bool CELLS_LDS = false, bool FEAS = false>
 __global__ __launch_bounds__(NT) void qehvi_backward_kernel(
     int B, int q, const double* __restrict__ mean, const double* __restrict__ L,
     const double* __restrict__ Z, int S, const double* __restrict__ lo,
-    const double* __restrict__ hi, int K, QehviExt ex, const double* __restrict__ dacq,
+    const double* __restrict__ hi, int K, QehviExtOf<FEAS> ex, const double* __restrict__ dacq,
     double* __restrict__ dmean, double* __restrict__ dL, double* __restrict__ dF, int H = 1,
     double* __restrict__ part = nullptr) {
   // H > 1: samples split over H workgroups as in qehvi_kernel; workgroup h
@@ -211,8 +266,9 @@ __global__ __launch_bounds__(NT) void qehvi_backward_kernel(
   const int tid = threadIdx.x;
   const int per_sample = q * M;
   // a chunk's samples (then their per-objective maxima over the points in f)
-  const int chunk = CH / (per_sample + M);
+  const int chunk = CH / (per_sample + M + (FEAS ? q : 0));
   double* const fmx = f + chunk * per_sample;
+  double* const wq = fmx + chunk * M;  // FEAS: the points' weights
   const double g = dacq[b] / (double)S;
   // entries owned by this thread: (t, p, j) with j <= p (j == p + 1 -> dmean)
   const int nent = M * q * (q + 3) / 2;
@@ -226,15 +282,26 @@ __global__ __launch_bounds__(NT) void qehvi_backward_kernel(
   for (int s0 = sbeg; s0 < send; s0 += chunk) {
     const int ns = min(chunk, send - s0);
     __syncthreads();
-    for (int e = tid; e < ns * per_sample; e += NT) zc[e] = Z[(int64_t)s0 * per_sample + e];
+    if constexpr (FEAS) {
+      // the objective members' columns gathered into the unweighted layout
+      for (int e = tid; e < ns * per_sample; e += NT) {
+        const int s = e / per_sample, r = e % per_sample;
+        zc[e] = Z[(int64_t)(s0 + s) * ex.zld + (r / M) * ex.zm + member_of<true>(ex, r % M)];
+      }
+      for (int e = tid; e < ns * q; e += NT)
+        wq[e] = ex.feas[((int64_t)(s0 + e / q) * B + b) * q + e % q];
+    } else {
+      for (int e = tid; e < ns * per_sample; e += NT) zc[e] = Z[(int64_t)s0 * per_sample + e];
+    }
     __syncthreads();
     for (int e = tid; e < ns * per_sample; e += NT) {
       // sample_value with the base samples from LDS (the same sum, in order)
       const int s = e / per_sample, p = (e / M) % q, t = e % M;
-      const double* Lt = L + (((int64_t)t * B + b) * q + p) * q;
+      const int mt = member_of<FEAS>(ex, t);
+      const double* Lt = L + (((int64_t)mt * B + b) * q + p) * q;
       const double* zs = zc + s * per_sample;
-      double v = mean[((int64_t)t * B + b) * q + p];
-      if (ex.F) v += ex.F[t * ex.sF + (int64_t)(s0 + s) * ex.ldF + (int64_t)b * ex.Qp + p];
+      double v = mean[((int64_t)mt * B + b) * q + p];
+      if (ex.F) v += ex.F[mt * ex.sF + (int64_t)(s0 + s) * ex.ldF + (int64_t)b * ex.Qp + p];
       for (int j = 0; j <= p; ++j) v = fma(Lt[j], zs[j * M + t], v);
       f[e] = v;
     }
@@ -256,6 +323,12 @@ __global__ __launch_bounds__(NT) void qehvi_backward_kernel(
       for (int p = 0; p < QB; ++p)
 #pragma unroll
         for (int t = 0; t < M; ++t) gacc[p][t] = 0.0;
+      double gw[FEAS ? QB : 1];
+      const double* ws = wq + s * q;
+      if constexpr (FEAS) {
+#pragma unroll
+        for (int p = 0; p < QB; ++p) gw[p] = 0.0;
+      }
       for (int k = tid % GROUP; k < K; k += GROUP) {
         double l[M], u[M];
         const int64_t co = (int64_t)(s0 + s) * ex.cstride + (int64_t)k * M;
@@ -298,7 +371,26 @@ __global__ __launch_bounds__(NT) void qehvi_backward_kernel(
                   mn[t] = a[p][t];
                   am[t] = p;
                 }
-          const double sg = (__popc(sub) & 1) ? 1.0 : -1.0;
+          double sg = (__popc(sub) & 1) ? 1.0 : -1.0;
+          if constexpr (FEAS) {
+            double pre[QB];
+            double wT = 1.0, vol = sg, suf = 1.0;
+#pragma unroll
+            for (int t = 0; t < M; ++t) vol *= mn[t];
+#pragma unroll
+            for (int p = 0; p < QB; ++p)
+              if (sub & (1u << p)) {
+                pre[p] = wT;
+                wT *= ws[p];
+              }
+#pragma unroll
+            for (int p = QB - 1; p >= 0; --p)
+              if (sub & (1u << p)) {
+                gw[p] = fma(vol, pre[p] * suf, gw[p]);
+                suf *= ws[p];
+              }
+            sg *= wT;
+          }
 #pragma unroll
           for (int t = 0; t < M; ++t) {
             double o = sg;
@@ -323,12 +415,22 @@ __global__ __launch_bounds__(NT) void qehvi_backward_kernel(
           if (tid % GROUP == 0) df[s * per_sample + p * M + t] = v;
         }
       }
+      if constexpr (FEAS) {
+#pragma unroll
+        for (int p = 0; p < QB; ++p) {
+          if (p >= q) break;
+          double v = gw[p];
+#pragma unroll
+          for (int o = GROUP / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, GROUP);
+          if (tid % GROUP == 0) ex.dfeas[((int64_t)(s0 + s) * B + b) * q + p] = g * v;
+        }
+      }
     }
     __syncthreads();
     if (dF) {  // cotangent of the cached-root baseline term (rows b * Qp + p)
       for (int e = tid; e < ns * per_sample; e += NT) {
         const int s = e / per_sample, p = (e / M) % q, t = e % M;
-        dF[t * ex.sF + (int64_t)(s0 + s) * ex.ldF + (int64_t)b * ex.Qp + p] = g * df[e];
+        dF[member_of<FEAS>(ex, t) * ex.sF + (int64_t)(s0 + s) * ex.ldF + (int64_t)b * ex.Qp + p] = g * df[e];
       }
     }
     for (int w = 0; w < 2; ++w) {
@@ -371,26 +473,34 @@ __global__ __launch_bounds__(NT) void qehvi_backward_kernel(
     }
     const int j = r;
     const double v = g * accv[w];
+    const int mt = member_of<FEAS>(ex, t);
     if (j <= p) {
-      double* dLt = dL + (((int64_t)t * B + b) * q + p) * q;
+      double* dLt = dL + (((int64_t)mt * B + b) * q + p) * q;
       dLt[j] = v;
     } else {
-      dmean[((int64_t)t * B + b) * q + p] = v;
+      dmean[((int64_t)mt * B + b) * q + p] = v;
     }
   }
   // strict upper triangle of dL
   for (int e = tid; e < M * q * q; e += NT) {
     const int t = e / (q * q), p = (e / q) % q, j = e % q;
-    if (j > p) dL[(((int64_t)t * B + b) * q + p) * q + j] = 0.0;
+    if (j > p) dL[(((int64_t)member_of<FEAS>(ex, t) * B + b) * q + p) * q + j] = 0.0;
   }
 }
 
 // Sum of the H sample-split partials of qehvi_backward_kernel (in order), then
 // its output layout: dL lower triangle + dmean, strict upper triangle zero.
+// MAP (the weighted variant only): one packed output map, as QehviExtFeas::oi.
+template <class... MAP>
 __global__ __launch_bounds__(256) void qehvi_backward_reduce_kernel(const double* __restrict__ part,
                                                                     int B, int q, int M, int H,
                                                                     double* __restrict__ dmean,
-                                                                    double* __restrict__ dL) {
+                                                                    double* __restrict__ dL,
+                                                                    MAP... map) {
+  const auto member = [&](int t) {
+    if constexpr (sizeof...(MAP) == 0) return t;
+    else return (int)(((map, ...) >> (8 * t)) & 0xffu);
+  };
   const int b = blockIdx.x;
   const int nent = M * q * (q + 3) / 2;
   const int per_t = q * (q + 3) / 2;
@@ -404,12 +514,12 @@ __global__ __launch_bounds__(256) void qehvi_backward_reduce_kernel(const double
       r -= p + 2;
       ++p;
     }
-    if (r <= p) dL[(((int64_t)t * B + b) * q + p) * q + r] = v;
-    else dmean[((int64_t)t * B + b) * q + p] = v;
+    if (r <= p) dL[(((int64_t)member(t) * B + b) * q + p) * q + r] = v;
+    else dmean[((int64_t)member(t) * B + b) * q + p] = v;
   }
   for (int e = threadIdx.x; e < M * q * q; e += 256) {
     const int t = e / (q * q), p = (e / q) % q, j = e % q;
-    if (j > p) dL[(((int64_t)t * B + b) * q + p) * q + j] = 0.0;
+    if (j > p) dL[(((int64_t)member(t) * B + b) * q + p) * q + j] = 0.0;
   }
 }
 
@@ -590,6 +700,138 @@ extern "C" int bo_qehvi_backward_ext(int B, int q, int m, const double* mean, co
   BO_LAUNCH_CHECK();
   if (H > 1) {
     qehvi_backward_reduce_kernel<<<(unsigned)B, 256, 0, st>>>(work, B, q, m, H, dmean, dL);
+    BO_LAUNCH_CHECK();
+  }
+  return BO_OK;
+}
+
+namespace {
+
+// Arguments shared by the weighted forward and backward: the output map packed
+// for the kernels, or BO_ERR_ARG.
+int feas_ext(const BoQehviFeasArgs* a, const char* who, QehviExtFeas* ex) {
+  BO_CHECK_ARG(a->q >= 1 && a->q <= QMAX, "%s: 1 <= q <= %d (got %d)", who, QMAX, a->q);
+  BO_CHECK_ARG(a->m >= 2 && a->m <= MMAX, "%s: 2 <= m <= %d (got %d)", who, MMAX, a->m);
+  BO_CHECK_ARG(a->S > 0 && a->K >= 0 && a->cell_stride >= 0, "%s: bad S/K/cell_stride", who);
+  BO_CHECK_ARG(a->F == nullptr || (a->Qp >= a->q && a->ldF >= (int64_t)a->B * a->Qp),
+               "%s: bad F layout", who);
+  BO_CHECK_ARG(a->feas != nullptr, "%s: feas is required", who);
+  BO_CHECK_ARG(a->Mt >= a->m && a->Mt <= 255, "%s: m <= Mt <= 255 (got %d)", who, a->Mt);
+  BO_CHECK_ARG(a->zm >= a->Mt && a->zld >= (int64_t)a->q * a->zm,
+               "%s: base samples need zm >= Mt and zld >= q zm", who);
+  unsigned oi = 0;
+  for (int t = 0; t < a->m; ++t) {
+    BO_CHECK_ARG(a->out_idx[t] >= 0 && a->out_idx[t] < a->Mt, "%s: out_idx[%d] = %d outside [0, %d)",
+                 who, t, a->out_idx[t], a->Mt);
+    for (int u = 0; u < t; ++u)
+      BO_CHECK_ARG(a->out_idx[u] != a->out_idx[t], "%s: out_idx must be injective", who);
+    oi |= (unsigned)a->out_idx[t] << (8 * t);
+  }
+  *ex = QehviExtFeas{{a->cell_stride, a->F, a->ldF, a->sF, a->Qp}, a->feas, a->dfeas, a->zm,
+                     (int)a->zld, oi};
+  return BO_OK;
+}
+
+}  // namespace
+
+// bo_qehvi_feas_v / bo_qehvi_feas_backward_v behind their header checks
+// (abi_structs.cpp): the launches of bo_qehvi_ext / bo_qehvi_backward_ext on
+// the weighted instantiations, with the same sample split and buckets.
+extern "C" int bo_qehvi_feas_impl(const BoQehviFeasArgs* a, void* stream) {
+  QehviExtFeas ex;
+  BO_CHECK_ARG(a->zld <= INT32_MAX, "bo_qehvi_feas: zld too large");
+  if (int st = feas_ext(a, "bo_qehvi_feas", &ex); st != BO_OK) return st;
+  BO_CHECK_ARG(a->acq != nullptr, "bo_qehvi_feas: acq is required");
+  const int B = a->B, q = a->q, m = a->m, S = a->S, K = a->K;
+  if (B == 0) return BO_OK;
+  hipStream_t st = as_stream(stream);
+  const bool cl = a->cell_stride == 0 && (int64_t)K * m <= LDS_CELL_DOUBLES / 2;
+  int H = 1;
+  if (a->work != nullptr && a->work_elems >= 2 * (int64_t)B) {
+    H = (int)std::min<int64_t>(std::min(8, std::max(1, 1024 / B)), a->work_elems / B);
+    H = std::max(1, std::min(H, S));
+  }
+  const unsigned grid = (unsigned)((int64_t)B * H);
+#define BO_QF(MM, QQ)                                                                          \
+  if (cl)                                                                                      \
+    qehvi_kernel<MM, FWD_THREADS, true, QQ, true><<<grid, FWD_THREADS, 0, st>>>(               \
+        B, q, a->mean, a->L, a->Z, S, a->cell_lo, a->cell_hi, K, ex, a->acq, H, a->work);      \
+  else                                                                                         \
+    qehvi_kernel<MM, FWD_THREADS, false, QQ, true><<<grid, FWD_THREADS, 0, st>>>(              \
+        B, q, a->mean, a->L, a->Z, S, a->cell_lo, a->cell_hi, K, ex, a->acq, H, a->work)
+#define BO_QFM(MM)          \
+  if (q <= 4) {             \
+    BO_QF(MM, 4);           \
+  } else if (q <= 8) {      \
+    BO_QF(MM, 8);           \
+  } else {                  \
+    BO_QF(MM, QMAX);        \
+  }
+  if (m == 2) {
+    BO_QFM(2);
+  } else if (m == 3) {
+    BO_QFM(3);
+  } else {
+    BO_QFM(4);
+  }
+#undef BO_QFM
+#undef BO_QF
+  BO_LAUNCH_CHECK();
+  if (H > 1) {
+    qehvi_part_reduce_kernel<<<(unsigned)ceil_div(B, 64), 64, 0, st>>>(a->work, B, H, S, a->acq);
+    BO_LAUNCH_CHECK();
+  }
+  return BO_OK;
+}
+
+extern "C" int bo_qehvi_feas_backward_impl(const BoQehviFeasArgs* a, void* stream) {
+  QehviExtFeas ex;
+  BO_CHECK_ARG(a->zld <= INT32_MAX, "bo_qehvi_feas_backward: zld too large");
+  if (int st = feas_ext(a, "bo_qehvi_feas_backward", &ex); st != BO_OK) return st;
+  BO_CHECK_ARG(a->dfeas != nullptr && a->dacq != nullptr && a->dmean != nullptr && a->dL != nullptr,
+               "bo_qehvi_feas_backward: dacq, dmean, dL and dfeas are required");
+  BO_CHECK_ARG((a->F == nullptr) == (a->dF == nullptr), "bo_qehvi_feas_backward: F and dF go together");
+  const int B = a->B, q = a->q, m = a->m, S = a->S, K = a->K;
+  if (B == 0) return BO_OK;
+  hipStream_t st = as_stream(stream);
+  const int64_t nent = (int64_t)m * q * (q + 3) / 2;
+  int H = 1;
+  if (a->work != nullptr && a->work_elems >= 2 * (int64_t)B * nent) {
+    H = (int)std::min<int64_t>(std::min(8, std::max(1, 256 / B)), a->work_elems / ((int64_t)B * nent));
+    H = std::max(1, std::min(H, S));
+  }
+  const unsigned grid = (unsigned)((int64_t)B * H);
+  const bool cl = a->cell_stride == 0 && (int64_t)K * m <= LDS_CELL_DOUBLES / 2;
+#define BO_QB(MM, NT, QQ)                                                                      \
+  if (cl)                                                                                      \
+    qehvi_backward_kernel<MM, NT, QQ, true, true><<<grid, NT, 0, st>>>(                        \
+        B, q, a->mean, a->L, a->Z, S, a->cell_lo, a->cell_hi, K, ex, a->dacq, a->dmean, a->dL, \
+        a->dF, H, a->work);                                                                    \
+  else                                                                                         \
+    qehvi_backward_kernel<MM, NT, QQ, false, true><<<grid, NT, 0, st>>>(                       \
+        B, q, a->mean, a->L, a->Z, S, a->cell_lo, a->cell_hi, K, ex, a->dacq, a->dmean, a->dL, \
+        a->dF, H, a->work)
+#define BO_QBM(MM, NT)        \
+  if (q <= 4) {               \
+    BO_QB(MM, NT, 4);         \
+  } else if (q <= 8) {        \
+    BO_QB(MM, NT, 8);         \
+  } else {                    \
+    BO_QB(MM, NT, QMAX);      \
+  }
+  if (m == 2) {
+    BO_QBM(2, BWD_THREADS);
+  } else if (m == 3) {
+    BO_QBM(3, BWD_THREADS);
+  } else {
+    BO_QBM(4, 256);
+  }
+#undef BO_QBM
+#undef BO_QB
+  BO_LAUNCH_CHECK();
+  if (H > 1) {
+    qehvi_backward_reduce_kernel<<<(unsigned)B, 256, 0, st>>>(a->work, B, q, m, H, a->dmean, a->dL,
+                                                              ex.oi);
     BO_LAUNCH_CHECK();
   }
   return BO_OK;

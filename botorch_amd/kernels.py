@@ -1670,6 +1670,85 @@ def qehvi_backward(mean: torch.Tensor, L: torch.Tensor, Z: torch.Tensor, cell_lo
     return dmean, dL
 
 
+def _qehvi_feas_args(mean, L, Z, cell_lo, cell_hi, feas, out_idx, F, Qp, **extra):
+    """The BoQehviFeasArgs of :func:`qehvi_feas` / :func:`qehvi_feas_backward`:
+    mean Mt x B x q, L Mt x B x q x q, Z S x (q Mt) (all members' base samples,
+    point-major / member-minor), feas S x B x q, out_idx the objectives' members."""
+    Mt, B, q = mean.shape
+    S = Z.shape[0]
+    out_idx = [int(i) for i in out_idx]
+    if not 2 <= len(out_idx) <= 4:
+        raise ValueError(f"qehvi_feas: 2 <= m <= 4 objectives (got {len(out_idx)})")
+    if tuple(feas.shape) != (S, B, q):
+        raise ValueError(f"qehvi_feas: feas must be S x B x q = {(S, B, q)}, got {tuple(feas.shape)}")
+    if L.shape != (Mt, B, q, q) or Z.numel() != S * q * Mt:
+        raise ValueError("qehvi_feas: L must be Mt x B x q x q and Z S x (q Mt)")
+    K, cstride = _cells_layout(cell_lo, S)
+    if cell_lo.shape[-1] != len(out_idx):
+        raise ValueError("qehvi_feas: the cells have one column per objective")
+    Fc = F.contiguous() if F is not None else None
+    if Fc is not None and (Fc.dim() != 3 or Fc.shape[0] != Mt or Fc.shape[1] != S):
+        raise ValueError("qehvi_feas: F must be Mt x S x ldF")
+    a = _lib.QehviFeasArgs(B=B, q=q, m=len(out_idx), S=S, mean=mean.contiguous(), L=L.contiguous(),
+                           Z=Z.reshape(S, q * Mt).contiguous(), cell_lo=cell_lo.contiguous(),
+                           cell_hi=cell_hi.contiguous(), K=K, Qp=Qp, cell_stride=cstride, F=Fc,
+                           ldF=Fc.shape[-1] if Fc is not None else 0,
+                           sF=Fc.shape[-1] * S if Fc is not None else 0,
+                           feas=feas.contiguous(), Mt=Mt, zm=Mt, zld=q * Mt, **extra)
+    for t, i in enumerate(out_idx):
+        a.out_idx[t] = i
+    return a, Fc
+
+
+def qehvi_feas(mean: torch.Tensor, L: torch.Tensor, Z: torch.Tensor, cell_lo: torch.Tensor,
+               cell_hi: torch.Tensor, feas: torch.Tensor, out_idx,
+               F: Optional[torch.Tensor] = None, Qp: int = 0) -> torch.Tensor:
+    """Feasibility-weighted :func:`qehvi` over a model list of Mt members whose
+    objectives are the members ``out_idx``: every inclusion-exclusion term times
+    the product of its points' weights feas[s, b, p] -> acq (B)."""
+    dev = _dev(mean, L, Z, cell_lo, cell_hi, feas)
+    B = mean.shape[1]
+    acq = torch.empty(B, dtype=torch.float64, device=dev)
+    work = torch.empty(8 * B, dtype=torch.float64, device=dev)
+    a, _ = _qehvi_feas_args(mean, L, Z, cell_lo, cell_hi, feas, out_idx, F, Qp, acq=acq, work=work,
+                            work_elems=work.numel())
+    check(lib().bo_qehvi_feas_v(ctypes.byref(a), _stream(dev)), "qehvi_feas")
+    return acq
+
+
+def qehvi_feas_backward(mean: torch.Tensor, L: torch.Tensor, Z: torch.Tensor, cell_lo: torch.Tensor,
+                        cell_hi: torch.Tensor, feas: torch.Tensor, out_idx, dacq: torch.Tensor,
+                        F: Optional[torch.Tensor] = None, Qp: int = 0,
+                        dmean: Optional[torch.Tensor] = None, dL: Optional[torch.Tensor] = None,
+                        dF: Optional[torch.Tensor] = None):
+    """Backward of :func:`qehvi_feas`: -> dmean (Mt x B x q), dL (Mt x B x q x q)
+    [, dF], dfeas (S x B x q).  The kernel writes the objective members' slices
+    of dmean / dL / dF only; the others are zero here, or the caller's where it
+    passes the (contiguous) outputs in."""
+    dev = _dev(mean, L, Z, cell_lo, cell_hi, feas)
+    Mt, B, q = mean.shape
+    m = len(out_idx)
+    f64 = dict(dtype=torch.float64, device=dev)
+    dmean = torch.zeros(Mt, B, q, **f64) if dmean is None else dmean
+    dL = torch.zeros(Mt, B, q, q, **f64) if dL is None else dL
+    if F is not None and dF is None:
+        dF = torch.zeros(F.shape, **f64)
+    for o, shape in ((dmean, (Mt, B, q)), (dL, (Mt, B, q, q)),
+                     (dF, tuple(F.shape) if F is not None else None)):
+        if o is not None and not (o.is_contiguous() and tuple(o.shape) == shape
+                                  and o.dtype == torch.float64 and o.device == dev):
+            raise ValueError(f"qehvi_feas_backward: outputs must be contiguous fp64 of shape {shape}")
+    dfeas = torch.empty(feas.shape, **f64)
+    work = torch.empty(8 * B * m * q * (q + 3) // 2, **f64)
+    a, _ = _qehvi_feas_args(mean, L, Z, cell_lo, cell_hi, feas, out_idx, F, Qp,
+                            dacq=dacq.contiguous(), dmean=dmean, dL=dL, dF=dF, dfeas=dfeas,
+                            work=work, work_elems=work.numel())
+    check(lib().bo_qehvi_feas_backward_v(ctypes.byref(a), _stream(dev)), "qehvi_feas_backward")
+    if F is not None:
+        return dmean, dL, dF, dfeas
+    return dmean, dL, dfeas
+
+
 def kernel_grad(X: torch.Tensor, Y: torch.Tensor, dK: torch.Tensor, lengthscale: torch.Tensor,
                 kind: int, outputscale: float = 1.0, group: int = 0,
                 dX: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -841,6 +841,40 @@ typedef struct BoQehviArgs { /* bo_qehvi and bo_qehvi_backward (d* fields: backw
 int bo_qehvi_v(const BoQehviArgs* a, void* stream);
 int bo_qehvi_backward_v(const BoQehviArgs* a, void* stream);
 
+/* Feasibility-weighted qEHVI (outcome constraints: botorch/acquisition/
+ * multi_objective/monte_carlo.py:245-251, 303-309; qNEHVI,
+ * botorch/utils/multi_objective/hypervolume.py:725-767): every
+ * inclusion-exclusion term of bo_qehvi is multiplied by prod_{p in T}
+ * feas[s][b][p] (feas: S x B x q, the smoothed feasibility indicator of the
+ * samples).  The model list has Mt >= m members, of which objective t is member
+ * out_idx[t] (injective, any order): mean is Mt x B x q, L is Mt x B x q x q, F is
+ * Mt x S x ldF, and objective t reads column j zm + out_idx[t] of a base-sample
+ * row zld doubles wide (zm >= Mt, zld >= q zm), so no caller gathers anything.
+ * The backward writes dmean / dL / dF at the objective members' slices only
+ * (the rest is the caller's) and dfeas (S x B x q), the cotangent of feas,
+ * formed without dividing by a weight. */
+typedef struct BoQehviFeasArgs {
+  BO_STRUCT_HEADER;
+  int32_t B, q, m, S;
+  const double *mean, *L, *Z, *cell_lo, *cell_hi;
+  int32_t K, Qp;
+  int64_t cell_stride;
+  const double* F;
+  int64_t ldF, sF;
+  double* acq;
+  const double* dacq;
+  double *dmean, *dL, *dF;
+  double* work; /* as BoQehviArgs: the sample split's workspace */
+  int64_t work_elems;
+  const double* feas;
+  double* dfeas; /* backward only */
+  int32_t Mt, zm;
+  int64_t zld;
+  int32_t out_idx[4];
+} BoQehviFeasArgs;
+int bo_qehvi_feas_v(const BoQehviFeasArgs* a, void* stream);
+int bo_qehvi_feas_backward_v(const BoQehviFeasArgs* a, void* stream);
+
 typedef struct BoLbfgsStepArgs { /* bo_lbfgs_step */
   BO_STRUCT_HEADER;
   int32_t B, n, m, _pad;
