@@ -229,6 +229,18 @@ class QehviFeasArgs(_Args):
                                      ("zld", c_int64), ("out_idx", c_int32 * 4)]
 
 
+class QlogehviArgs(_Args):
+    _fields_ = _HDR + [("B", c_int32), ("q", c_int32), ("m", c_int32), ("S", c_int32),
+                       ("mean", _D), ("L", _D), ("Z", _D), ("cell_lo", _D), ("cell_hi", _D),
+                       ("K", c_int32), ("Qp", c_int32), ("cell_stride", c_int64), ("F", _D),
+                       ("ldF", c_int64), ("sF", c_int64), ("acq", _D), ("hvi", _D), ("dacq", _D),
+                       ("dmean", _D), ("dL", _D), ("dF", _D), ("work", _D),
+                       ("work_elems", c_int64), ("logw", _D), ("dlogw", _D), ("Mt", c_int32),
+                       ("zm", c_int32), ("zld", c_int64), ("out_idx", c_int32 * 4),
+                       ("fat", c_int32), ("_pad", c_int32), ("tau_relu", c_double),
+                       ("tau_max", c_double)]
+
+
 class LbfgsStepArgs(_Args):
     _fields_ = _HDR + [("B", c_int32), ("n", c_int32), ("m", c_int32), ("_pad", c_int32),
                        ("x", _D), ("f", _D), ("g", _D), ("xt", _D), ("ft", _D), ("gt", _D),
@@ -250,6 +262,7 @@ for _name, _cls in (("bo_post_partials_v", PostPartialsArgs), ("bo_qmc_finalize_
                     ("bo_qmc_backward_v", QmcBackwardArgs), ("bo_post_backward_v", PostBackwardArgs),
                     ("bo_qehvi_v", QehviArgs), ("bo_qehvi_backward_v", QehviArgs),
                     ("bo_qehvi_feas_v", QehviFeasArgs), ("bo_qehvi_feas_backward_v", QehviFeasArgs),
+                    ("bo_qlogehvi_v", QlogehviArgs), ("bo_qlogehvi_backward_v", QlogehviArgs),
                     ("bo_lbfgs_step_v", LbfgsStepArgs), ("bo_lbfgsb_step_v", LbfgsbArgs)):
     _SIGNATURES[_name] = (c_int, [POINTER(_cls), _P])
 _SIGNATURES["bo_struct_size"] = (c_int64, [ctypes.c_char_p])
@@ -257,7 +270,7 @@ _SIGNATURES["bo_post_backward_jobs"] = (c_int, [c_int, POINTER(POINTER(PostBackw
 ARG_RECORDS = {"BoPostPartialsArgs": PostPartialsArgs, "BoQmcFinalizeArgs": QmcFinalizeArgs,
                "BoQmcBackwardArgs": QmcBackwardArgs, "BoPostBackwardArgs": PostBackwardArgs,
                "BoQehviArgs": QehviArgs, "BoQehviFeasArgs": QehviFeasArgs,
-               "BoLbfgsStepArgs": LbfgsStepArgs,
+               "BoQlogehviArgs": QlogehviArgs, "BoLbfgsStepArgs": LbfgsStepArgs,
                "BoLbfgsbArgs": LbfgsbArgs}
 
 _lib = None

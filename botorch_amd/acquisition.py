@@ -26,7 +26,8 @@ from torch import nn
 from . import _lib, kernels
 from .exceptions import (BotorchError, BotorchTensorDimensionError, BotorchWarning, NanError,
                          NotPSDError, UnsupportedError)
-from .safe_math import TAU_MAX, TAU_RELU, fatmax, log_improvement, logmeanexp, smooth_amax
+from .safe_math import (TAU_MAX, TAU_RELU, fatmax, log_improvement, logmeanexp, logplusexp,
+                        smooth_amax)
 from .objective import (ConstrainedMCObjective, GenericMCObjective, IdentityMCObjective,
                         MCAcquisitionObjective, MCObjective, compute_best_feasible_objective,
                         compute_feasibility_indicator, compute_smoothed_feasibility_indicator,
@@ -1022,7 +1023,10 @@ class _FusedQEHVI(torch.autograd.Function):
         # the kernel itself (as the backward below): this Function already is
         # the autograd node, the registered op's wrapper would only add host time
         feas = None
-        if acqf._weighted:
+        ctx.log = None
+        if acqf._log:
+            acq, ctx.log = _log_hvi_forward(acqf, mean, L, Z, lo, hi, None, 0, need_grad)
+        elif acqf._weighted:
             # outcome constraints: the weighted kernel on the objective members
             feas = _feas_weights(acqf, mean, L, Z, None, 0, need_grad)
             acq = kernels.qehvi_feas(mean, L, Z, lo, hi, feas[0].detach(), acqf._out_idx)
@@ -1041,13 +1045,16 @@ class _FusedQEHVI(torch.autograd.Function):
             kernels.raise_not_psd_many(status, "qEHVI posterior root")
         if need_grad:
             ctx.saved, ctx.mean, ctx.L, ctx.Z, ctx.cells = saved, mean, L, Z, (lo, hi)
-            ctx.feas, ctx.out_idx = feas, acqf._out_idx
+            ctx.feas, ctx.out_idx, ctx.acqf = feas, acqf._out_idx, acqf
         return acq
 
     @staticmethod
     def backward(ctx, dacq):
         lo, hi = ctx.cells
-        if ctx.feas is not None:
+        if ctx.log is not None:
+            dmean, dL, _ = _log_hvi_backward(ctx.acqf, ctx.log, ctx.mean, ctx.L, ctx.Z, lo, hi,
+                                             dacq, None, 0)
+        elif ctx.feas is not None:
             dmean, dL, dfeas = kernels.qehvi_feas_backward(ctx.mean, ctx.L, ctx.Z, lo, hi,
                                                            ctx.feas[0].detach(), ctx.out_idx, dacq)
             _feas_backward(ctx.feas, dfeas, dmean, dL, None)
@@ -1140,7 +1147,7 @@ def _init_outcome_constraints(acqf, num_members: int, objective, constraints, et
             raise UnsupportedError("the feasibility-weighted kernels support 2 to 4 objectives")
 
 
-def _feas_weights(acqf, mean, L, Z, F, Qp: int, need_grad: bool):
+def _feas_weights(acqf, mean, L, Z, F, Qp: int, need_grad: bool, log: bool = False):
     """The smoothed feasibility weights w (S x B x q) of the samples
     f = mean + L z (+ F) of ALL members (S x B x q x Mt; the constraint
     callables may read any output), as a differentiable function of detached
@@ -1158,7 +1165,7 @@ def _feas_weights(acqf, mean, L, Z, F, Qp: int, need_grad: bool):
         if F is not None:
             f = f + leaves[2][:, :, : B * Qp].reshape(Mt, S, B, Qp)[..., :q].permute(1, 2, 3, 0)
         w = compute_smoothed_feasibility_indicator(acqf.constraints, f, acqf.eta.to(f),
-                                                   fat=acqf.fat)
+                                                   log=log, fat=acqf.fat)
     return w.to(torch.float64).contiguous(), leaves
 
 
@@ -1193,6 +1200,7 @@ class qExpectedHypervolumeImprovement(MCAcquisitionFunction):
     path's gradient through torch autograd on the small sample tensor."""
 
     _default_sample_shape = torch.Size([128])
+    _log = False  # the log-space subclasses (qLogEHVI, qLogNEHVI) take bo_qlogehvi
 
     def __init__(self, model, ref_point, partitioning, sampler=None, objective=None,
                  constraints=None, X_pending=None, eta=1e-3, fat=False):
@@ -1231,10 +1239,11 @@ class qExpectedHypervolumeImprovement(MCAcquisitionFunction):
             raise UnsupportedError("qEHVI here runs on a ModelListGP of SingleTaskGPs")
         if not isinstance(self.objective, IdentityMCMultiOutputObjective):
             raise UnsupportedError("only the identity multi-output objective is accelerated")
+        _check_log_q(self, q)
         if q > 12 or d > kernels.DP:
             raise UnsupportedError("fused qEHVI supports q <= 12 and d <= 8")
         acq = None
-        if (not self._weighted and not (torch.is_grad_enabled() and X3.requires_grad)
+        if (not self._log and not self._weighted and not (torch.is_grad_enabled() and X3.requires_grad)
                 and X3.dtype == torch.float64):
             acq = _qehvi_members_eager(self, X3)
         if acq is None:
@@ -1390,7 +1399,10 @@ class _FusedQNEHVI(torch.autograd.Function):
         Zq = acqf._base_samples_q(q, X3.device)
         lo, hi = acqf._cells
         feas = None
-        if acqf._weighted:
+        ctx.log = None
+        if acqf._log:
+            acq, ctx.log = _log_hvi_forward(acqf, mean, L, Zq, lo, hi, F, pp.Qp, need_grad)
+        elif acqf._weighted:
             feas = _feas_weights(acqf, mean, L, Zq, F, pp.Qp, need_grad)
             acq = kernels.qehvi_feas(mean, L, Zq, lo, hi, feas[0].detach(), acqf._out_idx, F=F,
                                      Qp=pp.Qp)
@@ -1418,7 +1430,10 @@ class _FusedQNEHVI(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dacq):
         lo, hi = ctx.acqf._cells
-        if ctx.feas is not None:
+        if ctx.log is not None:
+            dmean, dL, dF = _log_hvi_backward(ctx.acqf, ctx.log, ctx.mean, ctx.L, ctx.Zq, lo, hi,
+                                              dacq, ctx.F, ctx.Qp)
+        elif ctx.feas is not None:
             dmean, dL, dF, dfeas = kernels.qehvi_feas_backward(
                 ctx.mean, ctx.L, ctx.Zq, lo, hi, ctx.feas[0].detach(), ctx.acqf._out_idx, dacq,
                 F=ctx.F, Qp=ctx.Qp)
@@ -1578,6 +1593,65 @@ class _QEHVIFeasFromRoots(torch.autograd.Function):
         dmean, dL, dF, dfeas = kernels.qehvi_feas_backward(mean, L, Zq, lo, hi, w, ctx.out_idx,
                                                            dacq.contiguous(), F=F, Qp=ctx.q)
         return dmean, dL, dF, dfeas, None, None, None, None, None
+
+
+def _check_log_q(acqf, q: int) -> None:
+    """The log-space kernels evaluate all 2^q - 1 subsets of every (sample,
+    cell) pair: q <= 8, pending points included."""
+    if acqf._log and q > kernels.QLOGEHVI_QMAX:
+        raise UnsupportedError(f"{type(acqf).__name__} supports q <= {kernels.QLOGEHVI_QMAX} "
+                               f"(pending points included), got q = {q}")
+
+
+def _log_hvi_forward(acqf, mean, L, Z, lo, hi, F, Qp: int, need_grad: bool):
+    """The log-space reduction of _FusedQEHVI / _FusedQNEHVI (bo_qlogehvi) on
+    the members' means and roots: -> (acq, state for _log_hvi_backward).  With
+    outcome constraints the points' log feasibility (logei.py:162-169) is formed
+    in torch from detached leaves, as _feas_weights does for the plain classes."""
+    feas, logw = None, None
+    if acqf.constraints is not None:
+        feas = _feas_weights(acqf, mean, L, Z, F, Qp, need_grad, log=True)
+        logw = feas[0].detach()
+    acq, hvi = kernels.qlogehvi(mean, L, Z, lo, hi, acqf._out_idx, logw, F=F, Qp=Qp, fat=acqf.fat,
+                                tau_relu=acqf.tau_relu, tau_max=acqf.tau_max)
+    # the state keeps an alias of acq, not the Function's output itself (which
+    # would tie the output to its own node)
+    return acq, (acq.detach(), hvi, feas)
+
+
+def _log_hvi_backward(acqf, state, mean, L, Z, lo, hi, dacq, F, Qp: int):
+    """bo_qlogehvi_backward -> dmean, dL, dF (the constraint path's cotangents
+    added through dlogw)."""
+    acq, hvi, feas = state
+    dmean, dL, dF, dlogw = kernels.qlogehvi_backward(
+        mean, L, Z, lo, hi, acq, hvi, dacq, acqf._out_idx,
+        feas[0].detach() if feas is not None else None, F=F, Qp=Qp, fat=acqf.fat,
+        tau_relu=acqf.tau_relu, tau_max=acqf.tau_max)
+    if feas is not None:
+        _feas_backward(feas, dlogw, dmean, dL, dF)
+    return dmean, dL, dF
+
+
+class _QLogEHVIFromRoots(torch.autograd.Function):
+    """_QEHVIFeasFromRoots in log space (bo_qlogehvi): a differentiable
+    function of (mean, L, F, logw); logw may be None."""
+
+    @staticmethod
+    def forward(ctx, mean, L, F, logw, Zq, lo, hi, q, out_idx, fat, tau_relu, tau_max):
+        acq, hvi = kernels.qlogehvi(mean, L, Zq, lo, hi, out_idx, logw, F=F, Qp=q, fat=fat,
+                                    tau_relu=tau_relu, tau_max=tau_max)
+        ctx.save_for_backward(mean, L, F, logw, Zq, lo, hi, acq, hvi)
+        ctx.opts = (q, out_idx, fat, tau_relu, tau_max)
+        return acq
+
+    @staticmethod
+    def backward(ctx, dacq):
+        mean, L, F, logw, Zq, lo, hi, acq, hvi = ctx.saved_tensors
+        q, out_idx, fat, tau_relu, tau_max = ctx.opts
+        dmean, dL, dF, dlogw = kernels.qlogehvi_backward(
+            mean, L, Zq, lo, hi, acq, hvi, dacq.contiguous(), out_idx, logw, F=F, Qp=q, fat=fat,
+            tau_relu=tau_relu, tau_max=tau_max)
+        return (dmean, dL, dF, dlogw) + (None,) * 8
 
 
 class qNoisyExpectedHypervolumeImprovement(qExpectedHypervolumeImprovement):
@@ -1774,6 +1848,7 @@ class qNoisyExpectedHypervolumeImprovement(qExpectedHypervolumeImprovement):
         X = self._concat_pending(t_batch_mode(X))
         batch = X.shape[:-2]
         q, d = X.shape[-2], X.shape[-1]
+        _check_log_q(self, q)
         if q > 12 or d > kernels.DP or not X.is_cuda:
             raise UnsupportedError(f"fused qNEHVI supports q <= 12 (pending points included) "
                                    f"and d <= {kernels.DP} on the device")
@@ -1782,6 +1857,11 @@ class qNoisyExpectedHypervolumeImprovement(qExpectedHypervolumeImprovement):
             acq = _FusedQNEHVI.apply(X3, self)
         else:
             acq = self._joint_forward(X3)
+        if self._log:
+            if self.incremental_nehvi:
+                return acq.reshape(batch)
+            # logei.py:471: the pending points' hypervolume joins in log space
+            return logplusexp(acq.reshape(batch), self._prev_nehvi.to(acq).log())
         return acq.reshape(batch) + self._prev_nehvi.to(acq)
 
     def _joint_forward(self, X3: torch.Tensor) -> torch.Tensor:
@@ -1809,6 +1889,19 @@ class qNoisyExpectedHypervolumeImprovement(qExpectedHypervolumeImprovement):
             Fs.append(F.reshape(Zb.shape[0], B * q))
         Zq = self._base_samples_q(q, X3.device)
         lo, hi = self._cells
+        if self._log:
+            mean, L, F = torch.stack(means), torch.stack(Ls), torch.stack(Fs)
+            S, Mt = Zq.shape[0], len(means)
+            logw = None
+            if self.constraints is not None:
+                f = (mean.permute(1, 2, 0).unsqueeze(0)
+                     + torch.einsum("tbpj,sjt->sbpt", L, Zq.reshape(S, q, Mt))
+                     + F.reshape(Mt, S, B, q).permute(1, 2, 3, 0))
+                logw = compute_smoothed_feasibility_indicator(
+                    self.constraints, f, self.eta.to(f), log=True,
+                    fat=self.fat).to(torch.float64).contiguous()
+            return _QLogEHVIFromRoots.apply(mean, L, F, logw, Zq, lo, hi, q, tuple(self._out_idx),
+                                            self.fat, self.tau_relu, self.tau_max)
         if self._weighted:
             mean, L, F = torch.stack(means), torch.stack(Ls), torch.stack(Fs)
             S, Mt = Zq.shape[0], len(means)
@@ -1824,6 +1917,54 @@ class qNoisyExpectedHypervolumeImprovement(qExpectedHypervolumeImprovement):
                                              tuple(self._out_idx))
         return _QEHVIFromRoots.apply(torch.stack(means), torch.stack(Ls), torch.stack(Fs), Zq,
                                      lo, hi, q)
+
+
+class qLogExpectedHypervolumeImprovement(qExpectedHypervolumeImprovement):
+    """MC qLogEHVI (acquisition/multi_objective/logei.py:48-317): the expected
+    hypervolume improvement with every clamp and minimum replaced by a smooth,
+    (with ``fat``) fat-tailed one, evaluated in log space, so the value stays
+    finite and the gradient informative where plain qEHVI is exactly zero.
+
+    Everything up to the reduction is qExpectedHypervolumeImprovement's (the
+    members' posteriors and roots, pending points, outcome constraints with
+    the log smoothed feasibility); the reduction is bo_qlogehvi /
+    bo_qlogehvi_backward over all subsets of the q <= 8 points (pending points
+    included).  The defaults are the reference's (logei.py:54-67)."""
+
+    _log = True
+
+    def __init__(self, model, ref_point, partitioning, sampler=None, objective=None,
+                 constraints=None, X_pending=None, eta=1e-2, fat=True,
+                 tau_relu: float = TAU_RELU, tau_max: float = TAU_MAX):
+        tau_relu, tau_max = _check_tau(tau_relu, "tau_relu"), _check_tau(tau_max, "tau_max")
+        super().__init__(model, ref_point, partitioning, sampler=sampler, objective=objective,
+                         constraints=constraints, X_pending=X_pending, eta=eta, fat=fat)
+        self.tau_relu, self.tau_max = tau_relu, tau_max
+
+
+class qLogNoisyExpectedHypervolumeImprovement(qNoisyExpectedHypervolumeImprovement):
+    """MC qLogNEHVI (acquisition/multi_objective/logei.py:320-471):
+    qNoisyExpectedHypervolumeImprovement's cached baseline roots, per-sample box
+    decompositions and pending-point handling, with qLogEHVI's log-space
+    reduction (bo_qlogehvi over the per-sample cells, whose padding cells are
+    skipped).  Without incremental_nehvi the pending points' hypervolume joins
+    as logplusexp(value, log prev_nehvi) (:471).  The defaults are the
+    reference's (:327-347)."""
+
+    _log = True
+
+    def __init__(self, model, ref_point, X_baseline, sampler=None, objective=None,
+                 constraints=None, X_pending=None, eta=1e-3, prune_baseline=False, alpha=0.0,
+                 cache_pending=True, max_iep=0, incremental_nehvi=True, cache_root=True,
+                 tau_relu: float = TAU_RELU, tau_max: float = 1e-3, fat=True,
+                 marginalize_dim=None):
+        tau_relu, tau_max = _check_tau(tau_relu, "tau_relu"), _check_tau(tau_max, "tau_max")
+        super().__init__(model, ref_point, X_baseline, sampler=sampler, objective=objective,
+                         constraints=constraints, X_pending=X_pending, eta=eta, fat=fat,
+                         prune_baseline=prune_baseline, alpha=alpha, cache_pending=cache_pending,
+                         max_iep=max_iep, incremental_nehvi=incremental_nehvi,
+                         cache_root=cache_root, marginalize_dim=marginalize_dim)
+        self.tau_relu, self.tau_max = tau_relu, tau_max
 
 
 def cells_hypervolume(Y: torch.Tensor, ref: torch.Tensor, lo: torch.Tensor,

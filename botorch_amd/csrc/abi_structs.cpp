@@ -62,6 +62,10 @@ int bo_qehvi_backward_ext(int B, int q, int m, const double* mean, const double*
 int bo_qehvi_feas_impl(const BoQehviFeasArgs* a, void* stream);
 int bo_qehvi_feas_backward_impl(const BoQehviFeasArgs* a, void* stream);
 
+// the log-space qEHVI launches (qlogehvi.hip)
+int bo_qlogehvi_impl(const BoQlogehviArgs* a, void* stream);
+int bo_qlogehvi_backward_impl(const BoQlogehviArgs* a, void* stream);
+
 int bo_post_partials_v(const BoPostPartialsArgs* a, void* stream) {
   if (!header_ok(a, "bo_post_partials_v")) return BO_ERR_ARG;
   return bo_post_partials_layout(a->kind, a->Xq, a->B, a->q, a->d, a->Xt_scaled, a->n, a->U,
@@ -118,6 +122,16 @@ int bo_qehvi_feas_backward_v(const BoQehviFeasArgs* a, void* stream) {
   return bo_qehvi_feas_backward_impl(a, stream);
 }
 
+int bo_qlogehvi_v(const BoQlogehviArgs* a, void* stream) {
+  if (!header_ok(a, "bo_qlogehvi_v")) return BO_ERR_ARG;
+  return bo_qlogehvi_impl(a, stream);
+}
+
+int bo_qlogehvi_backward_v(const BoQlogehviArgs* a, void* stream) {
+  if (!header_ok(a, "bo_qlogehvi_backward_v")) return BO_ERR_ARG;
+  return bo_qlogehvi_backward_impl(a, stream);
+}
+
 int bo_lbfgs_step_v(const BoLbfgsStepArgs* a, void* stream) {
   if (!header_ok(a, "bo_lbfgs_step_v")) return BO_ERR_ARG;
   return bo_lbfgs_step(a->B, a->n, a->m, a->x, a->f, a->g, a->xt, a->ft, a->gt, a->d, a->alpha,
@@ -143,6 +157,7 @@ extern "C" int64_t bo_struct_size(const char* name) {
   if (s == "BoPostBackwardArgs") return sizeof(BoPostBackwardArgs);
   if (s == "BoQehviArgs") return sizeof(BoQehviArgs);
   if (s == "BoQehviFeasArgs") return sizeof(BoQehviFeasArgs);
+  if (s == "BoQlogehviArgs") return sizeof(BoQlogehviArgs);
   if (s == "BoLbfgsStepArgs") return sizeof(BoLbfgsStepArgs);
   if (s == "BoLbfgsbArgs") return sizeof(BoLbfgsbArgs);
   return -1;

@@ -1749,6 +1749,92 @@ def qehvi_feas_backward(mean: torch.Tensor, L: torch.Tensor, Z: torch.Tensor, ce
     return dmean, dL, dfeas
 
 
+QLOGEHVI_QMAX = 8  # the fused log-space route: all 2^q - 1 subsets, no zero-skip
+
+
+def _qlogehvi_args(mean, L, Z, cell_lo, cell_hi, out_idx, logw, F, Qp, fat, tau_relu, tau_max,
+                   **extra):
+    """The BoQlogehviArgs of :func:`qlogehvi` / :func:`qlogehvi_backward`: the
+    tensor conventions of :func:`qehvi_feas` (mean Mt x B x q, L Mt x B x q x q,
+    Z S x (q Mt), cells K x m or S x K x m, F Mt x S x ldF), logw S x B x q or
+    None, out_idx the objectives' members (None: all Mt, in order)."""
+    Mt, B, q = mean.shape
+    S = Z.shape[0]
+    out_idx = list(range(Mt)) if out_idx is None else [int(i) for i in out_idx]
+    if not 2 <= len(out_idx) <= 4:
+        raise ValueError(f"qlogehvi: 2 <= m <= 4 objectives (got {len(out_idx)})")
+    if not 1 <= q <= QLOGEHVI_QMAX:
+        raise ValueError(f"qlogehvi: 1 <= q <= {QLOGEHVI_QMAX} (got {q})")
+    if logw is not None and tuple(logw.shape) != (S, B, q):
+        raise ValueError(f"qlogehvi: logw must be S x B x q = {(S, B, q)}, got {tuple(logw.shape)}")
+    if L.shape != (Mt, B, q, q) or Z.numel() != S * q * Mt:
+        raise ValueError("qlogehvi: L must be Mt x B x q x q and Z S x (q Mt)")
+    K, cstride = _cells_layout(cell_lo, S)
+    if cell_lo.shape[-1] != len(out_idx) or cell_hi.shape != cell_lo.shape:
+        raise ValueError("qlogehvi: the cells have one column per objective")
+    Fc = F.contiguous() if F is not None else None
+    if Fc is not None and (Fc.dim() != 3 or Fc.shape[0] != Mt or Fc.shape[1] != S):
+        raise ValueError("qlogehvi: F must be Mt x S x ldF")
+    a = _lib.QlogehviArgs(B=B, q=q, m=len(out_idx), S=S, mean=mean.contiguous(), L=L.contiguous(),
+                          Z=Z.reshape(S, q * Mt).contiguous(), cell_lo=cell_lo.contiguous(),
+                          cell_hi=cell_hi.contiguous(), K=K, Qp=Qp, cell_stride=cstride, F=Fc,
+                          ldF=Fc.shape[-1] if Fc is not None else 0,
+                          sF=Fc.shape[-1] * S if Fc is not None else 0,
+                          logw=logw.contiguous() if logw is not None else None, Mt=Mt, zm=Mt,
+                          zld=q * Mt, fat=int(bool(fat)), tau_relu=float(tau_relu),
+                          tau_max=float(tau_max), **extra)
+    for t, i in enumerate(out_idx):
+        a.out_idx[t] = i
+    return a, len(out_idx)
+
+
+def qlogehvi(mean: torch.Tensor, L: torch.Tensor, Z: torch.Tensor, cell_lo: torch.Tensor,
+             cell_hi: torch.Tensor, out_idx=None, logw: Optional[torch.Tensor] = None,
+             F: Optional[torch.Tensor] = None, Qp: int = 0, fat: bool = True,
+             tau_relu: float = 1e-6, tau_max: float = 1e-2):
+    """Log-space qEHVI of the samples f = mean + L z (+ F) (bo_qlogehvi, q <= 8)
+    -> (acq (B), the log values; hvi (S x B), every sample's log improvement,
+    which :func:`qlogehvi_backward` takes back)."""
+    dev = _dev(mean, L, Z, cell_lo, cell_hi)
+    B, S = mean.shape[1], Z.shape[0]
+    f64 = dict(dtype=torch.float64, device=dev)
+    acq = torch.empty(B, **f64)
+    hvi = torch.empty(S, B, **f64)
+    work = torch.empty(16 * B, **f64)  # sample split (B < 256): a pair per workgroup
+    a, _ = _qlogehvi_args(mean, L, Z, cell_lo, cell_hi, out_idx, logw, F, Qp, fat, tau_relu,
+                          tau_max, acq=acq, hvi=hvi, work=work, work_elems=work.numel())
+    check(lib().bo_qlogehvi_v(ctypes.byref(a), _stream(dev)), "qlogehvi")
+    return acq, hvi
+
+
+def qlogehvi_backward(mean: torch.Tensor, L: torch.Tensor, Z: torch.Tensor, cell_lo: torch.Tensor,
+                      cell_hi: torch.Tensor, acq: torch.Tensor, hvi: torch.Tensor,
+                      dacq: torch.Tensor, out_idx=None, logw: Optional[torch.Tensor] = None,
+                      F: Optional[torch.Tensor] = None, Qp: int = 0, fat: bool = True,
+                      tau_relu: float = 1e-6, tau_max: float = 1e-2):
+    """Backward of :func:`qlogehvi`: -> dmean (Mt x B x q), dL (Mt x B x q x q),
+    dF (or None), dlogw (S x B x q, or None).  The kernel writes the objective
+    members' slices of dmean / dL / dF; the others are zero."""
+    dev = _dev(mean, L, Z, cell_lo, cell_hi)
+    Mt, B, q = mean.shape
+    S = Z.shape[0]
+    f64 = dict(dtype=torch.float64, device=dev)
+    dmean = torch.zeros(Mt, B, q, **f64)
+    dL = torch.zeros(Mt, B, q, q, **f64)
+    dF = torch.zeros(F.shape, **f64) if F is not None else None
+    dlogw = torch.empty(S, B, q, **f64) if logw is not None else None
+    m = Mt if out_idx is None else len(out_idx)
+    work = torch.empty(8 * B * m * q * (q + 3) // 2, **f64)
+    if tuple(hvi.shape) != (S, B) or tuple(acq.shape) != (B,):
+        raise ValueError("qlogehvi_backward: acq (B) and hvi (S x B) are the forward's outputs")
+    a, _ = _qlogehvi_args(mean, L, Z, cell_lo, cell_hi, out_idx, logw, F, Qp, fat, tau_relu,
+                          tau_max, acq=acq.contiguous(), hvi=hvi.contiguous(),
+                          dacq=dacq.contiguous(), dmean=dmean, dL=dL, dF=dF, dlogw=dlogw,
+                          work=work, work_elems=work.numel())
+    check(lib().bo_qlogehvi_backward_v(ctypes.byref(a), _stream(dev)), "qlogehvi_backward")
+    return dmean, dL, dF, dlogw
+
+
 def kernel_grad(X: torch.Tensor, Y: torch.Tensor, dK: torch.Tensor, lengthscale: torch.Tensor,
                 kind: int, outputscale: float = 1.0, group: int = 0,
                 dX: Optional[torch.Tensor] = None) -> torch.Tensor:

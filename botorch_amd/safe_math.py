@@ -154,3 +154,42 @@ def fatmoid(X: torch.Tensor, tau=1.0) -> torch.Tensor:
 def log_fatmoid(X: torch.Tensor, tau=1.0) -> torch.Tensor:
     """log fatmoid (safe_math.py:422-426)."""
     return torch.log(fatmoid(X, tau=tau))
+
+
+def smooth_amin(X: torch.Tensor, dim: Dim = -1, keepdim: bool = False, tau=1.0) -> torch.Tensor:
+    """-smooth_amax(-X) (safe_math.py:276-283): the subset minimum of qLogEHVI
+    with fat=False."""
+    return -smooth_amax(-X, dim=dim, keepdim=keepdim, tau=tau)
+
+
+def fatmin(x: torch.Tensor, dim: Dim, keepdim: bool = False, tau=1.0, alpha: float = 2.0):
+    """-fatmax(-x) (safe_math.py:355-378): the fat-tailed smooth minimum,
+    m - tau log sum_j tail((x_j - m) / tau), anchored at the minimum m over
+    ``dim`` (_anchored's infinity contract on -x)."""
+    return -fatmax(-x, dim=dim, keepdim=keepdim, tau=tau, alpha=alpha)
+
+
+def fatminimum(a: torch.Tensor, b: torch.Tensor, tau=1.0, alpha: float = 2.0) -> torch.Tensor:
+    """Fat-tailed smooth torch.minimum(a, b) (safe_math.py:404-419): fatmin
+    over the stacked, broadcast pair."""
+    return fatmin(torch.stack(torch.broadcast_tensors(a, b), dim=-1), dim=-1, tau=tau, alpha=alpha)
+
+
+def logplusexp(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """log(e^a + e^b) (safe_math.py:102-105): logsumexp over the stacked,
+    broadcast pair, so two -inf give -inf."""
+    return logsumexp(torch.stack(torch.broadcast_tensors(a, b), dim=-1), dim=-1)
+
+
+def log1mexp(x: torch.Tensor) -> torch.Tensor:
+    """log(1 - e^x) for x < 0 (safe_math.py:72-82, Maechler 2012):
+    log(-expm1(x)) above -log 2, log1p(-e^x) below."""
+    return torch.where(-math.log(2) < x, (-x.expm1()).log(), (-x.exp()).log1p())
+
+
+def logdiffexp(log_a: torch.Tensor, log_b: torch.Tensor) -> torch.Tensor:
+    """log(b - a) from log a < log b (safe_math.py:108-121); log b = -inf
+    (hence log a = -inf) gives -inf without an inf - inf."""
+    log_a, log_b = torch.broadcast_tensors(log_a, log_b)
+    is_inf = log_b == -math.inf
+    return log_b + log1mexp(log_a - log_b.masked_fill(is_inf, 0.0))

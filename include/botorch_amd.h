@@ -875,6 +875,49 @@ typedef struct BoQehviFeasArgs {
 int bo_qehvi_feas_v(const BoQehviFeasArgs* a, void* stream);
 int bo_qehvi_feas_backward_v(const BoQehviFeasArgs* a, void* stream);
 
+/* qLogEHVI / qLogNEHVI (botorch/acquisition/multi_objective/logei.py:147-310):
+ * the log expected hypervolume improvement in log space.  Samples, cells, F and
+ * the member map exactly as BoQehviFeasArgs (Mt >= m members, objective t is
+ * member out_idx[t]; without constraint members Mt = m, out_idx = 0..m-1).  For
+ * every sample, cell and non-empty subset T of the q <= 8 points,
+ *   a_T = sum_t smin2(smin_{p in T} li[p][t], log(min(u_t, 1e10) - l_t))
+ *         + sum_{p in T} logw[s][b][p],
+ * li = log_fatplus (fat) or log_softplus of f - l at tau_relu, smin / smin2 =
+ * fatmin (fat) or smooth_amin at tau_max; the odd and the even subsets are
+ * summed in log space, differenced (logdiffexp), summed over the cells
+ * (-> hvi[s][b]) and averaged over the samples (-> acq[b], a log value).  Cells
+ * with a zero-length side are skipped.  logw (S x B x q, optional): the log
+ * smoothed feasibility of the points.
+ * Forward: writes acq (B) and hvi (S x B).  Backward: reads both, and dacq;
+ * writes dmean / dL / dF at the objective members' slices only and, with logw,
+ * dlogw (S x B x q).  work (optional, the sample split over workgroups):
+ * forward >= 4 B doubles, backward >= 2 B m q (q + 3) / 2.
+ * A pure addition to the ABI: BO_ABI_VERSION stays 11. */
+typedef struct BoQlogehviArgs {
+  BO_STRUCT_HEADER;
+  int32_t B, q, m, S;
+  const double *mean, *L, *Z, *cell_lo, *cell_hi;
+  int32_t K, Qp;
+  int64_t cell_stride;
+  const double* F;
+  int64_t ldF, sF;
+  double* acq; /* forward: output; backward: the forward's value */
+  double* hvi; /* S x B, likewise */
+  const double* dacq;
+  double *dmean, *dL, *dF;
+  double* work;
+  int64_t work_elems;
+  const double* logw;
+  double* dlogw; /* backward only, with logw */
+  int32_t Mt, zm;
+  int64_t zld;
+  int32_t out_idx[4];
+  int32_t fat, _pad;
+  double tau_relu, tau_max;
+} BoQlogehviArgs;
+int bo_qlogehvi_v(const BoQlogehviArgs* a, void* stream);
+int bo_qlogehvi_backward_v(const BoQlogehviArgs* a, void* stream);
+
 typedef struct BoLbfgsStepArgs { /* bo_lbfgs_step */
   BO_STRUCT_HEADER;
   int32_t B, n, m, _pad;
