@@ -241,6 +241,17 @@ class QlogehviArgs(_Args):
                        ("tau_max", c_double)]
 
 
+class QmcFeasArgs(_Args):
+    _fields_ = _HDR + [("B", c_int32), ("q", c_int32), ("Mt", c_int32), ("S", c_int32),
+                       ("mean", _D), ("L", _D), ("Z", _D), ("F", _D), ("ldF", c_int64),
+                       ("sF", c_int64), ("Qp", c_int32), ("k", c_int32), ("best_f", c_double),
+                       ("best_f_s", _D), ("c", c_double * 8), ("A", c_double * 64),
+                       ("rhs", c_double * 8), ("eta", c_double * 8), ("feas", _D), ("dfeas", _D),
+                       ("log", c_int32), ("fat", c_int32), ("tau_relu", c_double),
+                       ("tau_max", c_double), ("acq", _D), ("dacq", _D), ("dmean", _D),
+                       ("dL", _D), ("dF", _D)]
+
+
 class LbfgsStepArgs(_Args):
     _fields_ = _HDR + [("B", c_int32), ("n", c_int32), ("m", c_int32), ("_pad", c_int32),
                        ("x", _D), ("f", _D), ("g", _D), ("xt", _D), ("ft", _D), ("gt", _D),
@@ -263,6 +274,7 @@ for _name, _cls in (("bo_post_partials_v", PostPartialsArgs), ("bo_qmc_finalize_
                     ("bo_qehvi_v", QehviArgs), ("bo_qehvi_backward_v", QehviArgs),
                     ("bo_qehvi_feas_v", QehviFeasArgs), ("bo_qehvi_feas_backward_v", QehviFeasArgs),
                     ("bo_qlogehvi_v", QlogehviArgs), ("bo_qlogehvi_backward_v", QlogehviArgs),
+                    ("bo_qmc_feas_v", QmcFeasArgs), ("bo_qmc_feas_backward_v", QmcFeasArgs),
                     ("bo_lbfgs_step_v", LbfgsStepArgs), ("bo_lbfgsb_step_v", LbfgsbArgs)):
     _SIGNATURES[_name] = (c_int, [POINTER(_cls), _P])
 _SIGNATURES["bo_struct_size"] = (c_int64, [ctypes.c_char_p])
@@ -270,7 +282,8 @@ _SIGNATURES["bo_post_backward_jobs"] = (c_int, [c_int, POINTER(POINTER(PostBackw
 ARG_RECORDS = {"BoPostPartialsArgs": PostPartialsArgs, "BoQmcFinalizeArgs": QmcFinalizeArgs,
                "BoQmcBackwardArgs": QmcBackwardArgs, "BoPostBackwardArgs": PostBackwardArgs,
                "BoQehviArgs": QehviArgs, "BoQehviFeasArgs": QehviFeasArgs,
-               "BoQlogehviArgs": QlogehviArgs, "BoLbfgsStepArgs": LbfgsStepArgs,
+               "BoQlogehviArgs": QlogehviArgs, "BoQmcFeasArgs": QmcFeasArgs,
+               "BoLbfgsStepArgs": LbfgsStepArgs,
                "BoLbfgsbArgs": LbfgsbArgs}
 
 _lib = None

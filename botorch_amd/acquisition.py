@@ -29,12 +29,14 @@ from .exceptions import (BotorchError, BotorchTensorDimensionError, BotorchWarni
 from .safe_math import (TAU_MAX, TAU_RELU, fatmax, log_improvement, logmeanexp, logplusexp,
                         smooth_amax)
 from .objective import (ConstrainedMCObjective, GenericMCObjective, IdentityMCObjective,
-                        MCAcquisitionObjective, MCObjective, compute_best_feasible_objective,
-                        compute_feasibility_indicator, compute_smoothed_feasibility_indicator,
-                        repeat_to_match_aug_dim, _as_etas)
+                        LinearMCObjective, MCAcquisitionObjective, MCObjective,
+                        compute_best_feasible_objective, compute_feasibility_indicator,
+                        compute_smoothed_feasibility_indicator, repeat_to_match_aug_dim, _as_etas,
+                        _linear_outcome_constraints)
 from .models import prime_prediction_caches
 from .posteriors import FUSED_QMAX
-from .sampling import MCSampler, ShapeOnlyPosterior, SobolQMCNormalSampler, get_sampler
+from .sampling import (ListSampler, MCSampler, ShapeOnlyPosterior, SobolQMCNormalSampler,
+                       get_sampler)
 
 
 # -- input handling (utils/transforms.py:146-336) -----------------------------
@@ -264,6 +266,10 @@ class qExpectedImprovement(MCAcquisitionFunction):
             sampler = self._ensure_sampler()
             Z = sampler.base_samples_2d(q, X.device)
             return _SaasQEI.apply(X3, self, _host_scalar(self, "best_f"), Z).reshape(batch)
+        if self._constraints is not None:  # outcome constraints: the weighted fused route
+            acq = _weighted_qei_forward(self, X)
+            if acq is not None:
+                return acq
         return self._generic_forward(X)
 
 
@@ -609,7 +615,18 @@ class qNoisyExpectedImprovement(MCAcquisitionFunction):
         self._init_baseline(model, X_baseline, prune_baseline, cache_root, marginalize_dim)
 
     def _init_baseline(self, model, X_baseline, prune_baseline, cache_root, marginalize_dim):
-        if cache_root and not supports_cache_root(model, self.posterior_transform):
+        # outcome constraints on the fused route (per-member cached roots, _FusedQNEIFeas):
+        # a single Sobol sampler; on a model list it must be given (without one the
+        # generic route builds a ListSampler, which keeps that route)
+        wplan = _weighted_so_plan(self) if cache_root else None
+        if wplan is not None and not (
+                X_baseline.ndim == 2 and X_baseline.shape[-1] <= kernels.DP and X_baseline.is_cuda
+                and X_baseline.shape[-2] > 0 and len(self.sample_shape) == 1
+                and (type(self.sampler) is SobolQMCNormalSampler
+                     or (self.sampler is None and not hasattr(model, "models")))):
+            wplan = None
+        self._roots = None
+        if cache_root and wplan is None and not supports_cache_root(model, self.posterior_transform):
             warnings.warn("`cache_root` is only supported here for exact GPs (or a ModelListGP "
                           f"under a scalarising posterior transform); got {type(model)}. "
                           "Setting `cache_root = False`.", RuntimeWarning)
@@ -635,7 +652,24 @@ class qNoisyExpectedImprovement(MCAcquisitionFunction):
                    and X_baseline.ndim == 2 and X_baseline.shape[-1] <= kernels.DP
                    and X_baseline.is_cuda and len(self.sample_shape) == 1)
         with torch.no_grad():
-            if fusable:
+            if wplan is not None:
+                # qNEHVI's convention: member t's baseline base samples are the
+                # columns i Mt + t of the (r Mt)-dimensional draw
+                sampler = self._ensure_sampler()
+                Mt = len(wplan.members)
+                if Mt == 1:   # the sampler's own S x r draw, kept for the base sampler
+                    sampler._construct_base_samples(ShapeOnlyPosterior(torch.Size(), r, X_baseline.device))
+                    Zb = sampler.base_samples.reshape(-1, r, 1)
+                else:
+                    Zb = kernels.sobol_normal(r * Mt, sampler.sample_shape.numel(), sampler.seed,
+                                              X_baseline.device).view(-1, r, Mt)
+                self._roots = [_CachedBaselineRoot(mm, X_baseline, Zb[:, :, t].contiguous())
+                               for t, mm in enumerate(wplan.members)]
+                baseline_samples = torch.stack([rt.samples for rt in self._roots], dim=-1).reshape(
+                    *self.sample_shape, r, Mt)
+                baseline_L = self._roots[0].L if Mt == 1 else None
+                self._zqm = {}
+            elif fusable:
                 # the sampler's own base samples over X_baseline (S x r), then the
                 # device root + fused precomputations on them
                 sampler = self._ensure_sampler()
@@ -776,7 +810,28 @@ class qNoisyExpectedImprovement(MCAcquisitionFunction):
                               "ill-conditioned covariance matrix. Falling back to standard "
                               "sampling.", BotorchWarning)
                 return self._fallback_forward(X)
+        if self._roots is not None and self._cache_root:
+            plan = _weighted_so_route(self, X)
+            if plan is not None:
+                try:
+                    acq = _FusedQNEIFeas.apply(X.reshape(-1, q, d).to(torch.float64), self, plan)
+                    return acq.to(X.dtype).reshape(batch)
+                except (NotPSDError, NanError):
+                    warnings.warn("Low-rank cholesky updates failed due NaNs or due to an "
+                                  "ill-conditioned covariance matrix. Falling back to standard "
+                                  "sampling.", BotorchWarning)
+                    return self._fallback_forward(X)
         return self._generic_forward(X)
+
+    def _base_samples_members(self, q: int, Mt: int, device) -> torch.Tensor:
+        """The q Mt new columns of the (r + q) Mt-dimensional Sobol draw (column
+        p Mt + t for new point p, member t), behind the baseline's r Mt."""
+        if q not in self._zqm:
+            r = self.X_baseline.shape[-2]
+            full = kernels.sobol_normal((r + q) * Mt, self.sampler.sample_shape.numel(),
+                                        self.sampler.seed, device)
+            self._zqm[q] = full[:, r * Mt:].contiguous()
+        return self._zqm[q]
 
 
 class _FusedQNEI(torch.autograd.Function):
@@ -877,6 +932,10 @@ class qLogExpectedImprovement(qExpectedImprovement):
             acq = _fused_mc(X.reshape(-1, q, d), self, _lib.QMC_QLOGEI,
                             _host_scalar(self, "best_f"), None, Z)
             return acq.reshape(batch)
+        if self._constraints is not None:
+            acq = _weighted_qei_forward(self, X)
+            if acq is not None:
+                return acq
         return self._generic_forward(X)
 
 
@@ -1166,7 +1225,10 @@ def _feas_weights(acqf, mean, L, Z, F, Qp: int, need_grad: bool, log: bool = Fal
             f = f + leaves[2][:, :, : B * Qp].reshape(Mt, S, B, Qp)[..., :q].permute(1, 2, 3, 0)
         w = compute_smoothed_feasibility_indicator(acqf.constraints, f, acqf.eta.to(f),
                                                    log=log, fat=acqf.fat)
-    return w.to(torch.float64).contiguous(), leaves
+        # inside the grad mode above: a copy made outside it (w comes out
+        # non-contiguous for one member) would drop the graph
+        w = w.to(torch.float64).contiguous()
+    return w, leaves
 
 
 def _feas_backward(feas, dfeas, dmean, dL, dF) -> None:
@@ -1552,6 +1614,328 @@ def _roots_forward_batched(acqf, caches, pps, stats):
     T = kernels.gemm(Pb_s, Rt_all, alpha=-1.0, beta=1.0, C=T)
     F = kernels.gemm(Zb, T)
     return [T[t] for t in range(M)], F
+
+
+# -- outcome constraints on the single-objective classes ---------------------------------
+class _WeightedSOPlan:
+    """What the feasibility-weighted fused route of qEI / qLogEI / qNEI / qLogNEI
+    needs from the acquisition function, fixed at construction: the members (a
+    SingleTaskGP, or a ModelListGP's members), the objective weights ``c`` over
+    them, and the constraints -- ``lin = (A, rhs)`` when every callable comes
+    from get_outcome_constraint_transforms (then evaluated inside bo_qmc_feas),
+    else None (the callables run in torch on the members' samples,
+    _feas_weights).  ``constraints`` / ``eta`` / ``fat`` under the names
+    _feas_weights reads; the etas are set at the first forward, where the
+    generic route would check them."""
+
+    def __init__(self, members, c, constraints, lin, fat):
+        self.members, self.c, self.constraints, self.lin, self.fat = members, c, constraints, lin, fat
+        self.eta = None
+        self.etas = None
+
+    def set_eta(self, eta) -> None:
+        if self.etas is None:
+            self.eta = _as_etas(eta, len(self.constraints)).to(torch.float64)
+            self.etas = [float(v) for v in self.eta.tolist()]
+
+
+def _weighted_so_plan(acqf) -> Optional[_WeightedSOPlan]:
+    """The plan (built once), or None where the route does not apply: no
+    constraints, a posterior transform, an ensemble, a model that is neither a
+    SingleTaskGP under the identity objective nor a list of <= 8 of them under
+    LinearMCObjective(weights over the members)."""
+    plan = acqf.__dict__.get("_wso")
+    if plan is None:
+        plan = _make_weighted_so_plan(acqf) or False
+        acqf.__dict__["_wso"] = plan
+    return plan or None
+
+
+def _make_weighted_so_plan(acqf) -> Optional[_WeightedSOPlan]:
+    cons = acqf._constraints
+    if cons is None or len(cons) == 0 or acqf.posterior_transform is not None:
+        return None
+    model = acqf.model
+    models = getattr(model, "models", None)
+    if models is None:
+        if not hasattr(model, "prediction_cache") or type(acqf.objective) is not IdentityMCObjective:
+            return None
+        members, c = [model], [1.0]
+    else:
+        if (not 1 <= len(models) <= kernels.QMC_FEAS_MTMAX
+                or not all(hasattr(mm, "prediction_cache") for mm in models)
+                or type(acqf.objective) is not LinearMCObjective
+                or acqf.objective.weights.numel() != len(models)):
+            return None
+        members, c = list(models), [float(v) for v in acqf.objective.weights.tolist()]
+    if any(getattr(mm, "_is_ensemble", False) or getattr(mm, "_is_fully_bayesian", False)
+           for mm in members):
+        return None
+    lin = _linear_outcome_constraints(cons)
+    if lin is not None and (len(lin[0]) > kernels.QMC_FEAS_KMAX or len(lin[0][0]) != len(members)):
+        lin = None
+    return _WeightedSOPlan(members, c, list(cons), lin, acqf._fat)
+
+
+def _weighted_so_route(acqf, X: torch.Tensor) -> Optional[_WeightedSOPlan]:
+    """The plan where this call can take the fused route: X on the device,
+    q <= 16 (pending points included), d <= 8, a one-dimensional sample shape,
+    and no graph capture running (a capture takes the route it took before)."""
+    plan = _weighted_so_plan(acqf)
+    if (plan is None or not X.is_cuda or X.shape[-2] > kernels.QMC_FEAS_QMAX
+            or X.shape[-1] > kernels.DP or len(acqf.sample_shape) != 1
+            or kernels._dev_index(X.device) in kernels._CAPTURE):
+        return None
+    plan.set_eta(acqf._eta)
+    plan.fat = acqf._fat
+    return plan
+
+
+def _weighted_so_base_samples(acqf, plan, q: int, device) -> Optional[torch.Tensor]:
+    """Z (S x q Mt, column j Mt + t) of qEI / qLogEI: a single sampler's
+    base_samples_2d(q Mt) (the qEHVI convention); a ListSampler of Mt samplers
+    interleaved from each member's base_samples_2d(q) -- the samples the generic
+    route draws -- and cached per q.  Without a sampler, the one the generic
+    route would build.  None for any other sampler."""
+    Mt = len(plan.members)
+    if acqf.sampler is None:
+        if hasattr(acqf.model, "models"):
+            acqf.sampler = ListSampler(*[SobolQMCNormalSampler(sample_shape=acqf._default_sample_shape)
+                                         for _ in range(Mt)])
+        else:
+            acqf._ensure_sampler()
+    s = acqf.sampler
+    if isinstance(s, ListSampler):
+        if len(s.samplers) != Mt or not all(hasattr(x, "base_samples_2d") for x in s.samplers):
+            return None
+        parts = [x.base_samples_2d(q, device) for x in s.samplers]
+        key = tuple((p.data_ptr(), p._version) for p in parts)
+        cache = acqf.__dict__.setdefault("_zlist", {})
+        hit = cache.get(q)
+        if hit is None or hit[0] != key:
+            hit = (key, torch.stack(parts, dim=-1).reshape(parts[0].shape[0], q * Mt).contiguous())
+            cache[q] = hit
+        return hit[1]
+    if hasattr(s, "base_samples_2d"):
+        return s.base_samples_2d(q * Mt, device)
+    return None
+
+
+def _weighted_qei_forward(acqf, X: torch.Tensor) -> Optional[torch.Tensor]:
+    """qEI / qLogEI with outcome constraints on the fused route (X already in
+    t-batch mode with the pending points), or None where it does not apply."""
+    if acqf.best_f.numel() != 1:
+        return None
+    plan = _weighted_so_route(acqf, X)
+    if plan is None:
+        return None
+    q, d = X.shape[-2], X.shape[-1]
+    Z = _weighted_so_base_samples(acqf, plan, q, X.device)
+    if Z is None:
+        return None
+    X3 = X.reshape(-1, q, d)
+    acq = _FusedQEIFeas.apply(X3.to(torch.float64), acqf, plan, Z, _host_scalar(acqf, "best_f"))
+    return acq.to(X.dtype).reshape(X.shape[:-2])
+
+
+def _so_feas_forward(acqf, plan, mean, L, Z, F, Qp: int, best_f: float, best_f_s, need_grad: bool):
+    """bo_qmc_feas on the members' stacked means / roots: the linear
+    constraints inside the kernel, any other callable through _feas_weights
+    (log-weights in log mode) -> acq, the state the backward takes back."""
+    lp = getattr(acqf, "_log_params", None) or (0, TAU_RELU, TAU_MAX)
+    kw = dict(best_f=best_f, best_f_s=best_f_s, F=F, Qp=Qp, log=acqf._log, fat=plan.fat,
+              tau_relu=lp[1], tau_max=lp[2])
+    feas = None
+    if plan.lin is not None:
+        kw.update(A=plan.lin[0], rhs=plan.lin[1], eta=plan.etas)
+    else:
+        feas = _feas_weights(plan, mean, L, Z, F, Qp, need_grad, log=acqf._log)
+        kw.update(feas=feas[0].detach())
+    return kernels.qmc_feas(mean, L, Z, plan.c, **kw), (kw, feas)
+
+
+def _so_feas_backward(plan, state, mean, L, Z, acq, dacq):
+    """bo_qmc_feas_backward, plus the constraint callables' path -> dmean, dL, dF."""
+    kw, feas = state
+    dmean, dL, dF, dfeas = kernels.qmc_feas_backward(mean, L, Z, plan.c, dacq.contiguous(), acq=acq,
+                                                     **kw)
+    if feas is not None:
+        _feas_backward(feas, dfeas, dmean, dL, dF)
+    return dmean, dL, dF
+
+
+class _FusedQEIFeas(torch.autograd.Function):
+    """Constrained qEI / qLogEI of B t-batches over the plan's members, with its
+    gradient: _FusedQEHVI's chain with bo_qmc_feas as the reduction.
+
+    Forward: the members' post_partials, one qmc_finalize_members (CHOL: mean and
+    jittered q x q root of every member into the stacked inputs), bo_qmc_feas.
+    Backward: bo_qmc_feas_backward -> d mu_t, d L_t; bo_chol_backward over all
+    members; bo_post_backward_jobs.  The ladder status as _FusedQEHVI's."""
+
+    @staticmethod
+    def forward(ctx, X3, acqf, plan, Z, best_f):
+        models = plan.members
+        need_grad = ctx.needs_input_grad[0]
+        q = X3.shape[-2]
+        M = len(models)
+        what = type(acqf).__name__ + " posterior root"
+        keys = prime_prediction_caches(models)
+        caches = [mm.prediction_cache(key=key) for mm, key in zip(models, keys)]
+        pps = kernels.post_partials_members(caches, X3.detach(), store_R=need_grad)
+        f64 = dict(dtype=torch.float64, device=X3.device)
+        mean = torch.empty(M, X3.shape[0], q, **f64)
+        L = torch.empty(M, X3.shape[0], q, q, **f64)
+        ring = (kernels.ladder_ring(X3.device) if need_grad and not kernels.SYNC_LADDER else None)
+        ps = kernels.pinned_status(X3.device) if ring is None else None
+        if ring is not None:
+            token, words = ring.take(M, what)
+        else:
+            words = ps.arm(M)
+        stats = [mm.outcome_stats() for mm in models]
+        if (all(p_.Spart.shape == pps[0].Spart.shape for p_ in pps)
+                and all(c.kind == caches[0].kind for c in caches)):
+            kernels.qmc_finalize_members(caches, pps, stats, mean, L, status=words)
+        else:
+            for t, (cache, pp) in enumerate(zip(caches, pps)):
+                kernels.qmc_finalize(cache, pp, _lib.QMC_CHOL, *stats[t], want_mean=True,
+                                     want_cov=False, want_L=True, mean_out=mean[t], L_out=L[t],
+                                     status=words[t])
+        saved = []
+        if need_grad:
+            Ws = kernels.w_matrix_members(caches, pps)
+            saved = [(caches[t], pps[t], stats[t][1], Ws[t]) for t in range(M)]
+        acq, state = _so_feas_forward(acqf, plan, mean, L, Z, None, 0, best_f, None, need_grad)
+        ctx.ladder = None
+        if ring is not None:
+            ring.record(token)
+            ctx.ladder = (ring, token)
+        else:
+            kernels.raise_not_psd_members(ps, M, X3.device, what)
+        if need_grad:
+            ctx.plan, ctx.state, ctx.saved = plan, state, saved
+            ctx.mean, ctx.L, ctx.Z, ctx.acq = mean, L, Z, acq.detach().clone()
+        return acq
+
+    @staticmethod
+    def backward(ctx, dacq):
+        dmean, dL, _ = _so_feas_backward(ctx.plan, ctx.state, ctx.mean, ctx.L, ctx.Z, ctx.acq, dacq)
+        sv = ctx.saved
+        q_ = ctx.L.shape[-1]
+        dcovs = kernels.chol_backward(ctx.L.reshape(-1, q_, q_),
+                                      dL.reshape(-1, q_, q_)).reshape(ctx.L.shape)
+        if (_PB_JOBS and 1 < len(sv) <= 16 and all(
+                c.kind == sv[0][0].kind and c.d == sv[0][0].d for c, _, _, _ in sv)):
+            dX = kernels.post_backward_jobs([
+                dict(cache=cache, pp=pp, W=W, dmean=dmean[t], ystd=ystd, dcov=dcovs[t])
+                for t, (cache, pp, ystd, W) in enumerate(sv)])
+        else:
+            dX = None
+            for t, (cache, pp, ystd, W) in enumerate(sv):
+                dX = kernels.post_backward(cache, pp, W, dmean[t], dcovs[t], ystd, dX=dX)
+        _settle_ladder(ctx)
+        return dX, None, None, None, None
+
+
+class _FusedQNEIFeas(torch.autograd.Function):
+    """Constrained qNEI / qLogNEI of B t-batches over the plan's members with
+    cached baseline roots, with its gradient: _FusedQNEHVI's chain (the members'
+    T_t = L_rr,t^-1 Sigma'_t(X_b, X), F_t = Z_b,t T_t, the roots of Sigma'_t -
+    T_t^T T_t) with bo_qmc_feas against the per-sample baseline best as the
+    reduction."""
+
+    @staticmethod
+    def forward(ctx, X3, acqf, plan):
+        models = plan.members
+        roots = acqf._roots
+        need_grad = ctx.needs_input_grad[0]
+        B, q, _ = X3.shape
+        M = len(models)
+        what = type(acqf).__name__ + " posterior root"
+        keys = prime_prediction_caches(models)
+        caches = [mm.prediction_cache(key=key) for mm, key in zip(models, keys)]
+        c0 = caches[0]
+        pps = None
+        if (1 < M <= 8 and kernels.split_plan(B, q, c0.n)[0] != 0
+                and all(c.n == c0.n and c.np == c0.np and c.d == c0.d for c in caches)):
+            pps = kernels.post_partials_members(caches, X3.detach(), store_R=True)
+        f64 = dict(dtype=torch.float64, device=X3.device)
+        mean = torch.empty(M, B, q, **f64)
+        L = torch.empty(M, B, q, q, **f64)
+        F = None
+        # the ladder status as _FusedQNEHVI's: forward-only calls defer it, the
+        # gradient path reads pinned words at the end of the backward
+        defer = not need_grad and not kernels.SYNC_LADDER
+        ring = kernels.ladder_ring(X3.device) if not defer and not kernels.SYNC_LADDER else None
+        ps = kernels.pinned_status(X3.device) if not defer and ring is None else None
+        if ring is not None:
+            token, words = ring.take(M, what)
+        else:
+            words = ps.arm(M) if ps is not None else [None] * M
+        stats = [mm.outcome_stats() for mm in models]
+        saved, status = [], []
+        batched = pps is not None and _roots_batched(acqf, caches, pps, stats)
+        if batched:
+            Ts, F = _roots_forward_batched(acqf, caches, pps, stats)
+            pp_list = list(pps)
+            if need_grad:
+                Ws = kernels.w_matrix_members(caches, pps)
+                saved = [(caches[t], pps[t], stats[t][1], Ts[t], Ws[t]) for t in range(M)]
+        else:
+            Ts, pp_list = [], []
+            for t in range(M):
+                cache, ystd = caches[t], stats[t][1]
+                pp = pps[t] if pps is not None else kernels.post_partials(
+                    cache, X3.detach(), store_R=need_grad, cross=roots[t].Q_b)
+                pp_list.append(pp)
+                if F is None:
+                    F = torch.empty(M, roots[t].Z_base.shape[0], pp.nrows_pad, **f64)
+                T, _ = roots[t].forward(cache, pp, ystd, F_out=F[t])
+                Ts.append(T)
+                if need_grad:
+                    saved.append((cache, pp, ystd, T, kernels.w_matrix(cache, pp)))
+        pp = pp_list[-1]
+        if (all(p_.Spart.shape == pp_list[0].Spart.shape for p_ in pp_list)
+                and all(c.kind == c0.kind for c in caches)):
+            info, jit = kernels.qmc_finalize_members(
+                caches, pp_list, stats, mean, L, status=words if not defer else None, Ts=Ts, F=F)
+            status = [(info[t], jit[t]) for t in range(M)]
+        else:
+            for t in range(M):
+                out = kernels.qmc_finalize(caches[t], pp_list[t], _lib.QMC_CHOL, *stats[t],
+                                           want_mean=True, want_cov=False, want_L=True, T=Ts[t],
+                                           F=F[t], mean_out=mean[t], L_out=L[t], status=words[t])
+                status.append((out["info"], out["jitter"]))
+        Zq = acqf._base_samples_members(q, M, X3.device)
+        acq, state = _so_feas_forward(acqf, plan, mean, L, Zq, F, pp.Qp, 0.0,
+                                      acqf._baseline_best_f, need_grad)
+        ctx.ladder = None
+        if defer:
+            kernels.raise_not_psd_deferred(torch.cat([i_.reshape(-1) for i_, _ in status]),
+                                           torch.cat([j_.reshape(-1) for _, j_ in status]), what)
+        elif ring is not None:
+            ring.record(token)
+            ctx.ladder = (ring, token)
+        else:
+            kernels.raise_not_psd_members(ps, M, X3.device, what)
+        if need_grad:
+            ctx.acqf, ctx.plan, ctx.state, ctx.saved, ctx.batched = acqf, plan, state, saved, batched
+            ctx.mean, ctx.L, ctx.F, ctx.Zq, ctx.acq = mean, L, F, Zq, acq.detach().clone()
+        return acq
+
+    @staticmethod
+    def backward(ctx, dacq):
+        dmean, dL, dF = _so_feas_backward(ctx.plan, ctx.state, ctx.mean, ctx.L, ctx.Zq, ctx.acq, dacq)
+        if ctx.batched and _BWD_BATCHED:
+            dX = _roots_backward_batched(ctx, dmean, dL, dF)
+        else:
+            dX = None
+            for t, (cache, pp, ystd, T, W) in enumerate(ctx.saved):
+                dcov = kernels.chol_backward(ctx.L[t], dL[t])
+                dX = ctx.acqf._roots[t].backward(cache, pp, W, dmean[t], dcov, dF[t].contiguous(),
+                                                 T, ystd, dX=dX)
+        _settle_ladder(ctx)
+        return dX, None, None
 
 
 class _QEHVIFromRoots(torch.autograd.Function):

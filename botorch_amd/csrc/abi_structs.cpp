@@ -66,6 +66,10 @@ int bo_qehvi_feas_backward_impl(const BoQehviFeasArgs* a, void* stream);
 int bo_qlogehvi_impl(const BoQlogehviArgs* a, void* stream);
 int bo_qlogehvi_backward_impl(const BoQlogehviArgs* a, void* stream);
 
+// the feasibility-weighted single-objective launches (qmc_feas.hip)
+int bo_qmc_feas_impl(const BoQmcFeasArgs* a, void* stream);
+int bo_qmc_feas_backward_impl(const BoQmcFeasArgs* a, void* stream);
+
 int bo_post_partials_v(const BoPostPartialsArgs* a, void* stream) {
   if (!header_ok(a, "bo_post_partials_v")) return BO_ERR_ARG;
   return bo_post_partials_layout(a->kind, a->Xq, a->B, a->q, a->d, a->Xt_scaled, a->n, a->U,
@@ -132,6 +136,16 @@ int bo_qlogehvi_backward_v(const BoQlogehviArgs* a, void* stream) {
   return bo_qlogehvi_backward_impl(a, stream);
 }
 
+int bo_qmc_feas_v(const BoQmcFeasArgs* a, void* stream) {
+  if (!header_ok(a, "bo_qmc_feas_v")) return BO_ERR_ARG;
+  return bo_qmc_feas_impl(a, stream);
+}
+
+int bo_qmc_feas_backward_v(const BoQmcFeasArgs* a, void* stream) {
+  if (!header_ok(a, "bo_qmc_feas_backward_v")) return BO_ERR_ARG;
+  return bo_qmc_feas_backward_impl(a, stream);
+}
+
 int bo_lbfgs_step_v(const BoLbfgsStepArgs* a, void* stream) {
   if (!header_ok(a, "bo_lbfgs_step_v")) return BO_ERR_ARG;
   return bo_lbfgs_step(a->B, a->n, a->m, a->x, a->f, a->g, a->xt, a->ft, a->gt, a->d, a->alpha,
@@ -158,6 +172,7 @@ extern "C" int64_t bo_struct_size(const char* name) {
   if (s == "BoQehviArgs") return sizeof(BoQehviArgs);
   if (s == "BoQehviFeasArgs") return sizeof(BoQehviFeasArgs);
   if (s == "BoQlogehviArgs") return sizeof(BoQlogehviArgs);
+  if (s == "BoQmcFeasArgs") return sizeof(BoQmcFeasArgs);
   if (s == "BoLbfgsStepArgs") return sizeof(BoLbfgsStepArgs);
   if (s == "BoLbfgsbArgs") return sizeof(BoLbfgsbArgs);
   return -1;

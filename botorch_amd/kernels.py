@@ -1835,6 +1835,115 @@ def qlogehvi_backward(mean: torch.Tensor, L: torch.Tensor, Z: torch.Tensor, cell
     return dmean, dL, dF, dlogw
 
 
+QMC_FEAS_QMAX = 16  # the feasibility-weighted single-objective kernels (bo_qmc_feas)
+QMC_FEAS_MTMAX = 8
+QMC_FEAS_KMAX = 8
+
+
+def _qmc_feas_args(mean, L, Z, c, best_f, best_f_s, A, rhs, eta, feas, F, Qp, log, fat, tau_relu,
+                   tau_max, **extra):
+    """The BoQmcFeasArgs of :func:`qmc_feas` / :func:`qmc_feas_backward`: mean
+    Mt x B x q, L Mt x B x q x q, Z S x (q Mt), F Mt x S x ldF or None, c the
+    Mt objective weights, either the linear constraints (A k x Mt, rhs k, eta
+    k, host values) or feas S x B x q (weights; log-weights with ``log``)."""
+    Mt, B, q = mean.shape
+    S = Z.shape[0]
+    if not 1 <= Mt <= QMC_FEAS_MTMAX:
+        raise ValueError(f"qmc_feas: 1 <= Mt <= {QMC_FEAS_MTMAX} members (got {Mt})")
+    if not 1 <= q <= QMC_FEAS_QMAX:
+        raise ValueError(f"qmc_feas: 1 <= q <= {QMC_FEAS_QMAX} (got {q})")
+    if L.shape != (Mt, B, q, q) or Z.numel() != S * q * Mt:
+        raise ValueError("qmc_feas: L must be Mt x B x q x q and Z S x (q Mt)")
+    c = [float(v) for v in c]
+    if len(c) != Mt:
+        raise ValueError(f"qmc_feas: one objective weight per member ({Mt}), got {len(c)}")
+    A = [] if A is None else [[float(v) for v in row] for row in A]
+    k = len(A)
+    if k > QMC_FEAS_KMAX:
+        raise ValueError(f"qmc_feas: at most {QMC_FEAS_KMAX} in-kernel constraints (got {k})")
+    if feas is not None and k:
+        raise ValueError("qmc_feas: pass the constraint table or the weight tensor, not both")
+    if feas is not None and tuple(feas.shape) != (S, B, q):
+        raise ValueError(f"qmc_feas: feas must be S x B x q = {(S, B, q)}, got {tuple(feas.shape)}")
+    rhs = [float(v) for v in (rhs if rhs is not None else [])]
+    eta = [float(v) for v in (eta if eta is not None else [])]
+    if any(len(row) != Mt for row in A) or len(rhs) != k or len(eta) != k:
+        raise ValueError("qmc_feas: A must be k x Mt with one rhs and one eta per constraint")
+    if any(not e > 0 for e in eta):
+        raise ValueError("qmc_feas: eta must be positive")
+    if best_f_s is not None and best_f_s.numel() != S:
+        raise ValueError(f"qmc_feas: best_f_s holds one value per sample ({S})")
+    Fc = F.contiguous() if F is not None else None
+    if Fc is not None and (Fc.dim() != 3 or Fc.shape[0] != Mt or Fc.shape[1] != S
+                           or Qp < q or Fc.shape[2] < B * Qp):
+        raise ValueError("qmc_feas: F must be Mt x S x ldF with ldF >= B Qp and Qp >= q")
+    a = _lib.QmcFeasArgs(B=B, q=q, Mt=Mt, S=S, mean=mean.contiguous(), L=L.contiguous(),
+                         Z=Z.reshape(S, q * Mt).contiguous(), F=Fc,
+                         ldF=Fc.shape[-1] if Fc is not None else 0,
+                         sF=Fc.shape[-1] * S if Fc is not None else 0, Qp=Qp, k=k,
+                         best_f=float(best_f),
+                         best_f_s=best_f_s.contiguous() if best_f_s is not None else None,
+                         feas=feas.contiguous() if feas is not None else None,
+                         log=int(bool(log)), fat=int(bool(fat)), tau_relu=float(tau_relu),
+                         tau_max=float(tau_max), **extra)
+    for t in range(Mt):
+        a.c[t] = c[t]
+    for i in range(k):
+        a.rhs[i], a.eta[i] = rhs[i], eta[i]
+        for t in range(Mt):
+            a.A[i * 8 + t] = A[i][t]
+    return a
+
+
+def qmc_feas(mean: torch.Tensor, L: torch.Tensor, Z: torch.Tensor, c, best_f: float = 0.0,
+             best_f_s: Optional[torch.Tensor] = None, A=None, rhs=None, eta=None,
+             feas: Optional[torch.Tensor] = None, F: Optional[torch.Tensor] = None, Qp: int = 0,
+             log: bool = False, fat: bool = False, tau_relu: float = 1e-6,
+             tau_max: float = 1e-2) -> torch.Tensor:
+    """Feasibility-weighted qEI / qNEI (``log``: qLogEI / qLogNEI) of the samples
+    f = mean + L z (+ F) of a model list's Mt members (bo_qmc_feas): objective
+    sum_t c_t f_t against best_f (or best_f_s per sample), weighted by the
+    smoothed feasibility of the linear constraints A f - rhs <= 0 evaluated in
+    the kernel, or by the caller's ``feas`` -> acq (B)."""
+    a = _qmc_feas_args(mean, L, Z, c, best_f, best_f_s, A, rhs, eta, feas, F, Qp, log, fat,
+                       tau_relu, tau_max)
+    dev = _dev(mean, L, Z, feas, F, best_f_s)
+    acq = torch.empty(mean.shape[1], dtype=torch.float64, device=dev)
+    a.acq = acq.data_ptr()
+    check(lib().bo_qmc_feas_v(ctypes.byref(a), _stream(dev)), "qmc_feas")
+    return acq
+
+
+def qmc_feas_backward(mean: torch.Tensor, L: torch.Tensor, Z: torch.Tensor, c, dacq: torch.Tensor,
+                      best_f: float = 0.0, best_f_s: Optional[torch.Tensor] = None, A=None,
+                      rhs=None, eta=None, feas: Optional[torch.Tensor] = None,
+                      F: Optional[torch.Tensor] = None, Qp: int = 0, log: bool = False,
+                      fat: bool = False, tau_relu: float = 1e-6, tau_max: float = 1e-2,
+                      acq: Optional[torch.Tensor] = None):
+    """Backward of :func:`qmc_feas` (``acq``: the forward's value, required with
+    ``log``) -> dmean (Mt x B x q), dL (Mt x B x q x q), dF (or None), dfeas
+    (S x B x q with ``feas``, else None)."""
+    Mt, B, q = mean.shape
+    S = Z.shape[0]
+    if log and (acq is None or tuple(acq.shape) != (B,)):
+        raise ValueError("qmc_feas_backward: log mode needs the forward's acq (B)")
+    if tuple(dacq.shape) != (B,):
+        raise ValueError(f"qmc_feas_backward: dacq must have {B} entries")
+    _qmc_feas_args(mean, L, Z, c, best_f, best_f_s, A, rhs, eta, feas, F, Qp, log, fat, tau_relu,
+                   tau_max)  # the argument checks, before any device work
+    dev = _dev(mean, L, Z, feas, F, best_f_s, dacq, acq)
+    f64 = dict(dtype=torch.float64, device=dev)
+    dmean = torch.empty(Mt, B, q, **f64)
+    dL = torch.empty(Mt, B, q, q, **f64)
+    dF = torch.zeros(F.shape, **f64) if F is not None else None
+    dfeas = torch.empty(S, B, q, **f64) if feas is not None else None
+    a = _qmc_feas_args(mean, L, Z, c, best_f, best_f_s, A, rhs, eta, feas, F, Qp, log, fat,
+                       tau_relu, tau_max, acq=acq.contiguous() if acq is not None else None,
+                       dacq=dacq.contiguous(), dmean=dmean, dL=dL, dF=dF, dfeas=dfeas)
+    check(lib().bo_qmc_feas_backward_v(ctypes.byref(a), _stream(dev)), "qmc_feas_backward")
+    return dmean, dL, dF, dfeas
+
+
 def kernel_grad(X: torch.Tensor, Y: torch.Tensor, dK: torch.Tensor, lengthscale: torch.Tensor,
                 kind: int, outputscale: float = 1.0, group: int = 0,
                 dX: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -8,6 +8,7 @@ samples themselves come from the gfx950 posterior and sampling kernels).
 """
 from __future__ import annotations
 
+from functools import partial
 from typing import Callable, List, Optional, Union
 
 import torch
@@ -186,6 +187,43 @@ def compute_smoothed_feasibility_indicator(constraints: List[Callable], samples:
     for i in range(vals.shape[0]):  # in order: the same rounding as a running sum
         total = total + log_sig(-vals[i] / etas[i].to(samples))
     return total if log else total.exp()
+
+
+def _oc(a: torch.Tensor, rhs: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
+    """One linear outcome constraint a . Y - rhs over the last (output)
+    dimension of Y (... x q x m -> ... x q; <= 0 feasible), on Y's device."""
+    return torch.einsum("...m, m", [Y, a.to(Y)]) - rhs.to(Y)
+
+
+def get_outcome_constraint_transforms(outcome_constraints) -> Optional[List[Callable]]:
+    """utils/constraints.py:20-63: the callables of the k linear outcome
+    constraints ``A f(x) <= b`` (A k x m, b k x 1), one per row, broadcasting
+    over any leading dimensions of the samples.  The acquisition functions
+    recognise these callables and evaluate them inside the fused kernels."""
+    if outcome_constraints is None:
+        return None
+    A, b = outcome_constraints
+    return [partial(_oc, a, rhs) for a, rhs in zip(A, b)]
+
+
+def _linear_outcome_constraints(constraints):
+    """(A k x m, rhs k) as nested host lists when every callable is a partial
+    of :func:`get_outcome_constraint_transforms`; None for any other callable
+    or a mixed list."""
+    if not constraints:
+        return None
+    A, rhs = [], []
+    for c in constraints:
+        if not (isinstance(c, partial) and c.func is _oc and len(c.args) == 2 and not c.keywords):
+            return None
+        a, r = c.args
+        if not (torch.is_tensor(a) and a.dim() == 1 and torch.is_tensor(r) and r.numel() == 1):
+            return None
+        A.append([float(v) for v in a.tolist()])
+        rhs.append(float(r))
+    if len({len(row) for row in A}) != 1:
+        return None
+    return A, rhs
 
 
 def get_infeasible_cost(X: torch.Tensor, model, objective=None, posterior_transform=None):

@@ -918,6 +918,47 @@ typedef struct BoQlogehviArgs {
 int bo_qlogehvi_v(const BoQlogehviArgs* a, void* stream);
 int bo_qlogehvi_backward_v(const BoQlogehviArgs* a, void* stream);
 
+/* Feasibility-weighted qEI / qLogEI / qNEI / qLogNEI over the Mt <= 8
+ * single-output members of a model list (botorch/acquisition/monte_carlo.py:
+ * 253-330, logei.py:219-234, utils/objective.py:134-180), q <= 16.  Layouts as
+ * BoQehviFeasArgs with zm = Mt, zld = q Mt: mean Mt x B x q, L Mt x B x q x q
+ * (lower triangle read), Z S x (q Mt) with column j Mt + t, F (optional)
+ * Mt x S x ldF (member stride sF, rows b Qp + a).  Per sample and point
+ *   f_t = mean + L z (+ F),  obj = sum_t c[t] f_t,
+ *   con_i = sum_t A[i * 8 + t] f_t - rhs[i]   (i < k <= 8),
+ *   l = sum_i logsig(-con_i / eta[i])  in this order; logsig = logexpit, or
+ *       log_fatmoid with fat;
+ *   plain: u_s = max_a relu(obj_a - bf_s) exp(l_a),            acq = mean_s u_s
+ *   log:   u_s = q_reduce_a(log_soft_relu(obj_a - bf_s) + l_a), acq = logmeanexp_s u_s
+ * (the smooth functions at tau_relu / tau_max, fat as for the constraints),
+ * bf_s = best_f_s[s] if given, else best_f.  With feas (S x B x q; then k = 0)
+ * the weights exp(l) (plain) or the log-weights l (log) are the caller's, and
+ * the backward returns their cotangent dfeas.  Backward: from dacq (B), and in
+ * log mode the forward's acq, writes dmean, dL (full q x q, upper zero), dF
+ * (with F; entries of rows a < q) following torch autograd: amax shares the
+ * cotangent evenly among all maximal entries (ties at 0 included), clamp_min
+ * passes it where obj - bf >= 0.  No atomics; fixed summation order.
+ * A pure addition to the ABI: BO_ABI_VERSION stays 11. */
+typedef struct BoQmcFeasArgs {
+  BO_STRUCT_HEADER;
+  int32_t B, q, Mt, S;
+  const double *mean, *L, *Z, *F;
+  int64_t ldF, sF;
+  int32_t Qp, k;
+  double best_f;
+  const double* best_f_s;
+  double c[8], A[64], rhs[8], eta[8];
+  const double* feas;
+  double* dfeas; /* backward only, with feas */
+  int32_t log, fat;
+  double tau_relu, tau_max;
+  double* acq; /* forward: output; backward (log): the forward's value */
+  const double* dacq;
+  double *dmean, *dL, *dF;
+} BoQmcFeasArgs;
+int bo_qmc_feas_v(const BoQmcFeasArgs* a, void* stream);
+int bo_qmc_feas_backward_v(const BoQmcFeasArgs* a, void* stream);
+
 typedef struct BoLbfgsStepArgs { /* bo_lbfgs_step */
   BO_STRUCT_HEADER;
   int32_t B, n, m, _pad;
