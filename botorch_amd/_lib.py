@@ -18,7 +18,10 @@ BO_OK, BO_ERR_ARG, BO_ERR_HIP, BO_ERR_NOT_PSD, BO_ERR_NAN = 0, 1, 2, 3, 4
 RBF, MATERN52 = 0, 1
 GEMM_LOWER_C, GEMM_A_LOWER, GEMM_B_UPPER, GEMM_A_UPPER, GEMM_B_LOWER = 1, 2, 4, 8, 16
 QMC_POSTERIOR, QMC_QEI, QMC_QNEI, QMC_CHOL, QMC_QLOGEI, QMC_QLOGNEI = 0, 1, 2, 3, 4, 5
+QMC_QSR, QMC_QPI, QMC_QUCB = 6, 7, 8  # qSimpleRegret, qProbabilityOfImprovement, qUCB
 LOG_MODES = (QMC_QLOGEI, QMC_QLOGNEI)
+# every mode with an acquisition value (the rest return moments / roots only)
+MC_MODES = (QMC_QEI, QMC_QNEI) + LOG_MODES + (QMC_QSR, QMC_QPI, QMC_QUCB)
 ABI_VERSION = 11
 RT_ROWMAJOR, RT_BLOCKED = 0, 1  # BoPostPartialsArgs.rt_layout (include/botorch_amd.h)
 

@@ -1,7 +1,8 @@
 """Acquisition functions on the accelerated path (BoTorch-compatible API).
 
-MC family: acquisition/monte_carlo.py:60-645 (SampleReducingMCAcquisitionFunction,
-qExpectedImprovement, qNoisyExpectedImprovement); multi-objective qEHVI:
+MC family: acquisition/monte_carlo.py:60-871 (SampleReducingMCAcquisitionFunction,
+qExpectedImprovement, qNoisyExpectedImprovement, qProbabilityOfImprovement,
+qSimpleRegret, qUpperConfidenceBound); multi-objective qEHVI:
 acquisition/multi_objective/monte_carlo.py:146-322; analytic EI / PI / UCB:
 acquisition/analytic.py.
 
@@ -158,11 +159,15 @@ class MCAcquisitionFunction(AcquisitionFunction):
         return _ensemble_mean(self.model, self._sample_reduction(self._q_reduction(acqval)))
 
 
-def _fused_mc(X3: torch.Tensor, acqf, mode: int, best_f: float, best_f_s, Z: torch.Tensor):
-    """qEI / qLogEI value of B t-batches on the gfx950 fused path through
-    bo::qmc_acq (one torch.ops call; its registered backward gives dX).  The
-    jitter-ladder status is read at the end of the backward when a gradient
-    follows, else one call later (kernels.raise_not_psd_deferred)."""
+def _fused_mc(X3: torch.Tensor, acqf, mode: int, best_f: float, best_f_s, Z: torch.Tensor,
+              tau: Optional[float] = None):
+    """qEI / qLogEI / qSR / qPI / qUCB value of B t-batches on the gfx950 fused
+    path through bo::qmc_acq (one torch.ops call; its registered backward gives
+    dX).  The jitter-ladder status is read at the end of the backward when a
+    gradient follows, else one call later (kernels.raise_not_psd_deferred).
+    The modes' parameters ride in the existing slots (include/botorch_amd.h):
+    qPI's ``tau`` in tau_relu, qUCB's beta' in ``best_f`` and the base samples'
+    mean in ``best_f_s``."""
     from . import ops  # torch.ops.bo registration, QmcAcqGrad
     model = acqf.model
     cache = model.prediction_cache()
@@ -170,10 +175,12 @@ def _fused_mc(X3: torch.Tensor, acqf, mode: int, best_f: float, best_f_s, Z: tor
     need_grad = torch.is_grad_enabled() and X3.requires_grad
     lp = getattr(acqf, "_log_params", None)
     fat, tau_relu, tau_max = lp if lp is not None else (True, 1.0, 1.0)
+    if tau is not None:
+        tau_relu = tau
     dev = X3.device
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
     if X3.dtype != torch.float64:  # the model computes in fp64; the value returns in X's dtype
-        return _fused_mc(X3.to(torch.float64), acqf, mode, best_f, best_f_s, Z).to(X3.dtype)
+        return _fused_mc(X3.to(torch.float64), acqf, mode, best_f, best_f_s, Z, tau).to(X3.dtype)
     cap = kernels._CAPTURE_STATUS.get(idx) if idx in kernels._CAPTURE else None
     if not need_grad and not kernels.SYNC_LADDER and (idx not in kernels._CAPTURE or cap):
         # eager forward-only: ONE native call issues the whole chain and defers
@@ -338,6 +345,98 @@ class _SaasQEI(torch.autograd.Function):
             dX = kernels.kernel_grad(ctx.X2, ctx.X2, Gm[mi].contiguous(), ls, ens["kind"], os_,
                                      group=q, dX=dX)
         return dX.reshape(B, q, d), None, None, None
+
+
+class _PlainMaxMCAcquisitionFunction(MCAcquisitionFunction):
+    """The sample-reducing acquisitions without a relu (qSR, qPI, qUCB): qEI's
+    forward shape -- the fused kernels under ``_fused_eligible`` (mode
+    ``_fused_mode`` with the parameters of ``_fused_params``), else the generic
+    route through ``_sample_forward``."""
+
+    _fused_mode: int
+
+    def _fused_ok(self, X: torch.Tensor) -> bool:
+        return self._fused_eligible(X)
+
+    def _fused_params(self, q: int, device):
+        """(best_f slot, best_f_s slot, tau) as host floats / a device tensor."""
+        return 0.0, None, None
+
+    def forward(self, X: torch.Tensor) -> torch.Tensor:
+        X = self._concat_pending(t_batch_mode(X))
+        if self._fused_ok(X):
+            batch, q = X.shape[:-2], X.shape[-2]
+            Z = self._ensure_sampler().base_samples_2d(q, X.device)
+            best_f, best_f_s, tau = self._fused_params(q, X.device)
+            acq = _fused_mc(X.reshape(-1, q, X.shape[-1]), self, self._fused_mode, best_f, best_f_s,
+                            Z, tau)
+            return acq.reshape(batch)
+        return self._generic_forward(X)
+
+
+class qProbabilityOfImprovement(_PlainMaxMCAcquisitionFunction):
+    """MC batch PI (acquisition/monte_carlo.py:648-731): the indicator of
+    improvement smoothed by a sigmoid at temperature ``tau``,
+    qPI(X) = E[max_j sigmoid((Y_j - best_f) / tau)]."""
+
+    _fused_mode = _lib.QMC_QPI
+
+    def __init__(self, model, best_f: Union[float, torch.Tensor], sampler=None, objective=None,
+                 posterior_transform=None, X_pending=None, tau: float = 1e-3, constraints=None,
+                 eta=1e-3):
+        super().__init__(model, sampler, objective, posterior_transform, X_pending,
+                         constraints=constraints, eta=eta)
+        self.register_buffer("best_f", torch.as_tensor(best_f, dtype=torch.float64).unsqueeze(-1))
+        self.register_buffer("tau", torch.as_tensor(tau, dtype=torch.float64))
+
+    def _sample_forward(self, obj: torch.Tensor) -> torch.Tensor:
+        """monte_carlo.py:721-731."""
+        return torch.sigmoid((obj - self.best_f.to(obj)) / self.tau.to(obj))
+
+    def _fused_ok(self, X: torch.Tensor) -> bool:
+        return self._fused_eligible(X) and self.best_f.numel() == 1
+
+    def _fused_params(self, q: int, device):
+        return _host_scalar(self, "best_f"), None, _host_scalar(self, "tau")
+
+
+class qSimpleRegret(_PlainMaxMCAcquisitionFunction):
+    """MC batch simple regret (acquisition/monte_carlo.py:734-798):
+    qSR(X) = E[max_j Y_j].  Values may be negative, so there is no
+    ``constraints`` argument (use a ConstrainedMCObjective)."""
+
+    _fused_mode = _lib.QMC_QSR
+
+    def __init__(self, model, sampler=None, objective=None, posterior_transform=None,
+                 X_pending=None):
+        super().__init__(model, sampler, objective, posterior_transform, X_pending)
+
+    def _sample_forward(self, obj: torch.Tensor) -> torch.Tensor:
+        """monte_carlo.py:789-798."""
+        return obj
+
+
+class qUpperConfidenceBound(_PlainMaxMCAcquisitionFunction):
+    """MC batch UCB (acquisition/monte_carlo.py:801-871, [Wilson2017reparam]
+    appendix A): qUCB(X) = E[max_j (mu_j + beta' |Y_j - mu_j|)] with
+    beta' = sqrt(beta pi / 2) and mu the mean of the samples (not of the
+    posterior), as the reference computes it."""
+
+    _fused_mode = _lib.QMC_QUCB
+
+    def __init__(self, model, beta: float, sampler=None, objective=None, posterior_transform=None,
+                 X_pending=None):
+        super().__init__(model, sampler, objective, posterior_transform, X_pending)
+        self.beta_prime = math.sqrt(beta * math.pi / 2)
+
+    def _sample_forward(self, obj: torch.Tensor) -> torch.Tensor:
+        """monte_carlo.py:861-871."""
+        mean = obj.mean(dim=0)
+        return mean + self.beta_prime * (obj - mean).abs()
+
+    def _fused_params(self, q: int, device):
+        # mean_s f = mu' + L_q zbar: the base samples' mean, kept with them
+        return self.beta_prime, self._ensure_sampler().base_sample_mean_2d(q, device), None
 
 
 # -- analytic ------------------------------------------------------------------------

@@ -2,7 +2,8 @@
 //
 // gen_candidates_scipy differentiates -acqf(X).sum() w.r.t. X once per
 // L-BFGS-B iteration (botorch/generation/gen.py:194-222).  The chain is
-//   reduction (one-hot q-argmax of relu(f - best_f), 1/S)  ->  d mu', d L_q
+//   reduction (one-hot q-argmax of relu(f - best_f), 1/S; of f, sigmoid((f -
+//   best_f)/tau), fbar + beta' |f - fbar| for qSR / qPI / qUCB)  ->  d mu', d L_q
 //   -> Cholesky backward (torch's linalg.cholesky backward, Murray 2016)  -> d Sigma'
 //   -> Standardize: d mu* = s d mu', d Sigma* = s^2 d Sigma'
 //   -> exact prediction: mu* = c + K*x alpha,  Sigma* = K** - K*x A^{-1} K*x^T
@@ -28,7 +29,8 @@ constexpr int SMAX = 256;  // samples staged in LDS per pass (winner masks + bas
 // and a 16-double (128 B) stride put the wave's 64 rows on two bank groups
 constexpr int ZST = QMAX + 1;
 
-enum { MODE_QEI = 1, MODE_QNEI = 2, MODE_QLOGEI = 4, MODE_QLOGNEI = 5 };
+enum { MODE_QEI = 1, MODE_QNEI = 2, MODE_QLOGEI = 4, MODE_QLOGNEI = 5, MODE_QSR = 6, MODE_QPI = 7,
+       MODE_QUCB = 8 };
 
 // qNEI (cached root): the samples carry the baseline term F[s][row] =
 // (Z_base T)[s][row] (row = b * Qp + a); its cotangent dF (same layout) is the
@@ -157,12 +159,20 @@ __global__ __launch_bounds__(THREADS) void chol_backward_big_kernel(
   }
 }
 
+// qSR / qPI / qUCB (BO_QMC_QSR / QPI / QUCB): one-hot weights as qEI, without
+// the relu.  Slots: qPI's tau in tau, qUCB's beta' in best_f and zbar (q
+// doubles, the base samples' mean) in best_f_s.
+__host__ __device__ constexpr bool plain_max_mode(int mode) {
+  return mode == MODE_QSR || mode == MODE_QPI || mode == MODE_QUCB;
+}
+
 template <int MODE>
 __global__ __launch_bounds__(THREADS) void qmc_backward_kernel(
     int q, const double* __restrict__ mean, const double* __restrict__ Lq,
     const double* __restrict__ Z, int S, double best_f, const double* __restrict__ best_f_s,
     const double* __restrict__ dacq, double* __restrict__ dmean, double* __restrict__ dcov,
-    const double* __restrict__ F, int64_t ldF, int Qp, double* __restrict__ dF) {
+    const double* __restrict__ F, int64_t ldF, int Qp, double* __restrict__ dF, double tau) {
+  constexpr bool UCB = MODE == MODE_QUCB;
   __shared__ double L[QMAX][QMAX + 1];
   __shared__ double Li[QMAX][QMAX + 1];   // L^{-1}
   __shared__ double dL[QMAX][QMAX + 1];
@@ -170,6 +180,8 @@ __global__ __launch_bounds__(THREADS) void qmc_backward_kernel(
   __shared__ double Tm[QMAX][QMAX + 1];
   __shared__ double mu[QMAX];
   __shared__ unsigned short win[SMAX];
+  __shared__ unsigned short neg[UCB ? SMAX : 1];   // qUCB: winners with e < 0 / e == 0
+  __shared__ unsigned short zer[UCB ? SMAX : 1];
   __shared__ double wgt[SMAX];
   __shared__ double Zs[SMAX * ZST];    // the chunk's base samples (shared by every t-batch)
 
@@ -181,6 +193,15 @@ __global__ __launch_bounds__(THREADS) void qmc_backward_kernel(
   }
   if (tid < q) mu[tid] = mean[(int64_t)b * q + tid];
   __syncthreads();
+  if (UCB) {
+    // the sample mean of row a, fbar_a = mu'_a + (L_q zbar)_a, in mu's place
+    if (tid < q) {
+      double fb = mu[tid];
+      for (int j = 0; j <= tid; ++j) fb = fma(L[tid][j], best_f_s[j], fb);
+      mu[tid] = fb;
+    }
+    __syncthreads();
+  }
   const double g = dacq[b] / (double)S;
 
   double dmu_acc = 0.0, dl_acc = 0.0;
@@ -192,7 +213,12 @@ __global__ __launch_bounds__(THREADS) void qmc_backward_kernel(
   }
   for (int s0 = 0; s0 < S; s0 += SMAX) {
     const int ns = min(SMAX, S - s0);
-    for (int e = tid; e < ns * q; e += THREADS) Zs[(e / q) * ZST + e % q] = Z[(int64_t)s0 * q + e];
+    // (qUCB stages z - zbar: both passes read the centred samples)
+    for (int e = tid; e < ns * q; e += THREADS) {
+      double zv = Z[(int64_t)s0 * q + e];
+      if (UCB) zv -= best_f_s[e % q];
+      Zs[(e / q) * ZST + e % q] = zv;
+    }
     // Pass 1: the winning (maximal, non-clamped) q-index set per sample.
     __syncthreads();  // Zs
     for (int s = tid; s < ns; s += THREADS) {
@@ -200,6 +226,49 @@ __global__ __launch_bounds__(THREADS) void qmc_backward_kernel(
       double zr[QMAX];  // the sample's row once, in registers
 #pragma unroll
       for (int j = 0; j < QMAX; ++j) zr[j] = j < q ? z[j] : 0.0;
+      if (plain_max_mode(MODE)) {
+        // v_a: f_a (qSR), sigmoid((f_a - best_f) / tau) (qPI: torch takes amax
+        // over the sigmoid values, so ties are theirs), fbar_a + beta' |e_a| (qUCB)
+        double v[QMAX];
+        double m = -INFINITY;
+        unsigned ng = 0, zr0 = 0;
+#pragma unroll
+        for (int a = 0; a < QMAX; ++a) {
+          if (a < q) {
+            double f = UCB ? 0.0 : mu[a];
+#pragma unroll
+            for (int j = 0; j <= a; ++j) f = fma(L[a][j], zr[j], f);
+            if (UCB) {
+              if (f < 0.0) ng |= 1u << a;
+              if (f == 0.0) zr0 |= 1u << a;
+              v[a] = fma(best_f, fabs(f), mu[a]);
+            } else if (MODE == MODE_QPI) {
+              v[a] = 1.0 / (1.0 + exp(-((f - best_f) / tau)));
+            } else {
+              v[a] = f;
+            }
+            m = fmax(m, v[a]);
+          }
+        }
+        // torch: amax splits the gradient evenly among all maximal entries
+        unsigned mask = 0, cnt = 0;
+#pragma unroll
+        for (int a = 0; a < QMAX; ++a) {
+          if (a < q && v[a] == m) {
+            ++cnt;
+            mask |= 1u << a;
+          }
+        }
+        double w = cnt ? g / (double)cnt : 0.0;  // (cnt = 0: NaN values only)
+        if (MODE == MODE_QPI) w *= m * (1.0 - m) / tau;  // sigmoid' at the winning value
+        win[s] = (unsigned short)mask;
+        wgt[s] = w;
+        if (UCB) {
+          neg[s] = (unsigned short)(ng & mask);
+          zer[s] = (unsigned short)(zr0 & mask);
+        }
+        continue;
+      }
       const double bf = (MODE == MODE_QNEI) ? best_f_s[s0 + s] : best_f;
       double v[QMAX];
       double m = 0.0;
@@ -240,12 +309,20 @@ __global__ __launch_bounds__(THREADS) void qmc_backward_kernel(
 #pragma unroll 8
       for (int s = 0; s < ns; ++s) {
         const double w = (win[s] >> ta & 1u) ? wgt[s] : 0.0;
-        dl_acc = fma(w, Zs[s * ZST + tj], dl_acc);
+        if (UCB) {
+          // d|e|/dL[a][j] = sgn(e) (z_j - zbar_j), sgn(0) = 0 (torch.abs)
+          const double ws = (zer[s] >> ta & 1u) ? 0.0 : ((neg[s] >> ta & 1u) ? -w : w);
+          dl_acc = fma(ws, Zs[s * ZST + tj], dl_acc);
+        } else {
+          dl_acc = fma(w, Zs[s * ZST + tj], dl_acc);
+        }
         dmu_acc += w;
       }
     }
     __syncthreads();
   }
+  // qUCB: through the sample mean (fbar = mu' + L_q zbar) and through |e|
+  if (UCB && ta >= 0 && tj <= ta) dl_acc = fma(best_f, dl_acc, best_f_s[tj] * dmu_acc);
   if (ta >= 0) {
     dL[ta][tj] = (tj <= ta) ? dl_acc : 0.0;
     if (tj == 0) dmean[(int64_t)b * q + ta] = dmu_acc;
@@ -624,8 +701,12 @@ extern "C" int bo_qmc_backward(int mode, int B, int q, const double* mean, const
                                double* dcov, double* dF, const double* acq_fwd, int fat,
                                double tau_relu, double tau_max, void* stream) {
   BO_CHECK_ARG(q >= 1 && q <= QMAX, "bo_qmc_backward: q=%d out of range", q);
-  BO_CHECK_ARG(mode == MODE_QEI || mode == MODE_QNEI || mode == MODE_QLOGEI || mode == MODE_QLOGNEI,
+  BO_CHECK_ARG(mode == MODE_QEI || mode == MODE_QNEI || mode == MODE_QLOGEI ||
+                   mode == MODE_QLOGNEI || plain_max_mode(mode),
                "bo_qmc_backward: bad mode %d", mode);
+  BO_CHECK_ARG(mode != MODE_QPI || tau_relu > 0.0, "bo_qmc_backward: qPI needs tau > 0 (tau_relu)");
+  BO_CHECK_ARG(mode != MODE_QUCB || best_f_s,
+               "bo_qmc_backward: qUCB needs the base samples' mean zbar (best_f_s)");
   const bool per_sample = mode == MODE_QNEI || mode == MODE_QLOGNEI;
   const bool logm = mode == MODE_QLOGEI || mode == MODE_QLOGNEI;
   BO_CHECK_ARG(!per_sample || (best_f_s && F && dF),
@@ -639,9 +720,15 @@ extern "C" int bo_qmc_backward(int mode, int B, int q, const double* mean, const
   hipStream_t st = as_stream(stream);
   const LogRedParams lp{tau_relu, tau_max, fat};
   if (mode == MODE_QEI)
-    qmc_backward_kernel<MODE_QEI><<<B, THREADS, 0, st>>>(q, mean, Lq, Z, S, best_f, best_f_s, dacq, dmean, dcov, nullptr, 0, Qp, nullptr);
+    qmc_backward_kernel<MODE_QEI><<<B, THREADS, 0, st>>>(q, mean, Lq, Z, S, best_f, best_f_s, dacq, dmean, dcov, nullptr, 0, Qp, nullptr, 1.0);
   else if (mode == MODE_QNEI)
-    qmc_backward_kernel<MODE_QNEI><<<B, THREADS, 0, st>>>(q, mean, Lq, Z, S, best_f, best_f_s, dacq, dmean, dcov, F, ldF, Qp, dF);
+    qmc_backward_kernel<MODE_QNEI><<<B, THREADS, 0, st>>>(q, mean, Lq, Z, S, best_f, best_f_s, dacq, dmean, dcov, F, ldF, Qp, dF, 1.0);
+  else if (mode == MODE_QSR)
+    qmc_backward_kernel<MODE_QSR><<<B, THREADS, 0, st>>>(q, mean, Lq, Z, S, 0.0, nullptr, dacq, dmean, dcov, nullptr, 0, Qp, nullptr, 1.0);
+  else if (mode == MODE_QPI)
+    qmc_backward_kernel<MODE_QPI><<<B, THREADS, 0, st>>>(q, mean, Lq, Z, S, best_f, nullptr, dacq, dmean, dcov, nullptr, 0, Qp, nullptr, tau_relu);
+  else if (mode == MODE_QUCB)
+    qmc_backward_kernel<MODE_QUCB><<<B, THREADS, 0, st>>>(q, mean, Lq, Z, S, best_f, best_f_s, dacq, dmean, dcov, nullptr, 0, Qp, nullptr, 1.0);
   else if (mode == MODE_QLOGEI)
     qmc_log_backward_kernel<false><<<B, THREADS, 0, st>>>(q, mean, Lq, Z, S, best_f, best_f_s, acq_fwd, lp, dacq, dmean, dcov, nullptr, 0, Qp, nullptr);
   else

@@ -15,6 +15,10 @@
 //        qNEI : mean_s max_a relu(f - best_f[s])        (:580-589, cached baseline best)
 //        qLogEI / qLogNEI : logmeanexp_s fatmax_a log_fatplus(f - best_f(s))
 //                           (acquisition/logei.py:122, 219-234, 347-362; logred.h)
+//        qSR  : mean_s max_a f                          (acquisition/monte_carlo.py:789-798)
+//        qPI  : mean_s max_a sigmoid((f - best_f)/tau)  (:721-731)
+//        qUCB : mean_s max_a (fbar_a + beta' |f_a - fbar_a|), fbar = mean_s f = mu' + L_q zbar
+//               (:861-871; zbar = mean_s Z[s] comes with the base samples)
 //      q-max and the sample sum are wavefront shuffle reductions (an online
 //      (max, sum-exp) pair for logmeanexp).
 #include "common.h"
@@ -65,7 +69,13 @@ enum QmcMode : int {
   QMC_QNEI = 2,
   QMC_CHOL = 3,
   QMC_QLOGEI = 4,
-  QMC_QLOGNEI = 5
+  QMC_QLOGNEI = 5,
+  // the rest of the sample-reducing family (acquisition/monte_carlo.py:648-871):
+  // no relu, so their q-maxima start at -inf over the active rows
+  QMC_QSR = 6,   // mean_s max_a f
+  QMC_QPI = 7,   // mean_s max_a sigmoid((f - best_f) / tau); tau in lp.tau_relu
+  QMC_QUCB = 8   // mean_s max_a (fbar_a + beta' |f_a - fbar_a|), fbar = mu' + L_q zbar;
+                 // beta' in best_f, zbar (q doubles) in best_f_s
 };
 
 __host__ __device__ constexpr bool per_sample_best(int mode) {
@@ -74,6 +84,13 @@ __host__ __device__ constexpr bool per_sample_best(int mode) {
 __host__ __device__ constexpr bool log_mode(int mode) {
   return mode == QMC_QLOGEI || mode == QMC_QLOGNEI;
 }
+__host__ __device__ constexpr bool plain_max_mode(int mode) {
+  return mode == QMC_QSR || mode == QMC_QPI || mode == QMC_QUCB;
+}
+
+// torch.sigmoid's form: exp overflows to inf / underflows to 0 at |x| >> 700,
+// which gives exactly 0 / 1 (qPI's default tau = 1e-3 puts most samples there)
+__device__ __forceinline__ double sigmoid_d(double x) { return 1.0 / (1.0 + exp(-x)); }
 
 // sum_{ct < n} p[ct * stride] with U independent partial sums, so U of the
 // partials' loads are in flight together instead of one latency per partial
@@ -190,6 +207,16 @@ __device__ __forceinline__ void sample_phase(int tid, int q, int S, int row0,
 #pragma unroll
   for (int j = 0; j < QMAX; ++j) Lr[j] = (arow && j <= a_) ? Lq[a_][j] : 0.0;
   const double mu_a = arow ? mu[a_] : 0.0;
+  // qUCB: row a's sample mean fbar_a = mu'_a + (L_q zbar)_a (zbar in best_f_s)
+  // and the lane's own zbar_a, once per workgroup; the samples then carry
+  // e = L_q (z - zbar)
+  double fbar = mu_a, zbar_a = 0.0;
+  if (MODE == QMC_QUCB) {
+#pragma unroll
+    for (int j = 0; j < G; ++j)
+      if (j < q) fbar = fma(Lr[j], best_f_s[j], fbar);
+    zbar_a = arow ? best_f_s[a_] : 0.0;
+  }
   for (int s0 = 0; s0 < S; s0 += SB * PER) {
     double zb[SB], fb[SB], bb[SB];
 #pragma unroll
@@ -197,6 +224,7 @@ __device__ __forceinline__ void sample_phase(int tid, int q, int S, int row0,
       const int s = s0 + u * PER + SLOTS * wv + slot;
       const bool act = s < S && arow;
       zb[u] = act ? Z[(int64_t)s * q + a_] : 0.0;
+      if (MODE == QMC_QUCB && act) zb[u] -= zbar_a;
       fb[u] = (F != nullptr && act) ? F[(int64_t)s * ldF + row0 + a_] : 0.0;
       bb[u] = per_sample_best(MODE) ? (s < S ? best_f_s[s] : 0.0) : best_f;
     }
@@ -205,12 +233,19 @@ __device__ __forceinline__ void sample_phase(int tid, int q, int S, int row0,
       const int s = s0 + u * PER + SLOTS * wv + slot;
       const bool sv = s < S;
       const bool act = sv && arow;
-      const double f = lq_chain<G, 0>(Lr, zb[u], upper, mu_a + fb[u]);
+      // (qUCB: the chain carries e = L_q (z - zbar) alone)
+      const double f = lq_chain<G, 0>(Lr, zb[u], upper, MODE == QMC_QUCB ? 0.0 : mu_a + fb[u]);
       const double bf = bb[u];
       if (log_mode(MODE)) {
         const double li = act ? log_soft_relu(f - bf, lp, nullptr) : -INFINITY;
         const double uu = group_log_q_reduce<G>(li, act, lp);
         if (a_ == 0 && sv) lse = lse_push(lse, uu);
+      } else if (plain_max_mode(MODE)) {
+        // no relu: the maximum over the active rows only, possibly negative.
+        // qPI: the sigmoid is monotone, so one per sample after the q-max
+        const double val = MODE == QMC_QUCB ? fma(bf, fabs(f), fbar) : MODE == QMC_QPI ? f - bf : f;
+        const double v = group_max<G>(act ? val : -INFINITY);
+        if (a_ == 0 && sv) sum += MODE == QMC_QPI ? sigmoid_d(v / lp.tau_relu) : v;
       } else {
         // max_a relu(f_a - best_f) = relu(max_a (f_a - best_f)): fmax is exact
         const double v = group_max<G>(act ? f - bf : -INFINITY);
@@ -227,23 +262,39 @@ __device__ __forceinline__ void sample_serial(int tid, int q, int S, int row0,
                                               const double (&Lq)[QMAX][QMAX + 1],
                                               const double (&mu)[QMAX], const double (&zs)[QMAX],
                                               double bf, const double* __restrict__ F, int64_t ldF,
-                                              const LogRedParams& lp, double& sum, LseAcc& lse) {
+                                              const LogRedParams& lp, double& sum, LseAcc& lse,
+                                              const double* __restrict__ zbar_ucb) {
   const int s = tid;
   if (s >= S) return;
-  double vmax = 0.0;
+  // qEI's relu is folded into a maximum that starts at 0; qSR / qPI / qUCB
+  // have none (their values may be negative): -inf over the active rows
+  double vmax = plain_max_mode(MODE) ? -INFINITY : 0.0;
   double li[QMAX];
 #pragma unroll
   for (int a = 0; a < QMAX; ++a) {
     li[a] = 0.0;
     if (a < q) {
       double f = mu[a] + ((F != nullptr) ? F[(int64_t)s * ldF + row0 + a] : 0.0);
+      if (MODE == QMC_QUCB) {
+        // zs = z - zbar, zbar in zbar_ucb, bf = beta': fbar_a + beta' |e_a|
+        double e = 0.0;
+#pragma unroll
+        for (int j = 0; j <= a; ++j) {
+          f = fma(Lq[a][j], zbar_ucb[j], f);
+          e = fma(Lq[a][j], zs[j], e);
+        }
+        vmax = fmax(vmax, fma(bf, fabs(e), f));
+        continue;
+      }
 #pragma unroll
       for (int j = 0; j <= a; ++j) f = fma(Lq[a][j], zs[j], f);
       if (log_mode(MODE)) li[a] = log_soft_relu(f - bf, lp, nullptr);
+      else if (MODE == QMC_QSR) vmax = fmax(vmax, f);
       else vmax = fmax(vmax, f - bf);
     }
   }
   if (log_mode(MODE)) lse = lse_push(lse, log_q_reduce<QMAX>(li, q, lp, nullptr));
+  else if (MODE == QMC_QPI) sum += sigmoid_d(vmax / lp.tau_relu);
   else sum += vmax;
 }
 
@@ -402,7 +453,7 @@ __global__ __launch_bounds__(THREADS) void qmc_kernel(
     const double* z = Z + (int64_t)tid * q;
 #pragma unroll
     for (int j = 0; j < QMAX; ++j)
-      if (j < q) zs[j] = z[j];
+      if (j < q) zs[j] = MODE == QMC_QUCB ? z[j] - best_f_s[j] : z[j];  // qUCB: z - zbar
     if (per_sample_best(MODE)) bf_s = best_f_s[tid];
   }
 
@@ -570,7 +621,7 @@ __global__ __launch_bounds__(THREADS) void qmc_kernel(
   double sum = 0.0;
   LseAcc lse{-INFINITY, 0.0};
   if (serial)
-    sample_serial<MODE>(tid, q, S, row0, Lq, mu, zs, bf_s, F, ldF, lp, sum, lse);
+    sample_serial<MODE>(tid, q, S, row0, Lq, mu, zs, bf_s, F, ldF, lp, sum, lse, best_f_s);
   else if (q > 8)
     sample_phase<16, MODE>(tid, q, S, row0, Lq, mu, Z, F, ldF, best_f, best_f_s, lp, sum, lse);
   else
@@ -645,6 +696,9 @@ void launch_qmc(int mode, int B, const QmcArgs& a, hipStream_t st) {
   else if (mode == QMC_QNEI) launch_mode<KIND, QMC_QNEI>(B, a, st);
   else if (mode == QMC_QLOGEI) launch_mode<KIND, QMC_QLOGEI>(B, a, st);
   else if (mode == QMC_QLOGNEI) launch_mode<KIND, QMC_QLOGNEI>(B, a, st);
+  else if (mode == QMC_QSR) launch_mode<KIND, QMC_QSR>(B, a, st);
+  else if (mode == QMC_QPI) launch_mode<KIND, QMC_QPI>(B, a, st);
+  else if (mode == QMC_QUCB) launch_mode<KIND, QMC_QUCB>(B, a, st);
   else launch_mode<KIND, QMC_CHOL>(B, a, st);
 }
 
@@ -688,7 +742,7 @@ extern "C" int bo_qmc_finalize_ext(int kind, int mode, int B, int q, const doubl
                                const double* F, int64_t ldF, int fat, double tau_relu,
                                double tau_max, int nparts, int sym_parts, double* status_out,
                                int* status_count, void* stream) {
-  BO_CHECK_ARG(mode >= 0 && mode <= 5, "bo_qmc_finalize: bad mode %d", mode);
+  BO_CHECK_ARG(mode >= 0 && mode <= QMC_QUCB, "bo_qmc_finalize: bad mode %d", mode);
   BO_CHECK_ARG(nparts >= 0 && (sym_parts == 0 || nparts > 0),
                "bo_qmc_finalize: nparts %d / sym_parts %d", nparts, sym_parts);
   BO_CHECK_ARG(status_out == nullptr ||
@@ -701,6 +755,11 @@ extern "C" int bo_qmc_finalize_ext(int kind, int mode, int B, int q, const doubl
                "bo_qmc_finalize: missing MC args");
   BO_CHECK_ARG(!per_sample_best(mode) || best_f_s,
                "bo_qmc_finalize: qNEI / qLogNEI need per-sample best_f");
+  BO_CHECK_ARG(mode != QMC_QPI || tau_relu > 0.0, "bo_qmc_finalize: qPI needs tau > 0 (tau_relu)");
+  BO_CHECK_ARG(mode != QMC_QUCB || best_f_s,
+               "bo_qmc_finalize: qUCB needs the base samples' mean zbar (best_f_s)");
+  BO_CHECK_ARG(!plain_max_mode(mode) || (Tm == nullptr && F == nullptr),
+               "bo_qmc_finalize: qSR / qPI / qUCB take no cached-root terms");
   BO_CHECK_ARG((Tm == nullptr) == (F == nullptr) && (Tm == nullptr || r > 0),
                "bo_qmc_finalize: cached-root qNEI needs both T and F");
   int Qp, nrows_pad, nC;

@@ -805,6 +805,8 @@ def qmc_finalize(cache: GPCache, pp: PostPartials, mode: int, ymean: float, ystd
                  log_params: Optional[tuple] = None, mean_out: Optional[torch.Tensor] = None,
                  L_out: Optional[torch.Tensor] = None, status=None):
     """log_params = (fat, tau_relu, tau_max) for the qLogEI / qLogNEI modes.
+    QMC_QPI: tau in log_params' tau_relu; QMC_QUCB: beta' in best_f and the
+    base samples' mean zbar (q) in best_f_s (include/botorch_amd.h).
     mean_out / L_out: contiguous B x q / B x q x q buffers to write instead of
     fresh ones (a ModelListGP's members straight into their stacked slices).
     status: (status_out, status_count) device pointers the launch folds the
@@ -818,7 +820,7 @@ def qmc_finalize(cache: GPCache, pp: PostPartials, mode: int, ymean: float, ystd
     mean = (mean_out if mean_out is not None else torch.empty(B, q, **f64)) if want_mean else None
     cov = torch.empty(B, q, q, **f64) if want_cov else None
     L = (L_out if L_out is not None else torch.empty(B, q, q, **f64)) if want_L else None
-    need_mc = mode in (_lib.QMC_QEI, _lib.QMC_QNEI) + _lib.LOG_MODES
+    need_mc = mode in _lib.MC_MODES
     fat, tau_relu, tau_max = log_params if log_params is not None else (1, 1.0, 1.0)
     acq = torch.empty(B, **f64) if need_mc else None
     info = torch.empty(B, dtype=torch.int32, device=dev) if mode != _lib.QMC_POSTERIOR else None
@@ -1067,7 +1069,8 @@ def qmc_backward(mode: int, mean: torch.Tensor, L: torch.Tensor, Z: torch.Tensor
                  acq_fwd: Optional[torch.Tensor] = None, log_params: Optional[tuple] = None):
     """dacq -> (dmean, dcov[, dF]).  qNEI passes F = Z_base T (S x nrows_pad) and
     gets its cotangent dF back as a third output.  The log modes also take the
-    forward values acq_fwd and log_params = (fat, tau_relu, tau_max)."""
+    forward values acq_fwd and log_params = (fat, tau_relu, tau_max).  QMC_QPI /
+    QMC_QUCB: the parameter slots of qmc_finalize."""
     dev = mean.device
     B, q = mean.shape
     S = Z.shape[0]

@@ -18,8 +18,10 @@ Ops (reference computation each replaces):
   bo::post_partials   column-tile partials of R R^T and R beta  ([G] exact_predictive_covar)
   bo::qmc_finalize    posterior moments / q x q root / MC reduction
   bo::gp_posterior    outcome-space mean and covariance (+ autograd, posteriors/gpytorch.py)
-  bo::qmc_acq         fused qEI / qLogEI value of B t-batches (+ autograd,
-                      acquisition/monte_carlo.py:405-414, logei.py:137-234)
+  bo::qmc_acq         fused qEI / qLogEI / qSR / qPI / qUCB value of B t-batches
+                      (+ autograd, acquisition/monte_carlo.py:405-414, 648-871,
+                      logei.py:137-234; qPI's tau travels in tau_relu, qUCB's
+                      beta' in best_f and the base samples' mean in best_f_s)
   bo::qehvi           inclusion-exclusion qEHVI on the hypercells (+ autograd,
                       multi_objective/monte_carlo.py:230-317)
   bo::mll             exact marginal log likelihood data term and its gradient
@@ -222,7 +224,7 @@ def qmc_finalize(Spart: Tensor, mpart: Tensor, Xq: Tensor, Z: Optional[Tensor],
 def _(Spart, mpart, Xq, Z, best_f_s, B, q, n, kind, mode, outputscale, constant, ymean, ystd,
       best_f, fat, tau_relu, tau_max):
     mk = lambda *s: Xq.new_empty(*s, dtype=F64)  # noqa: E731
-    mc = mode in (_lib.QMC_QEI, _lib.QMC_QNEI) + _lib.LOG_MODES
+    mc = mode in _lib.MC_MODES
     post = mode == _lib.QMC_POSTERIOR
     return (mk(B) if mc else mk(0), mk(B, q), mk(B, q, q), mk(B, q, q),
             Xq.new_empty(0 if post else B, dtype=torch.int32), mk(0 if post else B))

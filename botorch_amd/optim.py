@@ -735,12 +735,14 @@ def _eval_flops(acquisition_function, B: int, q: int):
 
 
 def _fused_qei(acquisition_function, X: torch.Tensor) -> bool:
-    """The evaluation runs the fused qEI / qLogEI forward and backward (two
-    native calls, acquisition._fused_mc)."""
-    from .acquisition import qExpectedImprovement
+    """The evaluation runs the fused qEI / qLogEI / qSR / qPI / qUCB forward and
+    backward (two native calls, acquisition._fused_mc)."""
+    from .acquisition import _PlainMaxMCAcquisitionFunction, qExpectedImprovement
     acq = acquisition_function
     while hasattr(acq, "acq_func"):  # FixedFeatureAcquisitionFunction
         acq = acq.acq_func
+    if isinstance(acq, _PlainMaxMCAcquisitionFunction):
+        return bool(acq._fused_ok(X))
     return isinstance(acq, qExpectedImprovement) and bool(acq._fused_eligible(X))
 
 

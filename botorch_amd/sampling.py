@@ -59,6 +59,19 @@ class MCSampler(nn.Module):
             return True
         return False
 
+    def base_sample_mean_2d(self, dim: int, device) -> torch.Tensor:
+        """mean_s of base_samples_2d(dim) (``dim`` doubles on the device): what
+        the fused qUCB needs of the reference's ``obj.mean(dim=0)``.  Computed
+        when the base samples are made or replaced (their identity and version
+        are the key), not per forward."""
+        Z = self.base_samples_2d(dim, device)
+        bs = self.base_samples
+        hit = self.__dict__.get("_base_sample_mean")
+        if hit is None or hit[0] is not bs or hit[1] != bs._version:
+            hit = (bs, bs._version, Z.mean(dim=0))
+            self.__dict__["_base_sample_mean"] = hit
+        return hit[2]
+
     def _instance_check(self, base_sampler):
         """sampling/base.py:142-148."""
         if not isinstance(base_sampler, self.__class__):

@@ -62,6 +62,18 @@ extern "C" {
 #define BO_QMC_CHOL 3 /* finalise + jittered q x q Cholesky only (no MC) */
 #define BO_QMC_QLOGEI 4  /* qLogExpectedImprovement (acquisition/logei.py:137-234) */
 #define BO_QMC_QLOGNEI 5 /* qLogNoisyExpectedImprovement, cached root (logei.py:236-507) */
+/* The rest of the sample-reducing family (acquisition/monte_carlo.py:648-871).
+ * They reuse the parameter slots of bo_qmc_finalize / bo_qmc_backward:
+ *   mode      best_f           tau_relu   best_f_s
+ *   QSR       ignored          ignored    ignored
+ *   QPI       best_f           tau (> 0)  ignored
+ *   QUCB      beta' =          ignored    zbar (q doubles, not NULL):
+ *             sqrt(beta pi/2)             zbar[j] = mean_s Z[s][j]
+ * (fat, tau_max, Tm, F, dF, acq_fwd are not read). */
+#define BO_QMC_QSR 6  /* qSimpleRegret: mean_s max_a f */
+#define BO_QMC_QPI 7  /* qProbabilityOfImprovement: mean_s max_a sigmoid((f - best_f) / tau) */
+#define BO_QMC_QUCB 8 /* qUpperConfidenceBound: mean_s max_a (fbar_a + beta' |f_a - fbar_a|),
+                       * fbar = mean_s f (the sample mean, as the reference's obj.mean(dim=0)) */
 
 const char* bo_last_error(void);
 int bo_version(void);
@@ -495,6 +507,11 @@ int bo_post_split_table(int64_t B, int q, int64_t n, int kc_len, int* segs, int 
  *              with the q-reduction at temperature tau_max
  *              [acquisition/logei.py:122, 219-234, 347-362, 509-534;
  *               utils/safe_math.py:209-352]; fat/tau_* are ignored by other modes
+ *            qSR  mean_s max_a f                      [acquisition/monte_carlo.py:789-798]
+ *            qPI  mean_s max_a sigmoid((f - best_f) / tau), tau in tau_relu   [:721-731]
+ *            qUCB mean_s max_a (fbar_a + beta' |f_a - fbar_a|), fbar = mean_s f =
+ *                 mean' + L_q zbar; beta' in best_f, zbar (q) in best_f_s       [:861-871]
+ *            (the slots per mode: see BO_QMC_QSR above)
  * Z: S x q base samples (SobolQMCNormalSampler, sampling/normal.py:178-209).
  * Output pointers may be NULL when not needed (acq required for QEI/QNEI).
  * Cached-root qNEI (utils/low_rank.py:85-173, acquisition/cached_cholesky.py):
@@ -520,7 +537,13 @@ int bo_qmc_finalize(int kind, int mode, int B, int q, const double* Xq, const do
  * layout) receives its cotangent, from which dT = Z_base^T dF.  F/dF may be
  * NULL for qEI.  Log modes (BO_QMC_QLOGEI / BO_QMC_QLOGNEI) also take the
  * forward values acq_fwd (B) and the forward's fat / tau_relu / tau_max; their
- * weights are dense over (sample, q) rather than one-hot. */
+ * weights are dense over (sample, q) rather than one-hot.
+ * BO_QMC_QSR / BO_QMC_QPI / BO_QMC_QUCB: one-hot weights as qEI (amax ties
+ * split evenly; qPI's scaled by sigma (1 - sigma) / tau at the winning value,
+ * ties taken among the sigmoid values as torch.amax sees them); qUCB also
+ * carries the gradient through the sample mean,
+ *   dL[a][j] = zbar[j] sum_s w + beta' sum_s w sgn(e) (Z[s][j] - zbar[j]),
+ *   e = (L_q (z_s - zbar))[a], sgn(0) = 0.  Parameter slots as the forward's. */
 int bo_qmc_backward(int mode, int B, int q, const double* mean, const double* Lq,
                     const double* Z, int S, double best_f, const double* best_f_s,
                     const double* F, int64_t ldF, const double* dacq, double* dmean,
