@@ -17,9 +17,8 @@ from __future__ import annotations
 
 import copy
 import math
-import os
 import warnings
-from typing import Callable, List, Optional, Union
+from typing import Callable, List, NamedTuple, Optional, Union
 
 import torch
 from torch import nn
@@ -714,7 +713,7 @@ class qNoisyExpectedImprovement(MCAcquisitionFunction):
         self._init_baseline(model, X_baseline, prune_baseline, cache_root, marginalize_dim)
 
     def _init_baseline(self, model, X_baseline, prune_baseline, cache_root, marginalize_dim):
-        # outcome constraints on the fused route (per-member cached roots, _FusedQNEIFeas):
+        # outcome constraints on the fused route (per-member cached roots, _FusedSOFeas):
         # a single Sobol sampler; on a model list it must be given (without one the
         # generic route builds a ListSampler, which keeps that route)
         wplan = _weighted_so_plan(self) if cache_root else None
@@ -913,7 +912,7 @@ class qNoisyExpectedImprovement(MCAcquisitionFunction):
             plan = _weighted_so_route(self, X)
             if plan is not None:
                 try:
-                    acq = _FusedQNEIFeas.apply(X.reshape(-1, q, d).to(torch.float64), self, plan)
+                    acq = _FusedSOFeas.apply(X.reshape(-1, q, d).to(torch.float64), self, plan, None, None)
                     return acq.to(X.dtype).reshape(batch)
                 except (NotPSDError, NanError):
                     warnings.warn("Low-rank cholesky updates failed due NaNs or due to an "
@@ -1080,7 +1079,7 @@ def _qehvi_members_eager(acqf, X3: torch.Tensor):
     with BO_SYNC_LADDER=1, one stream sync and the members' outcomes raised /
     warned in member order.
     None where it does not apply (graph capture; members of unequal shape or
-    kernel; more than 8 members): the caller takes _FusedQEHVI."""
+    kernel; more than 8 members): the caller takes _FusedHVI."""
     dev = X3.device
     idx = kernels._dev_index(dev)
     if idx in kernels._CAPTURE:
@@ -1120,121 +1119,194 @@ def _qehvi_members_eager(acqf, X3: torch.Tensor):
     return acq
 
 
-class _FusedQEHVI(torch.autograd.Function):
-    """qEHVI of B t-batches over a ModelListGP, with its gradient.
+class _MemberPosterior(NamedTuple):
+    """What _member_posterior leaves for the reduction kernel and the backward."""
+    mean: torch.Tensor              # M x B x q
+    L: torch.Tensor                 # M x B x q x q
+    F: Optional[torch.Tensor]       # M x S x nrows_pad cached-root sample term (None without roots)
+    Qp: int                         # row stride of a t-batch in F (0 without roots)
+    saved: list                     # per member (cache, pp, ystd, T, W); empty without a gradient
+    batched: bool                   # the cached-root terms went as GEMMs batched over the members
+    info: object                    # the members' ladder outputs, indexed by member
+    jitter: object
+    root_acqf: object               # the acquisition function that owns the roots, or None
 
-    Forward: per output, post_partials + qmc_finalize(CHOL) (posterior mean and
-    jittered q x q root), then bo_qehvi over (sample, cell) pairs.
-    Backward: bo_qehvi_backward (inclusion-exclusion derivative) -> d mu_t, d L_t;
-    bo_chol_backward -> d Sigma_t; bo_post_backward per output model."""
+
+def _member_posterior(members, X3, need_grad: bool, ladder, root_acqf=None) -> _MemberPosterior:
+    """The posterior stage shared by the fused ModelListGP acquisitions (qEHVI,
+    qNEHVI, constrained qEI / qNEI and their log forms): every member's mean and
+    jittered q x q root of the B t-batches, written straight into their slices
+    of the stacked M x B x q (x q) inputs of the reduction launch (no stack
+    copies), the ladder outcomes folded into ``ladder.words`` where it has any.
+
+    Without ``root_acqf``: post_partials_members (one launch where the
+    small-grid or member stream-K plan applies), the finalisation, W.
+
+    With ``root_acqf`` (cached baseline roots, ``root_acqf._roots``): per
+    member additionally T_t = L_rr,t^{-1} Sigma'_t(X_b, X) and F_t = Z_b,t T_t,
+    and the root of Sigma'_t - T_t^T T_t.  Where the one-model plan splits k
+    (C4) the cross term cannot ride in the posterior pass and R^T is stored
+    anyway: then every member's partials + R^T in one launch, and the root
+    terms as GEMMs batched over the members where _roots_batched allows;
+    elsewhere per member (post_partials with the cross term, two GEMMs + one)."""
+    M = len(members)
+    B, q, _ = X3.shape
+    Xd = X3.detach()
+    roots = root_acqf._roots if root_acqf is not None else None
+    keys = prime_prediction_caches(members)
+    caches = [mm.prediction_cache(key=key) for mm, key in zip(members, keys)]
+    c0 = caches[0]
+    pps = None
+    if roots is None:
+        pps = kernels.post_partials_members(caches, Xd, store_R=need_grad)
+    elif (1 < M <= 8 and kernels.split_plan(B, q, c0.n)[0] != 0
+            and all(c.n == c0.n and c.np == c0.np and c.d == c0.d for c in caches)):
+        pps = kernels.post_partials_members(caches, Xd, store_R=True)
+    f64 = dict(dtype=torch.float64, device=X3.device)
+    mean = torch.empty(M, B, q, **f64)
+    L = torch.empty(M, B, q, q, **f64)
+    stats = [mm.outcome_stats() for mm in members]
+    Ts = F = Ws = None
+    batched = roots is not None and pps is not None and _roots_batched(root_acqf, caches, pps, stats)
+    if batched:
+        # every member's T and F in three batched GEMMs over the members
+        Ts, F = _roots_forward_batched(root_acqf, caches, pps, stats)
+        if need_grad:
+            Ws = kernels.w_matrix_members(caches, pps)
+    elif roots is not None:
+        given, pps, Ts, Ws = pps, [], [], []
+        for t, (cache, rt) in enumerate(zip(caches, roots)):
+            pp = given[t] if given is not None else kernels.post_partials(
+                cache, Xd, store_R=need_grad, cross=rt.Q_b)
+            pps.append(pp)
+            if F is None:
+                F = torch.empty(M, rt.Z_base.shape[0], pp.nrows_pad, **f64)
+            Ts.append(rt.forward(cache, pp, stats[t][1], F_out=F[t])[0])
+            if need_grad:
+                Ws.append(kernels.w_matrix(cache, pp))
+    if (M <= 8 and all(p_.Spart.shape == pps[0].Spart.shape for p_ in pps)
+            and all(c.kind == c0.kind for c in caches)):
+        # every member's finalisation in one launch
+        info, jitter = kernels.qmc_finalize_members(caches, pps, stats, mean, L,
+                                                    status=ladder.words, Ts=Ts, F=F)
+    else:
+        info, jitter = [], []
+        for t, (cache, pp) in enumerate(zip(caches, pps)):
+            out = kernels.qmc_finalize(cache, pp, _lib.QMC_CHOL, *stats[t], want_mean=True,
+                                       want_cov=False, want_L=True, T=Ts[t] if Ts else None,
+                                       F=F[t] if F is not None else None, mean_out=mean[t],
+                                       L_out=L[t], status=ladder.words[t] if ladder.words else None)
+            info.append(out["info"])
+            jitter.append(out["jitter"])
+    saved = []
+    if need_grad:
+        if roots is None:
+            Ws = kernels.w_matrix_members(caches, pps)   # one launch where stream-K
+        saved = [(caches[t], pps[t], stats[t][1], Ts[t] if Ts else None, Ws[t]) for t in range(M)]
+    return _MemberPosterior(mean, L, F, pps[-1].Qp if roots is not None else 0, saved, batched,
+                            info, jitter, root_acqf)
+
+
+def _chol_backward_members(L, dL):
+    """d Sigma of every member's t-batches (M x B x q x q) in one launch."""
+    q = L.shape[-1]
+    return kernels.chol_backward(L.reshape(-1, q, q), dL.reshape(-1, q, q)).reshape(L.shape)
+
+
+def _member_posterior_backward(post: _MemberPosterior, dmean, dL, dF):
+    """(d mean, d L, d F) of _member_posterior's outputs -> dX: bo_chol_backward
+    (d Sigma_t), then the members' bo_post_backward passes -- with roots, behind
+    the cached-root backward (dT = Z_b^T dF - T G) and with a second pass per
+    member through K(X_b, X)."""
+    if post.root_acqf is None:
+        dcovs = _chol_backward_members(post.L, dL)
+        jobs = [dict(cache=cache, pp=pp, W=W, dmean=dmean[t], dcov=dcovs[t], ystd=ystd)
+                for t, (cache, pp, ystd, _, W) in enumerate(post.saved)]
+    elif post.batched:
+        jobs = _roots_backward_jobs(post, dmean, dL, dF)
+    else:
+        dX = None
+        for t, (cache, pp, ystd, T, W) in enumerate(post.saved):
+            dcov = kernels.chol_backward(post.L[t], dL[t])
+            dX = post.root_acqf._roots[t].backward(cache, pp, W, dmean[t], dcov,
+                                                   dF[t].contiguous(), T, ystd, dX=dX)
+        return dX
+    c0 = jobs[0]["cache"]
+    if 1 < len(jobs) <= 16 and all(j["cache"].kind == c0.kind and j["cache"].d == c0.d
+                                   for j in jobs):
+        return kernels.post_backward_jobs(jobs)     # every pass in one launch
+    dX = None
+    for job in jobs:
+        dX = kernels.post_backward(**job, dX=dX)
+    return dX
+
+
+class _FusedHVI(torch.autograd.Function):
+    """qEHVI / qNEHVI (plain, feasibility-weighted or log-space) of B t-batches
+    over a ModelListGP, with its gradient; ``noisy``: qNEHVI, the members'
+    cached baseline roots and per-sample cells.
+
+    Forward: _member_posterior, then one bo_qehvi / bo_qehvi_feas / bo_qlogehvi
+    launch over (sample, hypercell) pairs with f = mean + L z (+ F).
+    Backward: the kernel's backward (inclusion-exclusion derivative) -> d mu_t,
+    d L_t (, d F_t), then _member_posterior_backward."""
 
     @staticmethod
-    def forward(ctx, X3, acqf):
-        models = acqf.model.models
+    def forward(ctx, X3, acqf, noisy):
+        members = acqf.model.models
         need_grad = ctx.needs_input_grad[0]
-        q = X3.shape[-2]
-        saved = []
-        keys = prime_prediction_caches(models)
-        caches = [mm.prediction_cache(key=key) for mm, key in zip(models, keys)]
-        # every member's posterior partials in one launch where the small-grid
-        # plan applies (C4: the three outputs of the ModelListGP)
-        pps = kernels.post_partials_members(caches, X3.detach(), store_R=need_grad)
-        status = []
-        # every member's mean and q x q root written straight into its slice of
-        # the stacked m x B x q (x q) inputs of the qEHVI launch (no stack copies)
-        f64 = dict(dtype=torch.float64, device=X3.device)
-        mean = torch.empty(len(models), X3.shape[0], q, **f64)
-        L = torch.empty(len(models), X3.shape[0], q, q, **f64)
-        # outside graph capture the finalisation launches fold their ladder
-        # outcomes straight into pinned words (no status launches or copy); on
-        # the gradient path those words are read at the end of the backward
-        # (kernels._LadderRing), else once behind the qEHVI launch
-        idx = kernels._dev_index(X3.device)
-        pinned = idx not in kernels._CAPTURE and len(models) <= 8
-        ring = (kernels.ladder_ring(X3.device) if pinned and need_grad and not kernels.SYNC_LADDER
-                else None)
-        ps = kernels.pinned_status(X3.device) if pinned and ring is None else None
-        if ring is not None:
-            token, words = ring.take(len(models), "qEHVI posterior root")
-        else:
-            words = ps.arm(len(models)) if ps is not None else [None] * len(models)
-        stats = [mm.outcome_stats() for mm in models]
-        if (len(models) <= 8 and all(p_.Spart.shape == pps[0].Spart.shape for p_ in pps)
-                and all(c.kind == caches[0].kind for c in caches)):
-            # every member's finalisation in one launch
-            info, jit = kernels.qmc_finalize_members(caches, pps, stats, mean, L,
-                                                     status=words if pinned else None)
-            status = [(info[t], jit[t]) for t in range(len(models))]
-        else:
-            for t, (cache, pp) in enumerate(zip(caches, pps)):
-                out = kernels.qmc_finalize(cache, pp, _lib.QMC_CHOL, *stats[t], want_mean=True,
-                                           want_cov=False, want_L=True, mean_out=mean[t],
-                                           L_out=L[t], status=words[t])
-                status.append((out["info"], out["jitter"]))
+        q, dev = X3.shape[-2], X3.device
+        # forward-only qNEHVI defers the ladder outcome (the eager qEI's ring:
+        # no stream sync per call); forward-only qEHVI comes here only for the
+        # log, weighted and capture cases and reads it behind the launch
+        with kernels.member_ladder(dev, len(members), need_grad,
+                                   ("qNEHVI" if noisy else "qEHVI") + " posterior root",
+                                   defer_forward_only=noisy) as ladder:
+            post = _member_posterior(members, X3, need_grad, ladder, acqf if noisy else None)
+            mean, L, F, Qp = post[:4]
+            if noisy:
+                Z = acqf._base_samples_q(q, dev)
+                lo, hi = acqf._cells
+            else:
+                Z = acqf._ensure_sampler().base_samples_2d(q * len(members), dev)
+                lo, hi = acqf._cells(dev)
+            # the kernel itself (as the backward below): this Function already is
+            # the autograd node, the registered op's wrapper would only add host time
+            feas = ctx.log = None
+            if acqf._log:
+                acq, ctx.log = _log_hvi_forward(acqf, mean, L, Z, lo, hi, F, Qp, need_grad)
+            elif acqf._weighted:
+                # outcome constraints: the weighted kernel on the objective members
+                feas = _feas_weights(acqf, mean, L, Z, F, Qp, need_grad)
+                acq = kernels.qehvi_feas(mean, L, Z, lo, hi, feas[0].detach(), acqf._out_idx, F=F,
+                                         Qp=Qp)
+            else:
+                acq = kernels.qehvi(mean, L, Z, lo, hi, F=F, Qp=Qp)
+            # the members' ladders checked once, behind the reduction launch (one
+            # host read per forward instead of one per member, each of which
+            # drained the queue: ~40 us of idle device between members at C4)
+            ladder.finish(ctx, post.info, post.jitter)
         if need_grad:
-            Ws = kernels.w_matrix_members(caches, pps)   # one launch where stream-K
-            for t, (cache, pp) in enumerate(zip(caches, pps)):
-                saved.append((cache, pp, stats[t][1], Ws[t]))
-        sampler = acqf._ensure_sampler()
-        Z = sampler.base_samples_2d(q * len(models), X3.device)
-        lo, hi = acqf._cells(X3.device)
-        # the kernel itself (as the backward below): this Function already is
-        # the autograd node, the registered op's wrapper would only add host time
-        feas = None
-        ctx.log = None
-        if acqf._log:
-            acq, ctx.log = _log_hvi_forward(acqf, mean, L, Z, lo, hi, None, 0, need_grad)
-        elif acqf._weighted:
-            # outcome constraints: the weighted kernel on the objective members
-            feas = _feas_weights(acqf, mean, L, Z, None, 0, need_grad)
-            acq = kernels.qehvi_feas(mean, L, Z, lo, hi, feas[0].detach(), acqf._out_idx)
-        else:
-            acq = kernels.qehvi(mean, L, Z, lo, hi)
-        # the members' ladders checked once, behind the qEHVI launch (one host
-        # read per forward instead of one per member, each of which drained
-        # the queue: ~40 us of idle device between members at C4)
-        ctx.ladder = None
-        if ring is not None:
-            ring.record(token)
-            ctx.ladder = (ring, token)
-        elif ps is not None:
-            kernels.raise_not_psd_members(ps, len(models), X3.device, "qEHVI posterior root")
-        else:
-            kernels.raise_not_psd_many(status, "qEHVI posterior root")
-        if need_grad:
-            ctx.saved, ctx.mean, ctx.L, ctx.Z, ctx.cells = saved, mean, L, Z, (lo, hi)
-            ctx.feas, ctx.out_idx, ctx.acqf = feas, acqf._out_idx, acqf
+            ctx.acqf, ctx.post, ctx.Z, ctx.cells, ctx.feas = acqf, post, Z, (lo, hi), feas
         return acq
 
     @staticmethod
     def backward(ctx, dacq):
-        lo, hi = ctx.cells
+        acqf, (mean, L, F, Qp), (lo, hi) = ctx.acqf, ctx.post[:4], ctx.cells
+        dF = None
         if ctx.log is not None:
-            dmean, dL, _ = _log_hvi_backward(ctx.acqf, ctx.log, ctx.mean, ctx.L, ctx.Z, lo, hi,
-                                             dacq, None, 0)
+            dmean, dL, dF = _log_hvi_backward(acqf, ctx.log, mean, L, ctx.Z, lo, hi, dacq, F, Qp)
         elif ctx.feas is not None:
-            dmean, dL, dfeas = kernels.qehvi_feas_backward(ctx.mean, ctx.L, ctx.Z, lo, hi,
-                                                           ctx.feas[0].detach(), ctx.out_idx, dacq)
-            _feas_backward(ctx.feas, dfeas, dmean, dL, None)
+            dmean, dL, *dF, dfeas = kernels.qehvi_feas_backward(
+                mean, L, ctx.Z, lo, hi, ctx.feas[0].detach(), acqf._out_idx, dacq, F=F, Qp=Qp)
+            dF = dF[0] if dF else None              # returned with roots only
+            _feas_backward(ctx.feas, dfeas, dmean, dL, dF)
         else:
-            dmean, dL = kernels.qehvi_backward(ctx.mean, ctx.L, ctx.Z, lo, hi, dacq)
-        dX = None
-        sv = ctx.saved
-        if (_PB_JOBS and 1 < len(sv) <= 16 and all(
-                c.kind == sv[0][0].kind and c.d == sv[0][0].d for c, _, _, _ in sv)):
-            # every member's Cholesky backward, then posterior backward pass, in one launch each
-            q_ = ctx.L.shape[-1]
-            dcovs = kernels.chol_backward(ctx.L.reshape(-1, q_, q_),
-                                          dL.reshape(-1, q_, q_)).reshape(ctx.L.shape)
-            dX = kernels.post_backward_jobs([
-                dict(cache=cache, pp=pp, W=W, dmean=dmean[t], ystd=ystd, dcov=dcovs[t])
-                for t, (cache, pp, ystd, W) in enumerate(sv)])
-        else:
-            for t, (cache, pp, ystd, W) in enumerate(sv):
-                dcov = kernels.chol_backward(ctx.L[t], dL[t])
-                dX = kernels.post_backward(cache, pp, W, dmean[t], dcov, ystd, dX=dX)
+            dmean, dL, *dF = kernels.qehvi_backward(mean, L, ctx.Z, lo, hi, dacq, F=F, Qp=Qp)
+            dF = dF[0] if dF else None
+        dX = _member_posterior_backward(ctx.post, dmean, dL, dF)
         _settle_ladder(ctx)
-        return dX, None
+        return dX, None, None
 
 
 def _settle_ladder(ctx) -> None:
@@ -1305,6 +1377,19 @@ def _init_outcome_constraints(acqf, num_members: int, objective, constraints, et
             raise UnsupportedError("the feasibility-weighted kernels support 2 to 4 objectives")
 
 
+def _member_samples(mean, L, Z, F, Qp: int):
+    """The samples f = mean + L z (+ F) of all members, S x B x q x Mt, in torch
+    (mean Mt x B x q, L Mt x B x q x q, Z S x (q Mt) point-major / member-minor,
+    F Mt x S x ldF with rows b Qp + p)."""
+    Mt, B, q = mean.shape
+    S = Z.shape[0]
+    f = mean.permute(1, 2, 0).unsqueeze(0) + torch.einsum(
+        "tbpj,sjt->sbpt", L.tril(), Z.reshape(S, q, Mt))
+    if F is not None:
+        f = f + F[:, :, : B * Qp].reshape(Mt, S, B, Qp)[..., :q].permute(1, 2, 3, 0)
+    return f
+
+
 def _feas_weights(acqf, mean, L, Z, F, Qp: int, need_grad: bool, log: bool = False):
     """The smoothed feasibility weights w (S x B x q) of the samples
     f = mean + L z (+ F) of ALL members (S x B x q x Mt; the constraint
@@ -1312,16 +1397,11 @@ def _feas_weights(acqf, mean, L, Z, F, Qp: int, need_grad: bool, log: bool = Fal
     leaf copies of mean, L (and F): -> (w, leaves).  Plain torch: the tensor is
     tiny next to the posterior.  Without constraints (an objective that only
     selects outcomes) every weight is 1."""
-    Mt, B, q = mean.shape
-    S = Z.shape[0]
     if acqf.constraints is None:
-        return torch.ones(S, B, q, dtype=torch.float64, device=mean.device), None
+        return torch.ones(Z.shape[0], *mean.shape[1:], dtype=torch.float64, device=mean.device), None
     leaves = [t.detach().requires_grad_(need_grad) for t in ((mean, L) if F is None else (mean, L, F))]
     with torch.enable_grad() if need_grad else torch.no_grad():
-        f = leaves[0].permute(1, 2, 0).unsqueeze(0) + torch.einsum(
-            "tbpj,sjt->sbpt", leaves[1].tril(), Z.reshape(S, q, Mt))
-        if F is not None:
-            f = f + leaves[2][:, :, : B * Qp].reshape(Mt, S, B, Qp)[..., :q].permute(1, 2, 3, 0)
+        f = _member_samples(*leaves[:2], Z, leaves[2] if F is not None else None, Qp)
         w = compute_smoothed_feasibility_indicator(acqf.constraints, f, acqf.eta.to(f),
                                                    log=log, fat=acqf.fat)
         # inside the grad mode above: a copy made outside it (w comes out
@@ -1408,7 +1488,7 @@ class qExpectedHypervolumeImprovement(MCAcquisitionFunction):
                 and X3.dtype == torch.float64):
             acq = _qehvi_members_eager(self, X3)
         if acq is None:
-            acq = _FusedQEHVI.apply(X3, self)
+            acq = _FusedHVI.apply(X3, self, False)
         return acq.reshape(batch)
 
 
@@ -1470,167 +1550,16 @@ def prune_inferior_points_multi_objective(model, X, ref_point, objective=None, c
     return X[idcs]
 
 
-class _FusedQNEHVI(torch.autograd.Function):
-    """qNEHVI of B t-batches over a ModelListGP with cached baseline roots,
-    with its gradient.
-
-    Forward, per output t: post_partials (+ R^T), the cached-root terms
-    T_t = L_rr,t^{-1} Sigma'_t(X_b, X) and F_t = Z_b,t T_t (two MFMA GEMMs + one),
-    qmc_finalize(CHOL) on Sigma'_t - T_t^T T_t -> mean_t, L_t; then one bo_qehvi
-    launch over (sample, per-sample hypercell) pairs with f = mean + F + L Z_q.
-    Backward: bo_qehvi_backward (d mean, d L, d F) -> bo_chol_backward ->
-    the cached-root backward of each output (dT = Z_b^T dF - T G)."""
-
-    @staticmethod
-    def forward(ctx, X3, acqf):
-        models = acqf.model.models
-        need_grad = ctx.needs_input_grad[0]
-        q = X3.shape[-2]
-        saved, status = [], []
-        pp = None
-        keys = prime_prediction_caches(models)
-        caches = [mm.prediction_cache(key=key) for mm, key in zip(models, keys)]
-        # where the one-model plan splits k (C4), the cross term cannot ride in
-        # the posterior pass and R^T is stored anyway: then every member's
-        # partials + R^T in one launch (post_partials_members)
-        B, q_, _ = X3.shape
-        c0 = caches[0]
-        pps = None
-        if (1 < len(models) <= 8 and kernels.split_plan(B, q_, c0.n)[0] != 0
-                and all(c.n == c0.n and c.np == c0.np and c.d == c0.d for c in caches)):
-            pps = kernels.post_partials_members(caches, X3.detach(), store_R=True)
-        # the members' means, roots and baseline terms written straight into
-        # the stacked qEHVI inputs; outside graph capture their ladder
-        # outcomes folded into pinned words (as qEHVI's forward)
-        f64 = dict(dtype=torch.float64, device=X3.device)
-        M = len(models)
-        mean = torch.empty(M, B, q_, **f64)
-        L = torch.empty(M, B, q_, q_, **f64)
-        F = None
-        idx = kernels._dev_index(X3.device)
-        # forward-only calls defer the ladder outcome (the eager qEI's ring:
-        # no stream sync per call); the gradient path folds it into pinned
-        # words read at the end of the backward (kernels._LadderRing)
-        defer = not need_grad and not kernels.SYNC_LADDER and idx not in kernels._CAPTURE
-        pinned = not defer and idx not in kernels._CAPTURE and M <= 8
-        ring = kernels.ladder_ring(X3.device) if pinned and not kernels.SYNC_LADDER else None
-        ps = kernels.pinned_status(X3.device) if pinned and ring is None else None
-        if ring is not None:
-            token, words = ring.take(M, "qNEHVI posterior root")
-        else:
-            words = ps.arm(M) if ps is not None else [None] * M
-        stats = [mm.outcome_stats() for mm in models]
-        batched = pps is not None and _roots_batched(acqf, caches, pps, stats)
-        if batched:
-            # every member's T and F in three batched GEMMs over the members
-            Ts, F = _roots_forward_batched(acqf, caches, pps, stats)
-            pp_list = list(pps)
-            if need_grad:
-                Ws = kernels.w_matrix_members(caches, pps)
-                for t in range(M):
-                    saved.append((caches[t], pps[t], stats[t][1], Ts[t], Ws[t]))
-        else:
-            Ts, pp_list = [], []
-            for t, mm in enumerate(models):
-                cache = caches[t]
-                ystd = stats[t][1]
-                pp = pps[t] if pps is not None else kernels.post_partials(
-                    cache, X3.detach(), store_R=need_grad, cross=acqf._roots[t].Q_b)
-                pp_list.append(pp)
-                if F is None:
-                    F = torch.empty(M, acqf._roots[t].Z_base.shape[0], pp.nrows_pad, **f64)
-                T, _ = acqf._roots[t].forward(cache, pp, ystd, F_out=F[t])
-                Ts.append(T)
-                if need_grad:
-                    saved.append((cache, pp, ystd, T, kernels.w_matrix(cache, pp)))
-        pp = pp_list[-1]
-        same_parts = all(p_.Spart.shape == pp_list[0].Spart.shape for p_ in pp_list)
-        if M <= 8 and same_parts and all(c.kind == caches[0].kind for c in caches):
-            # every member's finalisation in one launch
-            info, jit = kernels.qmc_finalize_members(
-                caches, pp_list, stats, mean, L, status=words if pinned else None,
-                Ts=Ts, F=F)
-            status = [(info[t], jit[t]) for t in range(M)]
-        else:
-            for t in range(M):
-                out = kernels.qmc_finalize(caches[t], pp_list[t], _lib.QMC_CHOL, *stats[t],
-                                           want_mean=True, want_cov=False, want_L=True, T=Ts[t],
-                                           F=F[t], mean_out=mean[t], L_out=L[t], status=words[t])
-                status.append((out["info"], out["jitter"]))
-        Zq = acqf._base_samples_q(q, X3.device)
-        lo, hi = acqf._cells
-        feas = None
-        ctx.log = None
-        if acqf._log:
-            acq, ctx.log = _log_hvi_forward(acqf, mean, L, Zq, lo, hi, F, pp.Qp, need_grad)
-        elif acqf._weighted:
-            feas = _feas_weights(acqf, mean, L, Zq, F, pp.Qp, need_grad)
-            acq = kernels.qehvi_feas(mean, L, Zq, lo, hi, feas[0].detach(), acqf._out_idx, F=F,
-                                     Qp=pp.Qp)
-        else:
-            acq = kernels.qehvi(mean, L, Zq, lo, hi, F=F, Qp=pp.Qp)
-        ctx.ladder = None
-        if defer:
-            kernels.raise_not_psd_deferred(torch.cat([i_.reshape(-1) for i_, _ in status]),
-                                           torch.cat([j_.reshape(-1) for _, j_ in status]),
-                                           "qNEHVI posterior root")
-        elif ring is not None:
-            ring.record(token)
-            ctx.ladder = (ring, token)
-        elif ps is not None:
-            kernels.raise_not_psd_members(ps, M, X3.device, "qNEHVI posterior root")
-        else:
-            kernels.raise_not_psd_many(status, "qNEHVI posterior root")  # one read (as qEHVI)
-        if need_grad:
-            ctx.acqf, ctx.saved, ctx.mean, ctx.L, ctx.F, ctx.Zq, ctx.Qp = (
-                acqf, saved, mean, L, F, Zq, pp.Qp)
-            ctx.batched = batched
-            ctx.feas = feas
-        return acq
-
-    @staticmethod
-    def backward(ctx, dacq):
-        lo, hi = ctx.acqf._cells
-        if ctx.log is not None:
-            dmean, dL, dF = _log_hvi_backward(ctx.acqf, ctx.log, ctx.mean, ctx.L, ctx.Zq, lo, hi,
-                                              dacq, ctx.F, ctx.Qp)
-        elif ctx.feas is not None:
-            dmean, dL, dF, dfeas = kernels.qehvi_feas_backward(
-                ctx.mean, ctx.L, ctx.Zq, lo, hi, ctx.feas[0].detach(), ctx.acqf._out_idx, dacq,
-                F=ctx.F, Qp=ctx.Qp)
-            _feas_backward(ctx.feas, dfeas, dmean, dL, dF)
-        else:
-            dmean, dL, dF = kernels.qehvi_backward(ctx.mean, ctx.L, ctx.Zq, lo, hi, dacq, F=ctx.F,
-                                                   Qp=ctx.Qp)
-        dX = None
-        if ctx.batched and _BWD_BATCHED:
-            dX = _roots_backward_batched(ctx, dmean, dL, dF)
-        else:
-            for t, (cache, pp, ystd, T, W) in enumerate(ctx.saved):
-                dcov = kernels.chol_backward(ctx.L[t], dL[t])
-                dX = ctx.acqf._roots[t].backward(cache, pp, W, dmean[t], dcov, dF[t].contiguous(),
-                                                 T, ystd, dX=dX)
-        _settle_ladder(ctx)
-        return dX, None
-
-
-# BO_QNEHVI_BWD_BATCHED=0: the per-member backward on the batched forward (A/B)
-_BWD_BATCHED = os.environ.get("BO_QNEHVI_BWD_BATCHED", "1") != "0"
-# BO_PB_JOBS=0: the members' post_backward passes one launch each (A/B)
-_PB_JOBS = os.environ.get("BO_PB_JOBS", "1") != "0"
-
-
-def _roots_backward_batched(ctx, dmean, dL, dF):
+def _roots_backward_jobs(post: _MemberPosterior, dmean, dL, dF) -> list:
     """_CachedBaselineRoot.backward for all members at once (the forward's
     batched route): dT = Z_base^T dF and the dK*x / dK(X_b, X) GEMMs batched
     over the members (s^2 folded into the stacked operands), the per-t-batch
-    dT -= T G and the two post_backward passes per member."""
-    acqf = ctx.acqf
+    dT -= T G -> the two post_backward passes per member (training, then
+    baseline points) as post_backward_jobs' dicts."""
+    acqf = post.root_acqf
     roots = acqf._roots
-    M = len(roots)
-    _, Linv_s, _, Zb, _ = acqf.__dict__["_root_stack"]
+    key, Linv_s, _, Zb, _ = acqf.__dict__["_root_stack"]
     Qb_s = acqf.__dict__.get("_root_stack_qb")
-    key = acqf.__dict__["_root_stack"][0]
     if Qb_s is None or Qb_s[0] != key:
         s2 = [float(sv) ** 2 for sv in key[0]]
         Qb_s = (key, torch.stack([rt.Q_b * (-s2[t]) for t, rt in enumerate(roots)]).contiguous())
@@ -1638,10 +1567,8 @@ def _roots_backward_batched(ctx, dmean, dL, dF):
     Qb_s = Qb_s[1]
     dT = kernels.gemm(Zb, dF.contiguous(), transA=True)                 # M x r x N
     r = dT.shape[1]
-    q_ = ctx.L.shape[-1]
-    dcovs = kernels.chol_backward(ctx.L.reshape(-1, q_, q_), dL.reshape(-1, q_, q_)).reshape(
-        ctx.L.shape)                                                    # all members, one launch
-    for t, (cache, pp, ystd, T, W) in enumerate(ctx.saved):
+    dcovs = _chol_backward_members(post.L, dL)
+    for t, (cache, pp, ystd, T, W) in enumerate(post.saved):
         dcov = dcovs[t]
         G = (dcov + dcov.mT).contiguous()
         q, Qp, nrows, B = pp.q, pp.Qp, pp.nrows_pad, pp.B
@@ -1650,21 +1577,12 @@ def _roots_backward_batched(ctx, dmean, dL, dF):
     E = kernels.gemm(dT, Qb_s, transA=True)                             # M x N x np
     # (s^2 L_rr^-T dT)^T = dT^T (s^2 L_rr^-1): already in post_backward's layout
     dKbxT = kernels.gemm(dT, Linv_s, transA=True, flags=_lib.GEMM_B_LOWER)  # M x N x r
-    if _PB_JOBS and 2 * M <= 16:
-        # every member's training and baseline passes in one launch
-        jobs = []
-        for t, (cache, pp, ystd, T, W) in enumerate(ctx.saved):
-            jobs.append(dict(cache=cache, pp=pp, W=W, dmean=dmean[t], dcov=dcovs[t], ystd=ystd,
-                             E=E[t]))
-            jobs.append(dict(cache=cache, pp=pp, ystd=ystd, E=dKbxT[t],
-                             Xt_scaled=roots[t].Xb_scaled, n=r))
-        return kernels.post_backward_jobs(jobs)
-    dX = None
-    for t, (cache, pp, ystd, T, W) in enumerate(ctx.saved):
-        dX = kernels.post_backward(cache, pp, W, dmean[t], dcovs[t], ystd, E=E[t], dX=dX)
-        dX = kernels.post_backward(cache, pp, None, None, None, ystd, E=dKbxT[t],
-                                   Xt_scaled=roots[t].Xb_scaled, n=r, dX=dX)
-    return dX
+    jobs = []
+    for t, (cache, pp, ystd, T, W) in enumerate(post.saved):
+        jobs.append(dict(cache=cache, pp=pp, W=W, dmean=dmean[t], dcov=dcovs[t], ystd=ystd, E=E[t]))
+        jobs.append(dict(cache=cache, pp=pp, W=None, dmean=None, dcov=None, ystd=ystd, E=dKbxT[t],
+                         Xt_scaled=roots[t].Xb_scaled, n=r))
+    return jobs
 
 
 def _roots_batched(acqf, caches, pps, stats) -> bool:
@@ -1833,7 +1751,7 @@ def _weighted_qei_forward(acqf, X: torch.Tensor) -> Optional[torch.Tensor]:
     if Z is None:
         return None
     X3 = X.reshape(-1, q, d)
-    acq = _FusedQEIFeas.apply(X3.to(torch.float64), acqf, plan, Z, _host_scalar(acqf, "best_f"))
+    acq = _FusedSOFeas.apply(X3.to(torch.float64), acqf, plan, Z, _host_scalar(acqf, "best_f"))
     return acq.to(X.dtype).reshape(X.shape[:-2])
 
 
@@ -1863,178 +1781,38 @@ def _so_feas_backward(plan, state, mean, L, Z, acq, dacq):
     return dmean, dL, dF
 
 
-class _FusedQEIFeas(torch.autograd.Function):
-    """Constrained qEI / qLogEI of B t-batches over the plan's members, with its
-    gradient: _FusedQEHVI's chain with bo_qmc_feas as the reduction.
-
-    Forward: the members' post_partials, one qmc_finalize_members (CHOL: mean and
-    jittered q x q root of every member into the stacked inputs), bo_qmc_feas.
-    Backward: bo_qmc_feas_backward -> d mu_t, d L_t; bo_chol_backward over all
-    members; bo_post_backward_jobs.  The ladder status as _FusedQEHVI's."""
+class _FusedSOFeas(torch.autograd.Function):
+    """Constrained qEI / qLogEI (``Z``, ``best_f`` given) or qNEI / qLogNEI
+    (both None: the members' cached baseline roots, the per-sample baseline
+    best) of B t-batches over the plan's members, with its gradient:
+    _FusedHVI's chain with bo_qmc_feas as the reduction."""
 
     @staticmethod
     def forward(ctx, X3, acqf, plan, Z, best_f):
-        models = plan.members
         need_grad = ctx.needs_input_grad[0]
-        q = X3.shape[-2]
-        M = len(models)
-        what = type(acqf).__name__ + " posterior root"
-        keys = prime_prediction_caches(models)
-        caches = [mm.prediction_cache(key=key) for mm, key in zip(models, keys)]
-        pps = kernels.post_partials_members(caches, X3.detach(), store_R=need_grad)
-        f64 = dict(dtype=torch.float64, device=X3.device)
-        mean = torch.empty(M, X3.shape[0], q, **f64)
-        L = torch.empty(M, X3.shape[0], q, q, **f64)
-        ring = (kernels.ladder_ring(X3.device) if need_grad and not kernels.SYNC_LADDER else None)
-        ps = kernels.pinned_status(X3.device) if ring is None else None
-        if ring is not None:
-            token, words = ring.take(M, what)
-        else:
-            words = ps.arm(M)
-        stats = [mm.outcome_stats() for mm in models]
-        if (all(p_.Spart.shape == pps[0].Spart.shape for p_ in pps)
-                and all(c.kind == caches[0].kind for c in caches)):
-            kernels.qmc_finalize_members(caches, pps, stats, mean, L, status=words)
-        else:
-            for t, (cache, pp) in enumerate(zip(caches, pps)):
-                kernels.qmc_finalize(cache, pp, _lib.QMC_CHOL, *stats[t], want_mean=True,
-                                     want_cov=False, want_L=True, mean_out=mean[t], L_out=L[t],
-                                     status=words[t])
-        saved = []
+        noisy = Z is None
+        M = len(plan.members)
+        with kernels.member_ladder(X3.device, M, need_grad, type(acqf).__name__ + " posterior root",
+                                   defer_forward_only=noisy) as ladder:
+            post = _member_posterior(plan.members, X3, need_grad, ladder, acqf if noisy else None)
+            best_f_s = None
+            if noisy:
+                Z = acqf._base_samples_members(X3.shape[-2], M, X3.device)
+                best_f, best_f_s = 0.0, acqf._baseline_best_f
+            acq, state = _so_feas_forward(acqf, plan, post.mean, post.L, Z, post.F, post.Qp, best_f,
+                                          best_f_s, need_grad)
+            ladder.finish(ctx, post.info, post.jitter)
         if need_grad:
-            Ws = kernels.w_matrix_members(caches, pps)
-            saved = [(caches[t], pps[t], stats[t][1], Ws[t]) for t in range(M)]
-        acq, state = _so_feas_forward(acqf, plan, mean, L, Z, None, 0, best_f, None, need_grad)
-        ctx.ladder = None
-        if ring is not None:
-            ring.record(token)
-            ctx.ladder = (ring, token)
-        else:
-            kernels.raise_not_psd_members(ps, M, X3.device, what)
-        if need_grad:
-            ctx.plan, ctx.state, ctx.saved = plan, state, saved
-            ctx.mean, ctx.L, ctx.Z, ctx.acq = mean, L, Z, acq.detach().clone()
+            ctx.plan, ctx.state, ctx.post, ctx.Z, ctx.acq = plan, state, post, Z, acq.detach().clone()
         return acq
 
     @staticmethod
     def backward(ctx, dacq):
-        dmean, dL, _ = _so_feas_backward(ctx.plan, ctx.state, ctx.mean, ctx.L, ctx.Z, ctx.acq, dacq)
-        sv = ctx.saved
-        q_ = ctx.L.shape[-1]
-        dcovs = kernels.chol_backward(ctx.L.reshape(-1, q_, q_),
-                                      dL.reshape(-1, q_, q_)).reshape(ctx.L.shape)
-        if (_PB_JOBS and 1 < len(sv) <= 16 and all(
-                c.kind == sv[0][0].kind and c.d == sv[0][0].d for c, _, _, _ in sv)):
-            dX = kernels.post_backward_jobs([
-                dict(cache=cache, pp=pp, W=W, dmean=dmean[t], ystd=ystd, dcov=dcovs[t])
-                for t, (cache, pp, ystd, W) in enumerate(sv)])
-        else:
-            dX = None
-            for t, (cache, pp, ystd, W) in enumerate(sv):
-                dX = kernels.post_backward(cache, pp, W, dmean[t], dcovs[t], ystd, dX=dX)
+        post = ctx.post
+        dmean, dL, dF = _so_feas_backward(ctx.plan, ctx.state, post.mean, post.L, ctx.Z, ctx.acq, dacq)
+        dX = _member_posterior_backward(post, dmean, dL, dF)
         _settle_ladder(ctx)
         return dX, None, None, None, None
-
-
-class _FusedQNEIFeas(torch.autograd.Function):
-    """Constrained qNEI / qLogNEI of B t-batches over the plan's members with
-    cached baseline roots, with its gradient: _FusedQNEHVI's chain (the members'
-    T_t = L_rr,t^-1 Sigma'_t(X_b, X), F_t = Z_b,t T_t, the roots of Sigma'_t -
-    T_t^T T_t) with bo_qmc_feas against the per-sample baseline best as the
-    reduction."""
-
-    @staticmethod
-    def forward(ctx, X3, acqf, plan):
-        models = plan.members
-        roots = acqf._roots
-        need_grad = ctx.needs_input_grad[0]
-        B, q, _ = X3.shape
-        M = len(models)
-        what = type(acqf).__name__ + " posterior root"
-        keys = prime_prediction_caches(models)
-        caches = [mm.prediction_cache(key=key) for mm, key in zip(models, keys)]
-        c0 = caches[0]
-        pps = None
-        if (1 < M <= 8 and kernels.split_plan(B, q, c0.n)[0] != 0
-                and all(c.n == c0.n and c.np == c0.np and c.d == c0.d for c in caches)):
-            pps = kernels.post_partials_members(caches, X3.detach(), store_R=True)
-        f64 = dict(dtype=torch.float64, device=X3.device)
-        mean = torch.empty(M, B, q, **f64)
-        L = torch.empty(M, B, q, q, **f64)
-        F = None
-        # the ladder status as _FusedQNEHVI's: forward-only calls defer it, the
-        # gradient path reads pinned words at the end of the backward
-        defer = not need_grad and not kernels.SYNC_LADDER
-        ring = kernels.ladder_ring(X3.device) if not defer and not kernels.SYNC_LADDER else None
-        ps = kernels.pinned_status(X3.device) if not defer and ring is None else None
-        if ring is not None:
-            token, words = ring.take(M, what)
-        else:
-            words = ps.arm(M) if ps is not None else [None] * M
-        stats = [mm.outcome_stats() for mm in models]
-        saved, status = [], []
-        batched = pps is not None and _roots_batched(acqf, caches, pps, stats)
-        if batched:
-            Ts, F = _roots_forward_batched(acqf, caches, pps, stats)
-            pp_list = list(pps)
-            if need_grad:
-                Ws = kernels.w_matrix_members(caches, pps)
-                saved = [(caches[t], pps[t], stats[t][1], Ts[t], Ws[t]) for t in range(M)]
-        else:
-            Ts, pp_list = [], []
-            for t in range(M):
-                cache, ystd = caches[t], stats[t][1]
-                pp = pps[t] if pps is not None else kernels.post_partials(
-                    cache, X3.detach(), store_R=need_grad, cross=roots[t].Q_b)
-                pp_list.append(pp)
-                if F is None:
-                    F = torch.empty(M, roots[t].Z_base.shape[0], pp.nrows_pad, **f64)
-                T, _ = roots[t].forward(cache, pp, ystd, F_out=F[t])
-                Ts.append(T)
-                if need_grad:
-                    saved.append((cache, pp, ystd, T, kernels.w_matrix(cache, pp)))
-        pp = pp_list[-1]
-        if (all(p_.Spart.shape == pp_list[0].Spart.shape for p_ in pp_list)
-                and all(c.kind == c0.kind for c in caches)):
-            info, jit = kernels.qmc_finalize_members(
-                caches, pp_list, stats, mean, L, status=words if not defer else None, Ts=Ts, F=F)
-            status = [(info[t], jit[t]) for t in range(M)]
-        else:
-            for t in range(M):
-                out = kernels.qmc_finalize(caches[t], pp_list[t], _lib.QMC_CHOL, *stats[t],
-                                           want_mean=True, want_cov=False, want_L=True, T=Ts[t],
-                                           F=F[t], mean_out=mean[t], L_out=L[t], status=words[t])
-                status.append((out["info"], out["jitter"]))
-        Zq = acqf._base_samples_members(q, M, X3.device)
-        acq, state = _so_feas_forward(acqf, plan, mean, L, Zq, F, pp.Qp, 0.0,
-                                      acqf._baseline_best_f, need_grad)
-        ctx.ladder = None
-        if defer:
-            kernels.raise_not_psd_deferred(torch.cat([i_.reshape(-1) for i_, _ in status]),
-                                           torch.cat([j_.reshape(-1) for _, j_ in status]), what)
-        elif ring is not None:
-            ring.record(token)
-            ctx.ladder = (ring, token)
-        else:
-            kernels.raise_not_psd_members(ps, M, X3.device, what)
-        if need_grad:
-            ctx.acqf, ctx.plan, ctx.state, ctx.saved, ctx.batched = acqf, plan, state, saved, batched
-            ctx.mean, ctx.L, ctx.F, ctx.Zq, ctx.acq = mean, L, F, Zq, acq.detach().clone()
-        return acq
-
-    @staticmethod
-    def backward(ctx, dacq):
-        dmean, dL, dF = _so_feas_backward(ctx.plan, ctx.state, ctx.mean, ctx.L, ctx.Zq, ctx.acq, dacq)
-        if ctx.batched and _BWD_BATCHED:
-            dX = _roots_backward_batched(ctx, dmean, dL, dF)
-        else:
-            dX = None
-            for t, (cache, pp, ystd, T, W) in enumerate(ctx.saved):
-                dcov = kernels.chol_backward(ctx.L[t], dL[t])
-                dX = ctx.acqf._roots[t].backward(cache, pp, W, dmean[t], dcov, dF[t].contiguous(),
-                                                 T, ystd, dX=dX)
-        _settle_ladder(ctx)
-        return dX, None, None
 
 
 class _QEHVIFromRoots(torch.autograd.Function):
@@ -2087,7 +1865,7 @@ def _check_log_q(acqf, q: int) -> None:
 
 
 def _log_hvi_forward(acqf, mean, L, Z, lo, hi, F, Qp: int, need_grad: bool):
-    """The log-space reduction of _FusedQEHVI / _FusedQNEHVI (bo_qlogehvi) on
+    """The log-space reduction of _FusedHVI (bo_qlogehvi) on
     the members' means and roots: -> (acq, state for _log_hvi_backward).  With
     outcome constraints the points' log feasibility (logei.py:162-169) is formed
     in torch from detached leaves, as _feas_weights does for the plain classes."""
@@ -2152,7 +1930,7 @@ class qNoisyExpectedHypervolumeImprovement(qExpectedHypervolumeImprovement):
     partitioning of NondominatedPartitioning, m > 2; both in native host code,
     as the reference runs them on the CPU for m > 2), padded with empty cells to
     a common count (BoxDecompositionList), resident on the device as S x K x m.
-    Forward / backward: _FusedQNEHVI over the q new points and the pending
+    Forward / backward: _FusedHVI over the q new points and the pending
     points not yet in the baseline.
 
     cache_root=False: every forward samples the joint posterior of each
@@ -2337,7 +2115,7 @@ class qNoisyExpectedHypervolumeImprovement(qExpectedHypervolumeImprovement):
                                    f"and d <= {kernels.DP} on the device")
         X3 = X.reshape(-1, q, d)
         if self._cache_root:
-            acq = _FusedQNEHVI.apply(X3, self)
+            acq = _FusedHVI.apply(X3, self, True)
         else:
             acq = self._joint_forward(X3)
         if self._log:
@@ -2372,34 +2150,21 @@ class qNoisyExpectedHypervolumeImprovement(qExpectedHypervolumeImprovement):
             Fs.append(F.reshape(Zb.shape[0], B * q))
         Zq = self._base_samples_q(q, X3.device)
         lo, hi = self._cells
+        mean, L, F = torch.stack(means), torch.stack(Ls), torch.stack(Fs)
+        if not self._log and not self._weighted:
+            return _QEHVIFromRoots.apply(mean, L, F, Zq, lo, hi, q)
+        w = None  # the points' (log) feasibility weights, S x B x q
+        if self.constraints is not None:
+            f = _member_samples(mean, L, Zq, F, q)
+            w = compute_smoothed_feasibility_indicator(
+                self.constraints, f, self.eta.to(f), log=self._log,
+                fat=self.fat).to(torch.float64).contiguous()
         if self._log:
-            mean, L, F = torch.stack(means), torch.stack(Ls), torch.stack(Fs)
-            S, Mt = Zq.shape[0], len(means)
-            logw = None
-            if self.constraints is not None:
-                f = (mean.permute(1, 2, 0).unsqueeze(0)
-                     + torch.einsum("tbpj,sjt->sbpt", L, Zq.reshape(S, q, Mt))
-                     + F.reshape(Mt, S, B, q).permute(1, 2, 3, 0))
-                logw = compute_smoothed_feasibility_indicator(
-                    self.constraints, f, self.eta.to(f), log=True,
-                    fat=self.fat).to(torch.float64).contiguous()
-            return _QLogEHVIFromRoots.apply(mean, L, F, logw, Zq, lo, hi, q, tuple(self._out_idx),
+            return _QLogEHVIFromRoots.apply(mean, L, F, w, Zq, lo, hi, q, tuple(self._out_idx),
                                             self.fat, self.tau_relu, self.tau_max)
-        if self._weighted:
-            mean, L, F = torch.stack(means), torch.stack(Ls), torch.stack(Fs)
-            S, Mt = Zq.shape[0], len(means)
-            if self.constraints is None:
-                w = torch.ones(S, B, q, dtype=torch.float64, device=X3.device)
-            else:
-                f = (mean.permute(1, 2, 0).unsqueeze(0)
-                     + torch.einsum("tbpj,sjt->sbpt", L, Zq.reshape(S, q, Mt))
-                     + F.reshape(Mt, S, B, q).permute(1, 2, 3, 0))
-                w = compute_smoothed_feasibility_indicator(self.constraints, f, self.eta.to(f),
-                                                           fat=self.fat).to(torch.float64)
-            return _QEHVIFeasFromRoots.apply(mean, L, F, w.contiguous(), Zq, lo, hi, q,
-                                             tuple(self._out_idx))
-        return _QEHVIFromRoots.apply(torch.stack(means), torch.stack(Ls), torch.stack(Fs), Zq,
-                                     lo, hi, q)
+        if w is None:
+            w = torch.ones(Zq.shape[0], B, q, dtype=torch.float64, device=X3.device)
+        return _QEHVIFeasFromRoots.apply(mean, L, F, w, Zq, lo, hi, q, tuple(self._out_idx))
 
 
 class qLogExpectedHypervolumeImprovement(qExpectedHypervolumeImprovement):

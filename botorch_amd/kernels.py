@@ -1369,6 +1369,14 @@ class _LadderRing:
     def record(self, token) -> None:
         self.events[token[0]].record(torch.cuda.current_stream(self.dev))
 
+    def release(self, token) -> None:
+        """Give back the block of a forward that raised before record(): no
+        event stands behind it, so nothing may wait on it or read its words."""
+        i, g = token
+        p = self.pending[i]
+        if p is not None and p[0] == g:
+            self.pending[i] = None
+
     def settle(self, token) -> None:
         i, g = token
         p = self.pending[i]
@@ -1399,6 +1407,66 @@ def ladder_ring(dev) -> "_LadderRing":
     return _RINGS[idx]
 
 
+class member_ladder:
+    """Where the ladder outcomes of one fused forward over ``M`` ModelListGP
+    members go -- the one policy of the member-posterior acquisitions:
+
+    * ring: with a gradient, outside graph capture, M <= 8 and not
+      BO_SYNC_LADDER -- a _LadderRing block, read at the end of the backward
+      (finish() leaves (ring, token) on ``ctx.ladder``);
+    * deferred: forward-only calls where ``defer_forward_only`` (the
+      cached-root acquisitions), outside capture, not BO_SYNC_LADDER --
+      raise_not_psd_deferred, one forward behind;
+    * pinned block: otherwise outside capture with M <= 8 -- one stream sync
+      behind the reduction launch (raise_not_psd_members);
+    * device tensors: under capture or with M > 8 -- raise_not_psd_many.
+
+    ``words``: the members' (status_out, status_count) pointers for the
+    finalisation launches, None where they do not fold their status.  Used as
+    a context manager around the forward: a forward that raises between the
+    ring's take() and record() gives its block back (_LadderRing.release)."""
+
+    def __init__(self, device, M: int, need_grad: bool, what: str, defer_forward_only: bool = False):
+        capture = _dev_index(device) in _CAPTURE
+        self.dev, self.M, self.what = device, M, what
+        self.ring = self.token = self.ps = self.words = None
+        self.defer = defer_forward_only and not need_grad and not SYNC_LADDER and not capture
+        if self.defer or capture or M > 8:
+            return
+        if need_grad and not SYNC_LADDER:
+            self.ring = ladder_ring(device)
+            self.token, self.words = self.ring.take(M, what)
+        else:
+            self.ps = pinned_status(device)
+            self.words = self.ps.arm(M)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, *exc):
+        if exc_type is not None and self.token is not None:
+            self.ring.release(self.token)
+        return False
+
+    def finish(self, ctx, info, jitter) -> None:
+        """Behind the reduction launch; ``info`` / ``jitter``: the members'
+        ladder outputs (indexed by member) for the routes that read device
+        tensors."""
+        ctx.ladder = None
+        if self.ring is not None:
+            self.ring.record(self.token)
+            ctx.ladder = (self.ring, self.token)
+            self.token = None
+        elif self.ps is not None:
+            raise_not_psd_members(self.ps, self.M, self.dev, self.what)
+        elif self.defer:
+            raise_not_psd_deferred(torch.cat([info[t].reshape(-1) for t in range(self.M)]),
+                                   torch.cat([jitter[t].reshape(-1) for t in range(self.M)]),
+                                   self.what)
+        else:
+            raise_not_psd_many([(info[t], jitter[t]) for t in range(self.M)], self.what)
+
+
 def raise_not_psd_members(ps: "_PinnedStatus", m: int, dev, what: str) -> None:
     """The members' ladder outcomes folded into ps's pinned words by their
     finalisation launches: one stream sync, then raised / warned in member
@@ -1412,15 +1480,7 @@ def raise_status_words(pairs, what: str) -> None:
     """[max info, max jitter] per member, in member order: NotPSDError for a
     failed ladder, the reference's NumericalWarning for added jitter."""
     for info_max, jit_max in pairs:
-        if info_max > 0:
-            from .exceptions import NotPSDError
-            raise NotPSDError(f"{what}: matrix not positive definite after repeatedly adding "
-                              f"jitter up to {CHOLESKY_JITTER_F64 * 10 ** (CHOLESKY_MAX_TRIES - 1):.1e}")
-        if jit_max > 0:
-            import warnings
-            from .exceptions import NumericalWarning
-            warnings.warn(f"A not p.d., added jitter of {float(jit_max):.1e} to the diagonal",
-                          NumericalWarning)
+        _ladder_outcome(info_max, jit_max, what)
 
 
 def _stream_sync(dev):
@@ -1446,17 +1506,7 @@ def raise_not_psd_many(pairs, what: str) -> None:
     for m, (info, jitter) in enumerate(pairs):
         check(lib().bo_ladder_status(_p(info.contiguous()), _p(jitter.contiguous()), info.numel(),
                                      _p(packed[m]), _stream(dev)), "ladder_status")
-    packed = packed.cpu()
-    for m in range(len(pairs)):
-        if packed[m, 0] > 0:
-            from .exceptions import NotPSDError
-            raise NotPSDError(f"{what}: matrix not positive definite after repeatedly adding "
-                              f"jitter up to {CHOLESKY_JITTER_F64 * 10 ** (CHOLESKY_MAX_TRIES - 1):.1e}")
-        if packed[m, 1] > 0:
-            import warnings
-            from .exceptions import NumericalWarning
-            warnings.warn(f"A not p.d., added jitter of {float(packed[m, 1]):.1e} to the diagonal",
-                          NumericalWarning)
+    raise_status_words(packed.cpu().tolist(), what)
 
 
 def _raise_not_psd(info: torch.Tensor, jitter: torch.Tensor, what: str):
@@ -1467,16 +1517,7 @@ def _raise_not_psd(info: torch.Tensor, jitter: torch.Tensor, what: str):
     packed = torch.empty(2, dtype=torch.float64, device=info.device)
     check(lib().bo_ladder_status(_p(info.contiguous()), _p(jitter.contiguous()), info.numel(),
                                  _p(packed), _stream(info.device)), "ladder_status")
-    packed = packed.cpu()
-    if packed[0] > 0:
-        from .exceptions import NotPSDError
-        raise NotPSDError(f"{what}: matrix not positive definite after repeatedly adding "
-                          f"jitter up to {CHOLESKY_JITTER_F64 * 10 ** (CHOLESKY_MAX_TRIES - 1):.1e}")
-    if packed[1] > 0:
-        import warnings
-        from .exceptions import NumericalWarning
-        warnings.warn(f"A not p.d., added jitter of {float(packed[1]):.1e} to the diagonal",
-                      NumericalWarning)
+    _ladder_outcome(*packed.cpu().tolist(), what)
 
 
 def chol_jitter(A: torch.Tensor, max_tries=CHOLESKY_MAX_TRIES,

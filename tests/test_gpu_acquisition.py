@@ -249,12 +249,17 @@ def test_qehvi_api_matches_oracle(golden, B, q, S):
     torch.testing.assert_close(v, ref, rtol=1e-7, atol=1e-10)
 
 
-@pytest.mark.parametrize("B,q,S", [(5, 2, 64), (3, 4, 128), (2, 8, 32)])
-def test_qehvi_gradient_matches_oracle(golden, B, q, S):
+@pytest.mark.parametrize("B,q,S,matern", [
+    pytest.param(5, 2, 64, (), id="5-2-64"), pytest.param(3, 4, 128, (), id="3-4-128"),
+    pytest.param(2, 8, 32, (), id="2-8-32"),
+    # members of different kernel kinds: the backward's passes one launch each
+    pytest.param(3, 2, 32, (1,), id="3-2-32-matern")])
+def test_qehvi_gradient_matches_oracle(golden, B, q, S, matern):
     """d qEHVI / dX (bo_qehvi_backward + bo_chol_backward + bo_post_backward per
-    output) vs. torch autograd through the oracle's _compute_qehvi restatement."""
+    output) vs. torch autograd through the oracle's _compute_qehvi restatement;
+    ``matern``: the members with a scaled Matern-5/2 kernel in place of RBF."""
     from botorch_amd.acquisition import qExpectedHypervolumeImprovement
-    from botorch_amd.models import ModelListGP, SingleTaskGP
+    from botorch_amd.models import MaternKernel, ModelListGP, ScaleKernel, SingleTaskGP
     from botorch_amd.multi_objective import FastNondominatedPartitioning
     from botorch_amd.sampling import SobolQMCNormalSampler
     from oracle.acquisition import qehvi
@@ -264,11 +269,15 @@ def test_qehvi_gradient_matches_oracle(golden, B, q, S):
     Y = torch.from_numpy(golden["dtlz2_Y"][:96])
     models, oracles = [], []
     for t in range(3):
-        mdl = SingleTaskGP(X.to(DEV), Y[:, t:t + 1].to(DEV))
-        mdl.covar_module.lengthscale = torch.full((1, 6), 0.6, dtype=torch.float64)
+        covar = ScaleKernel(MaternKernel(ard_num_dims=6), outputscale=1.3) if t in matern else None
+        mdl = SingleTaskGP(X.to(DEV), Y[:, t:t + 1].to(DEV), covar_module=covar)
+        getattr(mdl.covar_module, "base_kernel", mdl.covar_module).lengthscale = torch.full(
+            (1, 6), 0.6, dtype=torch.float64)
         mdl.likelihood.noise = torch.tensor([1e-3], dtype=torch.float64)
         models.append(mdl.eval())
-        oracles.append(ExactGPOracle(X, Y[:, t:t + 1], GPHyper(torch.full((6,), 0.6, dtype=torch.float64), 1e-3, 0.0)))
+        hyper = GPHyper(torch.full((6,), 0.6, dtype=torch.float64), 1e-3, 0.0,
+                        *((1.3, 1) if t in matern else ()))
+        oracles.append(ExactGPOracle(X, Y[:, t:t + 1], hyper))
     ref_point = torch.full((3,), -1.1, dtype=torch.float64)
     part = FastNondominatedPartitioning(ref_point, Y)
     acqf = qExpectedHypervolumeImprovement(ModelListGP(*models), ref_point.tolist(), part,

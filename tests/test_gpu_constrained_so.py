@@ -253,6 +253,65 @@ def test_qnei_constrained_matches_oracle(kind, Mt, q, S, cset, monkeypatch):
 
 
 @pytest.mark.gpu
+def test_qnei_constrained_batched_roots_match_per_member(monkeypatch):
+    """As test_qnehvi_members_batched_roots_match_per_member, for constrained
+    qNEI: at a size whose one-model plan splits k (n = 1024) the members'
+    cached-root terms go as GEMMs batched over the members; value,
+    forward-only value and gradient equal the per-member route (s^2 folded
+    into the operands: rounding only)."""
+    from botorch_amd import acquisition, kernels
+    from botorch_amd.models import ModelListGP, SingleTaskGP
+    from botorch_amd.objective import LinearMCObjective, get_outcome_constraint_transforms
+    from botorch_amd.sampling import SobolQMCNormalSampler
+    _no_generic(monkeypatch)
+    Mt, n, r, B, q, S = 2, 1024, 40, 32, 4, 64
+    assert kernels.split_plan(B, q, n)[0] != 0  # stream-K: the members' route applies
+    g = torch.Generator().manual_seed(3)
+    X = torch.rand(n, 6, generator=g, dtype=F64)
+    Y = torch.stack([torch.sin(3.0 * X[:, 0]) + X[:, 1:].pow(2).sum(-1),
+                     X[:, 0] + 0.5 * torch.sin(3.0 * X[:, 1]) - 0.8], dim=-1)
+    Y = Y + 0.05 * torch.randn(n, Mt, generator=g, dtype=F64)
+    models = []
+    for t in range(Mt):
+        mm = SingleTaskGP(X.to(DEV), Y[:, t:t + 1].to(DEV))
+        mm.covar_module.lengthscale = torch.full((1, 6), 0.6, dtype=F64)
+        mm.likelihood.noise = torch.tensor([1e-2], dtype=F64)
+        models.append(mm.eval())
+    lin, _, eta = constraint_sets(Mt)["one"]
+    acqf = acquisition.qNoisyExpectedImprovement(
+        ModelListGP(*models), X[:r].to(DEV), sampler=SobolQMCNormalSampler(torch.Size([S]), seed=0),
+        objective=LinearMCObjective(torch.tensor(WEIGHTS[Mt], dtype=F64, device=DEV)),
+        constraints=get_outcome_constraint_transforms(lin), eta=eta, prune_baseline=False)
+    Xc = _points(B, q, 1).to(DEV)
+    calls = []
+    orig = acquisition._roots_forward_batched
+
+    def spy(*a, **k):
+        calls.append(1)
+        return orig(*a, **k)
+
+    monkeypatch.setattr(acquisition, "_roots_forward_batched", spy)
+
+    def run():
+        v, gx = _value_and_grad(acqf, Xc)
+        with torch.no_grad():
+            v2 = acqf(Xc).cpu()
+        kernels.check_ladder_status(DEV)
+        return v, gx, v2
+
+    v1, g1, w1 = run()
+    assert calls, "the batched roots route did not run"
+    monkeypatch.setattr(acquisition, "_roots_batched", lambda *a, **k: False)
+    n1 = len(calls)
+    v0, g0, w0 = run()
+    assert len(calls) == n1, "the per-member route was not taken"
+    assert (v0 > 0).sum() > 5
+    torch.testing.assert_close(v1, v0, rtol=1e-10, atol=1e-13)
+    torch.testing.assert_close(w1, w0, rtol=1e-10, atol=1e-13)
+    torch.testing.assert_close(g1, g0, rtol=1e-8, atol=1e-11)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("kind", ["qEI", "qLogEI"])
 def test_list_sampler_draws_the_generic_routes_samples(kind):
     """A ListSampler of Mt samplers: the fused value is the generic route's on

@@ -164,6 +164,47 @@ def test_qehvi_member_status_words(monkeypatch):
         kernels.check_ladder_status(X.device)
 
 
+def test_forward_that_raises_releases_its_ladder_block():
+    """A gradient-path forward that raises behind the ring's take() (here a
+    constraint callable, host code) gives its block back: nothing stays
+    pending behind an event that was never recorded, and the next forward +
+    backward and the poll are clean."""
+    import warnings
+    from botorch_amd import kernels
+    from botorch_amd.acquisition import qExpectedHypervolumeImprovement
+    from botorch_amd.exceptions import NumericalWarning
+    from botorch_amd.models import ModelListGP
+    from botorch_amd.multi_objective import FastNondominatedPartitioning
+    from botorch_amd.sampling import SobolQMCNormalSampler
+    _, Y, models = _models(64, m=2)
+    ref = torch.full((2,), -1.1, dtype=torch.float64)
+    state = {"fail": True}
+
+    def con(samples):
+        if state["fail"]:
+            raise ValueError("constraint callable failed")
+        return samples[..., 0] - 10.0
+
+    acqf = qExpectedHypervolumeImprovement(ModelListGP(*models), ref.tolist(),
+                                           FastNondominatedPartitioning(ref, Y),
+                                           sampler=SobolQMCNormalSampler(torch.Size([16]), seed=0),
+                                           constraints=[con])
+    X = torch.rand(3, 2, 6, dtype=torch.float64, generator=torch.Generator().manual_seed(5)).to(DEV)
+    kernels.check_ladder_status(X.device)  # nothing pending from earlier tests
+    ring = kernels.ladder_ring(X.device)
+    with pytest.raises(ValueError, match="constraint callable failed"):
+        acqf(X.clone().requires_grad_(True))
+    assert all(p is None for p in ring.pending)
+    state["fail"] = False
+    with warnings.catch_warnings():
+        warnings.simplefilter("error", NumericalWarning)
+        Xg = X.clone().requires_grad_(True)
+        (g,) = torch.autograd.grad(acqf(Xg).sum(), Xg)
+        kernels.check_ladder_status(X.device)
+    assert torch.isfinite(g).all()
+    assert all(p is None for p in ring.pending)
+
+
 def test_kxt_rows_members_bit_equal_to_per_member():
     """bo_post_kxt_rows_members (one launch, grid z = model) writes exactly
     what bo_post_kxt_rows writes per model: the rows and K*x^T."""

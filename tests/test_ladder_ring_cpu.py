@@ -80,6 +80,98 @@ def test_block_coming_round_reports_the_forward_left_pending():
     assert r.pending[tok0[0]] is None
 
 
+def test_released_block_is_never_waited_on_or_read():
+    """A forward that raised between take() and record() gives its block back:
+    no event stands behind it, so the wrap-around, settle and settle_all must
+    neither wait on that slot's event nor read its words."""
+    r = _ring()
+    tok, _ = r.take(2, "raised")
+    r.release(tok)
+    assert r.pending[tok[0]] is None
+    r.blocks[tok[0]].words[0] = 1.0  # a stale failure word in the released block
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        r.settle(tok)  # the released token: a no-op
+        r.settle_all()
+        for _ in range(kernels._LadderRing.N):  # round the ring, onto that block again
+            later, _ = r.take(2, "later")
+        assert later[0] == tok[0] and r.events[tok[0]].synced == 0
+        r.settle(tok)  # still a no-op: the block now belongs to a newer forward
+    assert r.pending[tok[0]] is not None and r.events[tok[0]].synced == 0
+
+
+def test_release_of_a_stale_token_leaves_the_newer_forward_pending():
+    r = _ring()
+    tok0, _ = r.take(1, "a")
+    r.settle(tok0)
+    for _ in range(kernels._LadderRing.N):
+        tok, _ = r.take(1, "b")
+    assert tok[0] == tok0[0]
+    r.release(tok0)
+    assert r.pending[tok[0]] is not None
+
+
+class _Ctx:
+    ladder = "unset"
+
+
+def _policy(monkeypatch, capture=False, sync=False):
+    ring, block = _ring(), _Block()
+    monkeypatch.setattr(kernels, "ladder_ring", lambda dev: ring)
+    monkeypatch.setattr(kernels, "pinned_status", lambda dev: block)
+    monkeypatch.setattr(kernels, "_CAPTURE", {0: None} if capture else {})
+    monkeypatch.setattr(kernels, "SYNC_LADDER", sync)
+    monkeypatch.setattr(kernels.torch.cuda, "current_stream", lambda dev=None: None)  # no GPU here
+    return ring, block
+
+
+@pytest.mark.parametrize("need_grad,defer_only,capture,sync,M,route", [
+    (True, False, False, False, 3, "ring"), (True, True, False, False, 8, "ring"),
+    (False, True, False, False, 3, "defer"), (False, False, False, False, 3, "pinned"),
+    (True, False, False, True, 3, "pinned"), (False, True, False, True, 3, "pinned"),
+    (True, False, True, False, 3, "device"), (False, True, True, False, 3, "device"),
+    (True, True, False, False, 9, "device"), (False, True, False, False, 9, "defer")])
+def test_member_ladder_routes(monkeypatch, need_grad, defer_only, capture, sync, M, route):
+    """kernels.member_ladder: which of ring / deferred / pinned block / device
+    tensors a forward over M members takes, and what finish() then does."""
+    ring, block = _policy(monkeypatch, capture, sync)
+    seen = []
+    monkeypatch.setattr(kernels, "raise_not_psd_members", lambda ps, m, dev, what: seen.append(("pinned", ps, m)))
+    monkeypatch.setattr(kernels, "raise_not_psd_many", lambda pairs, what: seen.append(("device", len(pairs))))
+    monkeypatch.setattr(kernels, "raise_not_psd_deferred",
+                        lambda i, j, what: seen.append(("defer", i.numel(), j.numel())))
+    import torch
+    lad = kernels.member_ladder("cuda:0", M, need_grad, "x", defer_forward_only=defer_only)
+    assert (lad.words is None) == (route in ("defer", "device"))
+    ctx = _Ctx()
+    info, jit = torch.zeros(M, 2, dtype=torch.int32), torch.zeros(M, 2, dtype=torch.float64)
+    with lad:
+        lad.finish(ctx, info, jit)
+    if route == "ring":
+        assert ctx.ladder[0] is ring and ring.pending[ctx.ladder[1][0]] is not None and not seen
+        assert ring.events[ctx.ladder[1][0]].recorded == 1
+    else:
+        assert ctx.ladder is None and all(p is None for p in ring.pending)
+        assert seen == [{"pinned": ("pinned", block, M), "device": ("device", M),
+                         "defer": ("defer", 2 * M, 2 * M)}[route]]
+
+
+def test_member_ladder_releases_the_block_of_a_forward_that_raises(monkeypatch):
+    ring, _ = _policy(monkeypatch)
+    with pytest.raises(ValueError):
+        with kernels.member_ladder("cuda:0", 2, True, "x") as lad:
+            assert ring.pending[lad.token[0]] is not None
+            raise ValueError("host code failed")
+    assert all(p is None for p in ring.pending)
+    # a forward that finished keeps its block pending for the backward
+    ctx = _Ctx()
+    with pytest.raises(ValueError):
+        with kernels.member_ladder("cuda:0", 2, True, "x") as lad:
+            lad.finish(ctx, None, None)
+            raise ValueError("after the record")
+    assert ring.pending[ctx.ladder[1][0]] is not None
+
+
 def test_settle_all_oldest_first_and_member_order():
     r = _ring()
     t1, _ = r.take(2, "one")
