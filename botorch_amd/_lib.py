@@ -255,6 +255,14 @@ class QmcFeasArgs(_Args):
                        ("dL", _D), ("dF", _D)]
 
 
+class KgArgs(_Args):
+    _fields_ = _HDR + [("B", c_int32), ("T", c_int32), ("q_a", c_int32), ("slots", c_int32),
+                       ("N_f", c_int32), ("max_tries", c_int32), ("noise", c_double),
+                       ("jitter0", c_double), ("mean", _D), ("cov", _D), ("Z", _D), ("acq", _D),
+                       ("values", _D), ("L", _D), ("W", _D), ("info", _D), ("jitter", _D),
+                       ("dacq", _D), ("dvalues", _D), ("dmean", _D), ("dcov", _D)]
+
+
 class LbfgsStepArgs(_Args):
     _fields_ = _HDR + [("B", c_int32), ("n", c_int32), ("m", c_int32), ("_pad", c_int32),
                        ("x", _D), ("f", _D), ("g", _D), ("xt", _D), ("ft", _D), ("gt", _D),
@@ -278,6 +286,7 @@ for _name, _cls in (("bo_post_partials_v", PostPartialsArgs), ("bo_qmc_finalize_
                     ("bo_qehvi_feas_v", QehviFeasArgs), ("bo_qehvi_feas_backward_v", QehviFeasArgs),
                     ("bo_qlogehvi_v", QlogehviArgs), ("bo_qlogehvi_backward_v", QlogehviArgs),
                     ("bo_qmc_feas_v", QmcFeasArgs), ("bo_qmc_feas_backward_v", QmcFeasArgs),
+                    ("bo_kg_v", KgArgs), ("bo_kg_backward_v", KgArgs),
                     ("bo_lbfgs_step_v", LbfgsStepArgs), ("bo_lbfgsb_step_v", LbfgsbArgs)):
     _SIGNATURES[_name] = (c_int, [POINTER(_cls), _P])
 _SIGNATURES["bo_struct_size"] = (c_int64, [ctypes.c_char_p])
@@ -285,7 +294,7 @@ _SIGNATURES["bo_post_backward_jobs"] = (c_int, [c_int, POINTER(POINTER(PostBackw
 ARG_RECORDS = {"BoPostPartialsArgs": PostPartialsArgs, "BoQmcFinalizeArgs": QmcFinalizeArgs,
                "BoQmcBackwardArgs": QmcBackwardArgs, "BoPostBackwardArgs": PostBackwardArgs,
                "BoQehviArgs": QehviArgs, "BoQehviFeasArgs": QehviFeasArgs,
-               "BoQlogehviArgs": QlogehviArgs, "BoQmcFeasArgs": QmcFeasArgs,
+               "BoQlogehviArgs": QlogehviArgs, "BoQmcFeasArgs": QmcFeasArgs, "BoKgArgs": KgArgs,
                "BoLbfgsStepArgs": LbfgsStepArgs,
                "BoLbfgsbArgs": LbfgsbArgs}
 

@@ -518,6 +518,170 @@ class UpperConfidenceBound(AnalyticAcquisitionFunction):
         return (mean if self.maximize else -mean) + self.beta.to(mean).sqrt() * sigma
 
 
+class PosteriorMean(AnalyticAcquisitionFunction):
+    """acquisition/analytic.py (PosteriorMean): mu, or -mu with ``maximize=False``."""
+
+    def __init__(self, model, posterior_transform=None, maximize=True):
+        super().__init__(model, posterior_transform)
+        self.maximize = maximize
+
+    def forward(self, X):
+        X = t_batch_mode(X, expected_q=1)
+        mean, _ = self._mean_and_sigma(X, compute_sigma=False)
+        return mean if self.maximize else -mean
+
+
+# -- one-shot knowledge gradient --------------------------------------------------------
+class OneShotAcquisitionFunction:
+    """acquisition/acquisition.py:149-177: an acquisition function optimised
+    jointly over the candidates and the solutions of its inner problems."""
+
+    def get_augmented_q_batch_size(self, q: int) -> int:
+        raise NotImplementedError
+
+    def extract_candidates(self, X_full: torch.Tensor) -> torch.Tensor:
+        raise NotImplementedError
+
+
+def _split_fantasy_points(X: torch.Tensor, n_f: int):
+    """acquisition/knowledge_gradient.py:559-586, without the permutation to a
+    fantasy batch: (X_actual b x q x d, X_fantasies b x n_f x d)."""
+    if n_f > X.size(-2):
+        raise ValueError(f"n_f ({n_f}) must be less than the q-batch dimension of X ({X.size(-2)})")
+    return X[..., : X.size(-2) - n_f, :], X[..., X.size(-2) - n_f:, :]
+
+
+class qKnowledgeGradient(MCAcquisitionFunction, OneShotAcquisitionFunction):
+    """One-shot batch knowledge gradient (acquisition/knowledge_gradient.py:53-305)
+    of a single-output exact GP with the posterior mean as inner value
+    (``objective=None``): X is b x (q + N_f) x d, the q candidates followed by
+    the N_f solutions x'_i of the fantasy models' inner problems.
+
+    The reference draws Y_i = mu(X) + L z_i under observation noise (L the root
+    of A = Sigma(X, X) + s2 I, z_i the fantasy sampler's base samples),
+    conditions the model on (X, Y_i) and takes the fantasy model's posterior
+    mean at x'_i.  That mean is, in the current model's joint posterior,
+
+        v_i = mu(x'_i) + Sigma(x'_i, X) L^{-T} z_i,   KG = mean_i v_i - current_value
+
+    so no fantasy model is built.  For q (pending points included) up to
+    kernels.KG_FUSED_QMAX and d <= kernels.DP the points are packed into tiles
+    of at most 16 rows (kernels.kg_tile_plan), the fused posterior runs once
+    over all tiles and bo::kg reduces them; otherwise the generic posterior
+    kernels give the joint moments and the formula runs in torch.  Both are
+    differentiable in all q + N_f points."""
+
+    def __init__(self, model, num_fantasies: Optional[int] = 64, sampler=None, objective=None,
+                 posterior_transform=None, inner_sampler=None, X_pending=None,
+                 current_value=None):
+        if sampler is None:
+            if num_fantasies is None:
+                raise ValueError("Must specify `num_fantasies` if no `sampler` is provided.")
+            # base samples should be fixed for joint optimization over X, X_fantasies
+            sampler = SobolQMCNormalSampler(sample_shape=torch.Size([num_fantasies]))
+        elif num_fantasies is not None:
+            if sampler.sample_shape != torch.Size([num_fantasies]):
+                raise ValueError(f"The sampler shape must match num_fantasies={num_fantasies}.")
+        else:
+            num_fantasies = sampler.sample_shape[0]
+        AcquisitionFunction.__init__(self, model)
+        if objective is not None:
+            raise UnsupportedError("qKnowledgeGradient: an `objective` (the MC inner expectation "
+                                   "over an inner sampler) is not on the accelerated path; the "
+                                   "inner value is the posterior mean")
+        if getattr(model, "_is_ensemble", False):
+            raise UnsupportedError("qKnowledgeGradient: fully Bayesian (ensemble) models are not "
+                                   "on the accelerated path")
+        if model.num_outputs != 1 or not hasattr(model, "prediction_cache"):
+            raise UnsupportedError("qKnowledgeGradient: multi-output models and ModelListGP are "
+                                   "not on the accelerated path (single-output SingleTaskGP only)")
+        if posterior_transform is not None:
+            w = getattr(posterior_transform, "weights", None)
+            if not getattr(posterior_transform, "scalarize", False) or w is None or w.numel() != 1:
+                raise UnsupportedError("qKnowledgeGradient: only a single-output "
+                                       "ScalarizedPosteriorTransform is supported")
+            self._affine = (float(w.reshape(-1)[0]), float(posterior_transform.offset))
+        else:
+            self._affine = None
+        self.sampler = sampler
+        self.objective = None
+        self.posterior_transform = posterior_transform
+        self.set_X_pending(X_pending)
+        self.inner_sampler = inner_sampler
+        self.num_fantasies = int(num_fantasies)
+        self.current_value = current_value
+        self._tile_index = {}
+
+    def _noise(self) -> float:
+        """sigma'^2 of the fantasy observations in outcome space, from host
+        values: the likelihood's noise (fixed noise: its mean, models/model.py
+        fantasize) times ystd^2."""
+        ystd = self.model.outcome_stats()[1]
+        return self.model.prediction_cache().noise * ystd * ystd
+
+    def _fused(self, Xa: torch.Tensor, Xf: torch.Tensor, Z: torch.Tensor) -> torch.Tensor:
+        from . import ops  # noqa: F401  (torch.ops.bo registration)
+        from .posteriors import _fused_moments
+        B, q_a, d = Xa.shape
+        N_f = Xf.shape[1]
+        T, slots = kernels.kg_tile_plan(q_a, N_f)
+        key = (N_f, T, slots, Xa.device)
+        idx = self._tile_index.get(key)
+        if idx is None:  # fantasy of each slot; the spare slots repeat the last one
+            idx = torch.arange(T * slots, device=Xa.device).clamp_max(N_f - 1).view(T, slots)
+            self._tile_index[key] = idx
+        tiles = torch.cat([Xa.unsqueeze(1).expand(B, T, q_a, d), Xf[:, idx]], dim=2)
+        mean, cov = _fused_moments(tiles.reshape(B * T, q_a + slots, d), self.model)
+        acq, _, _, _, jit, info = torch.ops.bo.kg(mean, cov, Z, self._noise(), q_a, slots)
+        kernels.raise_not_psd_deferred(info, jit, type(self).__name__)
+        return acq
+
+    def _generic(self, Xa: torch.Tensor, Xf: torch.Tensor, Z: torch.Tensor) -> torch.Tensor:
+        from .posteriors import _CholJitter, posterior_moments
+        B, q_a, _ = Xa.shape
+        mean, cov = posterior_moments(self.model, torch.cat([Xa, Xf], dim=-2))
+        eye = torch.eye(q_a, dtype=cov.dtype, device=cov.device)
+        L = _CholJitter.apply(cov[:, :q_a, :q_a] + self._noise() * eye)
+        Wt = torch.linalg.solve_triangular(L.mT, Z.T.expand(B, q_a, Z.shape[0]), upper=True)
+        values = mean[:, q_a:] + (cov[:, q_a:, :q_a] * Wt.mT).sum(dim=-1)
+        return values.mean(dim=-1)
+
+    def forward(self, X: torch.Tensor) -> torch.Tensor:
+        X = t_batch_mode(X)
+        X_actual, X_fantasies = _split_fantasy_points(X, self.num_fantasies)
+        if X.dtype != torch.float64:  # the model computes in fp64; the value returns in X's dtype
+            return self.forward(X.to(torch.float64)).to(X.dtype)
+        # X_pending joins the actual points only after the split
+        X_actual = self._concat_pending(X_actual)
+        batch = X.shape[:-2]
+        q_a, d = X_actual.shape[-2], X.shape[-1]
+        if q_a < 1:
+            raise ValueError("qKnowledgeGradient: X holds no candidate besides the "
+                             f"{self.num_fantasies} fantasy points")
+        Xa = X_actual.reshape(-1, q_a, d)
+        Xf = X_fantasies.reshape(-1, self.num_fantasies, d)
+        Z = self.sampler.base_samples_2d(q_a, X.device)
+        if q_a <= kernels.KG_FUSED_QMAX and d <= kernels.DP and X.is_cuda:
+            acq = self._fused(Xa, Xf, Z)
+        else:
+            acq = self._generic(Xa, Xf, Z)
+        if self._affine is not None:
+            acq = self._affine[0] * acq + self._affine[1]
+        if self.current_value is not None:
+            acq = acq - torch.as_tensor(self.current_value).to(acq)
+        return acq.reshape(batch)
+
+    def evaluate(self, X: torch.Tensor, bounds: torch.Tensor, **kwargs):
+        raise UnsupportedError("qKnowledgeGradient.evaluate (the separate optimisation of the "
+                               "inner problem on fantasy models) is not on the accelerated path")
+
+    def get_augmented_q_batch_size(self, q: int) -> int:
+        return q + self.num_fantasies
+
+    def extract_candidates(self, X_full: torch.Tensor) -> torch.Tensor:
+        return X_full[..., : -self.num_fantasies, :]
+
+
 # -- qNEI -------------------------------------------------------------------------------
 def prune_inferior_points(model, X, objective=None, posterior_transform=None, constraints=None,
                           num_samples: int = 2048, max_frac: float = 1.0, sampler=None,

@@ -183,7 +183,7 @@ def _optimize_acqf_batch_sharded(acq_function, bounds, q, num_restarts, raw_samp
                                  return_best_only, gen_candidates, ic_generator, timeout_sec,
                                  retry_on_optimization_warning, ic_gen_kwargs,
                                  inequality_constraints=None, equality_constraints=None,
-                                 group=None):
+                                 return_full_tree=False, group=None):
     """optim._optimize_acqf_batch (optimize.py:246-394) with the restarts
     partitioned over the ranks: each rank runs the batch_limit chunks of its
     contiguous restart slice (fixed features, linear constraints and its share
@@ -192,7 +192,12 @@ def _optimize_acqf_batch_sharded(acq_function, bounds, q, num_restarts, raw_samp
     globally (all-reduce MAX of the ranks' flags), one all-reduce gathers every
     restart's [value, candidate], and ``post_processing_func`` + the
     re-evaluation run on the whole gathered batch on every rank (as one
-    process runs them)."""
+    process runs them).  One-shot acquisition functions are refused."""
+    from .acquisition import OneShotAcquisitionFunction
+    from .exceptions import UnsupportedError
+    if isinstance(acq_function, OneShotAcquisitionFunction):
+        raise UnsupportedError("one-shot acquisition functions (qKnowledgeGradient) are not "
+                               "supported by the restart-sharded optimize_acqf")
     ws, rank = world(group)
     options = options or {}
     provided = batch_initial_conditions is not None

@@ -1988,6 +1988,93 @@ def qmc_feas_backward(mean: torch.Tensor, L: torch.Tensor, Z: torch.Tensor, c, d
     return dmean, dL, dF, dfeas
 
 
+KG_QMAX = 16       # rows of a packed tile: q_a + slots <= 16 (bo_kg, the fused posterior)
+KG_FUSED_QMAX = 8  # largest q_a on the packed route (the X rows repeat in every tile)
+
+
+def kg_tile_plan(q_a: int, N_f: int):
+    """(T, slots) of the one-shot KG packing: each restart's q_a actual points
+    and N_f fantasy solutions go into T tiles of q_a + slots <= 16 rows (the
+    actual points, then ``slots`` fantasy solutions); fantasy i sits in tile
+    i // slots at row q_a + i % slots, the last tile's T slots - N_f spare
+    slots repeat the last fantasy solution."""
+    if not 1 <= q_a < KG_QMAX:
+        raise ValueError(f"kg_tile_plan: 1 <= q_a <= {KG_QMAX - 1} (got {q_a})")
+    if N_f < 1:
+        raise ValueError(f"kg_tile_plan: N_f >= 1 (got {N_f})")
+    T = -(-N_f // (KG_QMAX - q_a))
+    return T, -(-N_f // T)
+
+
+def _kg_args(mean, cov, Z, noise, q_a, slots, **extra):
+    """The BoKgArgs of :func:`kg` / :func:`kg_backward`: mean (B T) x q', cov
+    (B T) x q' x q' as bo::gp_posterior returns them for the packed tiles
+    (q' = q_a + slots), Z N_f x q_a."""
+    N_f = Z.shape[0]
+    qp = q_a + slots
+    if q_a < 1 or slots < 1 or qp > KG_QMAX:
+        raise ValueError(f"kg: q_a >= 1, slots >= 1 and q_a + slots <= {KG_QMAX} "
+                         f"(got {q_a} + {slots})")
+    if Z.dim() != 2 or Z.shape[1] != q_a or N_f < 1:
+        raise ValueError(f"kg: Z must be N_f x q_a = N_f x {q_a}, got {tuple(Z.shape)}")
+    if mean.dim() != 2 or mean.shape[1] != qp or tuple(cov.shape) != (mean.shape[0], qp, qp):
+        raise ValueError(f"kg: mean must be (B T) x {qp} and cov (B T) x {qp} x {qp}, got "
+                         f"{tuple(mean.shape)} and {tuple(cov.shape)}")
+    T = -(-N_f // slots)
+    if mean.shape[0] % T:
+        raise ValueError(f"kg: {mean.shape[0]} tiles are no multiple of T = {T}")
+    return _lib.KgArgs(B=mean.shape[0] // T, T=T, q_a=q_a, slots=slots, N_f=N_f,
+                       noise=float(noise), mean=mean.contiguous(), cov=cov.contiguous(),
+                       Z=Z.contiguous(), **extra)
+
+
+def kg(mean: torch.Tensor, cov: torch.Tensor, Z: torch.Tensor, noise: float, q_a: int, slots: int,
+       max_tries: int = CHOLESKY_MAX_TRIES, jitter0: float = CHOLESKY_JITTER_F64):
+    """One-shot knowledge gradient with the posterior mean as inner value, from
+    the packed moments (bo_kg): A = Sigma(X, X) + noise I of tile 0, L =
+    psd_safe_cholesky(A), w_i = L^{-T} z_i, v_i = mu(x'_i) + Sigma(x'_i, X) w_i
+    -> dict(acq B, values B x N_f, L B x q_a x q_a, W B x N_f x q_a, info B,
+    jitter B).  Nothing else of mean / cov is read."""
+    dev = _dev(mean, cov, Z)
+    a = _kg_args(mean, cov, Z, noise, q_a, slots, max_tries=int(max_tries), jitter0=float(jitter0))
+    B, N_f = a.B, a.N_f
+    f64 = dict(dtype=torch.float64, device=dev)
+    out = dict(acq=torch.empty(B, **f64), values=torch.empty(B, N_f, **f64),
+               L=torch.empty(B, q_a, q_a, **f64), W=torch.empty(B, N_f, q_a, **f64),
+               info=torch.empty(B, dtype=torch.int32, device=dev), jitter=torch.empty(B, **f64))
+    for k, v in out.items():
+        setattr(a, k, v.data_ptr())
+    check(lib().bo_kg_v(ctypes.byref(a), _stream(dev)), "kg")
+    return out
+
+
+def kg_backward(cov: torch.Tensor, L: torch.Tensor, W: torch.Tensor, dacq: torch.Tensor,
+                slots: int, dvalues: Optional[torch.Tensor] = None):
+    """Backward of :func:`kg` from its saved L and W -> (dmean, dcov) with the
+    forward's shapes, every entry written: the cotangent of each entry the
+    forward read (the tile-0 X x X block symmetric, as torch's Cholesky
+    backward leaves it), zero elsewhere."""
+    dev = _dev(cov, L, W, dacq, dvalues)
+    B, N_f, q_a = W.shape
+    qp = q_a + slots
+    if tuple(L.shape) != (B, q_a, q_a) or tuple(dacq.shape) != (B,):
+        raise ValueError(f"kg_backward: L must be {B} x {q_a} x {q_a} and dacq have {B} entries")
+    if dvalues is not None and tuple(dvalues.shape) != (B, N_f):
+        raise ValueError(f"kg_backward: dvalues must be {B} x {N_f}")
+    T = -(-N_f // max(slots, 1))
+    if slots < 1 or qp > KG_QMAX or tuple(cov.shape) != (B * T, qp, qp):
+        raise ValueError(f"kg_backward: cov must be {B * T} x {qp} x {qp} with q_a + slots <= "
+                         f"{KG_QMAX}, got {tuple(cov.shape)}")
+    dmean = torch.empty(B * T, qp, dtype=torch.float64, device=dev)
+    dcov = torch.empty(B * T, qp, qp, dtype=torch.float64, device=dev)
+    a = _lib.KgArgs(B=B, T=T, q_a=q_a, slots=slots, N_f=N_f, cov=cov.contiguous(),
+                    L=L.contiguous(), W=W.contiguous(), dacq=dacq.contiguous(),
+                    dvalues=dvalues.contiguous() if dvalues is not None else None,
+                    dmean=dmean, dcov=dcov)
+    check(lib().bo_kg_backward_v(ctypes.byref(a), _stream(dev)), "kg_backward")
+    return dmean, dcov
+
+
 def kernel_grad(X: torch.Tensor, Y: torch.Tensor, dK: torch.Tensor, lengthscale: torch.Tensor,
                 kind: int, outputscale: float = 1.0, group: int = 0,
                 dX: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -26,6 +26,8 @@ Ops (reference computation each replaces):
                       multi_objective/monte_carlo.py:230-317)
   bo::mll             exact marginal log likelihood data term and its gradient
                       (optim/closures/model_closures.py:171-184)
+  bo::kg              one-shot qKnowledgeGradient value of packed posterior moments
+                      (+ autograd, acquisition/knowledge_gradient.py:151-207)
 """
 from __future__ import annotations
 
@@ -517,6 +519,61 @@ def _(Xt, y, lengthscale, noise, constant, outputscale, kind, noise_vec=None):
     return Xt.new_empty(1, dtype=F64), Xt.new_empty(d + 3, dtype=F64)
 
 
+# ---- bo::kg (one-shot knowledge gradient, posterior-mean inner value) -------------------------
+@torch.library.custom_op("bo::kg", mutates_args=(), device_types="cuda")
+def kg(mean: Tensor, cov: Tensor, Z: Tensor, noise: float, q_a: int, slots: int
+       ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """(acq B, values B x N_f) of the packed moments mean (B T) x q', cov (B T)
+    x q' x q' (kernels.kg_tile_plan, q' = q_a + slots) and the fantasy base
+    samples Z (N_f x q_a), plus (L, W) for the backward and the ladder's
+    (jitter, info) per restart."""
+    o = kernels.kg(mean, cov, Z, noise, q_a, slots)
+    return o["acq"], o["values"], o["L"], o["W"], o["jitter"], o["info"]
+
+
+@kg.register_fake
+def _(mean, cov, Z, noise, q_a, slots):
+    N_f = Z.shape[0]
+    B = mean.shape[0] // ((N_f + slots - 1) // slots)
+    mk = lambda *s: mean.new_empty(*s, dtype=F64)  # noqa: E731
+    return (mk(B), mk(B, N_f), mk(B, q_a, q_a), mk(B, N_f, q_a), mk(B),
+            mean.new_empty(B, dtype=torch.int32))
+
+
+@torch.library.custom_op("bo::kg_backward", mutates_args=(), device_types="cuda")
+def kg_backward(dacq: Tensor, dvalues: Optional[Tensor], cov: Tensor, L: Tensor, W: Tensor,
+                slots: int) -> Tuple[Tensor, Tensor]:
+    return kernels.kg_backward(cov, L, W, dacq, slots, dvalues)
+
+
+@kg_backward.register_fake
+def _(dacq, dvalues, cov, L, W, slots):
+    return cov.new_empty(cov.shape[0], cov.shape[1]), torch.empty_like(cov)
+
+
+def _kg_setup(ctx, inputs, output):
+    mean, cov, Z, noise, q_a, slots = inputs
+    _, _, L, W, jitter, info = output
+    ctx.mark_non_differentiable(L, W, jitter, info)
+    ctx.set_materialize_grads(False)
+    ctx.save_for_backward(cov, L, W)
+    ctx.slots = slots
+
+
+def _kg_bwd(ctx, dacq, dvalues, *_):
+    cov, L, W = ctx.saved_tensors
+    if dacq is None and dvalues is None:
+        return (None,) * 6
+    if dacq is None:
+        dacq = W.new_zeros(W.shape[0])
+    dmean, dcov = torch.ops.bo.kg_backward(dacq, dvalues, cov, L, W, ctx.slots)
+    return dmean, dcov, None, None, None, None
+
+
+kg.register_autograd(_kg_bwd, setup_context=_kg_setup)
+
+
 OPS: List[str] = ["sobol_normal", "gp_cache", "gp_cache_extend", "chol_jitter", "chol_backward",
                   "post_partials", "qmc_finalize", "gp_posterior", "gp_posterior_backward",
-                  "qmc_acq", "qmc_acq_backward", "qehvi", "qehvi_backward", "mll"]
+                  "qmc_acq", "qmc_acq_backward", "qehvi", "qehvi_backward", "mll", "kg",
+                  "kg_backward"]

@@ -456,6 +456,54 @@ def gen_batch_initial_conditions(acq_function, bounds, q, num_restarts, raw_samp
     return ics
 
 
+def standardize(Y: torch.Tensor) -> torch.Tensor:
+    """utils/transforms.py:27-49: zero mean and unit variance along dim -2 (a
+    1-d tensor: along its only dim); a zero standard deviation divides by one."""
+    dim = -2 if Y.dim() >= 2 else -1
+    centred = Y - Y.mean(dim=dim, keepdim=True)
+    scale = Y.std(dim=dim, keepdim=True)
+    # (a single value has a NaN deviation: it too divides by one)
+    return centred / torch.where(scale >= 1e-9, scale, torch.ones_like(scale))
+
+
+def gen_one_shot_kg_initial_conditions(acq_function, bounds, q, num_restarts, raw_samples,
+                                       fixed_features=None, options=None,
+                                       inequality_constraints=None, equality_constraints=None):
+    """optim/initializers.py:441-557: initial conditions of one-shot KG.  All
+    q + N_f points start from gen_batch_initial_conditions; then the last
+    (1 - frac_random) N_f fantasy solutions of every restart are overwritten by
+    maximisers of the current posterior mean (PosteriorMean under the
+    acquisition's posterior transform, ``num_inner_restarts`` restarts from
+    ``raw_inner_samples`` raw samples), drawn with replacement with weights
+    exp(eta standardize(values)) -- a fantasy model's maximiser is usually
+    close to one of the current model's."""
+    from .acquisition import PosteriorMean
+    options = options or {}
+    frac_random = options.get("frac_random", 0.1)
+    if not 0 < frac_random < 1:
+        raise ValueError(f"frac_random must take on values in (0,1). Value: {frac_random}")
+    q_aug = acq_function.get_augmented_q_batch_size(q=q)
+    ics = gen_batch_initial_conditions(
+        acq_function=acq_function, bounds=bounds, q=q_aug, num_restarts=num_restarts,
+        raw_samples=raw_samples, fixed_features=fixed_features, options=options,
+        inequality_constraints=inequality_constraints, equality_constraints=equality_constraints)
+    value_function = PosteriorMean(acq_function.model,
+                                   posterior_transform=acq_function.posterior_transform)
+    fantasy_cands, fantasy_vals = optimize_acqf(
+        acq_function=value_function, bounds=bounds, q=1,
+        num_restarts=options.get("num_inner_restarts", 20),
+        raw_samples=options.get("raw_inner_samples", 1024), fixed_features=fixed_features,
+        return_best_only=False, inequality_constraints=inequality_constraints,
+        equality_constraints=equality_constraints)
+    n_value = int((1 - frac_random) * (q_aug - q))  # number of non-random ICs
+    if n_value > 0:
+        eta = options.get("eta", 2.0)
+        weights = torch.exp(eta * standardize(fantasy_vals.reshape(-1)))
+        idx = torch.multinomial(weights, num_restarts * n_value, replacement=True)
+        ics[..., -n_value:, :] = fantasy_cands[idx, 0].view(num_restarts, n_value, -1).to(ics)
+    return ics
+
+
 def minimize_with_timeout(fun, x0, args=(), method=None, jac=None, bounds=None, constraints=(),
                           tol=None, callback=None, options=None, timeout_sec=None):
     """optim/utils/timeout.py:19-108: scipy.optimize.minimize whose callback
@@ -1061,12 +1109,18 @@ def _optimize_acqf_batch(acq_function, bounds, q, num_restarts, raw_samples, opt
                          fixed_features, post_processing_func, batch_initial_conditions,
                          return_best_only, gen_candidates, ic_generator, timeout_sec,
                          retry_on_optimization_warning, ic_gen_kwargs,
-                         inequality_constraints=None, equality_constraints=None):
+                         inequality_constraints=None, equality_constraints=None,
+                         return_full_tree=False):
     """optimize.py:246-394 (the linear constraints go to the initial-condition
-    generator always and to ``gen_candidates`` when given, :255-303)."""
+    generator always and to ``gen_candidates`` when given, :255-303).  A
+    one-shot acquisition function starts from gen_one_shot_kg_initial_conditions
+    and returns only its candidates unless ``return_full_tree`` (:384-392)."""
+    from .acquisition import OneShotAcquisitionFunction
     options = options or {}
     provided = batch_initial_conditions is not None
-    ic_gen = ic_generator or gen_batch_initial_conditions
+    one_shot = isinstance(acq_function, OneShotAcquisitionFunction)
+    ic_gen = ic_generator or (gen_one_shot_kg_initial_conditions if one_shot
+                              else gen_batch_initial_conditions)
 
     def _ics():
         return ic_gen(acq_function=acq_function, bounds=bounds, q=q, num_restarts=num_restarts,
@@ -1109,7 +1163,9 @@ def _optimize_acqf_batch(acq_function, bounds, q, num_restarts, raw_samples, opt
     _check_deferred(cands)
     if return_best_only:
         best = torch.argmax(vals.view(-1), dim=0)
-        return cands[best], vals[best]
+        cands, vals = cands[best], vals[best]
+    if one_shot and not return_full_tree:
+        cands = acq_function.extract_candidates(X_full=cands)
     return cands, vals
 
 
@@ -1131,8 +1187,11 @@ def optimize_acqf(acq_function, bounds, q, num_restarts, raw_samples=None, optio
     samples (hit-and-run) for the initial conditions and SLSQP in
     gen_candidates_scipy (the device L-BFGS-B refuses them).  Nonlinear
     constraints raise UnsupportedError (out of scope); every other argument has
-    the reference's meaning.  ``return_full_tree`` only matters for one-shot
-    acquisitions, which are not on this path."""
+    the reference's meaning.  A one-shot acquisition function
+    (qKnowledgeGradient) is optimised over its q + N_f points jointly from
+    gen_one_shot_kg_initial_conditions; the candidates alone are returned
+    unless ``return_full_tree``, and ``sequential=True`` raises
+    NotImplementedError (optimize.py:195-199)."""
     return optimize_acqf_driver(
         _optimize_acqf_batch, acq_function, bounds, q, num_restarts, raw_samples, options,
         inequality_constraints, equality_constraints, nonlinear_inequality_constraints,
@@ -1173,6 +1232,10 @@ def optimize_acqf_driver(batch_fn, acq_function, bounds, q, num_restarts, raw_sa
                 retry_on_optimization_warning=retry_on_optimization_warning,
                 ic_gen_kwargs=ic_gen_kwargs, inequality_constraints=inequality_constraints,
                 equality_constraints=equality_constraints)
+    from .acquisition import OneShotAcquisitionFunction
+    one_shot = isinstance(acq_function, OneShotAcquisitionFunction)
+    if one_shot:  # only a one-shot function has a tree to return
+        args["return_full_tree"] = return_full_tree
     if not (sequential and q > 1):
         return batch_fn(**args)
     # _validate_sequential_inputs (optimize.py:162-199), then q greedy picks
@@ -1188,6 +1251,9 @@ def optimize_acqf_driver(batch_fn, acq_function, bounds, q, num_restarts, raw_sa
                                "constraints.")
     if not return_best_only:
         raise NotImplementedError("`return_best_only=False` only supported for joint optimization.")
+    if one_shot:
+        raise NotImplementedError("sequential optimization currently not supported for one-shot "
+                                  "acquisition functions. Must have `sequential=False`.")
     args.update(q=1, batch_initial_conditions=None, return_best_only=True,
                 timeout_sec=timeout_sec / q if timeout_sec is not None else None)
     base_pending = acq_function.X_pending

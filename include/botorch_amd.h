@@ -982,6 +982,39 @@ typedef struct BoQmcFeasArgs {
 int bo_qmc_feas_v(const BoQmcFeasArgs* a, void* stream);
 int bo_qmc_feas_backward_v(const BoQmcFeasArgs* a, void* stream);
 
+/* One-shot knowledge gradient with the posterior mean as inner value
+ * (botorch/acquisition/knowledge_gradient.py:151-207, models/model.py:328-407)
+ * from packed posterior moments.  Restart b owns T tiles of q' = q_a + slots
+ * rows: the q_a actual points, then `slots` fantasy solutions; fantasy i sits
+ * in tile i / slots, row q_a + i % slots.  mean: B T q', cov: B T q' q'.
+ *   A = cov[tile 0][:q_a, :q_a] + noise I,   L = psd_safe_cholesky(A)
+ *   w_i = L^{-T} z_i                         (z_i: row i of Z, N_f x q_a)
+ *   v_i = mean[row_i] + sum_j cov[row_i][j] w_ij   (j < q_a)
+ *   values[b][i] = v_i,   acq[b] = mean_i v_i      (fixed summation order)
+ * Only those entries of mean / cov are read.  The ladder is plain first, then
+ * jitter0 10^k (k < max_tries) on the diagonal; info[b] (0: factored) and
+ * jitter[b] (total added) are nullable; a failed restart's outputs are NaN.
+ * L (B q_a q_a, upper zero) and W (B N_f q_a) are kept for the backward,
+ * which from dacq (B) and optionally dvalues (B N_f) writes all of dmean and
+ * dcov: with c_i = dacq[b] / N_f + dvalues[b][i], dmean[row_i] = c_i,
+ * dcov[row_i][j] = c_i w_ij, the tile-0 q_a x q_a block the (symmetric)
+ * Cholesky backward of dL = -tril(sum_i c_i w_i u_i^T), u_i = L^{-1} cov[row_i][:q_a],
+ * and every other entry zero.  One workgroup per restart, one launch each way,
+ * no atomics.  A pure addition to the ABI: BO_ABI_VERSION stays 11. */
+typedef struct BoKgArgs {
+  BO_STRUCT_HEADER;
+  int32_t B, T, q_a, slots, N_f, max_tries;
+  double noise, jitter0;
+  const double *mean, *cov, *Z;
+  double *acq, *values, *L, *W; /* forward: outputs; backward: L, W are inputs */
+  int32_t* info;
+  double* jitter;
+  const double *dacq, *dvalues; /* backward only; dvalues nullable */
+  double *dmean, *dcov;         /* backward only */
+} BoKgArgs;
+int bo_kg_v(const BoKgArgs* a, void* stream);
+int bo_kg_backward_v(const BoKgArgs* a, void* stream);
+
 typedef struct BoLbfgsStepArgs { /* bo_lbfgs_step */
   BO_STRUCT_HEADER;
   int32_t B, n, m, _pad;
