@@ -94,6 +94,10 @@ _SIGNATURES = {
                                  _P, _P]),
     "bo_post_quad_plan": (c_int, [c_int64, c_int, c_int64, POINTER(c_int)]),
     "bo_post_small_plan": (c_int, [c_int64, c_int, c_int64, POINTER(c_int)]),
+    "bo_post_set_wide": (c_int, [c_int]),
+    "bo_post_wide_applies": (c_int, [c_int64, c_int, c_int64, c_int, c_int, c_int, POINTER(c_int)]),
+    "bo_post_wide_schedule": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int),
+                                      _P]),
     "bo_post_small": (c_int, [_P, c_int64, c_int, c_int64, _P, c_int64, _P, _P, _P, _P, _P]),
     "bo_post_small_batched": (c_int, [c_int, _P, _P, _P, _P, _P, _P, c_int64, c_int, c_int64,
                                       c_int64, _P]),

@@ -35,8 +35,10 @@
 // Test rows are laid out per t-batch: row b*Qp + a, a < q, Qp = q rounded up
 // to a power of two <= 16, so every t-batch sits inside one 16-row MFMA tile.
 #include "common.h"
+#include "post_wide_sched.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <map>
 #include <mutex>
@@ -756,6 +758,253 @@ __global__ __launch_bounds__(256, 2) void post_partials_kernel(
   }  // segments
 }
 
+// The 8-wave ("wide") form of the one-pass paired forward over K*x^T, i.e. of
+// post_partials_kernel<.., false, false, true> under grouped == 2: one
+// 512-thread workgroup per CU owns a 256-row x 128-column tile, wave w the 32
+// rows i0 + 32 w with the same acc[8][2] block, the same direct-to-register
+// K*x^T operands, the same k-walk (long tile ascending, short partner
+// descending), the same zero-block skip and the same epilogue as a wave of the
+// 256-thread kernel, so every output is that kernel's bit for bit.  The U ring
+// is shared by all 8 waves (half the U loads and LDS stores per MFMA); one
+// workgroup per CU has the LDS for stages of postw::kSS k-steps, so the
+// workgroup meets at a barrier once per kSS steps (post_wide_sched.h).  A
+// build with BO_POSTW_STAGGER lets the late half of the workgroup trail the
+// early half by postw::kLag units; it measured slower and is off (kLag = 0:
+// `late` is false and `lag` 0 for every wave).
+// A super-tile (8 column tiles x 8 row tiles per XCD and round) is dealt to 32
+// workgroups; grid = 256 * ceil((nC / 16) * (nI / 8) / 8).
+// Barriers: every wave executes postw::barriers(nsteps) per segment, all of
+// them outside the half-dependent branches.
+#ifndef BO_POSTW_PRIO
+#define BO_POSTW_PRIO 0  // 1: static s_setprio(1) for waves 4-7 (A/B)
+#endif
+__global__ __launch_bounds__(512, 2) void post_partials_wide_kernel(
+    int n, const double* __restrict__ U, int64_t ldu, const double* __restrict__ beta, int nC,
+    int nI, double* __restrict__ Spart, double* __restrict__ mpart, double* __restrict__ Rt,
+    const double* __restrict__ Kt, int rt_blk) {
+  constexpr int SS = postw::kSS, NU = postw::kNU;
+  __shared__ __attribute__((aligned(16))) double Us[postw::kStages][SS * PK][PLD];
+  const int bid = blockIdx.x;
+  const int xcd = bid & 7;
+  const int slot = bid >> 3;
+  const int tt = (slot >> 5) * 8 + xcd;
+  const int w = slot & 31;
+  const int nIG = nI >> 3;
+  const int p = tt / nIG;
+  if (p >= (nC >> 4)) return;  // surplus blocks of the last round: before any barrier
+  const int ci_long = ((nC >> 3) - 1 - p) * 8 + 7 - (w & 7);
+  const int ci_short = p * 8 + (w & 7);
+  const int i0 = ((tt % nIG) * 4 + (w >> 3)) * (2 * PI);
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const bool late = postw::kLag > 0 && wave >= 4;
+#if BO_POSTW_PRIO
+  if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
+#endif
+  const int64_t ldk = (int64_t)nI * PI;
+  const int nrows16 = nI * (PI / 16);
+  // Both halves run ONE program over the stream of units, NU per interval; the
+  // halves differ in a scalar offset (the late half is `lag` units behind), in
+  // where the U store sits and in when the interval's first slice is read.
+  // (Branching the units themselves by half costs the accumulators'
+  // coalescing: hundreds of spilled registers.)
+  const int lag = postw::lag_of(late);
+
+  for (int sidx = 0; sidx < 2; ++sidx) {
+    const int ci = sidx == 0 ? ci_long : ci_short;
+    const int c0 = ci * PC;
+    const int kend = min(n, c0 + PC);
+    const int nsteps = (kend + PK - 1) / PK;
+    const int nss = postw::supersteps(nsteps);
+    const bool rev = BO_POST_PAIRED_REV && sidx == 1;
+    const int kfirst = postw::walk_k0(0, nsteps, rev, PK);
+    const int kdir = rev ? -PK : PK;
+    // the skipping steps of the diagonal block (post_partials_kernel's DIAG run)
+    const int a0 = min(nsteps, c0 / PK + 1);
+    const int d0 = rev ? 0 : a0, d1 = rev ? nsteps - a0 : nsteps;
+
+    v4d acc[8][2];
+#pragma unroll
+    for (int a = 0; a < 8; ++a) {
+      acc[a][0] = v4d_zero();
+      acc[a][1] = v4d_zero();
+    }
+    // Per-thread staging: 2 x 16 B of U rows per step of a super-step (rows
+    // wave and wave + 8 of the step), the K*x^T operands of the interval's NU
+    // next two units (a unit's registers are reloaded with the operands of the
+    // unit after the next as soon as it is multiplied: no copies, and a whole
+    // unit's MFMAs to land in), the interval's first U slice.
+    double us_[SS][4];
+    double bu[2][2][2], an[8];
+    const double* ubase = U + (int64_t)(kfirst + wave) * ldu + c0 + 2 * lane;
+    const double* bbase = Kt + (int64_t)(kfirst + (lane >> 4)) * ldk + i0 + wave * 32 + (lane & 15);
+    const int64_t ustep = (int64_t)kdir * ldu, bstep = (int64_t)kdir * ldk;
+    // super-step G: its steps, clamped to the last one (harmless duplicate rows)
+#define BO_W_LOAD_U(G)                                                             \
+  {_Pragma("unroll") for (int e = 0; e < SS; ++e) {                               \
+    const double* up = ubase + (int64_t)min((G) * SS + e, nsteps - 1) * ustep;     \
+    const double2 v0 = *reinterpret_cast<const double2*>(up);                      \
+    const double2 v1 = *reinterpret_cast<const double2*>(up + 8 * ldu);            \
+    us_[e][0] = v0.x; us_[e][1] = v0.y; us_[e][2] = v1.x; us_[e][3] = v1.y;        \
+  }}
+#define BO_W_STORE(G)                                                              \
+  {_Pragma("unroll") for (int e = 0; e < SS; ++e) {                               \
+    double* dst = &Us[(G) & (postw::kStages - 1)][e * PK + wave][2 * lane];        \
+    *reinterpret_cast<double2*>(dst) = make_double2(us_[e][0], us_[e][1]);         \
+    *reinterpret_cast<double2*>(dst + 8 * PLD) = make_double2(us_[e][2], us_[e][3]); \
+  }}
+  // the K*x^T operands of unit UNIT (clamped to the segment's units: the
+  // operands of a unit that does not exist are loaded and never multiplied)
+#define BO_W_LOAD_B(UNIT, DST)                                                     \
+  {                                                                                \
+    const int u_ = min(max((UNIT), 0), 2 * nsteps - 1);                            \
+    const double* bp = bbase + (int64_t)postw::unit_step(u_) * bstep +             \
+                       (int64_t)(postw::unit_slice0(u_) * 4) * ldk;                \
+    _Pragma("unroll") for (int it = 0; it < 2; ++it)                              \
+      _Pragma("unroll") for (int sl = 0; sl < 2; ++sl)                               \
+        DST[it][sl] = bp[(int64_t)(4 * sl) * ldk + it * 16];                         \
+  }
+  // the LDS address of unit UNIT's first slice (this lane's row and column)
+#define BO_W_UADDR(UNIT)                                                           \
+  (&Us[postw::stage_of_step(postw::unit_step(UNIT))]                               \
+      [postw::stage_row_of_step(postw::unit_step(UNIT), PK) +                      \
+       postw::unit_slice0(UNIT) * 4 + (lane >> 4)][lane & 15])
+#define BO_W_PREF(UNIT)                                                            \
+  {                                                                                \
+    const double* us = BO_W_UADDR(UNIT);                                           \
+    _Pragma("unroll") for (int ct = 0; ct < 8; ++ct) an[ct] = us[ct * 16];        \
+  }
+  // Unit UNIT (two k-slices; BOP its K*x^T operands); PREF: its first slice is
+  // in `an`.  DIAG: the zero-block skip of post_partials_kernel (ctb = 0 on a
+  // step outside the diagonal block's skipping run).
+#define BO_W_UNIT(UNIT, BOP, PREF, DIAG)                                           \
+  {                                                                                \
+    const double* us = BO_W_UADDR(UNIT);                                           \
+    const int kd = kfirst + postw::unit_step(UNIT) * kdir - c0;                    \
+    const int ctb = (DIAG) ? __builtin_amdgcn_readfirstlane(max(kd, 0) >> 4) : 0;  \
+    _Pragma("unroll") for (int sl = 0; sl < 2; ++sl) {                             \
+      double a[8];                                                                 \
+      _Pragma("unroll") for (int ct = 0; ct < 8; ++ct)                            \
+        a[ct] = ((PREF) && sl == 0) ? an[ct] : us[sl * 4 * PLD + ct * 16];         \
+      _Pragma("unroll") for (int ct = 0; ct < 8; ++ct)                            \
+        if (!(DIAG) || ct >= ctb) {                                                \
+          _Pragma("unroll") for (int it = 0; it < 2; ++it)                        \
+            acc[ct][it] = mfma_f64(a[ct], BOP[it][sl], acc[ct][it]);              \
+        }                                                                          \
+    }                                                                              \
+  }
+  // Interval J: units NU J - lag + k, each one's operand registers reloaded
+  // behind it for the unit after the next; the store of super-step J + 1 behind
+  // the last unit (early half) or behind unit NU / 2 - 1 (late half: its drain
+  // hides under the units that follow and it reaches the barrier straight from
+  // MFMAs while the early half stores).  GUARD: the segment's first and last
+  // intervals, where some units do not exist (outside the loops: a branch
+  // around a unit inside them costs the accumulators' coalescing); STORE 0:
+  // the last interval.
+#define BO_W_INTERVAL(J, DIAG, GUARD, STORE)                                       \
+  {                                                                                \
+    const int u0 = NU * (J) - lag;                                                 \
+    if (!late) BO_W_PREF(u0);  /* behind the barrier: written in interval J - 1 */ \
+    _Pragma("unroll") for (int k = 0; k < NU; ++k) {                              \
+      if (!(GUARD) || postw::unit_valid(u0 + k, nsteps))                           \
+        BO_W_UNIT(u0 + k, bu[k & 1], k == 0, DIAG)                                 \
+      BO_W_LOAD_B(u0 + k + 2, bu[k & 1]);                                          \
+      if ((STORE) && k == postw::store_after_unit(true) && late) BO_W_STORE((J) + 1);  \
+    }                                                                              \
+    if (late) BO_W_PREF(u0 + NU);  /* complete since interval J - 1 */             \
+    if ((STORE) && !late) BO_W_STORE((J) + 1);                                     \
+    if (STORE) BO_W_LOAD_U((J) + 2);  /* unconditional: counted waits */           \
+    __syncthreads();                                                               \
+  }
+    static_assert(postw::unit_at(3, 1, false) == 3 * NU + 1 &&
+                      postw::unit_at(3, 1, true) == 3 * NU + 1 - postw::kLag &&
+                      postw::store_after_unit(false) == NU - 1,
+                  "BO_W_INTERVAL's units and stores are post_wide_sched.h's");
+
+    BO_W_LOAD_U(0);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) BO_W_LOAD_B(k - lag, bu[k]);
+    BO_W_STORE(0);
+    BO_W_LOAD_U(1);  // in flight over the barrier
+    __syncthreads();  // barrier 0
+    // The first interval and the ragged last ones are guarded; of the others,
+    // those that touch a skipping step (steps SS J - 1 .. SS J + SS - 1) run the
+    // DIAG form, in loops of their own so that the plain loop keeps its
+    // schedule.  Every bound is the same for both halves.
+    const int jfull = nsteps / SS;  // intervals 1 .. jfull - 1: every unit exists
+    constexpr int LB = postw::kLag > 1 ? (postw::kLag + 1) / 2 : 1;  // steps the late half reaches back
+    const int jd0 = min(jfull, max(1, d0 / SS));
+    const int jd1 = max(jd0, min(jfull, (d1 + LB - 1) / SS + 1));
+    int j = 0;
+    BO_W_INTERVAL(j, 1, 1, 1)
+    for (j = 1; j < jd0; ++j) BO_W_INTERVAL(j, 0, 0, 1)
+    for (; j < jd1; ++j) BO_W_INTERVAL(j, 1, 0, 1)
+    for (; j < jfull; ++j) BO_W_INTERVAL(j, 0, 0, 1)
+    if (j < nss) {  // a ragged last super-step (at most one)
+      BO_W_INTERVAL(j, 1, 1, 1)
+    }
+    // interval nss: the late half's trailing units; its barrier also keeps the
+    // next segment's prologue from rewriting stage 0 under the last readers
+    BO_W_INTERVAL(nss, 1, 1, 0)
+#undef BO_W_INTERVAL
+#undef BO_W_UNIT
+#undef BO_W_PREF
+#undef BO_W_UADDR
+#undef BO_W_LOAD_B
+#undef BO_W_STORE
+#undef BO_W_LOAD_U
+
+    // post_partials_kernel's one-pass epilogue over the [ct][it] accumulators
+    const int nrows_pad = nI * PI;
+    if (Rt != nullptr && rt_blk) {
+#pragma unroll
+      for (int ct = 0; ct < 8; ++ct)
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+          double* blk = Rt + ((int64_t)((c0 >> 4) + ct) * nrows16 +
+                              ((i0 + wave * 32 + it * 16) >> 4)) * 256 + lane;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) blk[r * 64] = acc[ct][it][r];
+        }
+    } else if (Rt != nullptr) {
+#pragma unroll
+      for (int ct = 0; ct < 8; ++ct)
+#pragma unroll
+        for (int it = 0; it < 2; ++it)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int c = c0 + ct * 16 + mfma_row(lane, r);
+            const int i = i0 + wave * 32 + it * 16 + mfma_col(lane);
+            Rt[(int64_t)c * nrows_pad + i] = acc[ct][it][r];
+          }
+    }
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      v4d P = v4d_zero();
+#pragma unroll
+      for (int ct = 0; ct < 8; ++ct)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) P = mfma_f64(acc[ct][it][r], acc[ct][it][r], P);
+      const int row0 = i0 + wave * 32 + it * 16;
+      double* sp = Spart + ((int64_t)ci * nrows16 + row0 / 16) * 256;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sp[mfma_row(lane, r) * 16 + mfma_col(lane)] = P[r];
+      double m = 0.0;
+#pragma unroll
+      for (int ct = 0; ct < 8; ++ct)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int c = c0 + ct * 16 + mfma_row(lane, r);
+          m = fma(acc[ct][it][r], (c < n) ? beta[c] : 0.0, m);
+        }
+      m += __shfl_xor(m, 16);
+      m += __shfl_xor(m, 32);
+      if (lane < 16) mpart[(int64_t)ci * nrows_pad + row0 + lane] = m;
+    }
+  }  // the two column tiles
+}
+
 // K*x^T once per call: Kt[k][i] = outputscale k(x_i, x_k), zero for k >= n
 // or padding rows; np x nrows_pad.  The one-pass grid re-reads each K*x tile
 // from L2/HBM for every column tile whose k-range covers it (nC / 2 times on
@@ -1256,6 +1505,29 @@ static bool paired_enabled() {
     return !(e && e[0] == '0');
   }();
   return on;
+}
+
+// Route of the one-pass paired forward over K*x^T (bo_post_set_wide): 0 the
+// library's choice (BO_POST_WIDE_DEFAULT), -1 the 256-thread kernel, 1 the
+// 8-wave kernel wherever it is eligible.  BO_POST_WIDE=-1|0|1 sets the initial
+// mode (A/B timing of whole programs).
+#ifndef BO_POST_WIDE_DEFAULT
+#define BO_POST_WIDE_DEFAULT 1
+#endif
+static std::atomic<int>& wide_mode() {
+  static std::atomic<int> m{[] {
+    const char* e = std::getenv("BO_POST_WIDE");
+    const int v = e ? std::atoi(e) : 0;
+    return v >= -1 && v <= 1 ? v : 0;
+  }()};
+  return m;
+}
+// Eligibility is the paired schedule's own: one pass, column groups that pair
+// up, 8 x 8 super-tiles; only the plain forward that reads K*x^T.
+static bool wide_applies(int nC, int nI, int kc_len, bool cross, bool pre) {
+  const int mode = wide_mode().load();
+  if (mode < 0 || (mode == 0 && !BO_POST_WIDE_DEFAULT)) return false;
+  return kc_len == 0 && !cross && pre && nI > 0 && nC % 16 == 0 && nI % 8 == 0 && paired_enabled();
 }
 
 // ---- split plans (host) ----------------------------------------------------------
@@ -1937,6 +2209,13 @@ int bo_post_partials_layout(int kind, const double* Xq, int B, int q, int d,
   const int4* segs = plan ? plan->segs : nullptr;
   const int* wg_off = plan ? plan->wg_off : nullptr;
   hipStream_t st = as_stream(stream);
+  if (wide_applies(nC, nI, kc_len, Qc != nullptr, pre)) {
+    const int64_t wblocks = 256 * (int64_t)ceil_div((nC / 16) * (nI / 8), 8);
+    post_partials_wide_kernel<<<(unsigned)wblocks, 512, 0, st>>>(
+        (int)n, U, ldu, beta, nC, nI, Spart, mpart, Rt, Kt, rt_layout == BO_RT_BLOCKED);
+    BO_LAUNCH_CHECK();
+    return BO_OK;
+  }
   // One instantiation per active input dimension (the padded coordinates
   // beyond d are zero, so fewer distance terms are exact, not approximate).
 #define BO_POST_GO(KIND, ND, SPL, CRS, PRE_)                                                \
@@ -1978,6 +2257,73 @@ int bo_post_partials_layout(int kind, const double* Xq, int B, int q, int d,
         work, plan->red, (int)n, nI, beta, Spart, mpart, Rt);
     BO_LAUNCH_CHECK();
   }
+  return BO_OK;
+}
+
+int bo_post_set_wide(int mode) {
+  BO_CHECK_ARG(mode >= -1 && mode <= 1, "bo_post_set_wide: mode %d (-1, 0 or 1)", mode);
+  wide_mode().store(mode);
+  return BO_OK;
+}
+
+int bo_post_wide_applies(int64_t B, int q, int64_t n, int kc_len, int has_cross, int has_kt,
+                         int* out) {
+  int Qp, nrows_pad, nC;
+  int s = bo_post_geometry(B, q, n, &Qp, &nrows_pad, &nC);
+  if (s) return s;
+  *out = wide_applies(nC, nrows_pad / PI, kc_len, has_cross != 0, has_kt != 0) ? 1 : 0;
+  return BO_OK;
+}
+
+// The wide kernel's LDS schedule for one half (0: waves 0-3, 1: waves 4-7) of
+// a segment of nsteps k-steps walked ascending (rev 0) or descending, as rows
+// of 6 ints (interval, kind, step, slice, stage, first training row of the
+// step) in program order: kind 0 = a k-slice read from LDS, 1 = the U store of
+// a step (slice -1), 2 = the k-slice's MFMAs.  Interval -1 is the prologue.
+int bo_post_wide_schedule(int nsteps, int half, int rev, int cap, int* n_barriers, int* n_events,
+                          int* events) {
+  BO_CHECK_ARG(nsteps >= 1 && (half == 0 || half == 1) && n_barriers && n_events,
+               "bo_post_wide_schedule: nsteps %d, half %d", nsteps, half);
+  const bool late = half == 1;  // lag_of is 0 for both halves in a build without the stagger
+  const int lag = postw::lag_of(late);
+  int ne = 0;
+  auto emit = [&](int j, int kind, int step, int slice) {
+    if (events && ne < cap) {
+      int* e = events + 6 * (int64_t)ne;
+      e[0] = j; e[1] = kind; e[2] = step; e[3] = slice; e[4] = postw::stage_of_step(step);
+      e[5] = postw::walk_k0(step, nsteps, rev != 0, PK);
+    }
+    ++ne;
+  };
+  auto first_read = [&](int j, int u) {  // a unit's first slice, read ahead of the unit
+    if (postw::unit_valid(u, nsteps)) emit(j, 0, postw::unit_step(u), postw::unit_slice0(u));
+  };
+  auto store = [&](int j) {
+    const int g = postw::store_superstep(j, nsteps);
+    for (int e = 0; g >= 0 && e < postw::kSS; ++e) emit(j, 1, g * postw::kSS + e, -1);
+  };
+  for (int e = 0; e < postw::kSS; ++e) emit(-1, 1, e, -1);  // the prologue: super-step 0
+  for (int j = 0; j < postw::intervals(nsteps); ++j) {
+    if (!postw::prefetches(lag > 0)) first_read(j, postw::unit_at(j, 0, late));
+    for (int k = 0; k < postw::kNU; ++k) {
+      const int u = postw::unit_at(j, k, late);
+      if (postw::unit_valid(u, nsteps)) {
+        for (int i = 0; i < postw::kSlices / 2; ++i) {
+          const int sl = postw::unit_slice0(u) + i;
+          // the interval's first slice was read ahead; the late half's first
+          // existing unit of interval 0 is not the interval's first: read in place
+          if (!(k == 0 && i == 0)) emit(j, 0, postw::unit_step(u), sl);
+          emit(j, 2, postw::unit_step(u), sl);
+        }
+      }
+      if (lag > 0 && k == postw::store_after_unit(true)) store(j);
+    }
+    if (postw::prefetches(lag > 0) && j + 1 < postw::intervals(nsteps))
+      first_read(j, postw::unit_at(j + 1, 0, late));
+    if (lag == 0) store(j);
+  }
+  *n_barriers = postw::barriers(nsteps);
+  *n_events = ne;
   return BO_OK;
 }
 

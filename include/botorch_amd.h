@@ -409,6 +409,27 @@ int bo_post_split_plan(int64_t B, int q, int64_t n, int slots, int* kc_len,
 /* Workspace doubles of bo_post_partials under a given kc_len (0, -1 or a
  * chunk length). */
 int bo_post_split_work(int64_t B, int q, int64_t n, int kc_len, int64_t* work_elems);
+/* Route of the one-pass paired forward that reads K*x^T (kc_len = 0, Kt given,
+ * no cross term, nC % 16 == 0 and nrows_pad / 128 % 8 == 0, BO_POST_PAIRED not
+ * 0): 0 (default) the library's choice, -1 the 256-thread kernel, 1 the 8-wave
+ * kernel (one 512-thread workgroup per 256 x 128 tile, U staged through LDS
+ * two k-steps per barrier).  Every output is bit for bit the same on
+ * both routes; every other shape and flag runs the 256-thread kernel.
+ * bo_post_wide_applies: *out = 1 where a bo_post_partials call of that shape
+ * would take the 8-wave kernel under the current mode (tests assert the route).
+ * bo_post_wide_schedule (host): the 8-wave kernel's LDS schedule for one half
+ * (0: waves 0-3, 1: waves 4-7) of a segment of nsteps k-steps walked ascending
+ * (rev = 0) or descending, as rows of 6 ints (barrier interval, kind, step,
+ * k-slice, LDS stage, first training row of the step) in program order; kind
+ * 0 = a k-slice read, 1 = the U store of a step (slice -1), 2 = the slice's
+ * MFMAs; interval -1 is the prologue in front of the first barrier.  Writes at
+ * most `cap` rows; *n_events = the number of rows, *n_barriers = the barriers
+ * every wave executes. */
+int bo_post_set_wide(int mode);
+int bo_post_wide_applies(int64_t B, int q, int64_t n, int kc_len, int has_cross, int has_kt,
+                         int* out);
+int bo_post_wide_schedule(int nsteps, int half, int rev, int cap, int* n_barriers, int* n_events,
+                          int* events);
 
 /* Small-grid forward posterior (round 5; replaces the stream-K split + split-k
  * reduction of small forward-only grids such as C2, the R R^T / R beta
