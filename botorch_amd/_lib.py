@@ -267,6 +267,15 @@ class KgArgs(_Args):
                        ("dacq", _D), ("dvalues", _D), ("dmean", _D), ("dcov", _D)]
 
 
+class PathsArgs(_Args):
+    _fields_ = _HDR + [("kind", c_int32), ("d", c_int32), ("S", c_int32), ("M", c_int32),
+                       ("R", c_int64), ("n", c_int64), ("inner", c_int64), ("X", _D),
+                       ("lengthscale", _D), ("Xt_scaled", _D), ("Omega", _D), ("W", _D),
+                       ("V", _D), ("outputscale", c_double), ("constant", c_double),
+                       ("ymean", c_double), ("ystd", c_double), ("out", _D), ("dout", _D),
+                       ("dX", _D)]
+
+
 class LbfgsStepArgs(_Args):
     _fields_ = _HDR + [("B", c_int32), ("n", c_int32), ("m", c_int32), ("_pad", c_int32),
                        ("x", _D), ("f", _D), ("g", _D), ("xt", _D), ("ft", _D), ("gt", _D),
@@ -291,6 +300,7 @@ for _name, _cls in (("bo_post_partials_v", PostPartialsArgs), ("bo_qmc_finalize_
                     ("bo_qlogehvi_v", QlogehviArgs), ("bo_qlogehvi_backward_v", QlogehviArgs),
                     ("bo_qmc_feas_v", QmcFeasArgs), ("bo_qmc_feas_backward_v", QmcFeasArgs),
                     ("bo_kg_v", KgArgs), ("bo_kg_backward_v", KgArgs),
+                    ("bo_paths_eval_v", PathsArgs), ("bo_paths_eval_backward_v", PathsArgs),
                     ("bo_lbfgs_step_v", LbfgsStepArgs), ("bo_lbfgsb_step_v", LbfgsbArgs)):
     _SIGNATURES[_name] = (c_int, [POINTER(_cls), _P])
 _SIGNATURES["bo_struct_size"] = (c_int64, [ctypes.c_char_p])
@@ -299,7 +309,7 @@ ARG_RECORDS = {"BoPostPartialsArgs": PostPartialsArgs, "BoQmcFinalizeArgs": QmcF
                "BoQmcBackwardArgs": QmcBackwardArgs, "BoPostBackwardArgs": PostBackwardArgs,
                "BoQehviArgs": QehviArgs, "BoQehviFeasArgs": QehviFeasArgs,
                "BoQlogehviArgs": QlogehviArgs, "BoQmcFeasArgs": QmcFeasArgs, "BoKgArgs": KgArgs,
-               "BoLbfgsStepArgs": LbfgsStepArgs,
+               "BoPathsArgs": PathsArgs, "BoLbfgsStepArgs": LbfgsStepArgs,
                "BoLbfgsbArgs": LbfgsbArgs}
 
 _lib = None

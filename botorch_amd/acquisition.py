@@ -531,6 +531,46 @@ class PosteriorMean(AnalyticAcquisitionFunction):
         return mean if self.maximize else -mean
 
 
+# -- pathwise Thompson sampling -----------------------------------------------------------
+BATCH_SIZE_CHANGE_ERROR = """The batch size of PathwiseThompsonSampling should \
+not change during a forward pass - was {}, now {}. Please re-initialize the \
+acquisition if you want to change the batch size."""
+
+
+class PathwiseThompsonSampling(AcquisitionFunction):
+    """acquisition/thompson_sampling.py:22-87: single-outcome Thompson sampling
+    as an acquisition function.  The q points of a t-batch are evaluated on q
+    posterior function draws (point i on draw i; pathwise.get_matheron_path_model,
+    the fused kernel's mapped mode) and the values summed, so maximising it
+    yields q Thompson samples.  The draws are made at the first call and kept
+    until :meth:`redraw`."""
+
+    def __init__(self, model, posterior_transform=None):
+        if getattr(model, "_is_fully_bayesian", False):
+            raise NotImplementedError(
+                "PathwiseThompsonSampling is not supported for fully Bayesian models")
+        super().__init__(model)
+        self.batch_size: Optional[int] = None
+        self.samples = None
+
+    def redraw(self) -> None:
+        from .pathwise import get_matheron_path_model
+        self.samples = get_matheron_path_model(model=self.model,
+                                               sample_shape=torch.Size([self.batch_size]))
+
+    def forward(self, X: torch.Tensor) -> torch.Tensor:
+        X = t_batch_mode(X)
+        batch_size = X.shape[-2]
+        if self.batch_size is None:
+            self.batch_size = batch_size
+            self.redraw()
+        elif self.batch_size != batch_size:
+            raise ValueError(BATCH_SIZE_CHANGE_ERROR.format(self.batch_size, batch_size))
+        # batch_shape x q x 1 x d on the q draws -> batch_shape x q x 1 x m
+        values = self.samples(X.unsqueeze(-2)).squeeze(-2)
+        return values.sum(-2).squeeze(-1)
+
+
 # -- one-shot knowledge gradient --------------------------------------------------------
 class OneShotAcquisitionFunction:
     """acquisition/acquisition.py:149-177: an acquisition function optimised

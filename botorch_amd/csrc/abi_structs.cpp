@@ -74,6 +74,10 @@ int bo_qmc_feas_backward_impl(const BoQmcFeasArgs* a, void* stream);
 int bo_kg_impl(const BoKgArgs* a, void* stream);
 int bo_kg_backward_impl(const BoKgArgs* a, void* stream);
 
+// the pathwise-sample evaluations (paths.hip)
+int bo_paths_eval_impl(const BoPathsArgs* a, void* stream);
+int bo_paths_eval_backward_impl(const BoPathsArgs* a, void* stream);
+
 int bo_post_partials_v(const BoPostPartialsArgs* a, void* stream) {
   if (!header_ok(a, "bo_post_partials_v")) return BO_ERR_ARG;
   return bo_post_partials_layout(a->kind, a->Xq, a->B, a->q, a->d, a->Xt_scaled, a->n, a->U,
@@ -160,6 +164,16 @@ int bo_kg_backward_v(const BoKgArgs* a, void* stream) {
   return bo_kg_backward_impl(a, stream);
 }
 
+int bo_paths_eval_v(const BoPathsArgs* a, void* stream) {
+  if (!header_ok(a, "bo_paths_eval_v")) return BO_ERR_ARG;
+  return bo_paths_eval_impl(a, stream);
+}
+
+int bo_paths_eval_backward_v(const BoPathsArgs* a, void* stream) {
+  if (!header_ok(a, "bo_paths_eval_backward_v")) return BO_ERR_ARG;
+  return bo_paths_eval_backward_impl(a, stream);
+}
+
 int bo_lbfgs_step_v(const BoLbfgsStepArgs* a, void* stream) {
   if (!header_ok(a, "bo_lbfgs_step_v")) return BO_ERR_ARG;
   return bo_lbfgs_step(a->B, a->n, a->m, a->x, a->f, a->g, a->xt, a->ft, a->gt, a->d, a->alpha,
@@ -188,6 +202,7 @@ extern "C" int64_t bo_struct_size(const char* name) {
   if (s == "BoQlogehviArgs") return sizeof(BoQlogehviArgs);
   if (s == "BoQmcFeasArgs") return sizeof(BoQmcFeasArgs);
   if (s == "BoKgArgs") return sizeof(BoKgArgs);
+  if (s == "BoPathsArgs") return sizeof(BoPathsArgs);
   if (s == "BoLbfgsStepArgs") return sizeof(BoLbfgsStepArgs);
   if (s == "BoLbfgsbArgs") return sizeof(BoLbfgsbArgs);
   return -1;

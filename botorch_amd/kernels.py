@@ -2075,6 +2075,92 @@ def kg_backward(cov: torch.Tensor, L: torch.Tensor, W: torch.Tensor, dacq: torch
     return dmean, dcov
 
 
+PATHS_DMAX = 128  # bo_paths_eval: d is a runtime loop up to here
+
+
+def paths_check(d: int, M: int, S: int) -> None:
+    """The argument limits of :func:`paths_eval`, raised on the host before any
+    native call (pathwise.py checks a draw's sizes with it)."""
+    if not 1 <= d <= PATHS_DMAX:
+        raise ValueError(f"paths_eval: 1 <= d <= {PATHS_DMAX} (got {d})")
+    if M < 2 or M % 2:
+        raise ValueError(f"paths_eval: the number of features must be even and >= 2 (got {M})")
+    if S < 1:
+        raise ValueError(f"paths_eval: S >= 1 (got {S})")
+
+
+def _paths_args(X, lengthscale, Omega, W, Xt_scaled, V, kind, outputscale, constant, ymean, ystd,
+                inner):
+    """The BoPathsArgs of :func:`paths_eval` / :func:`paths_eval_backward`: X
+    R x d, Omega H x d, W S x 2H, and Xt_scaled n x d with V S x n (both None:
+    the prior path alone, n = 0)."""
+    if X.dim() != 2:
+        raise ValueError(f"paths_eval: X must be R x d, got {tuple(X.shape)}")
+    R, d = X.shape
+    if W.dim() != 2 or Omega.dim() != 2:
+        raise ValueError("paths_eval: Omega must be H x d and W S x M")
+    S, M = W.shape
+    paths_check(d, M, S)
+    if tuple(Omega.shape) != (M // 2, d) or tuple(lengthscale.shape) != (d,):
+        raise ValueError(f"paths_eval: Omega must be {M // 2} x {d} and lengthscale have {d} "
+                         f"entries, got {tuple(Omega.shape)} and {tuple(lengthscale.shape)}")
+    if (V is None) != (Xt_scaled is None):
+        raise ValueError("paths_eval: Xt_scaled and V go together")
+    n = 0
+    if V is not None:
+        n = V.shape[1]
+        if V.dim() != 2 or V.shape[0] != S or tuple(Xt_scaled.shape) != (n, d):
+            raise ValueError(f"paths_eval: V must be {S} x n and Xt_scaled n x {d}, got "
+                             f"{tuple(V.shape)} and {tuple(Xt_scaled.shape)}")
+    inner = int(inner)
+    if inner < 0:
+        raise ValueError(f"paths_eval: inner >= 0 (got {inner})")
+    return _lib.PathsArgs(kind=int(kind), d=d, S=S, M=M, R=R, n=n, inner=inner, X=X.contiguous(),
+                          lengthscale=lengthscale.contiguous(), Omega=Omega.contiguous(),
+                          W=W.contiguous(), Xt_scaled=Xt_scaled.contiguous() if n else None,
+                          V=V.contiguous() if n else None, outputscale=float(outputscale),
+                          constant=float(constant), ymean=float(ymean), ystd=float(ystd))
+
+
+def paths_eval(X: torch.Tensor, lengthscale: torch.Tensor, Omega: torch.Tensor, W: torch.Tensor,
+               Xt_scaled: Optional[torch.Tensor], V: Optional[torch.Tensor], kind: int = _lib.RBF,
+               outputscale: float = 1.0, constant: float = 0.0, ymean: float = 0.0,
+               ystd: float = 1.0, inner: int = 0) -> torch.Tensor:
+    """S Matheron paths at the R rows of X (bo_paths_eval):
+    f_s(x) = ymean + ystd (constant + sqrt(2 o / M) sum_j (W[s, j] sin th_j + W[s, H + j] cos th_j)
+    + o sum_i V[s, i] k(x, Xt_i)), th_j = Omega[j] . (x / lengthscale).
+    ``inner = 0``: every path at every row -> S x R; ``inner >= 1``: row r on
+    path (r // inner) % S -> R.  The features and kernel rows stay in the
+    kernel's registers: there is no workspace, the only allocation is the
+    output (inputs that are not contiguous are copied first)."""
+    dev = _dev(X, lengthscale, Omega, W, Xt_scaled, V)
+    a = _paths_args(X, lengthscale, Omega, W, Xt_scaled, V, kind, outputscale, constant, ymean,
+                    ystd, inner)
+    out = torch.empty((a.R,) if a.inner else (a.S, a.R), dtype=torch.float64, device=dev)
+    a.out = out.data_ptr()
+    check(lib().bo_paths_eval_v(ctypes.byref(a), _stream(dev)), "paths_eval")
+    return out
+
+
+def paths_eval_backward(dout: torch.Tensor, X: torch.Tensor, lengthscale: torch.Tensor,
+                        Omega: torch.Tensor, W: torch.Tensor, Xt_scaled: Optional[torch.Tensor],
+                        V: Optional[torch.Tensor], kind: int = _lib.RBF, outputscale: float = 1.0,
+                        ystd: float = 1.0, inner: int = 0) -> torch.Tensor:
+    """dX (R x d) of :func:`paths_eval` from dout (S x R, or R when mapped),
+    summed over the paths of each row; no workspace."""
+    dev = _dev(dout, X, lengthscale, Omega, W, Xt_scaled, V)
+    a = _paths_args(X, lengthscale, Omega, W, Xt_scaled, V, kind, outputscale, 0.0, 0.0, ystd,
+                    inner)
+    want = (a.R,) if a.inner else (a.S, a.R)
+    if tuple(dout.shape) != want:
+        raise ValueError(f"paths_eval_backward: dout must be {want}, got {tuple(dout.shape)}")
+    dout = dout.contiguous()
+    dX = torch.empty(a.R, a.d, dtype=torch.float64, device=dev)
+    a.dout, a.dX = dout.data_ptr(), dX.data_ptr()
+    check(lib().bo_paths_eval_backward_v(ctypes.byref(a), _stream(dev)), "paths_eval_backward")
+    return dX
+
+
 def kernel_grad(X: torch.Tensor, Y: torch.Tensor, dK: torch.Tensor, lengthscale: torch.Tensor,
                 kind: int, outputscale: float = 1.0, group: int = 0,
                 dX: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -748,6 +748,38 @@ class ModelListGP(Model):
 MCMC_DIM = -3  # models/fully_bayesian.py: posterior batch dim of the MCMC samples
 
 
+class GenericDeterministicModel(Model):
+    """A deterministic model defined by a callable (models/deterministic.py):
+    ``f`` maps ``batch_shape x q x d`` to ``batch_shape x q x m``.  Its posterior
+    is the point mass at f(X) (posteriors.DeterministicPosterior); a posterior
+    transform with ``evaluate`` (ScalarizedPosteriorTransform) is applied to
+    the values."""
+
+    _is_ensemble = False
+
+    def __init__(self, f, num_outputs: int = 1):
+        super().__init__()
+        self._f = f
+        self._num_outputs = num_outputs
+
+    def forward(self, X: torch.Tensor) -> torch.Tensor:
+        return self._f(X)
+
+    def posterior(self, X, output_indices=None, observation_noise=False, posterior_transform=None):
+        from .posteriors import DeterministicPosterior
+        if observation_noise is not False:
+            raise UnsupportedError("a deterministic model has no observation noise")
+        values = self.forward(X)
+        if output_indices is not None:
+            values = values[..., list(output_indices)]
+        if posterior_transform is not None:
+            if not hasattr(posterior_transform, "evaluate"):
+                raise UnsupportedError("a deterministic model takes posterior transforms with "
+                                       "`evaluate` (ScalarizedPosteriorTransform)")
+            values = posterior_transform.evaluate(values).unsqueeze(-1)
+        return DeterministicPosterior(values)
+
+
 def sample_saas_prior(d: int, num_samples: int, seed: int = 0, dtype=torch.float64):
     """Hyperparameter sets from the SAAS prior (models/fully_bayesian.py:168-247):
     outputscale ~ Gamma(2, 0.15), mean ~ N(0, 1), noise = 1e-4 + Gamma(0.9, 10),

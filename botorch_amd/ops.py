@@ -28,6 +28,8 @@ Ops (reference computation each replaces):
                       (optim/closures/model_closures.py:171-184)
   bo::kg              one-shot qKnowledgeGradient value of packed posterior moments
                       (+ autograd, acquisition/knowledge_gradient.py:151-207)
+  bo::paths_eval      S Matheron paths at R points, features and kernel rows fused
+                      (+ autograd in X, sampling/pathwise/posterior_samplers.py:198-224)
 """
 from __future__ import annotations
 
@@ -573,7 +575,56 @@ def _kg_bwd(ctx, dacq, dvalues, *_):
 kg.register_autograd(_kg_bwd, setup_context=_kg_setup)
 
 
+# ---- bo::paths_eval (Matheron paths at R points, fused features + kernel rows) -----------------
+@torch.library.custom_op("bo::paths_eval", mutates_args=(), device_types="cuda")
+def paths_eval(X: Tensor, lengthscale: Tensor, Omega: Tensor, W: Tensor,
+               Xt_scaled: Optional[Tensor], V: Optional[Tensor], kind: int, outputscale: float,
+               constant: float, ymean: float, ystd: float, inner: int) -> Tensor:
+    """S pathwise posterior samples at the rows of X (R x d): S x R (inner = 0)
+    or, with row r on path (r // inner) % S, R values (kernels.paths_eval).
+    Differentiable in X only: Omega, W and V are buffers of the draw."""
+    return kernels.paths_eval(X, lengthscale, Omega, W, Xt_scaled, V, kind, outputscale, constant,
+                              ymean, ystd, inner)
+
+
+@paths_eval.register_fake
+def _(X, lengthscale, Omega, W, Xt_scaled, V, kind, outputscale, constant, ymean, ystd, inner):
+    R = X.shape[0]
+    return X.new_empty((R,) if inner else (W.shape[0], R), dtype=F64)
+
+
+@torch.library.custom_op("bo::paths_eval_backward", mutates_args=(), device_types="cuda")
+def paths_eval_backward(dout: Tensor, X: Tensor, lengthscale: Tensor, Omega: Tensor, W: Tensor,
+                        Xt_scaled: Optional[Tensor], V: Optional[Tensor], kind: int,
+                        outputscale: float, ystd: float, inner: int) -> Tensor:
+    return kernels.paths_eval_backward(dout, X, lengthscale, Omega, W, Xt_scaled, V, kind,
+                                       outputscale, ystd, inner)
+
+
+@paths_eval_backward.register_fake
+def _(dout, X, lengthscale, Omega, W, Xt_scaled, V, kind, outputscale, ystd, inner):
+    return X.new_empty(X.shape, dtype=F64)
+
+
+def _paths_setup(ctx, inputs, output):
+    X, lengthscale, Omega, W, Xt_scaled, V, kind, outputscale, _, _, ystd, inner = inputs
+    ctx.save_for_backward(X, lengthscale, Omega, W, Xt_scaled, V)
+    ctx.consts = (kind, outputscale, ystd, inner)
+
+
+def _paths_bwd(ctx, dout):
+    X, lengthscale, Omega, W, Xt_scaled, V = ctx.saved_tensors
+    dX = None
+    if ctx.needs_input_grad[0]:
+        dX = torch.ops.bo.paths_eval_backward(dout.contiguous(), X, lengthscale, Omega, W,
+                                              Xt_scaled, V, *ctx.consts)
+    return (dX,) + (None,) * 11
+
+
+paths_eval.register_autograd(_paths_bwd, setup_context=_paths_setup)
+
+
 OPS: List[str] = ["sobol_normal", "gp_cache", "gp_cache_extend", "chol_jitter", "chol_backward",
                   "post_partials", "qmc_finalize", "gp_posterior", "gp_posterior_backward",
                   "qmc_acq", "qmc_acq_backward", "qehvi", "qehvi_backward", "mll", "kg",
-                  "kg_backward"]
+                  "kg_backward", "paths_eval", "paths_eval_backward"]

@@ -270,3 +270,32 @@ class PosteriorList:
 
     def rsample(self, sample_shape=None):
         return self._reshape_and_cat([p.rsample(sample_shape) for p in self.posteriors])
+
+
+class DeterministicPosterior:
+    """The point-mass posterior of a deterministic model: ``mean`` the values
+    (batch_shape x q x m), zero ``variance``, and ``rsample`` the mean expanded
+    by the sample shape.  Enough for PosteriorMean and optimize_acqf; MC
+    acquisition functions over it are not supported."""
+
+    def __init__(self, values: torch.Tensor):
+        self.values = values
+
+    device = property(lambda self: self.values.device)
+    dtype = property(lambda self: self.values.dtype)
+    batch_shape = property(lambda self: self.values.shape[:-2])
+
+    @property
+    def mean(self) -> torch.Tensor:
+        return self.values
+
+    @property
+    def variance(self) -> torch.Tensor:
+        return torch.zeros_like(self.values)
+
+    def _extended_shape(self, sample_shape=torch.Size()) -> torch.Size:
+        return torch.Size(sample_shape) + self.values.shape
+
+    def rsample(self, sample_shape: Optional[torch.Size] = None):
+        sample_shape = torch.Size([1]) if sample_shape is None else torch.Size(sample_shape)
+        return self.values.expand(self._extended_shape(sample_shape))

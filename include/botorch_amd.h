@@ -1036,6 +1036,39 @@ typedef struct BoKgArgs {
 int bo_kg_v(const BoKgArgs* a, void* stream);
 int bo_kg_backward_v(const BoKgArgs* a, void* stream);
 
+/* Pathwise posterior samples (Matheron paths) of one single-output exact GP
+ * (botorch/sampling/pathwise: features/generators.py:66-193, prior_samplers.py:
+ * 52-106, update_strategies.py:72-135, posterior_samplers.py:198-224), S paths
+ * evaluated at the R rows of X (R x d, original scale) in one launch.  With
+ * theta_j(x) = sum_t Omega[j][t] x_t / lengthscale[t] and H = M / 2:
+ *   g_s(x) = constant + sqrt(2 outputscale / M) sum_{j<H} (W[s][j] sin theta_j(x)
+ *                                                        + W[s][H+j] cos theta_j(x))
+ *            + sum_{i<n} V[s][i] outputscale k(x, Xt_i)
+ *   f_s(x) = ymean + ystd g_s(x)
+ * Omega: H x d frequencies, W: S x M prior weights, V: S x n update weights,
+ * Xt_scaled: n x d training inputs divided by the lengthscale (row length d, no
+ * padding); n = 0 switches the update term off (Xt_scaled, V may be null).
+ *   inner = 0  (all):    out[s][r] = f_s(X_r),  out S x R, dout S x R
+ *   inner >= 1 (mapped): out[r] = f_p(X_r), p = (r / inner) % S,  out R, dout R
+ * Backward: dX[r][t] = sum_s dout[s][r] df_s/dx_t(X_r) over the paths of row r
+ * (every entry of dX written); Omega, W and V get no gradient.
+ * d <= 128 (a runtime loop), M even, fp64 throughout, sincos on the unreduced
+ * phase.  The features and the kernel row of a 16-row tile live in registers:
+ * no workspace, one launch each way, no atomics (repeated calls are bitwise
+ * identical).  A pure addition to the ABI: BO_ABI_VERSION stays 11. */
+typedef struct BoPathsArgs {
+  BO_STRUCT_HEADER;
+  int32_t kind, d, S, M;
+  int64_t R, n, inner;
+  const double *X, *lengthscale, *Xt_scaled, *Omega, *W, *V;
+  double outputscale, constant, ymean, ystd;
+  double* out;        /* forward */
+  const double* dout; /* backward */
+  double* dX;         /* backward */
+} BoPathsArgs;
+int bo_paths_eval_v(const BoPathsArgs* a, void* stream);
+int bo_paths_eval_backward_v(const BoPathsArgs* a, void* stream);
+
 typedef struct BoLbfgsStepArgs { /* bo_lbfgs_step */
   BO_STRUCT_HEADER;
   int32_t B, n, m, _pad;
