@@ -276,6 +276,15 @@ class PathsArgs(_Args):
                        ("dX", _D)]
 
 
+class JesArgs(_Args):
+    _fields_ = _HDR + [("kind", c_int32), ("d", c_int32), ("P", c_int32), ("_pad", c_int32),
+                       ("R", c_int64), ("n", c_int64), ("X", _D), ("lengthscale", _D),
+                       ("Xt_scaled", _D), ("Xopt_scaled", _D), ("V", _D), ("g", _D),
+                       ("sinv", _D), ("wf", _D), ("tau2", _D), ("mu", _D), ("var", _D),
+                       ("outputscale", c_double), ("w", c_double), ("out", _D), ("dout", _D),
+                       ("dX", _D), ("dmu", _D), ("dvar", _D)]
+
+
 class LbfgsStepArgs(_Args):
     _fields_ = _HDR + [("B", c_int32), ("n", c_int32), ("m", c_int32), ("_pad", c_int32),
                        ("x", _D), ("f", _D), ("g", _D), ("xt", _D), ("ft", _D), ("gt", _D),
@@ -301,6 +310,7 @@ for _name, _cls in (("bo_post_partials_v", PostPartialsArgs), ("bo_qmc_finalize_
                     ("bo_qmc_feas_v", QmcFeasArgs), ("bo_qmc_feas_backward_v", QmcFeasArgs),
                     ("bo_kg_v", KgArgs), ("bo_kg_backward_v", KgArgs),
                     ("bo_paths_eval_v", PathsArgs), ("bo_paths_eval_backward_v", PathsArgs),
+                    ("bo_jes_v", JesArgs), ("bo_jes_backward_v", JesArgs),
                     ("bo_lbfgs_step_v", LbfgsStepArgs), ("bo_lbfgsb_step_v", LbfgsbArgs)):
     _SIGNATURES[_name] = (c_int, [POINTER(_cls), _P])
 _SIGNATURES["bo_struct_size"] = (c_int64, [ctypes.c_char_p])
@@ -309,7 +319,7 @@ ARG_RECORDS = {"BoPostPartialsArgs": PostPartialsArgs, "BoQmcFinalizeArgs": QmcF
                "BoQmcBackwardArgs": QmcBackwardArgs, "BoPostBackwardArgs": PostBackwardArgs,
                "BoQehviArgs": QehviArgs, "BoQehviFeasArgs": QehviFeasArgs,
                "BoQlogehviArgs": QlogehviArgs, "BoQmcFeasArgs": QmcFeasArgs, "BoKgArgs": KgArgs,
-               "BoPathsArgs": PathsArgs, "BoLbfgsStepArgs": LbfgsStepArgs,
+               "BoPathsArgs": PathsArgs, "BoJesArgs": JesArgs, "BoLbfgsStepArgs": LbfgsStepArgs,
                "BoLbfgsbArgs": LbfgsbArgs}
 
 _lib = None

@@ -722,6 +722,215 @@ class qKnowledgeGradient(MCAcquisitionFunction, OneShotAcquisitionFunction):
         return X_full[..., : -self.num_fantasies, :]
 
 
+# -- joint entropy search (lower bound) -------------------------------------------------
+JES_ESTIMATION_TYPES = ["MC", "LB"]
+JES_FULLY_BAYESIAN_ERROR_MSG = (
+    "JES is not yet available with Fully Bayesian GPs. Track the issue, "
+    "which regards conditioning on a number of optima on a collection "
+    "of models, in detail at https://github.com/pytorch/botorch/issues/1680"
+)
+JES_S2_FLOOR, JES_PHI_FLOOR, JES_INNER_FLOOR = 1e-10, 1e-8, 1e-8
+
+
+def _jes_chain(c, mu, var, g, sinv, wf, tau2, w: float):
+    """H (...): the elementwise chain of the JES lower bound in torch, from
+    c (... x P) and the rows' mu, var (...) -- what bo::jes computes on its
+    accumulators (the generic route's formula)."""
+    mu_j = mu.unsqueeze(-1) + c * g
+    s2 = (var.unsqueeze(-1) - c * c * sinv).clamp_min(JES_S2_FLOOR)
+    z = (wf - w * mu_j) / s2.sqrt()
+    Phi = 0.5 * torch.erfc(-z / math.sqrt(2.0))
+    r = torch.exp(-0.5 * z * z) / math.sqrt(2.0 * math.pi) / Phi.clamp_min(JES_PHI_FLOOR)
+    vt = s2 * (1.0 - (z + r) * r).clamp_min(JES_INNER_FLOOR) + tau2
+    return 0.5 * torch.log(vt).mean(dim=-1)
+
+
+class qJointEntropySearch(AcquisitionFunction):
+    """Joint entropy search (acquisition/joint_entropy_search.py:60-265) with the
+    lower-bound estimate, for a single-output exact GP:
+
+        acq(X) = logdet(Sigma(X) + tau2 I) / 2 - sum_i mean_j log(vt_ji) / 2
+
+    where vt_ji is the (truncated) predictive variance at x_i of the model
+    conditioned on the optimum (x*_j, f*_j).  No conditioned model is built:
+    conditioning on one observation is a rank-one correction of the current
+    posterior, so model j's moments at x_i follow from the current posterior at
+    X, the posterior covariance c_ij of x_i with x*_j, and per-optimum constants
+    fixed at construction (with V = A^{-1} k(Xt, x*), two GEMMs on the cached
+    L^{-1}).  All of it is computed in the model's transformed outcome space;
+    the Standardize constant cancels between the two entropy terms.
+
+    ``optimal_inputs`` P x d and ``optimal_outputs`` P x 1 (outcome space), as
+    :func:`pathwise.get_optimal_samples` returns them.  For d <=
+    kernels.JES_DMAX the fused route forms c_ij on the matrix cores and runs
+    the chain on the accumulator (``bo::jes``); the generic route takes c_ij
+    from the joint posterior of the q + P points and applies the formula in
+    torch.  ``maximize=False`` takes the optima as minima (the outputs and the
+    conditioned means are both negated)."""
+
+    def __init__(self, model, optimal_inputs: torch.Tensor, optimal_outputs: torch.Tensor,
+                 condition_noiseless: bool = True, posterior_transform=None, X_pending=None,
+                 estimation_type: str = "LB", maximize: bool = True, num_samples: int = 64):
+        from .models import (MIN_INFERRED_NOISE_LEVEL, FixedNoiseGaussianLikelihood, ModelListGP,
+                             SaasFullyBayesianSingleTaskGP, SingleTaskGP)
+        super().__init__(model)
+        if isinstance(model, SaasFullyBayesianSingleTaskGP):
+            raise NotImplementedError(JES_FULLY_BAYESIAN_ERROR_MSG)
+        if (isinstance(model, ModelListGP) or not isinstance(model, SingleTaskGP)
+                or model.num_outputs != 1):
+            raise UnsupportedError("qJointEntropySearch: multi-output models and ModelListGP are "
+                                   "not on the accelerated path (single-output SingleTaskGP only)")
+        if posterior_transform is not None:
+            raise UnsupportedError("qJointEntropySearch: a `posterior_transform` is not on the "
+                                   "accelerated path")
+        if model.training:
+            raise UnsupportedError("qJointEntropySearch needs a model in eval mode (model.eval()): "
+                                   "the optima are conditioned on the trained model's prediction "
+                                   "caches")
+        if estimation_type == "MC":
+            raise UnsupportedError("qJointEntropySearch: estimation_type='MC' is not on the "
+                                   "accelerated path (the lower bound 'LB' is)")
+        if estimation_type != "LB":
+            raise ValueError(f"Estimation type {estimation_type} is not valid. "
+                             f"Please specify any of {JES_ESTIMATION_TYPES}")
+        d = model.train_inputs[0].shape[-1]
+        if optimal_inputs.dim() != 2 or optimal_inputs.shape[-1] != d or optimal_inputs.shape[0] < 1:
+            raise ValueError(f"qJointEntropySearch: optimal_inputs must be `num_optima x {d}`, got "
+                             f"{tuple(optimal_inputs.shape)}")
+        P = optimal_inputs.shape[0]
+        if tuple(optimal_outputs.shape) != (P, 1):
+            raise ValueError(f"qJointEntropySearch: optimal_outputs must be `{P} x 1`, got "
+                             f"{tuple(optimal_outputs.shape)}")
+        fixed = isinstance(model.likelihood, FixedNoiseGaussianLikelihood)
+        if fixed and not condition_noiseless:
+            raise RuntimeError("FixedNoiseGaussianLikelihood.fantasize requires a `noise` kwarg")
+        self.posterior_transform = None
+        self.condition_noiseless = bool(condition_noiseless)
+        self.estimation_type = estimation_type
+        self.maximize = bool(maximize)
+        self.num_samples = P
+        self.optimal_inputs = optimal_inputs.unsqueeze(-2)
+        self.optimal_outputs = optimal_outputs.unsqueeze(-2)
+        self._route = None  # None: by size; "fused" / "generic": forced (tests, tools)
+        self._w = 1.0 if maximize else -1.0
+        self._condition(model, optimal_inputs, optimal_outputs, fixed, MIN_INFERRED_NOISE_LEVEL)
+        self.set_X_pending(X_pending)
+
+    def _condition(self, model, optimal_inputs, optimal_outputs, fixed: bool, min_noise: float):
+        """The per-optimum constants, once: m_j, v_j (the current posterior at
+        x*_j), nu_j, s_j = v_j + nu_j, g_j = (f*_j - m_j) / s_j, tau2_j and
+        V = A^{-1} k(Xt, x*) against the cached L^{-1}."""
+        from .posteriors import posterior_moments
+        with torch.no_grad():
+            cache = model.prediction_cache()
+            ymean, ystd = model.outcome_stats()
+            n, dev = cache.n, cache.Xt.device
+            Xo = optimal_inputs.detach().to(device=dev, dtype=torch.float64).contiguous()
+            P, d = Xo.shape
+            f = (optimal_outputs.detach().to(device=dev, dtype=torch.float64).reshape(-1)
+                 - ymean) / ystd
+            mean_o, cov_o = posterior_moments(model, Xo.unsqueeze(-2))
+            m = (mean_o.reshape(-1) - ymean) / ystd
+            v = cov_o.reshape(-1) / (ystd * ystd)
+            tau2 = float(cache.noise)  # the level, or the mean of the fixed variances
+            nu = min_noise if self.condition_noiseless else tau2
+            s = v + nu
+            self._tau2 = tau2
+            self._Xo = Xo
+            self._Xo_scaled = (Xo / cache.lengthscale).contiguous()
+            self._Xt_scaled = (cache.Xt / cache.lengthscale).contiguous() if n else None
+            self._g = ((f - m) / s).contiguous()
+            self._sinv = (1.0 / s).contiguous()
+            self._wf = (self._w * f).contiguous()
+            self._tau2_j = torch.full((P,), (n * tau2 + nu) / (n + 1) if fixed else tau2,
+                                      dtype=torch.float64, device=dev)
+            self._V = None
+            if n and d <= kernels.JES_DMAX:
+                K = kernels.covar_matrix(Xo, cache.Xt, cache.lengthscale, cache.kind,
+                                         cache.outputscale)
+                E = K.t().contiguous()  # n x P
+                ld = cache.Linv.shape[1]
+                T = torch.empty(n, P, dtype=torch.float64, device=dev)
+                Vt = torch.empty(n, P, dtype=torch.float64, device=dev)
+                # the leading n x n block of the (padded) L^{-1}, read in place
+                kernels.gemm_strided(n, P, n, cache.Linv, ld, 0, E, P, 0, T, P, 0, 1)
+                kernels.gemm_strided(n, P, n, cache.Linv, ld, 0, T, P, 0, Vt, P, 0, 1, transA=True)
+                self._V = Vt.t().contiguous()
+            self._hyper = (cache.lengthscale, int(cache.kind), float(cache.outputscale))
+            self._stats = (float(ymean), float(ystd))
+
+    def _entropy(self, Sigma: torch.Tensor) -> torch.Tensor:
+        """logdet(Sigma + tau2 I) / 2 = sum log diag chol, through the
+        differentiable jitter-ladder Cholesky."""
+        from .posteriors import _CholJitter
+        q = Sigma.shape[-1]
+        A = Sigma + self._tau2 * torch.eye(q, dtype=Sigma.dtype, device=Sigma.device)
+        L = _CholJitter.apply(A) if torch.is_grad_enabled() and A.requires_grad \
+            else kernels.chol_jitter(A)
+        return L.diagonal(dim1=-2, dim2=-1).log().sum(dim=-1)
+
+    def _fused(self, X3: torch.Tensor) -> torch.Tensor:
+        from . import ops  # noqa: F401  (torch.ops.bo registration)
+        from .posteriors import posterior_moments
+        B, q, d = X3.shape
+        ymean, ystd = self._stats
+        mean, cov = posterior_moments(self.model, X3)
+        mu, Sigma = (mean - ymean) / ystd, cov / (ystd * ystd)
+        var = Sigma.diagonal(dim1=-2, dim2=-1)
+        ls, kind, o = self._hyper
+        H = torch.ops.bo.jes(X3.reshape(B * q, d), mu.reshape(B * q), var.reshape(B * q), ls,
+                             self._Xt_scaled if self._V is not None else None, self._Xo_scaled,
+                             self._V, self._g, self._sinv, self._wf, self._tau2_j, kind, o, self._w)
+        return self._entropy(Sigma) - H.view(B, q).sum(dim=-1)
+
+    def _generic(self, X3: torch.Tensor) -> torch.Tensor:
+        from .posteriors import posterior_moments
+        B, q, d = X3.shape
+        ymean, ystd = self._stats
+        P = self._Xo.shape[0]
+        mean, cov = posterior_moments(self.model, torch.cat([X3, self._Xo.expand(B, P, d)], dim=-2))
+        mu = (mean[:, :q] - ymean) / ystd
+        Sigma = cov[:, :q, :q] / (ystd * ystd)
+        c = cov[:, :q, q:] / (ystd * ystd)
+        H = _jes_chain(c, mu, Sigma.diagonal(dim1=-2, dim2=-1), self._g, self._sinv, self._wf,
+                       self._tau2_j, self._w)
+        return self._entropy(Sigma) - H.sum(dim=-1)
+
+    def conditioned_moments(self, X: torch.Tensor):
+        """(mean, variance) in outcome space, each ``batch x q x P``, that the
+        model conditioned on optimum j predicts at X with observation noise:
+        mu_ji and s2_ji + tau2_j of the class docstring (unclamped), from the
+        joint posterior of the q + P points and the constants of the
+        construction.  What ``condition_on_observations(x*_j, f*_j, noise=nu)``
+        followed by ``.posterior(X, observation_noise=True)`` gives, one
+        optimum at a time."""
+        from .posteriors import posterior_moments
+        X = t_batch_mode(X).to(torch.float64)
+        q, P = X.shape[-2], self._Xo.shape[0]
+        ymean, ystd = self._stats
+        Xo = self._Xo.expand(*X.shape[:-2], P, X.shape[-1])
+        mean, cov = posterior_moments(self.model, torch.cat([X, Xo], dim=-2))
+        mu = (mean[..., :q] - ymean) / ystd
+        c = cov[..., :q, q:] / (ystd * ystd)
+        var = cov[..., :q, :q].diagonal(dim1=-2, dim2=-1) / (ystd * ystd)
+        mu_j = mu.unsqueeze(-1) + c * self._g
+        vt = var.unsqueeze(-1) - c * c * self._sinv + self._tau2_j
+        return ymean + ystd * mu_j, (ystd * ystd) * vt
+
+    def forward(self, X: torch.Tensor) -> torch.Tensor:
+        X = t_batch_mode(X)
+        if X.dtype != torch.float64:  # the model computes in fp64; the value returns in X's dtype
+            return self.forward(X.to(torch.float64)).to(X.dtype)
+        batch = X.shape[:-2]
+        X = self._concat_pending(X)
+        q, d = X.shape[-2], X.shape[-1]
+        X3 = X.reshape(-1, q, d)
+        fused = d <= kernels.JES_DMAX and X.is_cuda if self._route is None \
+            else self._route == "fused"
+        acq = self._fused(X3) if fused else self._generic(X3)
+        return acq.reshape(batch)
+
+
 # -- qNEI -------------------------------------------------------------------------------
 def prune_inferior_points(model, X, objective=None, posterior_transform=None, constraints=None,
                           num_samples: int = 2048, max_frac: float = 1.0, sampler=None,

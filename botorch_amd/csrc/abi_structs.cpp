@@ -78,6 +78,10 @@ int bo_kg_backward_impl(const BoKgArgs* a, void* stream);
 int bo_paths_eval_impl(const BoPathsArgs* a, void* stream);
 int bo_paths_eval_backward_impl(const BoPathsArgs* a, void* stream);
 
+// the joint-entropy-search conditional entropies (jes.hip)
+int bo_jes_impl(const BoJesArgs* a, void* stream);
+int bo_jes_backward_impl(const BoJesArgs* a, void* stream);
+
 int bo_post_partials_v(const BoPostPartialsArgs* a, void* stream) {
   if (!header_ok(a, "bo_post_partials_v")) return BO_ERR_ARG;
   return bo_post_partials_layout(a->kind, a->Xq, a->B, a->q, a->d, a->Xt_scaled, a->n, a->U,
@@ -174,6 +178,16 @@ int bo_paths_eval_backward_v(const BoPathsArgs* a, void* stream) {
   return bo_paths_eval_backward_impl(a, stream);
 }
 
+int bo_jes_v(const BoJesArgs* a, void* stream) {
+  if (!header_ok(a, "bo_jes_v")) return BO_ERR_ARG;
+  return bo_jes_impl(a, stream);
+}
+
+int bo_jes_backward_v(const BoJesArgs* a, void* stream) {
+  if (!header_ok(a, "bo_jes_backward_v")) return BO_ERR_ARG;
+  return bo_jes_backward_impl(a, stream);
+}
+
 int bo_lbfgs_step_v(const BoLbfgsStepArgs* a, void* stream) {
   if (!header_ok(a, "bo_lbfgs_step_v")) return BO_ERR_ARG;
   return bo_lbfgs_step(a->B, a->n, a->m, a->x, a->f, a->g, a->xt, a->ft, a->gt, a->d, a->alpha,
@@ -203,6 +217,7 @@ extern "C" int64_t bo_struct_size(const char* name) {
   if (s == "BoQmcFeasArgs") return sizeof(BoQmcFeasArgs);
   if (s == "BoKgArgs") return sizeof(BoKgArgs);
   if (s == "BoPathsArgs") return sizeof(BoPathsArgs);
+  if (s == "BoJesArgs") return sizeof(BoJesArgs);
   if (s == "BoLbfgsStepArgs") return sizeof(BoLbfgsStepArgs);
   if (s == "BoLbfgsbArgs") return sizeof(BoLbfgsbArgs);
   return -1;

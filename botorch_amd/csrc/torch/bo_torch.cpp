@@ -850,9 +850,110 @@ std::vector<at::Tensor> qehvi_members_eager(
   return {acq, status};
 }
 
+// ---- joint entropy search, lower bound (bo_jes_v / bo_jes_backward_v) --------------------
+// The record of one call over torch tensors; X R x d, Xopt_scaled P x d, V P x n
+// with Xt_scaled n x d (both absent: n = 0), the rest vectors of P resp. R.
+BoJesArgs jes_args(const at::Tensor& X, const at::Tensor& mu, const at::Tensor& var,
+                   const at::Tensor& lengthscale, const c10::optional<at::Tensor>& Xt_scaled,
+                   const at::Tensor& Xopt_scaled, const c10::optional<at::Tensor>& V,
+                   const at::Tensor& g, const at::Tensor& sinv, const at::Tensor& wf,
+                   const at::Tensor& tau2, int64_t kind, double outputscale, double w) {
+  const char* who = "bo::jes_native";
+  TORCH_CHECK(X.dim() == 2 && Xopt_scaled.dim() == 2, who, ": X must be R x d and Xopt_scaled P x d");
+  const int64_t R = X.size(0), d = X.size(1), P = Xopt_scaled.size(0);
+  TORCH_CHECK(Xopt_scaled.size(1) == d && lengthscale.numel() == d, who,
+              ": Xopt_scaled and lengthscale must have d = ", d, " columns / entries");
+  TORCH_CHECK(V.has_value() == Xt_scaled.has_value(), who, ": Xt_scaled and V go together");
+  const int64_t n = V.has_value() ? V->size(-1) : 0;
+  auto dense = [&](const at::Tensor& t) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kDouble && t.is_contiguous(), who,
+                ": every tensor must be a contiguous fp64 ROCm device tensor");
+  };
+  for (const at::Tensor* t : {&X, &mu, &var, &lengthscale, &Xopt_scaled, &g, &sinv, &wf, &tau2})
+    dense(*t);
+  for (const at::Tensor* t : {&g, &sinv, &wf, &tau2})
+    TORCH_CHECK(t->dim() == 1 && t->size(0) == P, who, ": g, sinv, wf and tau2 must have P = ", P,
+                " entries");
+  TORCH_CHECK(mu.dim() == 1 && mu.size(0) == R && var.dim() == 1 && var.size(0) == R, who,
+              ": mu and var must have R = ", R, " entries");
+  if (n > 0) {
+    dense(*V);
+    dense(*Xt_scaled);
+    TORCH_CHECK(V->dim() == 2 && V->size(0) == P && Xt_scaled->dim() == 2 &&
+                    Xt_scaled->size(0) == n && Xt_scaled->size(1) == d,
+                who, ": V must be P x n and Xt_scaled n x d");
+  }
+  BoJesArgs a{};
+  a.struct_size = sizeof(a);
+  a.abi_version = BO_ABI_VERSION;
+  a.kind = static_cast<int32_t>(kind);
+  a.d = static_cast<int32_t>(d);
+  TORCH_CHECK(P <= INT32_MAX, who, ": P too large");
+  a.P = static_cast<int32_t>(P);
+  a.R = R;
+  a.n = n;
+  a.X = cp(X);
+  a.lengthscale = cp(lengthscale);
+  a.Xt_scaled = n > 0 ? cp(*Xt_scaled) : nullptr;
+  a.Xopt_scaled = cp(Xopt_scaled);
+  a.V = n > 0 ? cp(*V) : nullptr;
+  a.g = cp(g);
+  a.sinv = cp(sinv);
+  a.wf = cp(wf);
+  a.tau2 = cp(tau2);
+  a.mu = cp(mu);
+  a.var = cp(var);
+  a.outputscale = outputscale;
+  a.w = w;
+  return a;
+}
+
+at::Tensor jes_native(const at::Tensor& X, const at::Tensor& mu, const at::Tensor& var,
+                      const at::Tensor& lengthscale, const c10::optional<at::Tensor>& Xt_scaled,
+                      const at::Tensor& Xopt_scaled, const c10::optional<at::Tensor>& V,
+                      const at::Tensor& g, const at::Tensor& sinv, const at::Tensor& wf,
+                      const at::Tensor& tau2, int64_t kind, double outputscale, double w) {
+  BoJesArgs a = jes_args(X, mu, var, lengthscale, Xt_scaled, Xopt_scaled, V, g, sinv, wf, tau2,
+                         kind, outputscale, w);
+  const c10::DeviceIndex dev = X.device().index();
+  at::Tensor out = at::empty({a.R}, X.options());
+  a.out = out.data_ptr<double>();
+  ck(bo_jes_v(&a, c10::hip::getCurrentHIPStream(dev).stream()), "jes");
+  return out;
+}
+
+std::vector<at::Tensor> jes_backward_native(
+    const at::Tensor& dout, const at::Tensor& X, const at::Tensor& mu, const at::Tensor& var,
+    const at::Tensor& lengthscale, const c10::optional<at::Tensor>& Xt_scaled,
+    const at::Tensor& Xopt_scaled, const c10::optional<at::Tensor>& V, const at::Tensor& g,
+    const at::Tensor& sinv, const at::Tensor& wf, const at::Tensor& tau2, int64_t kind,
+    double outputscale, double w) {
+  BoJesArgs a = jes_args(X, mu, var, lengthscale, Xt_scaled, Xopt_scaled, V, g, sinv, wf, tau2,
+                         kind, outputscale, w);
+  TORCH_CHECK(dout.is_cuda() && dout.scalar_type() == at::kDouble && dout.is_contiguous() &&
+                  dout.dim() == 1 && dout.size(0) == a.R,
+              "bo::jes_backward_native: dout must be a contiguous fp64 device tensor of R = ", a.R,
+              " entries");
+  const c10::DeviceIndex dev = X.device().index();
+  at::Tensor dX = at::empty_like(X), dmu = at::empty({a.R}, X.options()),
+             dvar = at::empty({a.R}, X.options());
+  a.dout = dout.data_ptr<double>();
+  a.dX = dX.data_ptr<double>();
+  a.dmu = dmu.data_ptr<double>();
+  a.dvar = dvar.data_ptr<double>();
+  ck(bo_jes_backward_v(&a, c10::hip::getCurrentHIPStream(dev).stream()), "jes_backward");
+  return {dX, dmu, dvar};
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(bo, m) {
+  m.def("jes_native(Tensor X, Tensor mu, Tensor var, Tensor lengthscale, Tensor? Xt_scaled, "
+        "Tensor Xopt_scaled, Tensor? V, Tensor g, Tensor sinv, Tensor wf, Tensor tau2, int kind, "
+        "float outputscale, float w) -> Tensor");
+  m.def("jes_backward_native(Tensor dout, Tensor X, Tensor mu, Tensor var, Tensor lengthscale, "
+        "Tensor? Xt_scaled, Tensor Xopt_scaled, Tensor? V, Tensor g, Tensor sinv, Tensor wf, "
+        "Tensor tau2, int kind, float outputscale, float w) -> Tensor[]");
   m.def("qehvi_members_eager(Tensor X, Tensor[] Xt_scaled, Tensor[] U, Tensor[] beta, "
         "Tensor[] lengthscale, float[] outputscale, float[] constant, float[] ymean, float[] ystd, "
         "int kind, int n, Tensor Z, Tensor cell_lo, Tensor cell_hi, int kxt_cap, "
@@ -885,4 +986,6 @@ TORCH_LIBRARY_IMPL(bo, CUDA, m) {
   m.impl("qmc_acq_backward_native", &qmc_acq_backward_native);
   m.impl("ladder_defer", &ladder_defer);
   m.impl("qehvi_members_eager", &qehvi_members_eager);
+  m.impl("jes_native", &jes_native);
+  m.impl("jes_backward_native", &jes_backward_native);
 }

@@ -2161,6 +2161,101 @@ def paths_eval_backward(dout: torch.Tensor, X: torch.Tensor, lengthscale: torch.
     return dX
 
 
+JES_DMAX = 128  # bo_jes: d is a runtime loop up to here
+
+
+def jes_check(d: int, P: int, R: int = 1) -> None:
+    """The argument limits of :func:`jes`, raised on the host before any native
+    call (acquisition.qJointEntropySearch checks its sizes with it)."""
+    if not 1 <= d <= JES_DMAX:
+        raise ValueError(f"jes: 1 <= d <= {JES_DMAX} (got {d})")
+    if P < 1:
+        raise ValueError(f"jes: P >= 1 (got {P})")
+    if R < 1:
+        raise ValueError(f"jes: R >= 1 (got {R})")
+
+
+def _jes_args(X, lengthscale, Xt_scaled, Xopt_scaled, V, g, sinv, wf, tau2, mu, var, kind,
+              outputscale, w):
+    """The BoJesArgs of :func:`jes` / :func:`jes_backward`: X R x d, Xopt_scaled
+    P x d, the per-optimum g, sinv, wf, tau2 (P), the per-row mu, var (R), and
+    Xt_scaled n x d with V P x n (both None: n = 0)."""
+    if X.dim() != 2:
+        raise ValueError(f"jes: X must be R x d, got {tuple(X.shape)}")
+    R, d = X.shape
+    if Xopt_scaled.dim() != 2:
+        raise ValueError(f"jes: Xopt_scaled must be P x d, got {tuple(Xopt_scaled.shape)}")
+    P = Xopt_scaled.shape[0]
+    jes_check(d, P, R)
+    if Xopt_scaled.shape[1] != d or tuple(lengthscale.shape) != (d,):
+        raise ValueError(f"jes: Xopt_scaled must be P x {d} and lengthscale have {d} entries, got "
+                         f"{tuple(Xopt_scaled.shape)} and {tuple(lengthscale.shape)}")
+    for name, t, want in (("g", g, P), ("sinv", sinv, P), ("wf", wf, P), ("tau2", tau2, P),
+                          ("mu", mu, R), ("var", var, R)):
+        if tuple(t.shape) != (want,):
+            raise ValueError(f"jes: {name} must have {want} entries, got {tuple(t.shape)}")
+    if (V is None) != (Xt_scaled is None):
+        raise ValueError("jes: Xt_scaled and V go together")
+    n = 0
+    if V is not None:
+        n = V.shape[-1]
+        if V.dim() != 2 or V.shape[0] != P or tuple(Xt_scaled.shape) != (n, d):
+            raise ValueError(f"jes: V must be {P} x n and Xt_scaled n x {d}, got "
+                             f"{tuple(V.shape)} and {tuple(Xt_scaled.shape)}")
+    if float(w) not in (1.0, -1.0):
+        raise ValueError(f"jes: w must be +1 or -1 (got {w})")
+    for t in (X, lengthscale, Xopt_scaled, g, sinv, wf, tau2, mu, var, V, Xt_scaled):
+        if t is not None and t.dtype != torch.float64:
+            raise ValueError("jes: every tensor must be fp64")
+    return _lib.JesArgs(kind=int(kind), d=d, P=P, R=R, n=n, X=X.contiguous(),
+                        lengthscale=lengthscale.contiguous(),
+                        Xt_scaled=Xt_scaled.contiguous() if n else None,
+                        Xopt_scaled=Xopt_scaled.contiguous(), V=V.contiguous() if n else None,
+                        g=g.contiguous(), sinv=sinv.contiguous(), wf=wf.contiguous(),
+                        tau2=tau2.contiguous(), mu=mu.contiguous(), var=var.contiguous(),
+                        outputscale=float(outputscale), w=float(w))
+
+
+def jes(X: torch.Tensor, lengthscale: torch.Tensor, Xt_scaled: Optional[torch.Tensor],
+        Xopt_scaled: torch.Tensor, V: Optional[torch.Tensor], g: torch.Tensor, sinv: torch.Tensor,
+        wf: torch.Tensor, tau2: torch.Tensor, mu: torch.Tensor, var: torch.Tensor,
+        kind: int = _lib.RBF, outputscale: float = 1.0, w: float = 1.0) -> torch.Tensor:
+    """The mean conditional entropy of the R rows of X over P optima (bo_jes,
+    the record's comment in include/botorch_amd.h states the formula):
+    c_ij = o (k(x_i, x*_j) - sum_t k(x_i, Xt_t) V[j, t]) is formed on the matrix
+    cores and the elementwise chain runs on the accumulator, so the only
+    allocation is the output (R)."""
+    dev = _dev(X, lengthscale, Xt_scaled, Xopt_scaled, V, g, sinv, wf, tau2, mu, var)
+    a = _jes_args(X, lengthscale, Xt_scaled, Xopt_scaled, V, g, sinv, wf, tau2, mu, var, kind,
+                  outputscale, w)
+    out = torch.empty(a.R, dtype=torch.float64, device=dev)
+    a.out = out.data_ptr()
+    check(lib().bo_jes_v(ctypes.byref(a), _stream(dev)), "jes")
+    return out
+
+
+def jes_backward(dout: torch.Tensor, X: torch.Tensor, lengthscale: torch.Tensor,
+                 Xt_scaled: Optional[torch.Tensor], Xopt_scaled: torch.Tensor,
+                 V: Optional[torch.Tensor], g: torch.Tensor, sinv: torch.Tensor, wf: torch.Tensor,
+                 tau2: torch.Tensor, mu: torch.Tensor, var: torch.Tensor, kind: int = _lib.RBF,
+                 outputscale: float = 1.0, w: float = 1.0):
+    """(dX R x d, dmu R, dvar R) of :func:`jes` from dout (R); dX is the
+    gradient through c_ij alone.  One launch, no workspace, nothing to clear."""
+    dev = _dev(dout, X, lengthscale, Xt_scaled, Xopt_scaled, V, g, sinv, wf, tau2, mu, var)
+    a = _jes_args(X, lengthscale, Xt_scaled, Xopt_scaled, V, g, sinv, wf, tau2, mu, var, kind,
+                  outputscale, w)
+    if tuple(dout.shape) != (a.R,) or dout.dtype != torch.float64:
+        raise ValueError(f"jes_backward: dout must be fp64 of shape ({a.R},), got "
+                         f"{tuple(dout.shape)}")
+    dout = dout.contiguous()
+    dX = torch.empty(a.R, a.d, dtype=torch.float64, device=dev)
+    dmu = torch.empty(a.R, dtype=torch.float64, device=dev)
+    dvar = torch.empty(a.R, dtype=torch.float64, device=dev)
+    a.dout, a.dX, a.dmu, a.dvar = dout.data_ptr(), dX.data_ptr(), dmu.data_ptr(), dvar.data_ptr()
+    check(lib().bo_jes_backward_v(ctypes.byref(a), _stream(dev)), "jes_backward")
+    return dX, dmu, dvar
+
+
 def kernel_grad(X: torch.Tensor, Y: torch.Tensor, dK: torch.Tensor, lengthscale: torch.Tensor,
                 kind: int, outputscale: float = 1.0, group: int = 0,
                 dX: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -30,6 +30,10 @@ Ops (reference computation each replaces):
                       (+ autograd, acquisition/knowledge_gradient.py:151-207)
   bo::paths_eval      S Matheron paths at R points, features and kernel rows fused
                       (+ autograd in X, sampling/pathwise/posterior_samplers.py:198-224)
+  bo::jes             mean conditional entropy of R points over P optima, the
+                      rank-one conditioned moments fused with the entropy chain
+                      (+ autograd in X, mu, var; acquisition/joint_entropy_search.py:
+                      195-265; its launches go through bo::jes_native in C++)
 """
 from __future__ import annotations
 
@@ -624,7 +628,76 @@ def _paths_bwd(ctx, dout):
 paths_eval.register_autograd(_paths_bwd, setup_context=_paths_setup)
 
 
+# ---- bo::jes (joint entropy search, lower bound: mean conditional entropy per row) -------------
+def _jes_dense(X, mu, var, lengthscale, Xt_scaled, Xopt_scaled, V, g, sinv, wf, tau2):
+    """The tensor arguments of bo::jes[_backward]_native, contiguous, after
+    kernels.jes_check's limits (a ValueError before any native call)."""
+    if X.dim() != 2 or Xopt_scaled.dim() != 2:
+        raise ValueError("jes: X must be R x d and Xopt_scaled P x d")
+    kernels.jes_check(X.shape[1], Xopt_scaled.shape[0], X.shape[0])
+    return tuple(None if t is None else t.contiguous()
+                 for t in (X, mu, var, lengthscale, Xt_scaled, Xopt_scaled, V, g, sinv, wf, tau2))
+
+
+@torch.library.custom_op("bo::jes", mutates_args=(), device_types="cuda")
+def jes(X: Tensor, mu: Tensor, var: Tensor, lengthscale: Tensor, Xt_scaled: Optional[Tensor],
+        Xopt_scaled: Tensor, V: Optional[Tensor], g: Tensor, sinv: Tensor, wf: Tensor,
+        tau2: Tensor, kind: int, outputscale: float, w: float) -> Tensor:
+    """H (R): the mean over the P optima of log(vt_ij) / 2 at the rows of X
+    (R x d) with current posterior mean mu and variance var (R each)
+    (kernels.jes).  Differentiable in X (through the covariance with the
+    optima), mu and var; the optima's tensors are buffers of the construction.
+    One native call (bo::jes_native, csrc/torch/bo_torch.cpp) after the host's
+    limit checks."""
+    n = 0 if V is None else V.shape[-1]
+    args = _jes_dense(X, mu, var, lengthscale, Xt_scaled if n else None, Xopt_scaled,
+                      V if n else None, g, sinv, wf, tau2)
+    return _lib.torch_ops().jes_native(*args, kind, outputscale, w)
+
+
+@jes.register_fake
+def _(X, mu, var, lengthscale, Xt_scaled, Xopt_scaled, V, g, sinv, wf, tau2, kind, outputscale,
+      w):
+    return X.new_empty((X.shape[0],), dtype=F64)
+
+
+@torch.library.custom_op("bo::jes_backward", mutates_args=(), device_types="cuda")
+def jes_backward(dout: Tensor, X: Tensor, mu: Tensor, var: Tensor, lengthscale: Tensor,
+                 Xt_scaled: Optional[Tensor], Xopt_scaled: Tensor, V: Optional[Tensor], g: Tensor,
+                 sinv: Tensor, wf: Tensor, tau2: Tensor, kind: int, outputscale: float,
+                 w: float) -> Tuple[Tensor, Tensor, Tensor]:
+    n = 0 if V is None else V.shape[-1]
+    args = _jes_dense(X, mu, var, lengthscale, Xt_scaled if n else None, Xopt_scaled,
+                      V if n else None, g, sinv, wf, tau2)
+    dX, dmu, dvar = _lib.torch_ops().jes_backward_native(dout.contiguous(), *args, kind,
+                                                         outputscale, w)
+    return dX, dmu, dvar
+
+
+@jes_backward.register_fake
+def _(dout, X, mu, var, lengthscale, Xt_scaled, Xopt_scaled, V, g, sinv, wf, tau2, kind,
+      outputscale, w):
+    return (X.new_empty(X.shape, dtype=F64), X.new_empty((X.shape[0],), dtype=F64),
+            X.new_empty((X.shape[0],), dtype=F64))
+
+
+def _jes_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[:11])
+    ctx.consts = inputs[11:]
+
+
+def _jes_bwd(ctx, dout):
+    dX = dmu = dvar = None
+    if any(ctx.needs_input_grad[:3]):
+        dX, dmu, dvar = torch.ops.bo.jes_backward(dout.contiguous(), *ctx.saved_tensors,
+                                                  *ctx.consts)
+    return (dX, dmu, dvar) + (None,) * 11
+
+
+jes.register_autograd(_jes_bwd, setup_context=_jes_setup)
+
+
 OPS: List[str] = ["sobol_normal", "gp_cache", "gp_cache_extend", "chol_jitter", "chol_backward",
                   "post_partials", "qmc_finalize", "gp_posterior", "gp_posterior_backward",
                   "qmc_acq", "qmc_acq_backward", "qehvi", "qehvi_backward", "mll", "kg",
-                  "kg_backward", "paths_eval", "paths_eval_backward"]
+                  "kg_backward", "paths_eval", "paths_eval_backward", "jes", "jes_backward"]

@@ -1069,6 +1069,42 @@ typedef struct BoPathsArgs {
 int bo_paths_eval_v(const BoPathsArgs* a, void* stream);
 int bo_paths_eval_backward_v(const BoPathsArgs* a, void* stream);
 
+/* qJointEntropySearch, lower bound (botorch/acquisition/joint_entropy_search.py:
+ * 195-265): the mean over P optima (x*_j, f*_j) of the conditional entropies
+ * of the R rows of X (R x d, original scale) in one launch.  The GP conditioned
+ * on one pair is a rank-one correction of the current posterior, so with k the
+ * kernel without its outputscale and V[j] = A^{-1} outputscale k(Xt, x*_j) (P x n):
+ *   c_ij  = outputscale (k(x_i, x*_j) - sum_t k(x_i, Xt_t) V[j][t])
+ *   mu_ji = mu[i] + c_ij g[j]       s2_ji = max(var[i] - c_ij^2 sinv[j], 1e-10)
+ *   z     = (wf[j] - w mu_ji) / sqrt(s2_ji)
+ *   r     = phi(z) / max(Phi(z), 1e-8),   Phi(z) = erfc(-z / sqrt 2) / 2
+ *   vt_ji = s2_ji max(1 - (z + r) r, 1e-8) + tau2[j]
+ *   out[i] = (1 / P) sum_j log(vt_ji) / 2
+ * Xt_scaled (n x d) and Xopt_scaled (P x d) are divided by the lengthscale (row
+ * length d, no padding); n = 0 switches the training term off (Xt_scaled, V may
+ * be null).  g, sinv, wf, tau2: P per-optimum constants; mu, var: the current
+ * posterior mean and variance of each row; w = +1 (maximize) or -1.
+ * Backward, from dout (R): dX (R x d, through c_ij only), dmu (R), dvar (R);
+ * every entry is written, the caller clears nothing.
+ * d <= 128 (a runtime loop), P >= 1, R >= 1, fp64 throughout.  c_ij lives in
+ * the MFMA accumulators: no R x P array, no workspace, one launch each way, no
+ * atomics (repeated calls are bitwise identical).  A pure addition to the ABI:
+ * BO_ABI_VERSION stays 11. */
+typedef struct BoJesArgs {
+  BO_STRUCT_HEADER;
+  int32_t kind, d, P, _pad;
+  int64_t R, n;
+  const double *X, *lengthscale, *Xt_scaled, *Xopt_scaled, *V;
+  const double *g, *sinv, *wf, *tau2;
+  const double *mu, *var;
+  double outputscale, w;
+  double* out;               /* forward */
+  const double* dout;        /* backward */
+  double *dX, *dmu, *dvar;   /* backward */
+} BoJesArgs;
+int bo_jes_v(const BoJesArgs* a, void* stream);
+int bo_jes_backward_v(const BoJesArgs* a, void* stream);
+
 typedef struct BoLbfgsStepArgs { /* bo_lbfgs_step */
   BO_STRUCT_HEADER;
   int32_t B, n, m, _pad;
