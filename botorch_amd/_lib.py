@@ -285,6 +285,25 @@ class JesArgs(_Args):
                        ("dX", _D), ("dmu", _D), ("dvar", _D)]
 
 
+class MesArgs(_Args):
+    _fields_ = _HDR + [("S_M", c_int32), ("S_m", c_int32), ("R", c_int64), ("mu", _D), ("var", _D),
+                       ("fstar", _D), ("z", _D), ("kappa", c_double), ("var_h0", c_double),
+                       ("zsq_mean", c_double), ("tau2", c_double), ("w", c_double), ("out", _D),
+                       ("dout", _D), ("dmu", _D), ("dvar", _D)]
+
+
+class GibbonArgs(_Args):
+    _fields_ = _HDR + [("S_M", c_int32), ("m", c_int32), ("R", c_int64), ("mu", _D), ("var", _D),
+                       ("A", _D), ("Binv", _D), ("fstar", _D), ("tau2", c_double), ("w", c_double),
+                       ("out", _D), ("dout", _D), ("dmu", _D), ("dvar", _D), ("dA", _D)]
+
+
+class MvQuantilesArgs(_Args):
+    _fields_ = _HDR + [("have_bounds", c_int32), ("_pad", c_int32), ("N", c_int64), ("mu", _D),
+                       ("sigma", _D), ("lo", c_double), ("hi", c_double), ("out", _D),
+                       ("status", _D)]
+
+
 class LbfgsStepArgs(_Args):
     _fields_ = _HDR + [("B", c_int32), ("n", c_int32), ("m", c_int32), ("_pad", c_int32),
                        ("x", _D), ("f", _D), ("g", _D), ("xt", _D), ("ft", _D), ("gt", _D),
@@ -311,6 +330,9 @@ for _name, _cls in (("bo_post_partials_v", PostPartialsArgs), ("bo_qmc_finalize_
                     ("bo_kg_v", KgArgs), ("bo_kg_backward_v", KgArgs),
                     ("bo_paths_eval_v", PathsArgs), ("bo_paths_eval_backward_v", PathsArgs),
                     ("bo_jes_v", JesArgs), ("bo_jes_backward_v", JesArgs),
+                    ("bo_mes_v", MesArgs), ("bo_mes_backward_v", MesArgs),
+                    ("bo_gibbon_v", GibbonArgs), ("bo_gibbon_backward_v", GibbonArgs),
+                    ("bo_mv_quantiles_v", MvQuantilesArgs),
                     ("bo_lbfgs_step_v", LbfgsStepArgs), ("bo_lbfgsb_step_v", LbfgsbArgs)):
     _SIGNATURES[_name] = (c_int, [POINTER(_cls), _P])
 _SIGNATURES["bo_struct_size"] = (c_int64, [ctypes.c_char_p])
@@ -319,8 +341,9 @@ ARG_RECORDS = {"BoPostPartialsArgs": PostPartialsArgs, "BoQmcFinalizeArgs": QmcF
                "BoQmcBackwardArgs": QmcBackwardArgs, "BoPostBackwardArgs": PostBackwardArgs,
                "BoQehviArgs": QehviArgs, "BoQehviFeasArgs": QehviFeasArgs,
                "BoQlogehviArgs": QlogehviArgs, "BoQmcFeasArgs": QmcFeasArgs, "BoKgArgs": KgArgs,
-               "BoPathsArgs": PathsArgs, "BoJesArgs": JesArgs, "BoLbfgsStepArgs": LbfgsStepArgs,
-               "BoLbfgsbArgs": LbfgsbArgs}
+               "BoPathsArgs": PathsArgs, "BoJesArgs": JesArgs, "BoMesArgs": MesArgs,
+               "BoGibbonArgs": GibbonArgs, "BoMvQuantilesArgs": MvQuantilesArgs,
+               "BoLbfgsStepArgs": LbfgsStepArgs, "BoLbfgsbArgs": LbfgsbArgs}
 
 _lib = None
 

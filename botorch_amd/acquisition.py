@@ -931,6 +931,305 @@ class qJointEntropySearch(AcquisitionFunction):
         return acq.reshape(batch)
 
 
+# -- max-value entropy search: MES and GIBBON -------------------------------------------
+MES_CLAMP_LB = 1e-8
+MES_VDET_EPS = (1.0 + 1e-12) - 1.0  # lim - qf = qf MES_VDET_EPS on GIBBON's clamped branch
+
+
+def _mes_Phi(x):
+    return 0.5 * torch.erfc(-x / math.sqrt(2.0))
+
+
+def _mes_chain(mu, var, fstar, z, tau2: float, w: float):
+    """ig (R) of qMaxValueEntropy from the rows' posterior mean and variance (R
+    each), the max values fstar (S_M) and the base samples z (S_m), as broadcast
+    torch tensors R x S_M x S_m (max_value_entropy_search.py:427-515 without
+    fantasies): what bo::mes computes in registers (the generic route's
+    formula; DESIGN.md section 18 states it)."""
+    m = (w * mu)[:, None, None]
+    vM = var.clamp_min(MES_CLAMP_LB)[:, None, None]
+    vm = (var + tau2)[:, None, None]
+    zk, f = z[None, None, :], fstar[None, :, None]
+    mean_new = m + (vM / vm) * vm.sqrt() * (w * zk)
+    s2n = (vM - vM * vM / vm).clamp_min(MES_CLAMP_LB)
+    Z = _mes_Phi((f - mean_new) / s2n.sqrt()).clamp_min(MES_CLAMP_LB) \
+        / _mes_Phi((f - m) / vM.sqrt()).clamp_min(MES_CLAMP_LB)
+    lp = -0.5 * zk * zk - 0.5 * torch.log(2.0 * math.pi * vm)
+    h1 = -Z * Z.log() - Z * lp
+    h0 = -lp
+    H1bar, H0bar = h1.mean(dim=(1, 2)), h0.mean(dim=(1, 2))
+    cov = ((h1 - H1bar[:, None, None]) * (h0 - H0bar[:, None, None])).mean(dim=(1, 2))
+    beta = cov / (h0.var(dim=(1, 2)) * h1.var(dim=(1, 2))).sqrt()
+    H0 = 0.5 * torch.log(2.0 * math.pi * math.e * vm.reshape(-1))
+    return H0 - H1bar + beta * (H0bar - H0)
+
+
+def _gibbon_chain(mu, var, fstar, tau2: float, w: float, A=None, Binv=None):
+    """acq (R) of GIBBON in torch (max_value_entropy_search.py:563-664): the
+    quality term and, with A (R x m) and Binv (m x m), the repulsion term in
+    outcome space -- what bo::gibbon computes (the generic route's formula)."""
+    vM = var.clamp_min(MES_CLAMP_LB)
+    vm = (var + tau2).clamp_min(MES_CLAMP_LB)
+    g = (fstar[None, :] - (w * mu)[:, None]) / vM.sqrt()[:, None]
+    r = torch.exp(-0.5 * g * g) / math.sqrt(2.0 * math.pi) / _mes_Phi(g).clamp_min(MES_CLAMP_LB)
+    inner = 1.0 - (vM / vm)[:, None] * r * (g + r)
+    acq = -0.5 * inner.clamp_min(MES_CLAMP_LB).log().mean(dim=1)
+    if A is not None and A.shape[-1] > 0:
+        qf = ((A @ Binv) * A).sum(-1)
+        lim = qf * (1.0 + 1e-12)
+        # clamped: lim - qf without its cancellation; the gradient runs through qf
+        vdet = torch.where(vm >= lim, vm - qf, qf * MES_VDET_EPS)
+        acq = acq + 0.5 * (torch.log(vdet) - torch.log(vm))
+    return acq
+
+
+def _mv_moments(model, candidate_set: torch.Tensor, maximize: bool):
+    """(w mu, sigma), N each: the candidate set's posterior in one
+    posterior_moments call over N x 1 x d."""
+    from .posteriors import posterior_moments
+    mean, cov = posterior_moments(model, candidate_set.unsqueeze(-2))
+    w = 1.0 if maximize else -1.0
+    return w * mean.reshape(-1), cov.reshape(-1).clamp_min(1e-8).sqrt()
+
+
+def _sample_max_value_Thompson(model, candidate_set: torch.Tensor, num_samples: int,
+                               posterior_transform=None, maximize: bool = True) -> torch.Tensor:
+    """max_value_entropy_search.py:924-956: the maxima of ``num_samples`` joint
+    posterior draws over the candidate set, ``num_samples x 1``."""
+    posterior = model.posterior(candidate_set, posterior_transform=posterior_transform)
+    weight = 1.0 if maximize else -1.0
+    samples = weight * posterior.rsample(torch.Size([num_samples])).squeeze(-1)
+    return samples.max(dim=-1).values.unsqueeze(-1)
+
+
+def _sample_max_value_Gumbel(model, candidate_set: torch.Tensor, num_samples: int,
+                             posterior_transform=None, maximize: bool = True) -> torch.Tensor:
+    """max_value_entropy_search.py:959-1022: the Gumbel approximation of the
+    maximum over the candidate set under independence, ``num_samples x 1``.  The
+    three quantiles it is fitted to come from one on-device bisection launch
+    (bo::mv_quantiles) in place of brentq on host copies."""
+    from . import ops  # noqa: F401  (torch.ops.bo registration)
+    if posterior_transform is not None:
+        raise UnsupportedError("max-value sampling: a `posterior_transform` is not on the "
+                               "accelerated path")
+    mu, sigma = _mv_moments(model, candidate_set, maximize)
+    y, status = torch.ops.bo.mv_quantiles(mu, sigma, False, 0.0, 0.0)
+    kernels.mv_quantiles_raise(status.tolist())
+    q25, q50, q75 = y[0:1], y[1:2], y[2:3]
+    b = (q25 - q75) / (math.log(math.log(4.0 / 3.0)) - math.log(math.log(4.0)))
+    a = q50 + b * math.log(math.log(2.0))
+    eps = torch.rand(num_samples, 1, device=mu.device, dtype=mu.dtype)
+    return a - b * eps.log().mul(-1.0).log()
+
+
+def _mv_validate(name: str, model, posterior_transform) -> None:
+    """The supported configuration of the max-value family: a single-output
+    SingleTaskGP in eval mode without posterior transform."""
+    from .models import ModelListGP, SaasFullyBayesianSingleTaskGP, SingleTaskGP
+    if isinstance(model, SaasFullyBayesianSingleTaskGP):
+        raise UnsupportedError(f"{name}: SaasFullyBayesianSingleTaskGP is not on the accelerated "
+                               "path (single-output SingleTaskGP only)")
+    if (isinstance(model, ModelListGP) or not isinstance(model, SingleTaskGP)
+            or model.num_outputs != 1):
+        raise UnsupportedError(f"{name}: multi-output models and ModelListGP are not on the "
+                               "accelerated path (single-output SingleTaskGP only)")
+    if posterior_transform is not None:
+        raise UnsupportedError(f"{name}: a `posterior_transform` is not on the accelerated path")
+    if model.training:
+        raise UnsupportedError(f"{name} needs a model in eval mode (model.eval()): the posterior "
+                               "comes from the trained model's prediction caches")
+
+
+class MaxValueBase(AcquisitionFunction):
+    """max_value_entropy_search.py:60-191: the max-value entropy family for a
+    single-output exact GP.  Subclasses set ``posterior_max_values`` (S_M x 1,
+    in the w-signed outcome space) in ``_sample_max_values`` and compute the
+    value of the rows of a ``R x 1 x d`` tensor in ``_fused`` / ``_generic``.
+    Every t-batch is q = 1; everything is computed in outcome space."""
+
+    def __init__(self, model, num_mv_samples: int, posterior_transform=None,
+                 maximize: bool = True, X_pending=None):
+        _mv_validate(type(self).__name__, model, posterior_transform)
+        super().__init__(model)
+        self.num_mv_samples = num_mv_samples
+        self.posterior_transform = None
+        self.maximize = bool(maximize)
+        self.weight = 1.0 if maximize else -1.0
+        self._route = None  # None: by size; "fused" / "generic": forced (tests, tools)
+        _, ystd = model.outcome_stats()
+        # what GPyTorchPosterior.from_model(..., observation_noise=True) adds
+        self._tau2 = float(model.likelihood.noise.detach().mean()) * float(ystd) ** 2
+        self.set_X_pending(X_pending)
+
+    def set_X_pending(self, X_pending: Optional[torch.Tensor] = None) -> None:
+        if X_pending is not None:
+            X_pending = X_pending.detach().clone()
+        self._sample_max_values(num_samples=self.num_mv_samples, X_pending=X_pending)
+        self.X_pending = X_pending
+
+    def _sample_max_values(self, num_samples: int, X_pending=None) -> None:
+        raise NotImplementedError  # pragma: no cover
+
+    def _fused(self, X3: torch.Tensor) -> torch.Tensor:
+        raise NotImplementedError  # pragma: no cover
+
+    def _generic(self, X3: torch.Tensor) -> torch.Tensor:
+        raise NotImplementedError  # pragma: no cover
+
+    def _fused_applies(self, X3: torch.Tensor) -> bool:
+        return X3.is_cuda
+
+    def _fstar(self) -> torch.Tensor:
+        return self.posterior_max_values.reshape(-1).to(torch.float64)
+
+    def forward(self, X: torch.Tensor) -> torch.Tensor:
+        X = t_batch_mode(X, expected_q=1)
+        if X.dtype != torch.float64:  # the model computes in fp64; the value returns in X's dtype
+            return self.forward(X.to(torch.float64)).to(X.dtype)
+        batch = X.shape[:-2]
+        X3 = X.reshape(-1, 1, X.shape[-1])
+        fused = self._fused_applies(X3) if self._route is None else self._route == "fused"
+        return (self._fused(X3) if fused else self._generic(X3)).reshape(batch)
+
+
+class DiscreteMaxValueBase(MaxValueBase):
+    """max_value_entropy_search.py:194-297: max values drawn on a discrete
+    candidate set (with the training inputs, and the pending points, appended),
+    by the Gumbel approximation or by discrete Thompson sampling."""
+
+    def __init__(self, model, candidate_set: torch.Tensor, num_mv_samples: int = 10,
+                 posterior_transform=None, use_gumbel: bool = True, maximize: bool = True,
+                 X_pending=None, train_inputs=None):
+        _mv_validate(type(self).__name__, model, posterior_transform)
+        if train_inputs is None and hasattr(model, "train_inputs"):
+            train_inputs = model.train_inputs[0]
+        if train_inputs is not None:
+            if train_inputs.ndim > 2:
+                raise NotImplementedError("Batch GP models (e.g. fantasized models) "
+                                          "are not yet supported by `MaxValueBase`")
+            candidate_set = torch.cat([candidate_set, train_inputs.to(candidate_set)], dim=0)
+        self.use_gumbel = use_gumbel
+        self.candidate_set = candidate_set
+        super().__init__(model=model, num_mv_samples=num_mv_samples,
+                         posterior_transform=posterior_transform, maximize=maximize,
+                         X_pending=X_pending)
+
+    def _sample_max_values(self, num_samples: int, X_pending=None) -> None:
+        sample = _sample_max_value_Gumbel if self.use_gumbel else _sample_max_value_Thompson
+        candidate_set = self.candidate_set
+        with torch.no_grad():
+            if X_pending is not None:
+                candidate_set = torch.cat([candidate_set, X_pending.to(candidate_set)], dim=0)
+            self.posterior_max_values = sample(
+                model=self.model, candidate_set=candidate_set, num_samples=self.num_mv_samples,
+                posterior_transform=None, maximize=self.maximize).to(candidate_set.dtype)
+
+
+MES_PENDING_MSG = (
+    "qMaxValueEntropy with pending points needs batched fantasy models (`model.fantasize`), "
+    "which are not on the accelerated path (DESIGN.md section 7); use "
+    "qLowerBoundMaxValueEntropy (GIBBON) for batches with pending points")
+
+
+class qMaxValueEntropy(DiscreteMaxValueBase):
+    """Max-value entropy search (max_value_entropy_search.py:300-515) without
+    pending points: the mutual information of the maximum and the noisy
+    observation at x, with the regression-adjusted two-level estimate over
+    ``num_mv_samples`` max values and ``num_y_samples`` Sobol base samples
+    (drawn once at construction and shared by all t-batches).  The fused route
+    (``bo::mes``) keeps the S_M x S_m pairs of a row in one wave's registers; the
+    generic route is the same formula as broadcast torch tensors.
+    ``num_fantasies`` is accepted and unused: pending points raise
+    ``UnsupportedError``."""
+
+    def __init__(self, model, candidate_set: torch.Tensor, num_fantasies: int = 16,
+                 num_mv_samples: int = 10, num_y_samples: int = 128, posterior_transform=None,
+                 use_gumbel: bool = True, maximize: bool = True, X_pending=None,
+                 train_inputs=None):
+        _mv_validate("qMaxValueEntropy", model, posterior_transform)
+        if X_pending is not None:
+            raise UnsupportedError(MES_PENDING_MSG)
+        if num_y_samples < 2:
+            raise ValueError("qMaxValueEntropy: num_y_samples >= 2 (the regression adjustment "
+                             f"divides by the sample variance; got {num_y_samples})")
+        kernels.mes_check(num_mv_samples, num_y_samples)
+        super().__init__(model=model, candidate_set=candidate_set, num_mv_samples=num_mv_samples,
+                         posterior_transform=posterior_transform, use_gumbel=use_gumbel,
+                         maximize=maximize, X_pending=None, train_inputs=train_inputs)
+        self.num_fantasies = num_fantasies
+        self.num_y_samples = num_y_samples
+        # the seed comes from torch's global generator (sampling/base.py)
+        seed = int(torch.randint(0, 1000000, (1,)).item())
+        dev = model.train_inputs[0].device
+        self.base_samples = kernels.sobol_normal(1, num_y_samples, seed, dev).reshape(-1)
+        self._consts = kernels.mes_host_constants(self.base_samples)
+
+    def set_X_pending(self, X_pending: Optional[torch.Tensor] = None) -> None:
+        if X_pending is not None:
+            raise UnsupportedError(MES_PENDING_MSG)
+        super().set_X_pending(None)
+
+    def _moments(self, X3: torch.Tensor):
+        from .posteriors import posterior_moments
+        mean, cov = posterior_moments(self.model, X3)
+        return mean.reshape(-1), cov.reshape(-1)
+
+    def _fused(self, X3: torch.Tensor) -> torch.Tensor:
+        from . import ops  # noqa: F401  (torch.ops.bo registration)
+        mu, var = self._moments(X3)
+        return torch.ops.bo.mes(mu, var, self._fstar(), self.base_samples, *self._consts,
+                                self._tau2, self.weight)
+
+    def _generic(self, X3: torch.Tensor) -> torch.Tensor:
+        mu, var = self._moments(X3)
+        return _mes_chain(mu, var, self._fstar(), self.base_samples, self._tau2, self.weight)
+
+
+class qLowerBoundMaxValueEntropy(DiscreteMaxValueBase):
+    """GIBBON (max_value_entropy_search.py:518-664): the cheap lower bound of the
+    information gain, with the repulsion term of the pending points that
+    ``optimize_acqf(..., q > 1, sequential=True)`` sets.  With m pending points
+    one posterior over ``R x (1 + m) x d`` gives mu, sigma^2 (row 0) and the
+    cross-covariance A; B^{-1} is fixed at ``set_X_pending``.  The fused route
+    (``bo::gibbon``) applies up to kernels.GIBBON_MMAX pending points."""
+
+    def set_X_pending(self, X_pending: Optional[torch.Tensor] = None) -> None:
+        super().set_X_pending(X_pending)
+        self._Binv = None
+        if self.X_pending is not None:
+            from .posteriors import posterior_moments
+            with torch.no_grad():
+                Xp = self.X_pending.to(torch.float64)
+                _, cov = posterior_moments(self.model, Xp.unsqueeze(0))
+                m = Xp.shape[-2]
+                B = cov[0] + self._tau2 * torch.eye(m, dtype=torch.float64, device=cov.device)
+                self._Binv = torch.cholesky_inverse(kernels.chol_jitter(B))
+
+    def _moments(self, X3: torch.Tensor):
+        from .posteriors import posterior_moments
+        if self.X_pending is None:
+            mean, cov = posterior_moments(self.model, X3)
+            return mean.reshape(-1), cov.reshape(-1), None
+        Xp = self.X_pending.to(X3)
+        mean, cov = posterior_moments(self.model,
+                                      torch.cat([X3, Xp.expand(X3.shape[0], *Xp.shape)], dim=-2))
+        return mean[:, 0], cov[:, 0, 0], cov[:, 0, 1:]
+
+    def _fused_applies(self, X3: torch.Tensor) -> bool:
+        m = 0 if self.X_pending is None else self.X_pending.shape[-2]
+        return X3.is_cuda and m <= kernels.GIBBON_MMAX
+
+    def _fused(self, X3: torch.Tensor) -> torch.Tensor:
+        from . import ops  # noqa: F401  (torch.ops.bo registration)
+        mu, var, A = self._moments(X3)
+        return torch.ops.bo.gibbon(mu, var, A, self._Binv if A is not None else None,
+                                   self._fstar(), self._tau2, self.weight)
+
+    def _generic(self, X3: torch.Tensor) -> torch.Tensor:
+        mu, var, A = self._moments(X3)
+        return _gibbon_chain(mu, var, self._fstar(), self._tau2, self.weight, A, self._Binv)
+
+
 # -- qNEI -------------------------------------------------------------------------------
 def prune_inferior_points(model, X, objective=None, posterior_transform=None, constraints=None,
                           num_samples: int = 2048, max_frac: float = 1.0, sampler=None,

@@ -82,6 +82,13 @@ int bo_paths_eval_backward_impl(const BoPathsArgs* a, void* stream);
 int bo_jes_impl(const BoJesArgs* a, void* stream);
 int bo_jes_backward_impl(const BoJesArgs* a, void* stream);
 
+// max-value entropy search: MES, GIBBON and the Gumbel fit's quantiles (mes.hip)
+int bo_mes_impl(const BoMesArgs* a, void* stream);
+int bo_mes_backward_impl(const BoMesArgs* a, void* stream);
+int bo_gibbon_impl(const BoGibbonArgs* a, void* stream);
+int bo_gibbon_backward_impl(const BoGibbonArgs* a, void* stream);
+int bo_mv_quantiles_impl(const BoMvQuantilesArgs* a, void* stream);
+
 int bo_post_partials_v(const BoPostPartialsArgs* a, void* stream) {
   if (!header_ok(a, "bo_post_partials_v")) return BO_ERR_ARG;
   return bo_post_partials_layout(a->kind, a->Xq, a->B, a->q, a->d, a->Xt_scaled, a->n, a->U,
@@ -188,6 +195,31 @@ int bo_jes_backward_v(const BoJesArgs* a, void* stream) {
   return bo_jes_backward_impl(a, stream);
 }
 
+int bo_mes_v(const BoMesArgs* a, void* stream) {
+  if (!header_ok(a, "bo_mes_v")) return BO_ERR_ARG;
+  return bo_mes_impl(a, stream);
+}
+
+int bo_mes_backward_v(const BoMesArgs* a, void* stream) {
+  if (!header_ok(a, "bo_mes_backward_v")) return BO_ERR_ARG;
+  return bo_mes_backward_impl(a, stream);
+}
+
+int bo_gibbon_v(const BoGibbonArgs* a, void* stream) {
+  if (!header_ok(a, "bo_gibbon_v")) return BO_ERR_ARG;
+  return bo_gibbon_impl(a, stream);
+}
+
+int bo_gibbon_backward_v(const BoGibbonArgs* a, void* stream) {
+  if (!header_ok(a, "bo_gibbon_backward_v")) return BO_ERR_ARG;
+  return bo_gibbon_backward_impl(a, stream);
+}
+
+int bo_mv_quantiles_v(const BoMvQuantilesArgs* a, void* stream) {
+  if (!header_ok(a, "bo_mv_quantiles_v")) return BO_ERR_ARG;
+  return bo_mv_quantiles_impl(a, stream);
+}
+
 int bo_lbfgs_step_v(const BoLbfgsStepArgs* a, void* stream) {
   if (!header_ok(a, "bo_lbfgs_step_v")) return BO_ERR_ARG;
   return bo_lbfgs_step(a->B, a->n, a->m, a->x, a->f, a->g, a->xt, a->ft, a->gt, a->d, a->alpha,
@@ -218,6 +250,9 @@ extern "C" int64_t bo_struct_size(const char* name) {
   if (s == "BoKgArgs") return sizeof(BoKgArgs);
   if (s == "BoPathsArgs") return sizeof(BoPathsArgs);
   if (s == "BoJesArgs") return sizeof(BoJesArgs);
+  if (s == "BoMesArgs") return sizeof(BoMesArgs);
+  if (s == "BoGibbonArgs") return sizeof(BoGibbonArgs);
+  if (s == "BoMvQuantilesArgs") return sizeof(BoMvQuantilesArgs);
   if (s == "BoLbfgsStepArgs") return sizeof(BoLbfgsStepArgs);
   if (s == "BoLbfgsbArgs") return sizeof(BoLbfgsbArgs);
   return -1;

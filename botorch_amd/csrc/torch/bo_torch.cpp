@@ -945,9 +945,171 @@ std::vector<at::Tensor> jes_backward_native(
   return {dX, dmu, dvar};
 }
 
+// ---- max-value entropy search (bo_mes_v, bo_gibbon_v, bo_mv_quantiles_v and backwards) ----
+void mes_dense(const char* who, std::initializer_list<const at::Tensor*> ts) {
+  for (const at::Tensor* t : ts)
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kDouble && t->is_contiguous(), who,
+                ": every tensor must be a contiguous fp64 ROCm device tensor");
+}
+
+// mu, var (R), fstar (S_M), z (S_m); consts = (kappa, var_h0, zsq_mean)
+BoMesArgs mes_args(const at::Tensor& mu, const at::Tensor& var, const at::Tensor& fstar,
+                   const at::Tensor& z, double kappa, double var_h0, double zsq_mean, double tau2,
+                   double w) {
+  const char* who = "bo::mes_native";
+  mes_dense(who, {&mu, &var, &fstar, &z});
+  TORCH_CHECK(mu.dim() == 1 && var.dim() == 1 && var.size(0) == mu.size(0), who,
+              ": mu and var must have R entries each");
+  TORCH_CHECK(fstar.dim() == 1 && z.dim() == 1 && fstar.size(0) <= INT32_MAX &&
+                  z.size(0) <= INT32_MAX, who, ": fstar must have S_M and z S_m entries");
+  BoMesArgs a{};
+  a.struct_size = sizeof(a);
+  a.abi_version = BO_ABI_VERSION;
+  a.S_M = static_cast<int32_t>(fstar.size(0));
+  a.S_m = static_cast<int32_t>(z.size(0));
+  a.R = mu.size(0);
+  a.mu = cp(mu);
+  a.var = cp(var);
+  a.fstar = cp(fstar);
+  a.z = cp(z);
+  a.kappa = kappa;
+  a.var_h0 = var_h0;
+  a.zsq_mean = zsq_mean;
+  a.tau2 = tau2;
+  a.w = w;
+  return a;
+}
+
+at::Tensor mes_native(const at::Tensor& mu, const at::Tensor& var, const at::Tensor& fstar,
+                      const at::Tensor& z, double kappa, double var_h0, double zsq_mean,
+                      double tau2, double w) {
+  BoMesArgs a = mes_args(mu, var, fstar, z, kappa, var_h0, zsq_mean, tau2, w);
+  at::Tensor out = at::empty({a.R}, mu.options());
+  a.out = out.data_ptr<double>();
+  ck(bo_mes_v(&a, c10::hip::getCurrentHIPStream(mu.device().index()).stream()), "mes");
+  return out;
+}
+
+std::vector<at::Tensor> mes_backward_native(const at::Tensor& dout, const at::Tensor& mu,
+                                            const at::Tensor& var, const at::Tensor& fstar,
+                                            const at::Tensor& z, double kappa, double var_h0,
+                                            double zsq_mean, double tau2, double w) {
+  BoMesArgs a = mes_args(mu, var, fstar, z, kappa, var_h0, zsq_mean, tau2, w);
+  mes_dense("bo::mes_backward_native", {&dout});
+  TORCH_CHECK(dout.dim() == 1 && dout.size(0) == a.R,
+              "bo::mes_backward_native: dout must have R = ", a.R, " entries");
+  at::Tensor dmu = at::empty({a.R}, mu.options()), dvar = at::empty({a.R}, mu.options());
+  a.dout = dout.data_ptr<double>();
+  a.dmu = dmu.data_ptr<double>();
+  a.dvar = dvar.data_ptr<double>();
+  ck(bo_mes_backward_v(&a, c10::hip::getCurrentHIPStream(mu.device().index()).stream()),
+     "mes_backward");
+  return {dmu, dvar};
+}
+
+// A (R x m) with Binv (m x m), or neither (m = 0)
+BoGibbonArgs gibbon_args(const at::Tensor& mu, const at::Tensor& var,
+                         const c10::optional<at::Tensor>& A,
+                         const c10::optional<at::Tensor>& Binv, const at::Tensor& fstar,
+                         double tau2, double w) {
+  const char* who = "bo::gibbon_native";
+  mes_dense(who, {&mu, &var, &fstar});
+  TORCH_CHECK(mu.dim() == 1 && var.dim() == 1 && var.size(0) == mu.size(0), who,
+              ": mu and var must have R entries each");
+  TORCH_CHECK(fstar.dim() == 1 && fstar.size(0) <= INT32_MAX, who, ": fstar must have S_M entries");
+  TORCH_CHECK(A.has_value() == Binv.has_value(), who, ": A and Binv go together");
+  const int64_t R = mu.size(0), m = A.has_value() ? A->size(-1) : 0;
+  if (m > 0) {
+    mes_dense(who, {&*A, &*Binv});
+    TORCH_CHECK(A->dim() == 2 && A->size(0) == R && Binv->dim() == 2 && Binv->size(0) == m &&
+                    Binv->size(1) == m && m <= INT32_MAX, who, ": A must be R x m and Binv m x m");
+  }
+  BoGibbonArgs a{};
+  a.struct_size = sizeof(a);
+  a.abi_version = BO_ABI_VERSION;
+  a.S_M = static_cast<int32_t>(fstar.size(0));
+  a.m = static_cast<int32_t>(m);
+  a.R = R;
+  a.mu = cp(mu);
+  a.var = cp(var);
+  a.A = m > 0 ? cp(*A) : nullptr;
+  a.Binv = m > 0 ? cp(*Binv) : nullptr;
+  a.fstar = cp(fstar);
+  a.tau2 = tau2;
+  a.w = w;
+  return a;
+}
+
+at::Tensor gibbon_native(const at::Tensor& mu, const at::Tensor& var,
+                         const c10::optional<at::Tensor>& A,
+                         const c10::optional<at::Tensor>& Binv, const at::Tensor& fstar,
+                         double tau2, double w) {
+  BoGibbonArgs a = gibbon_args(mu, var, A, Binv, fstar, tau2, w);
+  at::Tensor out = at::empty({a.R}, mu.options());
+  a.out = out.data_ptr<double>();
+  ck(bo_gibbon_v(&a, c10::hip::getCurrentHIPStream(mu.device().index()).stream()), "gibbon");
+  return out;
+}
+
+// (dmu, dvar, dA); dA is R x m (R x 0 without pending points)
+std::vector<at::Tensor> gibbon_backward_native(const at::Tensor& dout, const at::Tensor& mu,
+                                               const at::Tensor& var,
+                                               const c10::optional<at::Tensor>& A,
+                                               const c10::optional<at::Tensor>& Binv,
+                                               const at::Tensor& fstar, double tau2, double w) {
+  BoGibbonArgs a = gibbon_args(mu, var, A, Binv, fstar, tau2, w);
+  mes_dense("bo::gibbon_backward_native", {&dout});
+  TORCH_CHECK(dout.dim() == 1 && dout.size(0) == a.R,
+              "bo::gibbon_backward_native: dout must have R = ", a.R, " entries");
+  at::Tensor dmu = at::empty({a.R}, mu.options()), dvar = at::empty({a.R}, mu.options()),
+             dA = at::empty({a.R, (int64_t)a.m}, mu.options());
+  a.dout = dout.data_ptr<double>();
+  a.dmu = dmu.data_ptr<double>();
+  a.dvar = dvar.data_ptr<double>();
+  a.dA = a.m > 0 ? dA.data_ptr<double>() : nullptr;
+  ck(bo_gibbon_backward_v(&a, c10::hip::getCurrentHIPStream(mu.device().index()).stream()),
+     "gibbon_backward");
+  return {dmu, dvar, dA};
+}
+
+// (y (3) fp64, status (3) int32); with have_bounds the bisection runs on [lo, hi]
+std::vector<at::Tensor> mv_quantiles_native(const at::Tensor& mu, const at::Tensor& sigma,
+                                            bool have_bounds, double lo, double hi) {
+  const char* who = "bo::mv_quantiles_native";
+  mes_dense(who, {&mu, &sigma});
+  TORCH_CHECK(mu.dim() == 1 && mu.size(0) >= 1 && sigma.dim() == 1 && sigma.size(0) == mu.size(0),
+              who, ": mu and sigma must have N >= 1 entries each");
+  at::Tensor out = at::empty({3}, mu.options());
+  at::Tensor status = at::empty({3}, mu.options().dtype(at::kInt));
+  BoMvQuantilesArgs a{};
+  a.struct_size = sizeof(a);
+  a.abi_version = BO_ABI_VERSION;
+  a.have_bounds = have_bounds ? 1 : 0;
+  a.N = mu.size(0);
+  a.mu = cp(mu);
+  a.sigma = cp(sigma);
+  a.lo = lo;
+  a.hi = hi;
+  a.out = out.data_ptr<double>();
+  a.status = status.data_ptr<int32_t>();
+  ck(bo_mv_quantiles_v(&a, c10::hip::getCurrentHIPStream(mu.device().index()).stream()),
+     "mv_quantiles");
+  return {out, status};
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(bo, m) {
+  m.def("mes_native(Tensor mu, Tensor var, Tensor fstar, Tensor z, float kappa, float var_h0, "
+        "float zsq_mean, float tau2, float w) -> Tensor");
+  m.def("mes_backward_native(Tensor dout, Tensor mu, Tensor var, Tensor fstar, Tensor z, "
+        "float kappa, float var_h0, float zsq_mean, float tau2, float w) -> Tensor[]");
+  m.def("gibbon_native(Tensor mu, Tensor var, Tensor? A, Tensor? Binv, Tensor fstar, float tau2, "
+        "float w) -> Tensor");
+  m.def("gibbon_backward_native(Tensor dout, Tensor mu, Tensor var, Tensor? A, Tensor? Binv, "
+        "Tensor fstar, float tau2, float w) -> Tensor[]");
+  m.def("mv_quantiles_native(Tensor mu, Tensor sigma, bool have_bounds, float lo, float hi) "
+        "-> Tensor[]");
   m.def("jes_native(Tensor X, Tensor mu, Tensor var, Tensor lengthscale, Tensor? Xt_scaled, "
         "Tensor Xopt_scaled, Tensor? V, Tensor g, Tensor sinv, Tensor wf, Tensor tau2, int kind, "
         "float outputscale, float w) -> Tensor");
@@ -988,4 +1150,9 @@ TORCH_LIBRARY_IMPL(bo, CUDA, m) {
   m.impl("qehvi_members_eager", &qehvi_members_eager);
   m.impl("jes_native", &jes_native);
   m.impl("jes_backward_native", &jes_backward_native);
+  m.impl("mes_native", &mes_native);
+  m.impl("mes_backward_native", &mes_backward_native);
+  m.impl("gibbon_native", &gibbon_native);
+  m.impl("gibbon_backward_native", &gibbon_backward_native);
+  m.impl("mv_quantiles_native", &mv_quantiles_native);
 }

@@ -2256,6 +2256,177 @@ def jes_backward(dout: torch.Tensor, X: torch.Tensor, lengthscale: torch.Tensor,
     return dX, dmu, dvar
 
 
+MES_SM_MAX, MES_SY_MAX = 1024, 4096  # bo_mes: S_M and S_m are runtime loops up to here
+GIBBON_MMAX = 15  # bo_gibbon: pending points (x plus them is one 16-row posterior tile)
+
+
+def mes_check(S_M: int, S_m: int, R: int = 1) -> None:
+    """The argument limits of :func:`mes`, raised on the host before any native
+    call (acquisition.qMaxValueEntropy checks its sizes with it)."""
+    if not 1 <= S_M <= MES_SM_MAX:
+        raise ValueError(f"mes: 1 <= S_M <= {MES_SM_MAX} (got {S_M})")
+    if not 2 <= S_m <= MES_SY_MAX:
+        raise ValueError(f"mes: 2 <= S_m <= {MES_SY_MAX} (got {S_m})")
+    if not 1 <= R < 2 ** 31:
+        raise ValueError(f"mes: 1 <= R < 2^31 (got {R})")
+
+
+def gibbon_check(S_M: int, m: int, R: int = 1) -> None:
+    """The argument limits of :func:`gibbon`, raised on the host."""
+    if S_M < 1:
+        raise ValueError(f"gibbon: S_M >= 1 (got {S_M})")
+    if not 0 <= m <= GIBBON_MMAX:
+        raise ValueError(f"gibbon: 0 <= m <= {GIBBON_MMAX} (got {m})")
+    if R < 1:
+        raise ValueError(f"gibbon: R >= 1 (got {R})")
+
+
+def mes_host_constants(z: torch.Tensor):
+    """(kappa, var_h0, zsq_mean) of the base samples z (S_m): mean_k h0 - H0 =
+    (mean z^2 - 1) / 2, the unbiased variance of h0_k = z_k^2 / 2 + const, and
+    mean z^2 -- the three row-independent constants of bo_mes."""
+    zz = z.detach().to(torch.float64).reshape(-1) ** 2
+    zsq = zz.mean().item()
+    return 0.5 * (zsq - 1.0), (0.5 * zz).var().item(), zsq
+
+
+def _w_ok(who: str, w: float) -> float:
+    if float(w) not in (1.0, -1.0):
+        raise ValueError(f"{who}: w must be +1 or -1 (got {w})")
+    return float(w)
+
+
+def _mes_args(mu, var, fstar, z, consts, tau2, w):
+    if mu.dim() != 1 or tuple(var.shape) != tuple(mu.shape):
+        raise ValueError(f"mes: mu and var must have R entries each, got {tuple(mu.shape)} and "
+                         f"{tuple(var.shape)}")
+    if fstar.dim() != 1 or z.dim() != 1:
+        raise ValueError("mes: fstar must have S_M and z S_m entries")
+    mes_check(fstar.shape[0], z.shape[0], mu.shape[0])
+    kappa, var_h0, zsq_mean = consts
+    if not var_h0 > 0.0 or float(tau2) < 0.0:
+        raise ValueError(f"mes: var_h0 > 0 and tau2 >= 0 (got {var_h0}, {tau2})")
+    return _lib.MesArgs(S_M=fstar.shape[0], S_m=z.shape[0], R=mu.shape[0], mu=mu.contiguous(),
+                        var=var.contiguous(), fstar=fstar.contiguous(), z=z.contiguous(),
+                        kappa=float(kappa), var_h0=float(var_h0), zsq_mean=float(zsq_mean),
+                        tau2=float(tau2), w=_w_ok("mes", w))
+
+
+def mes(mu: torch.Tensor, var: torch.Tensor, fstar: torch.Tensor, z: torch.Tensor, consts,
+        tau2: float, w: float = 1.0) -> torch.Tensor:
+    """qMaxValueEntropy's information gain of R rows (bo_mes; the record's
+    comment in include/botorch_amd.h states the formula) from their posterior
+    mean and variance, the S_M max values, the S_m base samples and
+    ``consts = mes_host_constants(z)``.  The only allocation is the output."""
+    dev = _dev(mu, var, fstar, z)
+    a = _mes_args(mu, var, fstar, z, consts, tau2, w)
+    out = torch.empty(a.R, dtype=torch.float64, device=dev)
+    a.out = out.data_ptr()
+    check(lib().bo_mes_v(ctypes.byref(a), _stream(dev)), "mes")
+    return out
+
+
+def mes_backward(dout: torch.Tensor, mu: torch.Tensor, var: torch.Tensor, fstar: torch.Tensor,
+                 z: torch.Tensor, consts, tau2: float, w: float = 1.0):
+    """(dmu, dvar), R each, of :func:`mes` from dout (R).  One launch."""
+    dev = _dev(dout, mu, var, fstar, z)
+    a = _mes_args(mu, var, fstar, z, consts, tau2, w)
+    if tuple(dout.shape) != (a.R,) or dout.dtype != torch.float64:
+        raise ValueError(f"mes_backward: dout must be fp64 of shape ({a.R},), got "
+                         f"{tuple(dout.shape)}")
+    dout = dout.contiguous()
+    dmu = torch.empty(a.R, dtype=torch.float64, device=dev)
+    dvar = torch.empty(a.R, dtype=torch.float64, device=dev)
+    a.dout, a.dmu, a.dvar = dout.data_ptr(), dmu.data_ptr(), dvar.data_ptr()
+    check(lib().bo_mes_backward_v(ctypes.byref(a), _stream(dev)), "mes_backward")
+    return dmu, dvar
+
+
+def _gibbon_args(mu, var, A, Binv, fstar, tau2, w):
+    if mu.dim() != 1 or tuple(var.shape) != tuple(mu.shape):
+        raise ValueError(f"gibbon: mu and var must have R entries each, got {tuple(mu.shape)} "
+                         f"and {tuple(var.shape)}")
+    if fstar.dim() != 1:
+        raise ValueError("gibbon: fstar must have S_M entries")
+    R = mu.shape[0]
+    m = 0 if A is None else A.shape[-1]
+    gibbon_check(fstar.shape[0], m, R)
+    if m and (tuple(A.shape) != (R, m) or Binv is None or tuple(Binv.shape) != (m, m)):
+        raise ValueError(f"gibbon: A must be {R} x m and Binv m x m, got {tuple(A.shape)} and "
+                         f"{None if Binv is None else tuple(Binv.shape)}")
+    if float(tau2) < 0.0:
+        raise ValueError(f"gibbon: tau2 >= 0 (got {tau2})")
+    return _lib.GibbonArgs(S_M=fstar.shape[0], m=m, R=R, mu=mu.contiguous(), var=var.contiguous(),
+                           A=A.contiguous() if m else None, Binv=Binv.contiguous() if m else None,
+                           fstar=fstar.contiguous(), tau2=float(tau2), w=_w_ok("gibbon", w))
+
+
+def gibbon(mu: torch.Tensor, var: torch.Tensor, A: Optional[torch.Tensor],
+           Binv: Optional[torch.Tensor], fstar: torch.Tensor, tau2: float,
+           w: float = 1.0) -> torch.Tensor:
+    """GIBBON's value of R rows (bo_gibbon): the quality term from mu, var and
+    the S_M max values, plus, with A (R x m) and Binv (m x m), the repulsion
+    term of m <= GIBBON_MMAX pending points."""
+    dev = _dev(mu, var, A, Binv, fstar)
+    a = _gibbon_args(mu, var, A, Binv, fstar, tau2, w)
+    out = torch.empty(a.R, dtype=torch.float64, device=dev)
+    a.out = out.data_ptr()
+    check(lib().bo_gibbon_v(ctypes.byref(a), _stream(dev)), "gibbon")
+    return out
+
+
+def gibbon_backward(dout: torch.Tensor, mu: torch.Tensor, var: torch.Tensor,
+                    A: Optional[torch.Tensor], Binv: Optional[torch.Tensor], fstar: torch.Tensor,
+                    tau2: float, w: float = 1.0):
+    """(dmu R, dvar R, dA R x m or None) of :func:`gibbon` from dout (R)."""
+    dev = _dev(dout, mu, var, A, Binv, fstar)
+    a = _gibbon_args(mu, var, A, Binv, fstar, tau2, w)
+    if tuple(dout.shape) != (a.R,) or dout.dtype != torch.float64:
+        raise ValueError(f"gibbon_backward: dout must be fp64 of shape ({a.R},), got "
+                         f"{tuple(dout.shape)}")
+    dout = dout.contiguous()
+    dmu = torch.empty(a.R, dtype=torch.float64, device=dev)
+    dvar = torch.empty(a.R, dtype=torch.float64, device=dev)
+    dA = torch.empty(a.R, a.m, dtype=torch.float64, device=dev) if a.m else None
+    a.dout, a.dmu, a.dvar = dout.data_ptr(), dmu.data_ptr(), dvar.data_ptr()
+    if a.m:
+        a.dA = dA.data_ptr()
+    check(lib().bo_gibbon_backward_v(ctypes.byref(a), _stream(dev)), "gibbon_backward")
+    return dmu, dvar, dA
+
+
+def mv_quantiles_raise(status) -> None:
+    """The host's side of bo_mv_quantiles' status words: a non-zero word means
+    the end points did not bracket that quantile -- the ``ValueError`` that
+    ``scipy.optimize.brentq`` raises there."""
+    if any(int(s) != 0 for s in status):
+        raise ValueError("f(a) and f(b) must have different signs")
+
+
+def mv_quantiles(mu: torch.Tensor, sigma: torch.Tensor, bounds=None) -> torch.Tensor:
+    """The y (3) with sum_i log Phi((y - mu_i) / sigma_i) = log p for p = 0.25,
+    0.5, 0.75 (bo_mv_quantiles: one launch, a bisection per quantile on
+    [min(mu - 3 sigma), max(mu + 5 sigma)], or on ``bounds = (lo, hi)``).
+    Raises brentq's ``ValueError`` when the end points do not bracket."""
+    dev = _dev(mu, sigma)
+    if mu.dim() != 1 or mu.shape[0] < 1 or tuple(sigma.shape) != tuple(mu.shape):
+        raise ValueError(f"mv_quantiles: mu and sigma must have N >= 1 entries each, got "
+                         f"{tuple(mu.shape)} and {tuple(sigma.shape)}")
+    if mu.dtype != torch.float64 or sigma.dtype != torch.float64:
+        raise ValueError("mv_quantiles: mu and sigma must be fp64")
+    lo, hi = (0.0, 0.0) if bounds is None else (float(bounds[0]), float(bounds[1]))
+    if bounds is not None and not lo < hi:
+        raise ValueError(f"mv_quantiles: bounds must be lo < hi (got {lo}, {hi})")
+    out = torch.empty(3, dtype=torch.float64, device=dev)
+    status = torch.empty(3, dtype=torch.int32, device=dev)
+    a = _lib.MvQuantilesArgs(have_bounds=int(bounds is not None), N=mu.shape[0],
+                             mu=mu.contiguous(), sigma=sigma.contiguous(), lo=lo, hi=hi, out=out,
+                             status=status)
+    check(lib().bo_mv_quantiles_v(ctypes.byref(a), _stream(dev)), "mv_quantiles")
+    mv_quantiles_raise(status.tolist())
+    return out
+
+
 def kernel_grad(X: torch.Tensor, Y: torch.Tensor, dK: torch.Tensor, lengthscale: torch.Tensor,
                 kind: int, outputscale: float = 1.0, group: int = 0,
                 dX: Optional[torch.Tensor] = None) -> torch.Tensor:

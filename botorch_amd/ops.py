@@ -34,6 +34,13 @@ Ops (reference computation each replaces):
                       rank-one conditioned moments fused with the entropy chain
                       (+ autograd in X, mu, var; acquisition/joint_entropy_search.py:
                       195-265; its launches go through bo::jes_native in C++)
+  bo::mes             qMaxValueEntropy's information gain of R rows from their posterior
+                      mean and variance (+ autograd in mu, var;
+                      acquisition/max_value_entropy_search.py:399-515)
+  bo::gibbon          GIBBON's quality and repulsion terms of R rows (+ autograd in mu,
+                      var, A; max_value_entropy_search.py:537-664)
+  bo::mv_quantiles    the three quantiles the Gumbel max-value sampler fits, one launch
+                      (max_value_entropy_search.py:994-1010, in place of brentq on host copies)
 """
 from __future__ import annotations
 
@@ -697,7 +704,144 @@ def _jes_bwd(ctx, dout):
 jes.register_autograd(_jes_bwd, setup_context=_jes_setup)
 
 
+# ---- bo::mes, bo::gibbon, bo::mv_quantiles (max-value entropy search) ----------------------------
+def _mes_dense(mu, var, fstar, z):
+    """The tensor arguments of bo::mes[_backward]_native, contiguous, after
+    kernels.mes_check's limits (a ValueError before any native call)."""
+    if mu.dim() != 1 or fstar.dim() != 1 or z.dim() != 1:
+        raise ValueError("mes: mu, fstar and z must be vectors")
+    kernels.mes_check(fstar.shape[0], z.shape[0], mu.shape[0])
+    return tuple(t.contiguous() for t in (mu, var, fstar, z))
+
+
+@torch.library.custom_op("bo::mes", mutates_args=(), device_types="cuda")
+def mes(mu: Tensor, var: Tensor, fstar: Tensor, z: Tensor, kappa: float, var_h0: float,
+        zsq_mean: float, tau2: float, w: float) -> Tensor:
+    """ig (R): qMaxValueEntropy's information gain of R rows with posterior mean
+    mu and variance var (R each), S_M max values fstar and S_m base samples z
+    (kernels.mes; kappa, var_h0, zsq_mean = kernels.mes_host_constants(z)).
+    Differentiable in mu and var."""
+    return _lib.torch_ops().mes_native(*_mes_dense(mu, var, fstar, z), kappa, var_h0, zsq_mean,
+                                       tau2, w)
+
+
+@mes.register_fake
+def _(mu, var, fstar, z, kappa, var_h0, zsq_mean, tau2, w):
+    return mu.new_empty((mu.shape[0],), dtype=F64)
+
+
+@torch.library.custom_op("bo::mes_backward", mutates_args=(), device_types="cuda")
+def mes_backward(dout: Tensor, mu: Tensor, var: Tensor, fstar: Tensor, z: Tensor, kappa: float,
+                 var_h0: float, zsq_mean: float, tau2: float, w: float) -> Tuple[Tensor, Tensor]:
+    dmu, dvar = _lib.torch_ops().mes_backward_native(dout.contiguous(),
+                                                     *_mes_dense(mu, var, fstar, z), kappa,
+                                                     var_h0, zsq_mean, tau2, w)
+    return dmu, dvar
+
+
+@mes_backward.register_fake
+def _(dout, mu, var, fstar, z, kappa, var_h0, zsq_mean, tau2, w):
+    return mu.new_empty((mu.shape[0],), dtype=F64), mu.new_empty((mu.shape[0],), dtype=F64)
+
+
+def _mes_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[:4])
+    ctx.consts = inputs[4:]
+
+
+def _mes_bwd(ctx, dout):
+    dmu = dvar = None
+    if any(ctx.needs_input_grad[:2]):
+        dmu, dvar = torch.ops.bo.mes_backward(dout.contiguous(), *ctx.saved_tensors, *ctx.consts)
+    return (dmu, dvar) + (None,) * 7
+
+
+mes.register_autograd(_mes_bwd, setup_context=_mes_setup)
+
+
+def _gibbon_dense(mu, var, A, Binv, fstar):
+    if mu.dim() != 1 or fstar.dim() != 1:
+        raise ValueError("gibbon: mu and fstar must be vectors")
+    m = 0 if A is None else A.shape[-1]
+    kernels.gibbon_check(fstar.shape[0], m, mu.shape[0])
+    if m and Binv is None:
+        raise ValueError("gibbon: A and Binv go together")
+    return (mu.contiguous(), var.contiguous(), A.contiguous() if m else None,
+            Binv.contiguous() if m else None, fstar.contiguous())
+
+
+@torch.library.custom_op("bo::gibbon", mutates_args=(), device_types="cuda")
+def gibbon(mu: Tensor, var: Tensor, A: Optional[Tensor], Binv: Optional[Tensor], fstar: Tensor,
+           tau2: float, w: float) -> Tensor:
+    """acq (R): GIBBON's value of R rows (kernels.gibbon); with A (R x m) and
+    Binv (m x m) the repulsion term of m pending points is added.
+    Differentiable in mu, var and A."""
+    return _lib.torch_ops().gibbon_native(*_gibbon_dense(mu, var, A, Binv, fstar), tau2, w)
+
+
+@gibbon.register_fake
+def _(mu, var, A, Binv, fstar, tau2, w):
+    return mu.new_empty((mu.shape[0],), dtype=F64)
+
+
+@torch.library.custom_op("bo::gibbon_backward", mutates_args=(), device_types="cuda")
+def gibbon_backward(dout: Tensor, mu: Tensor, var: Tensor, A: Optional[Tensor],
+                    Binv: Optional[Tensor], fstar: Tensor, tau2: float,
+                    w: float) -> Tuple[Tensor, Tensor, Tensor]:
+    """(dmu, dvar, dA); dA is R x m (R x 0 without pending points)."""
+    dmu, dvar, dA = _lib.torch_ops().gibbon_backward_native(
+        dout.contiguous(), *_gibbon_dense(mu, var, A, Binv, fstar), tau2, w)
+    return dmu, dvar, dA
+
+
+@gibbon_backward.register_fake
+def _(dout, mu, var, A, Binv, fstar, tau2, w):
+    R = mu.shape[0]
+    return (mu.new_empty((R,), dtype=F64), mu.new_empty((R,), dtype=F64),
+            mu.new_empty((R, 0 if A is None else A.shape[-1]), dtype=F64))
+
+
+def _gibbon_setup(ctx, inputs, output):
+    ctx.present = [t is not None for t in inputs[:5]]  # (A and Binv may be None)
+    ctx.save_for_backward(*[t for t in inputs[:5] if t is not None])
+    ctx.consts = inputs[5:]
+
+
+def _gibbon_bwd(ctx, dout):
+    dmu = dvar = dA = None
+    if any(ctx.needs_input_grad[:3]):
+        saved = iter(ctx.saved_tensors)
+        tensors = [next(saved) if p else None for p in ctx.present]
+        dmu, dvar, dA = torch.ops.bo.gibbon_backward(dout.contiguous(), *tensors, *ctx.consts)
+        if tensors[2] is None:
+            dA = None
+    return (dmu, dvar, dA) + (None,) * 4
+
+
+gibbon.register_autograd(_gibbon_bwd, setup_context=_gibbon_setup)
+
+
+@torch.library.custom_op("bo::mv_quantiles", mutates_args=(), device_types="cuda")
+def mv_quantiles(mu: Tensor, sigma: Tensor, have_bounds: bool, lo: float,
+                 hi: float) -> Tuple[Tensor, Tensor]:
+    """(y (3), status (3) int32): the y with sum_i log Phi((y - mu_i) / sigma_i)
+    = log p for p = 0.25, 0.5, 0.75 by one on-device bisection launch
+    (kernels.mv_quantiles); a non-zero status word means the end points did not
+    bracket (kernels.mv_quantiles_raise turns it into brentq's ValueError)."""
+    if mu.dim() != 1 or mu.shape[0] < 1 or tuple(sigma.shape) != tuple(mu.shape):
+        raise ValueError("mv_quantiles: mu and sigma must have N >= 1 entries each")
+    y, status = _lib.torch_ops().mv_quantiles_native(mu.contiguous(), sigma.contiguous(),
+                                                     have_bounds, lo, hi)
+    return y, status
+
+
+@mv_quantiles.register_fake
+def _(mu, sigma, have_bounds, lo, hi):
+    return mu.new_empty((3,), dtype=F64), mu.new_empty((3,), dtype=torch.int32)
+
+
 OPS: List[str] = ["sobol_normal", "gp_cache", "gp_cache_extend", "chol_jitter", "chol_backward",
                   "post_partials", "qmc_finalize", "gp_posterior", "gp_posterior_backward",
                   "qmc_acq", "qmc_acq_backward", "qehvi", "qehvi_backward", "mll", "kg",
-                  "kg_backward", "paths_eval", "paths_eval_backward", "jes", "jes_backward"]
+                  "kg_backward", "paths_eval", "paths_eval_backward", "jes", "jes_backward", "mes",
+                  "mes_backward", "gibbon", "gibbon_backward", "mv_quantiles"]

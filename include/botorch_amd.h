@@ -1105,6 +1105,88 @@ typedef struct BoJesArgs {
 int bo_jes_v(const BoJesArgs* a, void* stream);
 int bo_jes_backward_v(const BoJesArgs* a, void* stream);
 
+/* Max-value entropy search (botorch/acquisition/max_value_entropy_search.py),
+ * one t-batch of q = 1 per row, everything in outcome space.  mu, var: the
+ * noiseless posterior mean and variance of each row (R); tau2 the observation
+ * noise a noisy posterior adds; w = +1 (maximize) or -1; fstar (S_M) the
+ * max-value samples in the w-signed space; CLAMP_LB = 1e-8;
+ * Phi(x) = erfc(-x / sqrt 2) / 2.
+ *
+ * qMaxValueEntropy (lines 399-515 without fantasies or trace observations),
+ * with z (S_m) the base samples shared by all rows:
+ *   m = w mu   vM = max(var, 1e-8)   vm = var + tau2   t = vM / vm
+ *   mean_new_k = m + t sqrt(vm) w z_k       s2n = max(vM - vM^2 / vm, 1e-8)
+ *   Phin_jk = max(Phi((fstar_j - mean_new_k) / sqrt s2n), 1e-8)
+ *   Phi0_j  = max(Phi((fstar_j - m) / sqrt vM), 1e-8)     Z_jk = Phin_jk / Phi0_j
+ *   lp_k = -z_k^2 / 2 - log(2 pi vm) / 2    h1_jk = -Z_jk log Z_jk - Z_jk lp_k
+ *   h0_k = -lp_k     H1bar = mean_jk h1     cov = mean_jk (h1 - H1bar)(h0_k - mean h0)
+ *   beta = cov / sqrt(var_k(h0) var_jk(h1))   (both variances unbiased)
+ *   out = H0 - H1bar + beta (mean_k h0 - H0),   H0 = log(2 pi e vm) / 2
+ * The row-independent constants come from the host: kappa = mean_k h0 - H0 =
+ * (mean z^2 - 1) / 2, var_h0 = var_k(z^2 / 2) and zsq_mean = mean z^2
+ * (h0_k - mean h0 = (z_k^2 - zsq_mean) / 2).
+ * Backward, from dout (R): dmu, dvar (R each), analytic; the clamps pass
+ * gradient as torch.clamp_min does.  Every entry is written.
+ * 1 <= S_M <= 1024, 2 <= S_m <= 4096, 1 <= R < 2^31.  One wave per row, the
+ * pairs spread over its lanes; sums folded in a fixed order by lane exchanges:
+ * no atomics, no workspace, no R x S_M x S_m array; repeated calls are bitwise
+ * identical.  A pure addition to the ABI: BO_ABI_VERSION stays 11. */
+typedef struct BoMesArgs {
+  BO_STRUCT_HEADER;
+  int32_t S_M, S_m;
+  int64_t R;
+  const double *mu, *var, *fstar, *z;
+  double kappa, var_h0, zsq_mean, tau2, w;
+  double* out;             /* forward */
+  const double* dout;      /* backward */
+  double *dmu, *dvar;      /* backward */
+} BoMesArgs;
+int bo_mes_v(const BoMesArgs* a, void* stream);
+int bo_mes_backward_v(const BoMesArgs* a, void* stream);
+
+/* qLowerBoundMaxValueEntropy, GIBBON (lines 537-664):
+ *   vM = max(var, 1e-8)   vm = max(var + tau2, 1e-8)   rho2 = vM / vm
+ *   gamma_j = (fstar_j - w mu) / sqrt vM    r_j = phi(gamma_j) / max(Phi(gamma_j), 1e-8)
+ *   out = -mean_j log max(1 - rho2 r_j (gamma_j + r_j), 1e-8) / 2
+ * and with m > 0 pending points, A (R x m) the noiseless posterior covariance of
+ * each row with them and Binv (m x m) the inverse of their noisy covariance:
+ *   qf = A Binv A^T    out += (log(max(vm, qf (1 + 1e-12)) - qf) - log vm) / 2
+ * (on the clamped branch the gradient runs through qf, as torch.clamp with a
+ * tensor bound does).  Backward, from dout (R): dmu, dvar (R) and dA (R x m),
+ * every entry written; Binv is read as (Binv + Binv^T) / 2.
+ * S_M >= 1, 0 <= m <= 15 (A, Binv, dA may be null at m = 0), 1 <= R < 2^34. */
+typedef struct BoGibbonArgs {
+  BO_STRUCT_HEADER;
+  int32_t S_M, m;
+  int64_t R;
+  const double *mu, *var, *A, *Binv, *fstar;
+  double tau2, w;
+  double* out;                 /* forward */
+  const double* dout;          /* backward */
+  double *dmu, *dvar, *dA;     /* backward */
+} BoGibbonArgs;
+int bo_gibbon_v(const BoGibbonArgs* a, void* stream);
+int bo_gibbon_backward_v(const BoGibbonArgs* a, void* stream);
+
+/* The quantiles the Gumbel sampler of the max values fits (lines 983-1010):
+ * out[q], q < 3, is the y with sum_i log Phi((y - mu_i) / sigma_i) = log p_q,
+ * p = 0.25, 0.5, 0.75, for the N candidates' w-signed means and standard
+ * deviations (sigma > 0).  One launch: a bisection on [min(mu - 3 sigma),
+ * max(mu + 5 sigma)] (or on [lo, hi] when have_bounds is set) down to an
+ * interval of four ulp, one workgroup per quantile.  status[q] (device int32) is
+ * non-zero when the end points do not bracket the root; out[q] is then the
+ * midpoint.  log Phi is evaluated tail-safe; a sum of -inf counts as below p. */
+typedef struct BoMvQuantilesArgs {
+  BO_STRUCT_HEADER;
+  int32_t have_bounds, _pad;
+  int64_t N;
+  const double *mu, *sigma;
+  double lo, hi;
+  double* out;
+  int32_t* status;
+} BoMvQuantilesArgs;
+int bo_mv_quantiles_v(const BoMvQuantilesArgs* a, void* stream);
+
 typedef struct BoLbfgsStepArgs { /* bo_lbfgs_step */
   BO_STRUCT_HEADER;
   int32_t B, n, m, _pad;
