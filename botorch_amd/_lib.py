@@ -304,6 +304,13 @@ class MvQuantilesArgs(_Args):
                        ("status", _D)]
 
 
+class NipvArgs(_Args):
+    _fields_ = _HDR + [("kind", c_int32), ("d", c_int32), ("q", c_int32), ("split", c_int32),
+                       ("R", c_int64), ("n", c_int64), ("N", c_int64), ("X", _D),
+                       ("lengthscale", _D), ("Xt_scaled", _D), ("Z_scaled", _D), ("V", _D),
+                       ("outputscale", c_double), ("G", _D), ("dG", _D), ("dX", _D)]
+
+
 class LbfgsStepArgs(_Args):
     _fields_ = _HDR + [("B", c_int32), ("n", c_int32), ("m", c_int32), ("_pad", c_int32),
                        ("x", _D), ("f", _D), ("g", _D), ("xt", _D), ("ft", _D), ("gt", _D),
@@ -333,6 +340,7 @@ for _name, _cls in (("bo_post_partials_v", PostPartialsArgs), ("bo_qmc_finalize_
                     ("bo_mes_v", MesArgs), ("bo_mes_backward_v", MesArgs),
                     ("bo_gibbon_v", GibbonArgs), ("bo_gibbon_backward_v", GibbonArgs),
                     ("bo_mv_quantiles_v", MvQuantilesArgs),
+                    ("bo_nipv_gram_v", NipvArgs), ("bo_nipv_gram_backward_v", NipvArgs),
                     ("bo_lbfgs_step_v", LbfgsStepArgs), ("bo_lbfgsb_step_v", LbfgsbArgs)):
     _SIGNATURES[_name] = (c_int, [POINTER(_cls), _P])
 _SIGNATURES["bo_struct_size"] = (c_int64, [ctypes.c_char_p])
@@ -343,6 +351,7 @@ ARG_RECORDS = {"BoPostPartialsArgs": PostPartialsArgs, "BoQmcFinalizeArgs": QmcF
                "BoQlogehviArgs": QlogehviArgs, "BoQmcFeasArgs": QmcFeasArgs, "BoKgArgs": KgArgs,
                "BoPathsArgs": PathsArgs, "BoJesArgs": JesArgs, "BoMesArgs": MesArgs,
                "BoGibbonArgs": GibbonArgs, "BoMvQuantilesArgs": MvQuantilesArgs,
+               "BoNipvArgs": NipvArgs,
                "BoLbfgsStepArgs": LbfgsStepArgs, "BoLbfgsbArgs": LbfgsbArgs}
 
 _lib = None

@@ -1230,6 +1230,211 @@ class qLowerBoundMaxValueEntropy(DiscreteMaxValueBase):
         return _gibbon_chain(mu, var, self._fstar(), self._tau2, self.weight, A, self._Binv)
 
 
+# -- active learning: integrated posterior variance ---------------------------------------
+NIPV_GENERIC_TRANSIENT = 1 << 24  # doubles of one array of a chunk of the generic route
+
+
+def _nipv_value(Sigma, G, tau2: float, vbar: float, N: int, chol=None):
+    """-(vbar - tr((Sigma + tau2 I)^{-1} G) / N) (...), from Sigma and G
+    (... x q x q): the integrated posterior variance after observing the q
+    points with noise tau2, negated (transformed outcome space).  ``chol``
+    factors Sigma + tau2 I (default torch.linalg.cholesky); the trace is taken
+    through two triangular solves, tr(L^{-1} G L^{-T})."""
+    q = Sigma.shape[-1]
+    M = Sigma + tau2 * torch.eye(q, dtype=Sigma.dtype, device=Sigma.device)
+    L = torch.linalg.cholesky(M) if chol is None else chol(M)
+    W = torch.linalg.solve_triangular(L, G, upper=False)
+    W = torch.linalg.solve_triangular(L, W.mT, upper=False)
+    return W.diagonal(dim1=-2, dim2=-1).sum(dim=-1) / N - vbar
+
+
+class _NipvMember:
+    """What qNegIntegratedPosteriorVariance keeps of one single-output member."""
+    __slots__ = ("model", "Z_scaled", "Xt_scaled", "V", "vbar", "tau2", "hyper", "ystd", "w2")
+
+
+class qNegIntegratedPosteriorVariance(AcquisitionFunction):
+    """Negative integrated posterior variance (acquisition/active_learning.py:
+    40-126) for exact GPs:
+
+        acq(X) = -mean_z var(z | data, observations at X with noise tau2)
+
+    over the N integration points ``mc_points`` (N x d).  The reference builds
+    ``model.fantasize(X)`` per t-batch and evaluates its posterior at the
+    integration points.  No fantasy model is built here: observing q points is
+    a rank-q correction of the current posterior,
+
+        acq(X) = -ystd^2 (vbar - tr((Sigma(X, X) + tau2 I)^{-1} G(X)) / N),
+        G(X) = C C^T,  C = [cov(f(x_i), f(z) | data)]  (q x N),
+
+    with vbar the current mean variance over the integration points (fixed at
+    construction), tau2 the noise level (the mean of the fixed variances for a
+    fixed-noise likelihood, as ``Model.fantasize`` passes it), everything in the
+    model's transformed outcome space.  The fused route (X on the device, d <=
+    kernels.NIPV_DMAX, q with pending points <= kernels.NIPV_QMAX) forms C on
+    the matrix cores and contracts it to G without storing it (``bo::nipv_gram``);
+    the generic route takes C from the joint posterior of X and chunks of the
+    integration points and applies the same formula in torch.
+
+    ``sampler`` is accepted and kept for the reference's signature; it is not
+    used, because the posterior variance of an exact GP does not depend on the
+    fantasised values.  A multi-output ``SingleTaskGP`` or a ``ModelListGP`` of
+    single-output ``SingleTaskGP``s needs a ``ScalarizedPosteriorTransform``:
+    the outputs are independent, so acq = sum_t w_t^2 acq_t (the offset drops
+    out)."""
+
+    def __init__(self, model, mc_points: torch.Tensor, sampler=None, posterior_transform=None,
+                 X_pending=None):
+        from .models import ModelListGP, SaasFullyBayesianSingleTaskGP, SingleTaskGP
+        from .objective import ScalarizedPosteriorTransform
+        super().__init__(model)
+        if isinstance(model, SaasFullyBayesianSingleTaskGP):
+            raise UnsupportedError("qNegIntegratedPosteriorVariance: SaasFullyBayesianSingleTaskGP "
+                                   "is not supported (SingleTaskGP, or a ModelListGP of "
+                                   "single-output SingleTaskGPs, is)")
+        if isinstance(model, ModelListGP) or (isinstance(model, SingleTaskGP)
+                                              and model.num_outputs > 1):
+            members = list(model.models)
+        elif isinstance(model, SingleTaskGP):
+            members = [model]
+        else:
+            raise UnsupportedError(f"qNegIntegratedPosteriorVariance: {type(model).__name__} is not "
+                                   "supported (SingleTaskGP, or a ModelListGP of single-output "
+                                   "SingleTaskGPs, is)")
+        for mm in members:
+            if not isinstance(mm, SingleTaskGP) or isinstance(mm, SaasFullyBayesianSingleTaskGP) \
+                    or mm.num_outputs != 1:
+                raise UnsupportedError("qNegIntegratedPosteriorVariance: every member of a "
+                                       "ModelListGP must be a single-output SingleTaskGP")
+        if posterior_transform is None:
+            if len(members) > 1:
+                raise UnsupportedError("Must specify a posterior transform when using a "
+                                       "multi-output model (a ScalarizedPosteriorTransform is "
+                                       "supported).")
+            weights = [1.0]
+        elif isinstance(posterior_transform, ScalarizedPosteriorTransform):
+            weights = [float(w) for w in posterior_transform.weights.detach().reshape(-1).tolist()]
+            if len(weights) != len(members):
+                raise ValueError(f"qNegIntegratedPosteriorVariance: {len(weights)} weights for a "
+                                 f"model with {len(members)} outputs")
+        else:
+            raise UnsupportedError("qNegIntegratedPosteriorVariance: only a "
+                                   "ScalarizedPosteriorTransform is supported as "
+                                   "`posterior_transform`")
+        if model.training or any(mm.training for mm in members):
+            raise UnsupportedError("qNegIntegratedPosteriorVariance needs a model in eval mode "
+                                   "(model.eval()): the integration points are conditioned on the "
+                                   "trained model's prediction caches")
+        d = members[0].train_inputs[0].shape[-1]
+        if mc_points.dim() != 2 or mc_points.shape[-1] != d or mc_points.shape[0] < 1:
+            raise UnsupportedError("qNegIntegratedPosteriorVariance: mc_points must be `N x "
+                                   f"{d}` without batch dimensions, got {tuple(mc_points.shape)}")
+        self.posterior_transform = posterior_transform
+        self.sampler = sampler  # unused: the variance does not depend on the fantasies
+        self.register_buffer("mc_points", mc_points)
+        self._route = None  # None: by size; "fused" / "generic": forced (tests, tools)
+        self._members = [self._condition(mm, mc_points, w) for mm, w in zip(members, weights)]
+        self.set_X_pending(X_pending)
+
+    @staticmethod
+    def _condition(model, mc_points, w: float) -> _NipvMember:
+        """One member's constants, once: the scaled integration points, V =
+        A^{-1} o k(Xt, Z) against the cached L^{-1}, the current mean variance
+        over Z, the noise level, the hyperparameters and the outcome scale."""
+        from .posteriors import posterior_moments
+        m = _NipvMember()
+        with torch.no_grad():
+            cache = model.prediction_cache()
+            _, ystd = model.outcome_stats()
+            n, dev = cache.n, cache.Xt.device
+            Z = mc_points.detach().to(device=dev, dtype=torch.float64).contiguous()
+            N, d = Z.shape
+            _, cov = posterior_moments(model, Z.unsqueeze(-2))
+            m.model = model
+            m.vbar = float(cov.reshape(-1).mean()) / (ystd * ystd)
+            m.tau2 = float(cache.noise)  # the level, or the mean of the fixed variances
+            m.Z_scaled = (Z / cache.lengthscale).contiguous()
+            m.Xt_scaled = (cache.Xt / cache.lengthscale).contiguous() if n else None
+            m.V = None
+            if n and d <= kernels.NIPV_DMAX:
+                K = kernels.covar_matrix(Z, cache.Xt, cache.lengthscale, cache.kind,
+                                         cache.outputscale)
+                E = K.t().contiguous()  # n x N
+                ld = cache.Linv.shape[1]
+                T = torch.empty(n, N, dtype=torch.float64, device=dev)
+                Vt = torch.empty(n, N, dtype=torch.float64, device=dev)
+                # the leading n x n block of the (padded) L^{-1}, read in place
+                kernels.gemm_strided(n, N, n, cache.Linv, ld, 0, E, N, 0, T, N, 0, 1)
+                kernels.gemm_strided(n, N, n, cache.Linv, ld, 0, T, N, 0, Vt, N, 0, 1, transA=True)
+                m.V = Vt.t().contiguous()
+            m.hyper = (cache.lengthscale, int(cache.kind), float(cache.outputscale))
+            m.ystd = float(ystd)
+            m.w2 = float(w) * float(w)
+        return m
+
+    @staticmethod
+    def _chol(M: torch.Tensor) -> torch.Tensor:
+        from .posteriors import _CholJitter
+        return _CholJitter.apply(M) if torch.is_grad_enabled() and M.requires_grad \
+            else kernels.chol_jitter(M)
+
+    def _fused(self, X3: torch.Tensor) -> torch.Tensor:
+        from . import ops  # noqa: F401  (torch.ops.bo registration)
+        from .posteriors import posterior_moments
+        B, q, d = X3.shape
+        N = self.mc_points.shape[0]
+        X2 = X3.reshape(B * q, d)
+        acq = None
+        for m in self._members:
+            _, cov = posterior_moments(m.model, X3)
+            ls, kind, o = m.hyper
+            G = torch.ops.bo.nipv_gram(X2, q, ls, m.Xt_scaled if m.V is not None else None,
+                                       m.Z_scaled, m.V, kind, o, 0)
+            a = _nipv_value(cov / (m.ystd * m.ystd), G, m.tau2, m.vbar, N, self._chol)
+            a = (m.w2 * m.ystd * m.ystd) * a
+            acq = a if acq is None else acq + a
+        return acq
+
+    def _generic(self, X3: torch.Tensor) -> torch.Tensor:
+        from .posteriors import posterior_moments
+        B, q, d = X3.shape
+        Z = self.mc_points.to(device=X3.device, dtype=torch.float64)
+        N = Z.shape[0]
+        acq = None
+        for m in self._members:
+            s2 = m.ystd * m.ystd
+            # chunks of the integration points: the B (q + nc) x n kernel rows and the
+            # B x (q + nc)^2 covariance of one chunk stay within the transient bound
+            n = m.model.train_inputs[0].shape[0]
+            nc = max(16, min(NIPV_GENERIC_TRANSIENT // (B * max(n, 1)),
+                             int(math.sqrt(NIPV_GENERIC_TRANSIENT / B))) - q)
+            Sigma, G = None, 0.0
+            for z0 in range(0, N, nc):
+                Zc = Z[z0:z0 + nc]
+                _, cov = posterior_moments(m.model,
+                                           torch.cat([X3, Zc.expand(B, *Zc.shape)], dim=-2))
+                if Sigma is None:
+                    Sigma = cov[:, :q, :q] / s2
+                C = cov[:, :q, q:] / s2
+                G = G + C @ C.mT
+            a = (m.w2 * s2) * _nipv_value(Sigma, G, m.tau2, m.vbar, N, self._chol)
+            acq = a if acq is None else acq + a
+        return acq
+
+    def forward(self, X: torch.Tensor) -> torch.Tensor:
+        X = t_batch_mode(X)
+        if X.dtype != torch.float64:  # the model computes in fp64; the value returns in X's dtype
+            return self.forward(X.to(torch.float64)).to(X.dtype)
+        batch = X.shape[:-2]
+        X = self._concat_pending(X)
+        q, d = X.shape[-2], X.shape[-1]
+        X3 = X.reshape(-1, q, d)
+        fused = (X.is_cuda and d <= kernels.NIPV_DMAX and q <= kernels.NIPV_QMAX) \
+            if self._route is None else self._route == "fused"
+        acq = self._fused(X3) if fused else self._generic(X3)
+        return acq.reshape(batch)
+
+
 # -- qNEI -------------------------------------------------------------------------------
 def prune_inferior_points(model, X, objective=None, posterior_transform=None, constraints=None,
                           num_samples: int = 2048, max_frac: float = 1.0, sampler=None,

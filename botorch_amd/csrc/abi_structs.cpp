@@ -89,6 +89,10 @@ int bo_gibbon_impl(const BoGibbonArgs* a, void* stream);
 int bo_gibbon_backward_impl(const BoGibbonArgs* a, void* stream);
 int bo_mv_quantiles_impl(const BoMvQuantilesArgs* a, void* stream);
 
+// the integrated-posterior-variance Gram matrices (nipv.hip)
+int bo_nipv_gram_impl(const BoNipvArgs* a, void* stream);
+int bo_nipv_gram_backward_impl(const BoNipvArgs* a, void* stream);
+
 int bo_post_partials_v(const BoPostPartialsArgs* a, void* stream) {
   if (!header_ok(a, "bo_post_partials_v")) return BO_ERR_ARG;
   return bo_post_partials_layout(a->kind, a->Xq, a->B, a->q, a->d, a->Xt_scaled, a->n, a->U,
@@ -220,6 +224,16 @@ int bo_mv_quantiles_v(const BoMvQuantilesArgs* a, void* stream) {
   return bo_mv_quantiles_impl(a, stream);
 }
 
+int bo_nipv_gram_v(const BoNipvArgs* a, void* stream) {
+  if (!header_ok(a, "bo_nipv_gram_v")) return BO_ERR_ARG;
+  return bo_nipv_gram_impl(a, stream);
+}
+
+int bo_nipv_gram_backward_v(const BoNipvArgs* a, void* stream) {
+  if (!header_ok(a, "bo_nipv_gram_backward_v")) return BO_ERR_ARG;
+  return bo_nipv_gram_backward_impl(a, stream);
+}
+
 int bo_lbfgs_step_v(const BoLbfgsStepArgs* a, void* stream) {
   if (!header_ok(a, "bo_lbfgs_step_v")) return BO_ERR_ARG;
   return bo_lbfgs_step(a->B, a->n, a->m, a->x, a->f, a->g, a->xt, a->ft, a->gt, a->d, a->alpha,
@@ -253,6 +267,7 @@ extern "C" int64_t bo_struct_size(const char* name) {
   if (s == "BoMesArgs") return sizeof(BoMesArgs);
   if (s == "BoGibbonArgs") return sizeof(BoGibbonArgs);
   if (s == "BoMvQuantilesArgs") return sizeof(BoMvQuantilesArgs);
+  if (s == "BoNipvArgs") return sizeof(BoNipvArgs);
   if (s == "BoLbfgsStepArgs") return sizeof(BoLbfgsStepArgs);
   if (s == "BoLbfgsbArgs") return sizeof(BoLbfgsbArgs);
   return -1;

@@ -2427,6 +2427,95 @@ def mv_quantiles(mu: torch.Tensor, sigma: torch.Tensor, bounds=None) -> torch.Te
     return out
 
 
+NIPV_DMAX = 128  # bo_nipv_gram: d is a runtime loop up to here
+NIPV_QMAX = 16   # t-batches are packed into 16-row tiles
+NIPV_MAX_SPLIT = 1024
+
+
+def nipv_check(d: int, q: int, N: int, R: int = None, split: int = 0) -> None:
+    """The argument limits of :func:`nipv_gram`, raised on the host before any
+    native call (acquisition.qNegIntegratedPosteriorVariance checks its sizes
+    with it).  R defaults to q (one t-batch)."""
+    if not 1 <= d <= NIPV_DMAX:
+        raise ValueError(f"nipv_gram: 1 <= d <= {NIPV_DMAX} (got {d})")
+    if not 1 <= q <= NIPV_QMAX:
+        raise ValueError(f"nipv_gram: 1 <= q <= {NIPV_QMAX} (got {q})")
+    if N < 1:
+        raise ValueError(f"nipv_gram: N >= 1 (got {N})")
+    R = q if R is None else R
+    if R < 1 or R % q:
+        raise ValueError(f"nipv_gram: R >= 1 and q must divide R (got R = {R}, q = {q})")
+    if not 0 <= split <= NIPV_MAX_SPLIT:
+        raise ValueError(f"nipv_gram: 0 <= split <= {NIPV_MAX_SPLIT} (got {split})")
+
+
+def _nipv_args(X, q, lengthscale, Xt_scaled, Z_scaled, V, kind, outputscale, split):
+    """The BoNipvArgs of :func:`nipv_gram` / :func:`nipv_gram_backward`: X R x d,
+    Z_scaled N x d, and Xt_scaled n x d with V N x n (both None: n = 0)."""
+    if X.dim() != 2:
+        raise ValueError(f"nipv_gram: X must be R x d, got {tuple(X.shape)}")
+    R, d = X.shape
+    if Z_scaled.dim() != 2:
+        raise ValueError(f"nipv_gram: Z_scaled must be N x d, got {tuple(Z_scaled.shape)}")
+    N = Z_scaled.shape[0]
+    nipv_check(d, int(q), N, R, int(split))
+    if Z_scaled.shape[1] != d or tuple(lengthscale.shape) != (d,):
+        raise ValueError(f"nipv_gram: Z_scaled must be N x {d} and lengthscale have {d} entries, "
+                         f"got {tuple(Z_scaled.shape)} and {tuple(lengthscale.shape)}")
+    if (V is None) != (Xt_scaled is None):
+        raise ValueError("nipv_gram: Xt_scaled and V go together")
+    n = 0
+    if V is not None:
+        n = V.shape[-1]
+        if V.dim() != 2 or V.shape[0] != N or tuple(Xt_scaled.shape) != (n, d):
+            raise ValueError(f"nipv_gram: V must be {N} x n and Xt_scaled n x {d}, got "
+                             f"{tuple(V.shape)} and {tuple(Xt_scaled.shape)}")
+    for t in (X, lengthscale, Z_scaled, V, Xt_scaled):
+        if t is not None and t.dtype != torch.float64:
+            raise ValueError("nipv_gram: every tensor must be fp64")
+    return _lib.NipvArgs(kind=int(kind), d=d, q=int(q), split=int(split), R=R, n=n, N=N,
+                         X=X.contiguous(), lengthscale=lengthscale.contiguous(),
+                         Xt_scaled=Xt_scaled.contiguous() if n else None,
+                         Z_scaled=Z_scaled.contiguous(), V=V.contiguous() if n else None,
+                         outputscale=float(outputscale))
+
+
+def nipv_gram(X: torch.Tensor, q: int, lengthscale: torch.Tensor,
+              Xt_scaled: Optional[torch.Tensor], Z_scaled: torch.Tensor,
+              V: Optional[torch.Tensor], kind: int = _lib.RBF, outputscale: float = 1.0,
+              split: int = 0) -> torch.Tensor:
+    """G (B x q x q), B = R / q: G[b] = C_b C_b^T with C_b the posterior
+    cross-covariance of the q rows of t-batch b with the N integration points,
+    c(x_i, z) = o (k(x_i, z) - sum_t k(x_i, Xt_t) V[z, t]) (bo_nipv_gram, the
+    record's comment in include/botorch_amd.h).  C is formed and contracted on
+    the matrix cores and never stored.  ``split``: slices of Z taken by separate
+    workgroups (0: by size); their partial Grams are summed in slice order."""
+    a = _nipv_args(X, q, lengthscale, Xt_scaled, Z_scaled, V, kind, outputscale, split)
+    dev = _dev(X, lengthscale, Xt_scaled, Z_scaled, V)
+    G = torch.empty(a.R // a.q, a.q, a.q, dtype=torch.float64, device=dev)
+    a.G = G.data_ptr()
+    check(lib().bo_nipv_gram_v(ctypes.byref(a), _stream(dev)), "nipv_gram")
+    return G
+
+
+def nipv_gram_backward(dG: torch.Tensor, X: torch.Tensor, q: int, lengthscale: torch.Tensor,
+                       Xt_scaled: Optional[torch.Tensor], Z_scaled: torch.Tensor,
+                       V: Optional[torch.Tensor], kind: int = _lib.RBF, outputscale: float = 1.0,
+                       split: int = 0) -> torch.Tensor:
+    """dX (R x d) of :func:`nipv_gram` from dG (B x q x q, arbitrary: it need
+    not be symmetric).  Every entry is written, nothing to clear."""
+    a = _nipv_args(X, q, lengthscale, Xt_scaled, Z_scaled, V, kind, outputscale, split)
+    if tuple(dG.shape) != (a.R // a.q, a.q, a.q) or dG.dtype != torch.float64:
+        raise ValueError(f"nipv_gram_backward: dG must be fp64 of shape "
+                         f"({a.R // a.q}, {a.q}, {a.q}), got {tuple(dG.shape)}")
+    dev = _dev(dG, X, lengthscale, Xt_scaled, Z_scaled, V)
+    dG = dG.contiguous()
+    dX = torch.empty(a.R, a.d, dtype=torch.float64, device=dev)
+    a.dG, a.dX = dG.data_ptr(), dX.data_ptr()
+    check(lib().bo_nipv_gram_backward_v(ctypes.byref(a), _stream(dev)), "nipv_gram_backward")
+    return dX
+
+
 def kernel_grad(X: torch.Tensor, Y: torch.Tensor, dK: torch.Tensor, lengthscale: torch.Tensor,
                 kind: int, outputscale: float = 1.0, group: int = 0,
                 dX: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -41,6 +41,9 @@ Ops (reference computation each replaces):
                       var, A; max_value_entropy_search.py:537-664)
   bo::mv_quantiles    the three quantiles the Gumbel max-value sampler fits, one launch
                       (max_value_entropy_search.py:994-1010, in place of brentq on host copies)
+  bo::nipv_gram       Gram matrices C_b C_b^T of the posterior cross-covariance of every
+                      t-batch with N integration points, C never stored (+ autograd in
+                      X; acquisition/active_learning.py:40-135)
 """
 from __future__ import annotations
 
@@ -840,8 +843,58 @@ def _(mu, sigma, have_bounds, lo, hi):
     return mu.new_empty((3,), dtype=F64), mu.new_empty((3,), dtype=torch.int32)
 
 
+# ---- bo::nipv_gram (integrated posterior variance: cross-covariance Gram matrices) ---------------
+@torch.library.custom_op("bo::nipv_gram", mutates_args=(), device_types="cuda")
+def nipv_gram(X: Tensor, q: int, lengthscale: Tensor, Xt_scaled: Optional[Tensor],
+              Z_scaled: Tensor, V: Optional[Tensor], kind: int, outputscale: float,
+              split: int) -> Tensor:
+    """G (B x q x q): C_b C_b^T of the t-batches of q rows of X (R x d, R = B q)
+    with c(x_i, z) the posterior covariance of x_i and integration point z
+    (kernels.nipv_gram).  Differentiable in X only: Z_scaled and V are buffers of
+    the construction."""
+    return kernels.nipv_gram(X, q, lengthscale, Xt_scaled, Z_scaled, V, kind, outputscale, split)
+
+
+@nipv_gram.register_fake
+def _(X, q, lengthscale, Xt_scaled, Z_scaled, V, kind, outputscale, split):
+    return X.new_empty((X.shape[0] // q, q, q), dtype=F64)
+
+
+@torch.library.custom_op("bo::nipv_gram_backward", mutates_args=(), device_types="cuda")
+def nipv_gram_backward(dG: Tensor, X: Tensor, q: int, lengthscale: Tensor,
+                       Xt_scaled: Optional[Tensor], Z_scaled: Tensor, V: Optional[Tensor],
+                       kind: int, outputscale: float, split: int) -> Tensor:
+    return kernels.nipv_gram_backward(dG, X, q, lengthscale, Xt_scaled, Z_scaled, V, kind,
+                                      outputscale, split)
+
+
+@nipv_gram_backward.register_fake
+def _(dG, X, q, lengthscale, Xt_scaled, Z_scaled, V, kind, outputscale, split):
+    return X.new_empty(X.shape, dtype=F64)
+
+
+def _nipv_setup(ctx, inputs, output):
+    X, q, lengthscale, Xt_scaled, Z_scaled, V, kind, outputscale, split = inputs
+    ctx.save_for_backward(X, lengthscale, Xt_scaled, Z_scaled, V)
+    ctx.consts = (q, kind, outputscale, split)
+
+
+def _nipv_bwd(ctx, dG):
+    X, lengthscale, Xt_scaled, Z_scaled, V = ctx.saved_tensors
+    q, kind, outputscale, split = ctx.consts
+    dX = None
+    if ctx.needs_input_grad[0]:
+        dX = torch.ops.bo.nipv_gram_backward(dG.contiguous(), X, q, lengthscale, Xt_scaled,
+                                             Z_scaled, V, kind, outputscale, split)
+    return (dX,) + (None,) * 8
+
+
+nipv_gram.register_autograd(_nipv_bwd, setup_context=_nipv_setup)
+
+
 OPS: List[str] = ["sobol_normal", "gp_cache", "gp_cache_extend", "chol_jitter", "chol_backward",
                   "post_partials", "qmc_finalize", "gp_posterior", "gp_posterior_backward",
                   "qmc_acq", "qmc_acq_backward", "qehvi", "qehvi_backward", "mll", "kg",
                   "kg_backward", "paths_eval", "paths_eval_backward", "jes", "jes_backward", "mes",
-                  "mes_backward", "gibbon", "gibbon_backward", "mv_quantiles"]
+                  "mes_backward", "gibbon", "gibbon_backward", "mv_quantiles", "nipv_gram",
+                  "nipv_gram_backward"]

@@ -1187,6 +1187,40 @@ typedef struct BoMvQuantilesArgs {
 } BoMvQuantilesArgs;
 int bo_mv_quantiles_v(const BoMvQuantilesArgs* a, void* stream);
 
+/* qNegIntegratedPosteriorVariance (botorch/acquisition/active_learning.py:
+ * 40-135): the Gram matrices of the posterior cross-covariance of every
+ * t-batch of q rows of X (R x d, original scale, R = B q) with N integration
+ * points, in one launch.  With k the kernel without its outputscale and
+ * V[z] = A^{-1} outputscale k(Xt, z) (N x n):
+ *   c(x_i, z) = outputscale (k(x_i, z) - sum_t k(x_i, Xt_t) V[z][t])
+ *   G[b]      = C_b C_b^T  (q x q),  C_b = [c(x_i, z)]  (q x N), rows of t-batch b
+ * The integrated posterior variance after observing X_b with noise tau2 is
+ * mean_z var(z) - tr((Sigma(X_b, X_b) + tau2 I)^{-1} G[b]) / N.
+ * Xt_scaled (n x d) and Z_scaled (N x d) are divided by the lengthscale (row
+ * length d, no padding); n = 0 switches the training term off (Xt_scaled, V may
+ * be null).  split: the number of slices of Z that separate workgroups take
+ * (0: chosen by size; at most 1024, and never more than one slice per 16
+ * points); their partial sums are added in slice order.
+ * Backward, from dG (B x q x q, arbitrary, need not be symmetric): dX (R x d);
+ * every entry is written, the caller clears nothing.
+ * 1 <= q <= 16, q | R, d <= 128 (a runtime loop), N >= 1, fp64 throughout.
+ * Neither C (R x N) nor the kernel rows (R x n) reach memory; with more than
+ * one slice a stream-ordered workspace of split x B q q (forward) or split x
+ * R d (backward) doubles is taken and returned.  No atomics (repeated calls
+ * are bitwise identical).  A pure addition to the ABI: BO_ABI_VERSION stays 11. */
+typedef struct BoNipvArgs {
+  BO_STRUCT_HEADER;
+  int32_t kind, d, q, split;
+  int64_t R, n, N;
+  const double *X, *lengthscale, *Xt_scaled, *Z_scaled, *V;
+  double outputscale;
+  double* G;          /* forward: (R / q) x q x q */
+  const double* dG;   /* backward */
+  double* dX;         /* backward: R x d */
+} BoNipvArgs;
+int bo_nipv_gram_v(const BoNipvArgs* a, void* stream);
+int bo_nipv_gram_backward_v(const BoNipvArgs* a, void* stream);
+
 typedef struct BoLbfgsStepArgs { /* bo_lbfgs_step */
   BO_STRUCT_HEADER;
   int32_t B, n, m, _pad;
