@@ -6,3 +6,17 @@ numerics run as hand-written gfx950 HIP kernels behind the C ABI in
 ``include/botorch_amd.h`` (``libbotorch_amd.so``, loaded by ``_lib.py``).
 """
 __version__ = "0.1.0"
+
+# names served from their submodules on first use (importing the package
+# itself loads no native library)
+_EXPORTS = {"FullyBayesianAcquisitionFunction": "acquisition",
+            "qBayesianActiveLearningByDisagreement": "acquisition",
+            "GaussianMixturePosterior": "posteriors"}
+__all__ = sorted(_EXPORTS)
+
+
+def __getattr__(name):
+    if name in _EXPORTS:
+        import importlib
+        return getattr(importlib.import_module(f"{__name__}.{_EXPORTS[name]}"), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -311,6 +311,13 @@ class NipvArgs(_Args):
                        ("outputscale", c_double), ("G", _D), ("dG", _D), ("dX", _D)]
 
 
+class BaldArgs(_Args):
+    _fields_ = _HDR + [("M", c_int32), ("q", c_int32), ("S", c_int32), ("_pad", c_int32),
+                       ("B", c_int64), ("mean", _D), ("L", _D), ("Z", _D), ("out", _D),
+                       ("dout", _D), ("dmean", _D), ("dL", _D), ("work", _D),
+                       ("work_size", c_int64)]
+
+
 class LbfgsStepArgs(_Args):
     _fields_ = _HDR + [("B", c_int32), ("n", c_int32), ("m", c_int32), ("_pad", c_int32),
                        ("x", _D), ("f", _D), ("g", _D), ("xt", _D), ("ft", _D), ("gt", _D),
@@ -341,6 +348,7 @@ for _name, _cls in (("bo_post_partials_v", PostPartialsArgs), ("bo_qmc_finalize_
                     ("bo_gibbon_v", GibbonArgs), ("bo_gibbon_backward_v", GibbonArgs),
                     ("bo_mv_quantiles_v", MvQuantilesArgs),
                     ("bo_nipv_gram_v", NipvArgs), ("bo_nipv_gram_backward_v", NipvArgs),
+                    ("bo_bald_v", BaldArgs), ("bo_bald_backward_v", BaldArgs),
                     ("bo_lbfgs_step_v", LbfgsStepArgs), ("bo_lbfgsb_step_v", LbfgsbArgs)):
     _SIGNATURES[_name] = (c_int, [POINTER(_cls), _P])
 _SIGNATURES["bo_struct_size"] = (c_int64, [ctypes.c_char_p])
@@ -351,7 +359,7 @@ ARG_RECORDS = {"BoPostPartialsArgs": PostPartialsArgs, "BoQmcFinalizeArgs": QmcF
                "BoQlogehviArgs": QlogehviArgs, "BoQmcFeasArgs": QmcFeasArgs, "BoKgArgs": KgArgs,
                "BoPathsArgs": PathsArgs, "BoJesArgs": JesArgs, "BoMesArgs": MesArgs,
                "BoGibbonArgs": GibbonArgs, "BoMvQuantilesArgs": MvQuantilesArgs,
-               "BoNipvArgs": NipvArgs,
+               "BoNipvArgs": NipvArgs, "BoBaldArgs": BaldArgs,
                "BoLbfgsStepArgs": LbfgsStepArgs, "BoLbfgsbArgs": LbfgsbArgs}
 
 _lib = None

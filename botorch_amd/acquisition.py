@@ -3157,6 +3157,170 @@ def dominated_hypervolume(Y: torch.Tensor, ref: torch.Tensor) -> torch.Tensor:
     return cells_hypervolume(Y, ref, lo, hi)
 
 
+# -- Bayesian active learning by disagreement (acquisition/bayesian_active_learning.py) ------
+class FullyBayesianAcquisitionFunction(AcquisitionFunction):
+    """bayesian_active_learning.py:34-49: the base of the acquisitions that need
+    an MCMC ensemble."""
+
+    def __init__(self, model):
+        if not getattr(model, "_is_fully_bayesian", False):
+            raise ValueError("Fully Bayesian acquisition functions require "
+                             "a SaasFullyBayesianSingleTaskGP to run.")
+        super().__init__(model)
+
+
+def _bald_value(mean: torch.Tensor, L: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """out (B x M) = H_b - C_bm of bayesian_active_learning.py:96-126 in torch,
+    on any device: mean (B x M x q) and L (B x M x q x q) the components of the
+    mixture posterior (observation noise included), y (S x B x M x q) their
+    samples.  The log-density of every sample under every component is the
+    S x B x M x M tensor the fused kernel never stores.  The mixture density is
+    taken as a log-sum-exp where the reference writes exp().mean().log(): the
+    same number wherever that is finite."""
+    M, q = mean.shape[-2], mean.shape[-1]
+    eye = torch.eye(q, dtype=L.dtype, device=L.device).expand_as(L)
+    Linv = torch.linalg.solve_triangular(L, eye, upper=False)
+    r = y.unsqueeze(-2) - mean.unsqueeze(-3)                    # S x B x M (drawn) x M (evaluated) x q
+    w = torch.einsum("bnij,sbmnj->sbmni", Linv, r)
+    half_log_det = L.diagonal(dim1=-2, dim2=-1).log().sum(-1)   # B x M
+    lp = (-0.5 * w.pow(2).sum(-1) - half_log_det.unsqueeze(-2)
+          - 0.5 * q * math.log(2.0 * math.pi))                  # S x B x M x M
+    H = -(torch.logsumexp(lp, dim=-1) - math.log(M)).mean(dim=(0, 2))
+    C = -lp.diagonal(dim1=-2, dim2=-1).mean(dim=0)
+    return H.unsqueeze(-1) - C
+
+
+class _FusedBALD(torch.autograd.Function):
+    """BALD over the MCMC ensemble of a SAAS model in batched launches: the
+    ensemble moments as in _SaasQEI.forward, the members' noise on the diagonal
+    (model space, before the outcome untransform), the jittered q x q roots
+    (bo_chol_small over M x B) and bo_bald; averaged over M.  Backward:
+    bo_bald_backward -> d mu, d L; bo_chol_backward -> d Sigma; then the d mu,
+    d Sigma chain of _SaasQEI.backward."""
+
+    @staticmethod
+    def forward(ctx, X3, acqf, Z):
+        model = acqf.model
+        B, q, d = X3.shape
+        dev = X3.device
+        X2 = X3.detach().reshape(B * q, d).contiguous()
+        ym, ys = model.outcome_stats()
+        ens = model.ensemble_cache()
+        M, n = ens["U"].shape[0], ens["n"]
+        f64 = dict(dtype=torch.float64, device=dev)
+        Bq = B * q
+        Kx = torch.empty(M, Bq, n, **f64)
+        kernels.covar_batched(ens["kind"], X2, (0, 0), Bq, ens["Xt"], (0, 0), n, d, ens["ls"],
+                              (d, 0), ens["os"], (1, 0), Kx, (Bq * n, 0), n, M, 1)
+        R = kernels.gemm(Kx, ens["U"], flags=_lib.GEMM_B_UPPER)              # M x Bq x n
+        mean = kernels.gemm(Kx, ens["alpha"].unsqueeze(-1)).reshape(M, B, q)
+        RR = kernels.gemm(R.view(M * B, q, n), R.view(M * B, q, n), transB=True)  # MB x q x q
+        Kxx = torch.empty(M * B, q, q, **f64)
+        kernels.covar_batched(ens["kind"], X2, (0, q * d), q, X2, (0, q * d), q, d, ens["ls"],
+                              (d, 0), ens["os"], (1, 0), Kxx, (B * q * q, q * q), q, M, B)
+        cov = Kxx - RR
+        tau2 = torch.stack([mm.likelihood.noise.reshape(()) for mm in model._members]).to(**f64)
+        cov.view(M, B, q, q).diagonal(dim1=-2, dim2=-1).add_(tau2.view(M, 1, 1))
+        cov *= ys * ys
+        mean = (ym + ys * (mean + ens["const"].view(M, 1, 1))).reshape(M * B, q)
+        L = kernels.chol_jitter(cov)                                          # MB x q x q
+        acq = kernels.bald(mean, L, Z, M).mean(dim=-1)
+        if ctx.needs_input_grad[0]:
+            ctx.ens, ctx.X2, ctx.Z, ctx.shape, ctx.ys = ens, X2, Z, (B, q, d), ys
+            ctx.R, ctx.mean, ctx.L = R, mean, L
+        return acq
+
+    @staticmethod
+    def backward(ctx, dacq):
+        B, q, d = ctx.shape
+        ens, ys = ctx.ens, ctx.ys
+        M, n = ens["U"].shape[0], ens["n"]
+        dout = (dacq / M).unsqueeze(-1).expand(B, M).contiguous()
+        dmean, dL = kernels.bald_backward(dout, ctx.mean, ctx.L, ctx.Z, M)
+        dcov = kernels.chol_backward(ctx.L, dL)                               # MB x q x q
+        dmu = (ys * dmean).reshape(M, B * q)                                  # standardized
+        G = ((ys * ys) * (dcov + dcov.mT)).contiguous()
+        W = kernels.gemm(ctx.R, ens["U"], transB=True, flags=_lib.GEMM_B_LOWER)  # M x Bq x n
+        dK = (dmu.unsqueeze(-1) * ens["alpha"].unsqueeze(1)).contiguous()    # M x Bq x n
+        kernels.gemm(G, W.view(M * B, q, n), alpha=-1.0, beta=1.0, C=dK.view(M * B, q, n))
+        Gm = G.view(M, B * q, q)
+        dX = None
+        for mi in range(M):
+            ls = ens["ls"][mi]
+            os_ = ens["os_host"][mi]
+            dX = kernels.kernel_grad(ctx.X2, ens["Xt"], dK[mi], ls, ens["kind"], os_, dX=dX)
+            dX = kernels.kernel_grad(ctx.X2, ctx.X2, Gm[mi].contiguous(), ls, ens["kind"], os_,
+                                     group=q, dX=dX)
+        return dX.reshape(B, q, d), None, None
+
+
+class qBayesianActiveLearningByDisagreement(FullyBayesianAcquisitionFunction):
+    """Batch BALD (bayesian_active_learning.py:52-126): the mutual information
+    between the next q noisy observations and the model's hyperparameters, as
+    the entropy of the Gaussian-mixture posterior of the MCMC ensemble minus the
+    mean entropy of its components, by Monte Carlo over base samples shared by
+    the components.  On the device, for q (pending points included) <= 16 and
+    up to 64 ensemble members without a posterior transform, one fused launch
+    evaluates every sample under every component in registers (bald.hip,
+    DESIGN.md section 20); everything else takes ``_generic``, the same formula
+    in torch."""
+
+    _default_sample_shape = torch.Size([512])
+    _GENERIC_CHUNK = 1 << 25  # doubles of one S x B x M x M x q intermediate per chunk
+
+    def __init__(self, model, sampler: Optional[MCSampler] = None, posterior_transform=None,
+                 X_pending=None):
+        super().__init__(model)
+        model.num_mcmc_samples  # (RuntimeError for a model that has not been fitted)
+        if model.training:
+            raise UnsupportedError("qBayesianActiveLearningByDisagreement needs a model in eval "
+                                   "mode (model.eval())")
+        self.sampler = sampler if sampler is not None else SobolQMCNormalSampler(
+            self._default_sample_shape)
+        self.posterior_transform = posterior_transform
+        self.set_X_pending(X_pending)
+
+    @property
+    def sample_shape(self) -> torch.Size:
+        return self.sampler.sample_shape
+
+    def _fused_ok(self, X: torch.Tensor) -> bool:
+        return (X.is_cuda and self.posterior_transform is None and X.shape[-2] <= FUSED_QMAX
+                and X.shape[-1] <= 128 and self.model.num_mcmc_samples <= kernels.BALD_MMAX
+                and len(self.sample_shape) == 1 and hasattr(self.sampler, "base_samples_2d")
+                and self.sample_shape.numel() <= kernels.BALD_SMAX)
+
+    def _generic(self, X: torch.Tensor) -> torch.Tensor:
+        """The reference's formula in torch on the model's posterior, in chunks of
+        t-batches that bound the S x B x M x M x q intermediates."""
+        batch, q, d = X.shape[:-2], X.shape[-2], X.shape[-1]
+        X3 = X.reshape(-1, q, d)
+        if X3.shape[0] == 0:
+            return X.new_empty(batch)
+        M, S = self.model.num_mcmc_samples, self.sample_shape.numel()
+        chunk = max(1, self._GENERIC_CHUNK // (M * M * S * q))
+        ns = len(self.sample_shape)
+        vals = []
+        for Xc in X3.split(chunk):
+            post = self.model.posterior(Xc, observation_noise=True,
+                                        posterior_transform=self.posterior_transform)
+            y = self.sampler(post).squeeze(-1)                # sample_shape x B x M x q
+            mvn = post.distribution
+            vals.append(_bald_value(mvn.loc, mvn.scale_tril, y.flatten(0, ns - 1)).mean(dim=-1))
+        return torch.cat(vals).reshape(batch)
+
+    def forward(self, X: torch.Tensor) -> torch.Tensor:
+        X = self._concat_pending(t_batch_mode(X))
+        if not self._fused_ok(X):
+            return self._generic(X)
+        batch, q, d = X.shape[:-2], X.shape[-2], X.shape[-1]
+        X3 = X.reshape(-1, q, d).to(torch.float64)
+        if X3.shape[0] == 0:
+            return X.new_empty(batch)
+        Z = self.sampler.base_samples_2d(q, X.device)
+        return _FusedBALD.apply(X3, self, Z).reshape(batch).to(X.dtype)
+
+
 def _acq_device(acqf) -> Optional[torch.device]:
     """The device an acquisition's model lives on (its training inputs, or a
     ModelListGP member's), None when it has none."""

@@ -93,6 +93,10 @@ int bo_mv_quantiles_impl(const BoMvQuantilesArgs* a, void* stream);
 int bo_nipv_gram_impl(const BoNipvArgs* a, void* stream);
 int bo_nipv_gram_backward_impl(const BoNipvArgs* a, void* stream);
 
+// the mixture-entropy acquisition of an MCMC ensemble (bald.hip)
+int bo_bald_impl(const BoBaldArgs* a, void* stream);
+int bo_bald_backward_impl(const BoBaldArgs* a, void* stream);
+
 int bo_post_partials_v(const BoPostPartialsArgs* a, void* stream) {
   if (!header_ok(a, "bo_post_partials_v")) return BO_ERR_ARG;
   return bo_post_partials_layout(a->kind, a->Xq, a->B, a->q, a->d, a->Xt_scaled, a->n, a->U,
@@ -234,6 +238,16 @@ int bo_nipv_gram_backward_v(const BoNipvArgs* a, void* stream) {
   return bo_nipv_gram_backward_impl(a, stream);
 }
 
+int bo_bald_v(const BoBaldArgs* a, void* stream) {
+  if (!header_ok(a, "bo_bald_v")) return BO_ERR_ARG;
+  return bo_bald_impl(a, stream);
+}
+
+int bo_bald_backward_v(const BoBaldArgs* a, void* stream) {
+  if (!header_ok(a, "bo_bald_backward_v")) return BO_ERR_ARG;
+  return bo_bald_backward_impl(a, stream);
+}
+
 int bo_lbfgs_step_v(const BoLbfgsStepArgs* a, void* stream) {
   if (!header_ok(a, "bo_lbfgs_step_v")) return BO_ERR_ARG;
   return bo_lbfgs_step(a->B, a->n, a->m, a->x, a->f, a->g, a->xt, a->ft, a->gt, a->d, a->alpha,
@@ -268,6 +282,7 @@ extern "C" int64_t bo_struct_size(const char* name) {
   if (s == "BoGibbonArgs") return sizeof(BoGibbonArgs);
   if (s == "BoMvQuantilesArgs") return sizeof(BoMvQuantilesArgs);
   if (s == "BoNipvArgs") return sizeof(BoNipvArgs);
+  if (s == "BoBaldArgs") return sizeof(BoBaldArgs);
   if (s == "BoLbfgsStepArgs") return sizeof(BoLbfgsStepArgs);
   if (s == "BoLbfgsbArgs") return sizeof(BoLbfgsbArgs);
   return -1;

@@ -2516,6 +2516,83 @@ def nipv_gram_backward(dG: torch.Tensor, X: torch.Tensor, q: int, lengthscale: t
     return dX
 
 
+BALD_MMAX = 64       # bo_bald: the ensemble's means and roots of a t-batch sit in LDS
+BALD_QMAX = 16
+BALD_SMAX = 1 << 20
+
+
+def bald_check(M: int, q: int, S: int, B: int = 1) -> None:
+    """The argument limits of :func:`bald`, raised on the host before any native
+    call."""
+    if not 1 <= M <= BALD_MMAX:
+        raise ValueError(f"bald: 1 <= M <= {BALD_MMAX} (got {M})")
+    if not 1 <= q <= BALD_QMAX:
+        raise ValueError(f"bald: 1 <= q <= {BALD_QMAX} (got {q})")
+    if not 1 <= S <= BALD_SMAX:
+        raise ValueError(f"bald: 1 <= S <= {BALD_SMAX} (got {S})")
+    if B < 0 or B * M >= 1 << 31:
+        raise ValueError(f"bald: B >= 0 and B M < 2^31 (got B = {B}, M = {M})")
+
+
+def _bald_args(mean, L, Z, M):
+    """The BoBaldArgs of :func:`bald` / :func:`bald_backward`: mean M B x q, L
+    M B x q x q (row m B + b: component m of t-batch b), Z S x q."""
+    if mean.dim() != 2 or L.dim() != 3 or Z.dim() != 2:
+        raise ValueError(f"bald: mean must be MB x q, L MB x q x q and Z S x q, got "
+                         f"{tuple(mean.shape)}, {tuple(L.shape)} and {tuple(Z.shape)}")
+    R, q = mean.shape
+    S = Z.shape[0]
+    M = int(M)
+    if M < 1 or R % M:
+        raise ValueError(f"bald: M >= 1 must divide the {R} rows of mean (got M = {M})")
+    bald_check(M, q, S, R // M)
+    if tuple(L.shape) != (R, q, q) or Z.shape[1] != q:
+        raise ValueError(f"bald: L must be {R} x {q} x {q} and Z S x {q}, got "
+                         f"{tuple(L.shape)} and {tuple(Z.shape)}")
+    for t in (mean, L, Z):
+        if t.dtype != torch.float64:
+            raise ValueError("bald: every tensor must be fp64")
+    return _lib.BaldArgs(M=M, q=q, S=S, B=R // M, mean=mean.contiguous(), L=L.contiguous(),
+                         Z=Z.contiguous())
+
+
+def bald(mean: torch.Tensor, L: torch.Tensor, Z: torch.Tensor, M: int) -> torch.Tensor:
+    """out (B x M): the entropy of the mixture of the M Gaussians N(mean[m B + b],
+    L L^T[m B + b]) of t-batch b minus the entropy of component m, by Monte Carlo
+    over the shared base samples Z (bo_bald, the record's comment in
+    include/botorch_amd.h).  The M x S x M log-densities stay in registers."""
+    a = _bald_args(mean, L, Z, M)
+    dev = _dev(mean, L, Z)
+    out = torch.empty(a.B, a.M, dtype=torch.float64, device=dev)
+    if a.B == 0:
+        return out
+    work = torch.empty(a.B * a.M, dtype=torch.float64, device=dev)
+    a.out, a.work, a.work_size = out.data_ptr(), work.data_ptr(), work.numel()
+    check(lib().bo_bald_v(ctypes.byref(a), _stream(dev)), "bald")
+    return out
+
+
+def bald_backward(dout: torch.Tensor, mean: torch.Tensor, L: torch.Tensor, Z: torch.Tensor,
+                  M: int):
+    """(dmean (MB x q), dL (MB x q x q, lower triangle; the upper is zero)) of
+    :func:`bald` from dout (B x M).  Every entry is written, nothing to clear."""
+    a = _bald_args(mean, L, Z, M)
+    if tuple(dout.shape) != (a.B, a.M) or dout.dtype != torch.float64:
+        raise ValueError(f"bald_backward: dout must be fp64 of shape ({a.B}, {a.M}), got "
+                         f"{tuple(dout.shape)}")
+    dev = _dev(dout, mean, L, Z)
+    dmean = torch.empty(a.B * a.M, a.q, dtype=torch.float64, device=dev)
+    dL = torch.empty(a.B * a.M, a.q, a.q, dtype=torch.float64, device=dev)
+    if a.B == 0:
+        return dmean, dL
+    dout = dout.contiguous()
+    work = torch.empty(a.B * a.M * a.S, dtype=torch.float64, device=dev)
+    a.dout, a.dmean, a.dL = dout.data_ptr(), dmean.data_ptr(), dL.data_ptr()
+    a.work, a.work_size = work.data_ptr(), work.numel()
+    check(lib().bo_bald_backward_v(ctypes.byref(a), _stream(dev)), "bald_backward")
+    return dmean, dL
+
+
 def kernel_grad(X: torch.Tensor, Y: torch.Tensor, dK: torch.Tensor, lengthscale: torch.Tensor,
                 kind: int, outputscale: float = 1.0, group: int = 0,
                 dX: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -907,7 +907,7 @@ class SaasFullyBayesianSingleTaskGP(Model):
 
     def posterior(self, X, output_indices=None, observation_noise=False, posterior_transform=None):
         """models/fully_bayesian.py:509-546 -> GaussianMixturePosterior (batch b x M)."""
-        from .posteriors import GPyTorchPosterior, MultivariateNormal, posterior_moments
+        from .posteriors import GaussianMixturePosterior, MultivariateNormal, posterior_moments
         M = self.num_mcmc_samples
         batch, q, d = X.shape[:-2], X.shape[-2], X.shape[-1]
         X3 = X.reshape(-1, q, d)
@@ -927,8 +927,7 @@ class SaasFullyBayesianSingleTaskGP(Model):
             covs.append(cov)
         mean = torch.stack(means, dim=1).reshape(*batch, M, q)
         cov = torch.stack(covs, dim=1).reshape(*batch, M, q, q)
-        post = GPyTorchPosterior(MultivariateNormal(mean, cov), model=self, X=X)
-        post._is_ensemble = True
+        post = GaussianMixturePosterior(MultivariateNormal(mean, cov), model=self, X=X)
         return post if posterior_transform is None else posterior_transform(post)
 
 

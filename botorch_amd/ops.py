@@ -44,6 +44,9 @@ Ops (reference computation each replaces):
   bo::nipv_gram       Gram matrices C_b C_b^T of the posterior cross-covariance of every
                       t-batch with N integration points, C never stored (+ autograd in
                       X; acquisition/active_learning.py:40-135)
+  bo::bald            mixture entropy minus component entropies of an ensemble's Gaussian
+                      posteriors at every t-batch, the M x S x M log-densities in registers
+                      (+ autograd in mean, L; acquisition/bayesian_active_learning.py:52-126)
 """
 from __future__ import annotations
 
@@ -892,9 +895,48 @@ def _nipv_bwd(ctx, dG):
 nipv_gram.register_autograd(_nipv_bwd, setup_context=_nipv_setup)
 
 
+# ---- bo::bald (BALD over a Gaussian-mixture posterior) -------------------------------------------
+@torch.library.custom_op("bo::bald", mutates_args=(), device_types="cuda")
+def bald(mean: Tensor, L: Tensor, Z: Tensor, M: int) -> Tensor:
+    """out (B x M) = H_b - C_bm from the components' means (M B x q), Cholesky
+    roots (M B x q x q) and the shared base samples Z (S x q) (kernels.bald).
+    Differentiable in mean and L."""
+    return kernels.bald(mean, L, Z, M)
+
+
+@bald.register_fake
+def _(mean, L, Z, M):
+    return mean.new_empty((mean.shape[0] // M, M), dtype=F64)
+
+
+@torch.library.custom_op("bo::bald_backward", mutates_args=(), device_types="cuda")
+def bald_backward(dout: Tensor, mean: Tensor, L: Tensor, Z: Tensor, M: int) -> Tuple[Tensor, Tensor]:
+    return kernels.bald_backward(dout, mean, L, Z, M)
+
+
+@bald_backward.register_fake
+def _(dout, mean, L, Z, M):
+    return mean.new_empty(mean.shape, dtype=F64), L.new_empty(L.shape, dtype=F64)
+
+
+def _bald_setup(ctx, inputs, output):
+    mean, L, Z, M = inputs
+    ctx.save_for_backward(mean, L, Z)
+    ctx.M = M
+
+
+def _bald_bwd(ctx, dout):
+    mean, L, Z = ctx.saved_tensors
+    dmean, dL = torch.ops.bo.bald_backward(dout.contiguous(), mean, L, Z, ctx.M)
+    return dmean, dL, None, None
+
+
+bald.register_autograd(_bald_bwd, setup_context=_bald_setup)
+
+
 OPS: List[str] = ["sobol_normal", "gp_cache", "gp_cache_extend", "chol_jitter", "chol_backward",
                   "post_partials", "qmc_finalize", "gp_posterior", "gp_posterior_backward",
                   "qmc_acq", "qmc_acq_backward", "qehvi", "qehvi_backward", "mll", "kg",
                   "kg_backward", "paths_eval", "paths_eval_backward", "jes", "jes_backward", "mes",
                   "mes_backward", "gibbon", "gibbon_backward", "mv_quantiles", "nipv_gram",
-                  "nipv_gram_backward"]
+                  "nipv_gram_backward", "bald", "bald_backward"]

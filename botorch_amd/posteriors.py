@@ -6,6 +6,7 @@ differentiable w.r.t. the inputs through ``bo_post_backward``.
 """
 from __future__ import annotations
 
+import math
 from typing import List, Optional
 
 import torch
@@ -162,6 +163,19 @@ class MultivariateNormal:
                 self._scale_tril = kernels.chol_jitter(C)
         return self._scale_tril
 
+    def log_prob(self, value: torch.Tensor) -> torch.Tensor:
+        """log N(value; loc, scale_tril scale_tril^T) by a triangular solve against
+        the root; ``value`` (... x k) broadcasts against the batch shape as in
+        torch.distributions."""
+        L = self.scale_tril
+        diff = value - self.loc
+        k = diff.shape[-1]
+        batch = torch.broadcast_shapes(diff.shape[:-1], L.shape[:-2])
+        w = torch.linalg.solve_triangular(L.expand(*batch, k, k),
+                                          diff.expand(*batch, k).unsqueeze(-1), upper=False)
+        half_log_det = L.diagonal(dim1=-2, dim2=-1).log().sum(-1)
+        return -0.5 * w.squeeze(-1).pow(2).sum(-1) - half_log_det - 0.5 * k * math.log(2 * math.pi)
+
 
 class GPyTorchPosterior:
     """botorch/posteriors/gpytorch.py:35-179 for single-output exact GPs."""
@@ -245,6 +259,86 @@ class GPyTorchPosterior:
         sample_shape = torch.Size([1]) if sample_shape is None else torch.Size(sample_shape)
         Z = torch.randn(sample_shape + self.base_sample_shape, dtype=self.dtype, device=self.device)
         return self.rsample_from_base_samples(sample_shape, Z)
+
+
+MCMC_DIM = -3  # the ensemble dimension of a mixture posterior's mean (... x M x q x 1)
+BISECT_TOL = 1e-6
+
+
+def batched_bisect(f, target: float, bounds: torch.Tensor, tol: float = BISECT_TOL,
+                   max_steps: int = 32) -> torch.Tensor:
+    """x with f(x) = target for a monotone batched f, by at most ``max_steps``
+    halvings of ``bounds`` (2 x batch) (posteriors/fully_bayesian.py:21-55)."""
+    if not ((f(bounds[0]) <= target) & (target <= f(bounds[1]))).all():
+        raise ValueError("The target is not contained in the interval specified by the bounds")
+    lo, hi = bounds[0].clone(), bounds[1].clone()
+    mid = 0.5 * (lo + hi)
+    for _ in range(max_steps):
+        above = f(mid) > target
+        hi = torch.where(above, mid, hi)
+        lo = torch.where(above, lo, mid)
+        mid = 0.5 * (lo + hi)
+        if (f(mid) - target).abs().max() <= tol:
+            break
+    return mid
+
+
+class GaussianMixturePosterior(GPyTorchPosterior):
+    """The posterior of an MCMC ensemble (posteriors/fully_bayesian.py:82-158): a
+    batch of M Gaussians at MCMC_DIM, which as a whole is a mixture with equal
+    weights.  ``mean`` / ``variance`` / ``rsample`` are per component, as the
+    parent's; the ``mixture_*`` moments and ``quantile`` are the mixture's."""
+
+    _is_ensemble = True
+
+    def __init__(self, distribution: MultivariateNormal, model=None, X=None):
+        super().__init__(distribution, model=model, X=X)
+        self._mixture = {}
+
+    @property
+    def mixture_mean(self) -> torch.Tensor:
+        if "mean" not in self._mixture:
+            self._mixture["mean"] = self.mean.mean(dim=MCMC_DIM)
+        return self._mixture["mean"]
+
+    @property
+    def mixture_variance(self) -> torch.Tensor:
+        """E[var] + E[mean^2] - E[mean]^2 over the components."""
+        if "variance" not in self._mixture:
+            mean, M = self.mean, self.mean.shape[MCMC_DIM]
+            self._mixture["variance"] = (self.variance.sum(dim=MCMC_DIM) / M
+                                         + mean.pow(2).sum(dim=MCMC_DIM) / M
+                                         - (mean.sum(dim=MCMC_DIM) / M).pow(2))
+        return self._mixture["variance"]
+
+    @property
+    def mixture_covariance_matrix(self) -> torch.Tensor:
+        """E[Sigma] + the covariance of the components' means."""
+        if "cov" not in self._mixture:
+            M = self.mean.shape[MCMC_DIM]
+            dev = self.mean - self.mixture_mean.unsqueeze(MCMC_DIM)
+            self._mixture["cov"] = (self.covariance_matrix.sum(dim=MCMC_DIM) / M
+                                    + (dev @ dev.mT).sum(dim=MCMC_DIM) / M)
+        return self._mixture["cov"]
+
+    def quantile(self, value: torch.Tensor) -> torch.Tensor:
+        """The mixture's marginal quantiles at every point (... x q x 1): the
+        normal icdf for one component, else a bisection of the mixture cdf
+        between the components' extreme quantiles."""
+        value = torch.as_tensor(value)
+        if value.numel() > 1:
+            return torch.stack([self.quantile(v) for v in value], dim=0)
+        if value <= 0 or value >= 1:
+            raise ValueError("value is expected to be in the range (0, 1).")
+        dist = torch.distributions.Normal(loc=self.mean, scale=self.variance.sqrt())
+        level = value.to(self.mean)
+        if self.mean.shape[MCMC_DIM] == 1:
+            return dist.icdf(level).squeeze(MCMC_DIM)
+        comp = dist.icdf(level)
+        bounds = torch.stack([comp.min(dim=MCMC_DIM).values - BISECT_TOL,
+                              comp.max(dim=MCMC_DIM).values + BISECT_TOL])
+        return batched_bisect(lambda x: dist.cdf(x.unsqueeze(MCMC_DIM)).mean(dim=MCMC_DIM),
+                              float(value), bounds)
 
 
 class PosteriorList:

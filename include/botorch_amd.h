@@ -1221,6 +1221,41 @@ typedef struct BoNipvArgs {
 int bo_nipv_gram_v(const BoNipvArgs* a, void* stream);
 int bo_nipv_gram_backward_v(const BoNipvArgs* a, void* stream);
 
+/* qBayesianActiveLearningByDisagreement (botorch/acquisition/
+ * bayesian_active_learning.py:52-126) over the Gaussian-mixture posterior of an
+ * ensemble of M models at B t-batches of q points, in outcome space with the
+ * observation noise in the covariances.  Row r = m B + b of mean (M B x q) and
+ * L (M B x q x q, lower Cholesky roots, row-major; the upper triangle is not
+ * read) is component m of t-batch b; Z (S x q) are the base samples all
+ * components and t-batches share.  With y_ms = mu_m + L_m z_s and
+ *   l_msm' = -|L_m'^{-1} (y_ms - mu_m')|^2 / 2 - sum_i log L_m',ii - (q / 2) log 2 pi
+ *   H_b    = -(1 / (M S)) sum_{m,s} [logsumexp_m' l_msm' - log M]   (mixture entropy)
+ *   C_bm   = mean_s |z_s|^2 / 2 + sum_i log L_m,ii + (q / 2) log 2 pi  (component entropy)
+ *   out[b][m] = H_b - C_bm                                           (B x M)
+ * The log-sum-exp runs online in registers (finite where exp underflows); the
+ * means and roots of a t-batch sit in LDS, one workgroup per (b, m); nothing of
+ * size M^2 S reaches memory.  Backward, from dout (B x M): dmean (M B x q) and dL
+ * (M B x q x q; the lower triangle holds the gradient, the upper is zero), every
+ * entry written, the caller clears nothing.
+ * work: scratch of work_size doubles, at least B M (forward) or B M S
+ * (backward: the per-sample log-sum-exp).
+ * 1 <= M <= 64, 1 <= q <= 16, 1 <= S <= 2^20, B >= 1 with B M < 2^31, fp64.
+ * Sums fold in a fixed order, no atomics: repeated calls are bitwise identical.
+ * A pure addition to the ABI: BO_ABI_VERSION stays 11. */
+typedef struct BoBaldArgs {
+  BO_STRUCT_HEADER;
+  int32_t M, q, S, _pad;
+  int64_t B;
+  const double *mean, *L, *Z;
+  double* out;          /* forward: B x M */
+  const double* dout;   /* backward: B x M */
+  double *dmean, *dL;   /* backward: M B x q, M B x q x q */
+  double* work;
+  int64_t work_size;
+} BoBaldArgs;
+int bo_bald_v(const BoBaldArgs* a, void* stream);
+int bo_bald_backward_v(const BoBaldArgs* a, void* stream);
+
 typedef struct BoLbfgsStepArgs { /* bo_lbfgs_step */
   BO_STRUCT_HEADER;
   int32_t B, n, m, _pad;
