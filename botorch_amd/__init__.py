@@ -11,7 +11,13 @@ __version__ = "0.1.0"
 # itself loads no native library)
 _EXPORTS = {"FullyBayesianAcquisitionFunction": "acquisition",
             "qBayesianActiveLearningByDisagreement": "acquisition",
-            "GaussianMixturePosterior": "posteriors"}
+            "GaussianMixturePosterior": "posteriors",
+            "LogExpectedImprovement": "acquisition",
+            "LogProbabilityOfImprovement": "acquisition",
+            "LogConstrainedExpectedImprovement": "acquisition",
+            "ConstrainedExpectedImprovement": "acquisition",
+            "PosteriorStandardDeviation": "acquisition",
+            "ScalarizedPosteriorMean": "acquisition"}
 __all__ = sorted(_EXPORTS)
 
 

@@ -318,6 +318,23 @@ class BaldArgs(_Args):
                        ("work_size", c_int64)]
 
 
+AN_CMAX = 15  # BoAnalyticArgs: constraints of one launch (with the objective: a 16-member tile)
+AN_LOG_EI, AN_EI, AN_LOG_PI, AN_PI, AN_UCB, AN_STD = range(6)  # BoAnalyticArgs.mode
+AN_CON_LOWER, AN_CON_UPPER, AN_CON_BOTH = range(3)             # BoAnalyticArgs.con_kind
+
+
+class AnalyticArgs(_Args):
+    _fields_ = _HDR + [("mode", c_int32), ("Mt", c_int32), ("obj", c_int32), ("ncon", c_int32),
+                       ("best_f_stride", c_int32), ("_pad", c_int32), ("R", c_int64),
+                       ("mean", _D), ("var", _D), ("best_f", _D), ("w", c_double),
+                       ("beta", c_double), ("min_var", c_double),
+                       ("con_member", c_int32 * (AN_CMAX + 1)),
+                       ("con_kind", c_int32 * (AN_CMAX + 1)),
+                       ("con_lower", c_double * (AN_CMAX + 1)),
+                       ("con_upper", c_double * (AN_CMAX + 1)), ("acq", _D), ("dacq", _D),
+                       ("dmean", _D), ("dvar", _D)]
+
+
 class LbfgsStepArgs(_Args):
     _fields_ = _HDR + [("B", c_int32), ("n", c_int32), ("m", c_int32), ("_pad", c_int32),
                        ("x", _D), ("f", _D), ("g", _D), ("xt", _D), ("ft", _D), ("gt", _D),
@@ -349,6 +366,7 @@ for _name, _cls in (("bo_post_partials_v", PostPartialsArgs), ("bo_qmc_finalize_
                     ("bo_mv_quantiles_v", MvQuantilesArgs),
                     ("bo_nipv_gram_v", NipvArgs), ("bo_nipv_gram_backward_v", NipvArgs),
                     ("bo_bald_v", BaldArgs), ("bo_bald_backward_v", BaldArgs),
+                    ("bo_analytic_v", AnalyticArgs), ("bo_analytic_backward_v", AnalyticArgs),
                     ("bo_lbfgs_step_v", LbfgsStepArgs), ("bo_lbfgsb_step_v", LbfgsbArgs)):
     _SIGNATURES[_name] = (c_int, [POINTER(_cls), _P])
 _SIGNATURES["bo_struct_size"] = (c_int64, [ctypes.c_char_p])
@@ -359,7 +377,7 @@ ARG_RECORDS = {"BoPostPartialsArgs": PostPartialsArgs, "BoQmcFinalizeArgs": QmcF
                "BoQlogehviArgs": QlogehviArgs, "BoQmcFeasArgs": QmcFeasArgs, "BoKgArgs": KgArgs,
                "BoPathsArgs": PathsArgs, "BoJesArgs": JesArgs, "BoMesArgs": MesArgs,
                "BoGibbonArgs": GibbonArgs, "BoMvQuantilesArgs": MvQuantilesArgs,
-               "BoNipvArgs": NipvArgs, "BoBaldArgs": BaldArgs,
+               "BoNipvArgs": NipvArgs, "BoBaldArgs": BaldArgs, "BoAnalyticArgs": AnalyticArgs,
                "BoLbfgsStepArgs": LbfgsStepArgs, "BoLbfgsbArgs": LbfgsbArgs}
 
 _lib = None

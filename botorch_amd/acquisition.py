@@ -531,6 +531,297 @@ class PosteriorMean(AnalyticAcquisitionFunction):
         return mean if self.maximize else -mean
 
 
+# -- analytic, log forms and outcome constraints: one fused chain on the moments ------------
+def _exact_members(model) -> Optional[list]:
+    """The single-output exact GPs behind ``model`` -- itself, the outputs of a
+    multi-output SingleTaskGP, or a ModelListGP's members -- or None where the
+    model is anything else (the generic route then)."""
+    from .models import ModelListGP, SingleTaskGP
+    if isinstance(model, ModelListGP) or (isinstance(model, SingleTaskGP)
+                                          and model._is_multi_output):
+        members = list(model.models)
+    else:
+        members = [model]
+    if all(isinstance(mm, SingleTaskGP) and not mm._is_multi_output for mm in members):
+        return members
+    return None
+
+
+class _MomentChainAcquisition(AnalyticAcquisitionFunction):
+    """The analytic q = 1 acquisitions that are a chain on the posterior mean
+    and variance (LogEI, LogPI, the posterior standard deviation and the
+    constrained (Log)EI).  ``forward`` takes one of two routes:
+
+    fused: the moments of the members the value reads, from
+    ``posteriors.posterior_moments`` (differentiable), stacked ``Mt x R`` into
+    ``bo::analytic`` -- one launch forward, one backward, instead of the 40 to 60
+    small launches of the torch chain each way;
+
+    generic: the reference's formula with the ``safe_math`` functions on
+    ``model.posterior`` (any model, any device, posterior transforms).
+
+    ``_route``: None (by ``_fused_applies``), "fused" or "generic" (tests, tools)."""
+
+    _an_mode: int = -1
+
+    def __init__(self, model, posterior_transform=None, check_outputs: bool = True):
+        super().__init__(model, posterior_transform)
+        if check_outputs and posterior_transform is None and model.num_outputs != 1:
+            raise UnsupportedError("Must specify a posterior transform when using a "
+                                   "multi-output model.")
+        self._route = None
+
+    # what the kernel reads: the members' indices in the model (the objective
+    # first) and the constraint table over their positions
+    def _an_members(self) -> List[int]:
+        return [0]
+
+    def _an_constraints(self) -> list:
+        return []
+
+    def _fused_applies(self, X3: torch.Tensor) -> bool:
+        if not X3.is_cuda or self.posterior_transform is not None:
+            return False
+        members = _exact_members(self.model)
+        if members is None:
+            return False
+        idx = self._an_members()
+        return (len(idx) <= kernels.AN_MT_MAX and len(self._an_constraints()) <= kernels.AN_CMAX
+                and max(idx) < len(members))
+
+    def _best_f_rows(self, batch: torch.Size, like: torch.Tensor) -> Optional[torch.Tensor]:
+        best_f = getattr(self, "best_f", None)
+        if best_f is None:
+            return None
+        best_f = best_f.to(like)
+        if best_f.numel() == 1:
+            return best_f.reshape(1)
+        return torch.broadcast_to(best_f, batch).reshape(-1)
+
+    def _fused(self, X3: torch.Tensor, batch: torch.Size) -> torch.Tensor:
+        from . import ops  # noqa: F401  (torch.ops.bo registration)
+        from .posteriors import posterior_moments
+        members = _exact_members(self.model)
+        if members is None:
+            raise UnsupportedError(f"{type(self).__name__}: the fused route needs an exact GP "
+                                   "(SingleTaskGP or a ModelListGP of them)")
+        picked = [members[i] for i in self._an_members()]
+        for mm in picked:
+            if mm.training:
+                mm.eval()
+        prime_prediction_caches(picked)
+        means, variances = [], []
+        for mm in picked:
+            mean, cov = posterior_moments(mm, X3)
+            means.append(mean.reshape(-1))
+            variances.append(cov.reshape(-1))
+        mean, var = torch.stack(means), torch.stack(variances)
+        cons = self._an_constraints()
+        return torch.ops.bo.analytic(
+            mean, var, self._best_f_rows(batch, mean), self._an_mode, 0,
+            1.0 if self.maximize else -1.0, 0.0, kernels.AN_MIN_VAR, [c[0] for c in cons],
+            [c[1] for c in cons], [c[2] for c in cons], [c[3] for c in cons])
+
+    def _generic(self, X: torch.Tensor) -> torch.Tensor:
+        raise NotImplementedError  # pragma: no cover
+
+    def forward(self, X: torch.Tensor) -> torch.Tensor:
+        X = t_batch_mode(X, expected_q=1)
+        if X.dtype != torch.float64:  # the model computes in fp64; the value returns in X's dtype
+            return self.forward(X.to(torch.float64)).to(X.dtype)
+        batch = X.shape[:-2]
+        X3 = X.reshape(-1, 1, X.shape[-1])
+        fused = self._fused_applies(X3) if self._route is None else self._route == "fused"
+        if fused:
+            return self._fused(X3, batch).reshape(batch)
+        return self._generic(X)
+
+
+def _scaled_improvement(mean, sigma, best_f, maximize: bool):
+    """acquisition/analytic.py:960-965."""
+    u = (mean - best_f) / sigma
+    return u if maximize else -u
+
+
+class LogExpectedImprovement(_MomentChainAcquisition):
+    """acquisition/analytic.py:356-416: log EI(x) = log_ei(u) + log sigma with
+    u = (mu - best_f) / sigma; finite, with a usable gradient, where EI itself
+    underflows to 0."""
+
+    _log: bool = True
+    _an_mode = kernels.AN_LOG_EI
+
+    def __init__(self, model, best_f, posterior_transform=None, maximize: bool = True):
+        super().__init__(model, posterior_transform)
+        self.register_buffer("best_f", torch.as_tensor(best_f, dtype=torch.float64))
+        self.maximize = maximize
+
+    def _generic(self, X):
+        from .safe_math import log_ei_helper
+        mean, sigma = self._mean_and_sigma(X)
+        u = _scaled_improvement(mean, sigma, self.best_f.to(mean), self.maximize)
+        return log_ei_helper(u) + sigma.log()
+
+
+class LogProbabilityOfImprovement(_MomentChainAcquisition):
+    """acquisition/analytic.py:111-170: log Phi((mu - best_f) / sigma)."""
+
+    _log: bool = True
+    _an_mode = kernels.AN_LOG_PI
+
+    def __init__(self, model, best_f, posterior_transform=None, maximize: bool = True):
+        super().__init__(model, posterior_transform)
+        self.register_buffer("best_f", torch.as_tensor(best_f, dtype=torch.float64))
+        self.maximize = maximize
+
+    def _generic(self, X):
+        from .safe_math import log_Phi
+        mean, sigma = self._mean_and_sigma(X)
+        return log_Phi(_scaled_improvement(mean, sigma, self.best_f.to(mean), self.maximize))
+
+
+class PosteriorStandardDeviation(_MomentChainAcquisition):
+    """acquisition/analytic.py:890-954: sigma, or -sigma with ``maximize=False``."""
+
+    _an_mode = kernels.AN_STD
+
+    def __init__(self, model, posterior_transform=None, maximize: bool = True):
+        super().__init__(model, posterior_transform)
+        self.maximize = maximize
+
+    def _generic(self, X):
+        _, std = self._mean_and_sigma(X)
+        return std if self.maximize else -std
+
+
+class ScalarizedPosteriorMean(AnalyticAcquisitionFunction):
+    """acquisition/analytic.py:849-887: the posterior mean of the q points
+    weighted by ``weights`` (q).  A weighted sum of means: torch only."""
+
+    def __init__(self, model, weights: torch.Tensor, posterior_transform=None):
+        super().__init__(model, posterior_transform)
+        if posterior_transform is None and model.num_outputs != 1:
+            raise UnsupportedError("Must specify a posterior transform when using a "
+                                   "multi-output model.")
+        self.register_buffer("weights", weights)
+
+    def forward(self, X):
+        X = t_batch_mode(X)
+        mean, _ = self._mean_and_sigma(X, compute_sigma=False)
+        return mean @ self.weights.to(mean)
+
+
+def _preprocess_constraint_bounds(acqf, constraints) -> None:
+    """acquisition/analytic.py:1137-1179: the constraints ``{i: (lower, upper)}``
+    (None: unbounded) sorted into lower, upper and two-sided groups, as buffers."""
+    con_lower, con_lower_inds = [], []
+    con_upper, con_upper_inds = [], []
+    con_both, con_both_inds = [], []
+    con_indices = list(constraints.keys())
+    if len(con_indices) == 0:
+        raise ValueError("There must be at least one constraint.")
+    if acqf.objective_index in con_indices:
+        raise ValueError("Output corresponding to objective should not be a constraint.")
+    for k in con_indices:
+        if constraints[k][0] is not None and constraints[k][1] is not None:
+            if constraints[k][1] <= constraints[k][0]:
+                raise ValueError("Upper bound is less than the lower bound.")
+            con_both_inds.append(k)
+            con_both.append([constraints[k][0], constraints[k][1]])
+        elif constraints[k][0] is not None:
+            con_lower_inds.append(k)
+            con_lower.append(constraints[k][0])
+        elif constraints[k][1] is not None:
+            con_upper_inds.append(k)
+            con_upper.append(constraints[k][1])
+    for name, indices in [("con_lower_inds", con_lower_inds), ("con_upper_inds", con_upper_inds),
+                          ("con_both_inds", con_both_inds), ("con_both", con_both),
+                          ("con_lower", con_lower), ("con_upper", con_upper)]:
+        # (the bounds in fp64: as the default dtype they would reach the formula rounded to fp32)
+        dtype = torch.long if name.endswith("_inds") else torch.float64
+        acqf.register_buffer(name, torch.as_tensor(indices, dtype=dtype))
+    # the same table on the host, in the groups' order, for the fused route:
+    # (output, lower, upper, kind)
+    acqf._con_table = (
+        [(k, float(v), 0.0, kernels.AN_CON_LOWER) for k, v in zip(con_lower_inds, con_lower)]
+        + [(k, 0.0, float(v), kernels.AN_CON_UPPER) for k, v in zip(con_upper_inds, con_upper)]
+        + [(k, float(lo), float(hi), kernels.AN_CON_BOTH)
+           for k, (lo, hi) in zip(con_both_inds, con_both)])
+
+
+def _compute_log_prob_feas(acqf, means: torch.Tensor, sigmas: torch.Tensor) -> torch.Tensor:
+    """acquisition/analytic.py:1182-1220: the log probability that every
+    constrained output lies within its bounds, the outputs independent."""
+    from .safe_math import log_Phi, log_prob_normal_in
+    acqf.to(device=means.device)
+    log_prob = torch.zeros_like(means[..., 0])
+    if len(acqf.con_lower_inds) > 0:
+        i = acqf.con_lower_inds
+        dist_l = (acqf.con_lower - means[..., i]) / sigmas[..., i]
+        log_prob = log_prob + log_Phi(-dist_l).sum(dim=-1)  # 1 - Phi(x) = Phi(-x)
+    if len(acqf.con_upper_inds) > 0:
+        i = acqf.con_upper_inds
+        dist_u = (acqf.con_upper - means[..., i]) / sigmas[..., i]
+        log_prob = log_prob + log_Phi(dist_u).sum(dim=-1)
+    if len(acqf.con_both_inds) > 0:
+        i = acqf.con_both_inds
+        con_lower, con_upper = acqf.con_both[:, 0], acqf.con_both[:, 1]
+        dist_l = (con_lower - means[..., i]) / sigmas[..., i]
+        dist_u = (con_upper - means[..., i]) / sigmas[..., i]
+        log_prob = log_prob + log_prob_normal_in(a=dist_l, b=dist_u).sum(dim=-1)
+    return log_prob
+
+
+class LogConstrainedExpectedImprovement(_MomentChainAcquisition):
+    """acquisition/analytic.py:419-495: log EI of output ``objective_index`` plus
+    the log probability that the constrained outputs are feasible, over a
+    multi-output SingleTaskGP or a ModelListGP (independent outputs)."""
+
+    _log: bool = True
+    _an_mode = kernels.AN_LOG_EI
+
+    def __init__(self, model, best_f, objective_index: int, constraints: dict,
+                 maximize: bool = True):
+        super().__init__(model, None, check_outputs=False)
+        self.maximize = maximize
+        self.objective_index = objective_index
+        self.constraints = constraints
+        self.register_buffer("best_f", torch.as_tensor(best_f, dtype=torch.float64))
+        _preprocess_constraint_bounds(self, constraints=constraints)
+
+    def _an_members(self) -> List[int]:
+        return [self.objective_index] + [c[0] for c in self._con_table]
+
+    def _an_constraints(self) -> list:
+        return [(pos + 1, lo, hi, kind) for pos, (_, lo, hi, kind) in enumerate(self._con_table)]
+
+    def _objective_terms(self, X):
+        means, sigmas = self._mean_and_sigma(X)
+        ind = self.objective_index
+        mean_obj, sigma_obj = means[..., ind], sigmas[..., ind]
+        u = _scaled_improvement(mean_obj, sigma_obj, self.best_f.to(mean_obj), self.maximize)
+        return u, sigma_obj, _compute_log_prob_feas(self, means=means, sigmas=sigmas)
+
+    def _generic(self, X):
+        from .safe_math import log_ei_helper
+        u, sigma_obj, log_prob_feas = self._objective_terms(X)
+        return log_ei_helper(u) + sigma_obj.log() + log_prob_feas
+
+
+class ConstrainedExpectedImprovement(LogConstrainedExpectedImprovement):
+    """acquisition/analytic.py:498-574: EI of the objective output times the
+    probability of feasibility.  LogConstrainedExpectedImprovement has the
+    better numerics (this one is exactly 0 where either factor underflows)."""
+
+    _log: bool = False
+    _an_mode = kernels.AN_EI
+
+    def _generic(self, X):
+        from .safe_math import ei_helper
+        u, sigma_obj, log_prob_feas = self._objective_terms(X)
+        return (sigma_obj * ei_helper(u)).mul(log_prob_feas.exp())
+
+
 # -- pathwise Thompson sampling -----------------------------------------------------------
 BATCH_SIZE_CHANGE_ERROR = """The batch size of PathwiseThompsonSampling should \
 not change during a forward pass - was {}, now {}. Please re-initialize the \

@@ -97,6 +97,10 @@ int bo_nipv_gram_backward_impl(const BoNipvArgs* a, void* stream);
 int bo_bald_impl(const BoBaldArgs* a, void* stream);
 int bo_bald_backward_impl(const BoBaldArgs* a, void* stream);
 
+// the analytic q = 1 acquisition chain (analytic.hip)
+int bo_analytic_impl(const BoAnalyticArgs* a, void* stream);
+int bo_analytic_backward_impl(const BoAnalyticArgs* a, void* stream);
+
 int bo_post_partials_v(const BoPostPartialsArgs* a, void* stream) {
   if (!header_ok(a, "bo_post_partials_v")) return BO_ERR_ARG;
   return bo_post_partials_layout(a->kind, a->Xq, a->B, a->q, a->d, a->Xt_scaled, a->n, a->U,
@@ -248,6 +252,16 @@ int bo_bald_backward_v(const BoBaldArgs* a, void* stream) {
   return bo_bald_backward_impl(a, stream);
 }
 
+int bo_analytic_v(const BoAnalyticArgs* a, void* stream) {
+  if (!header_ok(a, "bo_analytic_v")) return BO_ERR_ARG;
+  return bo_analytic_impl(a, stream);
+}
+
+int bo_analytic_backward_v(const BoAnalyticArgs* a, void* stream) {
+  if (!header_ok(a, "bo_analytic_backward_v")) return BO_ERR_ARG;
+  return bo_analytic_backward_impl(a, stream);
+}
+
 int bo_lbfgs_step_v(const BoLbfgsStepArgs* a, void* stream) {
   if (!header_ok(a, "bo_lbfgs_step_v")) return BO_ERR_ARG;
   return bo_lbfgs_step(a->B, a->n, a->m, a->x, a->f, a->g, a->xt, a->ft, a->gt, a->d, a->alpha,
@@ -283,6 +297,7 @@ extern "C" int64_t bo_struct_size(const char* name) {
   if (s == "BoMvQuantilesArgs") return sizeof(BoMvQuantilesArgs);
   if (s == "BoNipvArgs") return sizeof(BoNipvArgs);
   if (s == "BoBaldArgs") return sizeof(BoBaldArgs);
+  if (s == "BoAnalyticArgs") return sizeof(BoAnalyticArgs);
   if (s == "BoLbfgsStepArgs") return sizeof(BoLbfgsStepArgs);
   if (s == "BoLbfgsbArgs") return sizeof(BoLbfgsbArgs);
   return -1;

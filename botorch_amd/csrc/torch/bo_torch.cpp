@@ -1097,9 +1097,94 @@ std::vector<at::Tensor> mv_quantiles_native(const at::Tensor& mu, const at::Tens
   return {out, status};
 }
 
+// ---- the analytic q = 1 family (bo_analytic_v and its backward) ------------------------------
+// mean, var (Mt x R); best_f: one entry or R (undefined where the mode reads none); the
+// constraint table as four lists of equal length
+BoAnalyticArgs analytic_args(const at::Tensor& mean, const at::Tensor& var,
+                             const c10::optional<at::Tensor>& best_f, int64_t mode, int64_t obj,
+                             double w, double beta, double min_var, at::IntArrayRef con_member,
+                             at::ArrayRef<double> con_lower, at::ArrayRef<double> con_upper,
+                             at::IntArrayRef con_kind) {
+  const char* who = "bo::analytic_native";
+  mes_dense(who, {&mean, &var});
+  TORCH_CHECK(mean.dim() == 2 && var.dim() == 2 && var.size(0) == mean.size(0) &&
+                  var.size(1) == mean.size(1), who, ": mean and var must be Mt x R each");
+  const size_t nc = con_member.size();
+  TORCH_CHECK(con_lower.size() == nc && con_upper.size() == nc && con_kind.size() == nc, who,
+              ": the constraint lists must have one length");
+  TORCH_CHECK(nc <= BO_AN_CMAX, who, ": at most ", BO_AN_CMAX, " constraints (got ", nc, ")");
+  TORCH_CHECK(mean.size(0) <= INT32_MAX, who, ": Mt out of range");
+  BoAnalyticArgs a{};
+  a.struct_size = sizeof(a);
+  a.abi_version = BO_ABI_VERSION;
+  a.mode = static_cast<int32_t>(mode);
+  a.Mt = static_cast<int32_t>(mean.size(0));
+  a.obj = static_cast<int32_t>(obj);
+  a.ncon = static_cast<int32_t>(nc);
+  a.R = mean.size(1);
+  a.mean = cp(mean);
+  a.var = cp(var);
+  if (best_f.has_value() && best_f->defined()) {
+    mes_dense(who, {&*best_f});
+    TORCH_CHECK(best_f->numel() == 1 || best_f->numel() == a.R, who,
+                ": best_f must have 1 or R = ", a.R, " entries");
+    a.best_f = best_f->data_ptr<double>();
+    a.best_f_stride = best_f->numel() == 1 ? 0 : 1;
+  }
+  a.w = w;
+  a.beta = beta;
+  a.min_var = min_var;
+  for (size_t c = 0; c < nc; ++c) {
+    a.con_member[c] = static_cast<int32_t>(con_member[c]);
+    a.con_kind[c] = static_cast<int32_t>(con_kind[c]);
+    a.con_lower[c] = con_lower[c];
+    a.con_upper[c] = con_upper[c];
+  }
+  return a;
+}
+
+at::Tensor analytic_native(const at::Tensor& mean, const at::Tensor& var,
+                           const c10::optional<at::Tensor>& best_f, int64_t mode, int64_t obj,
+                           double w, double beta, double min_var, at::IntArrayRef con_member,
+                           at::ArrayRef<double> con_lower, at::ArrayRef<double> con_upper,
+                           at::IntArrayRef con_kind) {
+  BoAnalyticArgs a = analytic_args(mean, var, best_f, mode, obj, w, beta, min_var, con_member,
+                                   con_lower, con_upper, con_kind);
+  at::Tensor out = at::empty({a.R}, mean.options());
+  a.acq = mp(out);
+  ck(bo_analytic_v(&a, c10::hip::getCurrentHIPStream(mean.device().index()).stream()), "analytic");
+  return out;
+}
+
+std::vector<at::Tensor> analytic_backward_native(
+    const at::Tensor& dacq, const at::Tensor& mean, const at::Tensor& var,
+    const c10::optional<at::Tensor>& best_f, int64_t mode, int64_t obj, double w, double beta,
+    double min_var, at::IntArrayRef con_member, at::ArrayRef<double> con_lower,
+    at::ArrayRef<double> con_upper, at::IntArrayRef con_kind) {
+  BoAnalyticArgs a = analytic_args(mean, var, best_f, mode, obj, w, beta, min_var, con_member,
+                                   con_lower, con_upper, con_kind);
+  mes_dense("bo::analytic_backward_native", {&dacq});
+  TORCH_CHECK(dacq.dim() == 1 && dacq.size(0) == a.R,
+              "bo::analytic_backward_native: dacq must have R = ", a.R, " entries");
+  at::Tensor dmean = at::empty({(int64_t)a.Mt, a.R}, mean.options()),
+             dvar = at::empty({(int64_t)a.Mt, a.R}, mean.options());
+  a.dacq = cp(dacq);
+  a.dmean = mp(dmean);
+  a.dvar = mp(dvar);
+  ck(bo_analytic_backward_v(&a, c10::hip::getCurrentHIPStream(mean.device().index()).stream()),
+     "analytic_backward");
+  return {dmean, dvar};
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(bo, m) {
+  m.def("analytic_native(Tensor mean, Tensor var, Tensor? best_f, int mode, int obj, float w, "
+        "float beta, float min_var, int[] con_member, float[] con_lower, float[] con_upper, "
+        "int[] con_kind) -> Tensor");
+  m.def("analytic_backward_native(Tensor dacq, Tensor mean, Tensor var, Tensor? best_f, int mode, "
+        "int obj, float w, float beta, float min_var, int[] con_member, float[] con_lower, "
+        "float[] con_upper, int[] con_kind) -> Tensor[]");
   m.def("mes_native(Tensor mu, Tensor var, Tensor fstar, Tensor z, float kappa, float var_h0, "
         "float zsq_mean, float tau2, float w) -> Tensor");
   m.def("mes_backward_native(Tensor dout, Tensor mu, Tensor var, Tensor fstar, Tensor z, "
@@ -1155,4 +1240,6 @@ TORCH_LIBRARY_IMPL(bo, CUDA, m) {
   m.impl("gibbon_native", &gibbon_native);
   m.impl("gibbon_backward_native", &gibbon_backward_native);
   m.impl("mv_quantiles_native", &mv_quantiles_native);
+  m.impl("analytic_native", &analytic_native);
+  m.impl("analytic_backward_native", &analytic_backward_native);
 }

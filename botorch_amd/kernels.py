@@ -2427,6 +2427,113 @@ def mv_quantiles(mu: torch.Tensor, sigma: torch.Tensor, bounds=None) -> torch.Te
     return out
 
 
+AN_CMAX = _lib.AN_CMAX  # bo_analytic: constraints of one launch
+AN_MT_MAX = AN_CMAX + 1  # and members (the objective and its constraints: one 16-row tile)
+AN_LOG_EI, AN_EI, AN_LOG_PI, AN_PI, AN_UCB, AN_STD = (_lib.AN_LOG_EI, _lib.AN_EI, _lib.AN_LOG_PI,
+                                                      _lib.AN_PI, _lib.AN_UCB, _lib.AN_STD)
+AN_LOG_MODES = (AN_LOG_EI, AN_LOG_PI)
+AN_CON_LOWER, AN_CON_UPPER, AN_CON_BOTH = _lib.AN_CON_LOWER, _lib.AN_CON_UPPER, _lib.AN_CON_BOTH
+AN_MIN_VAR = 1e-12  # acquisition/analytic.py:84 (_mean_and_sigma's floor)
+
+
+def analytic_check(Mt: int, mode: int, obj: int = 0, constraints=(), min_var: float = AN_MIN_VAR,
+                   w: float = 1.0, beta: float = 0.0) -> None:
+    """The argument limits of :func:`analytic`, raised on the host before any
+    native call.  ``constraints``: (member, lower, upper, kind) each."""
+    if not 1 <= Mt <= AN_MT_MAX:
+        raise ValueError(f"analytic: 1 <= Mt <= {AN_MT_MAX} (got {Mt})")
+    if mode not in range(6):
+        raise ValueError(f"analytic: mode must be 0..5 (got {mode})")
+    if len(constraints) > AN_CMAX:
+        raise ValueError(f"analytic: at most {AN_CMAX} constraints (got {len(constraints)})")
+    if not 0 <= obj < Mt:
+        raise ValueError(f"analytic: 0 <= obj < Mt (got {obj})")
+    if not min_var > 0.0:
+        raise ValueError(f"analytic: min_var > 0 (got {min_var})")
+    _w_ok("analytic", w)
+    if not beta >= 0.0:
+        raise ValueError(f"analytic: beta >= 0 (got {beta})")
+    seen = set()
+    for c, (member, lower, upper, kind) in enumerate(constraints):
+        if not 0 <= member < Mt:
+            raise ValueError(f"analytic: constraint {c}: 0 <= member < Mt (got {member})")
+        if member == obj:
+            raise ValueError(f"analytic: constraint {c} is on the objective's member {member}")
+        if member in seen:
+            raise ValueError(f"analytic: member {member} carries more than one constraint")
+        seen.add(member)
+        if kind not in (AN_CON_LOWER, AN_CON_UPPER, AN_CON_BOTH):
+            raise ValueError(f"analytic: constraint {c}: kind must be 0..2 (got {kind})")
+        if kind == AN_CON_BOTH and not upper > lower:
+            raise ValueError(f"analytic: constraint {c}: upper > lower (got {lower}, {upper})")
+
+
+def _analytic_args(mean, var, best_f, mode, obj, w, beta, min_var, constraints):
+    if mean.dim() != 2 or tuple(var.shape) != tuple(mean.shape):
+        raise ValueError(f"analytic: mean and var must be Mt x R each, got {tuple(mean.shape)} "
+                         f"and {tuple(var.shape)}")
+    Mt, R = mean.shape
+    constraints = [(int(m), float(lo), float(hi), int(k)) for m, lo, hi, k in constraints]
+    analytic_check(Mt, int(mode), int(obj), constraints, float(min_var), w, float(beta))
+    for t in (mean, var, best_f):
+        if t is not None and t.dtype != torch.float64:
+            raise ValueError("analytic: every tensor must be fp64")
+    stride = 0
+    if int(mode) <= AN_PI:
+        if best_f is None or best_f.numel() not in (1, R):
+            raise ValueError(f"analytic: best_f must have 1 or R = {R} entries")
+        stride = 0 if best_f.numel() == 1 else 1
+        best_f = best_f.reshape(-1).contiguous()
+    else:
+        best_f = None
+    a = _lib.AnalyticArgs(mode=int(mode), Mt=Mt, obj=int(obj), ncon=len(constraints),
+                          best_f_stride=stride, R=R, mean=mean.contiguous(), var=var.contiguous(),
+                          best_f=best_f, w=float(w), beta=float(beta), min_var=float(min_var))
+    for c, (m, lo, hi, k) in enumerate(constraints):
+        a.con_member[c], a.con_lower[c], a.con_upper[c], a.con_kind[c] = m, lo, hi, k
+    return a
+
+
+def analytic(mean: torch.Tensor, var: torch.Tensor, best_f: Optional[torch.Tensor], mode: int,
+             obj: int = 0, w: float = 1.0, beta: float = 0.0, min_var: float = AN_MIN_VAR,
+             constraints=()) -> torch.Tensor:
+    """acq (R): an analytic q = 1 acquisition value of R rows from the members'
+    posterior means and variances (Mt x R each) in one launch (bo_analytic; the
+    record's comment in include/botorch_amd.h states the formulae).  ``mode``: one
+    of AN_LOG_EI, AN_EI, AN_LOG_PI, AN_PI, AN_UCB, AN_STD on member ``obj``;
+    ``best_f``: one entry or R; ``constraints``: (member, lower, upper, kind),
+    kind one of AN_CON_LOWER / AN_CON_UPPER / AN_CON_BOTH, whose log feasibility
+    probabilities are added (log modes) or whose product multiplies."""
+    dev = _dev(mean, var, best_f)
+    a = _analytic_args(mean, var, best_f, mode, obj, w, beta, min_var, constraints)
+    out = torch.empty(a.R, dtype=torch.float64, device=dev)
+    if a.R == 0:
+        return out
+    a.acq = out.data_ptr()
+    check(lib().bo_analytic_v(ctypes.byref(a), _stream(dev)), "analytic")
+    return out
+
+
+def analytic_backward(dacq: torch.Tensor, mean: torch.Tensor, var: torch.Tensor,
+                      best_f: Optional[torch.Tensor], mode: int, obj: int = 0, w: float = 1.0,
+                      beta: float = 0.0, min_var: float = AN_MIN_VAR, constraints=()):
+    """(dmean, dvar), Mt x R each, of :func:`analytic` from dacq (R).  One
+    launch; every element is written."""
+    dev = _dev(dacq, mean, var, best_f)
+    a = _analytic_args(mean, var, best_f, mode, obj, w, beta, min_var, constraints)
+    if tuple(dacq.shape) != (a.R,) or dacq.dtype != torch.float64:
+        raise ValueError(f"analytic_backward: dacq must be fp64 of shape ({a.R},), got "
+                         f"{tuple(dacq.shape)}")
+    dacq = dacq.contiguous()
+    dmean = torch.empty(a.Mt, a.R, dtype=torch.float64, device=dev)
+    dvar = torch.empty(a.Mt, a.R, dtype=torch.float64, device=dev)
+    if a.R == 0:
+        return dmean, dvar
+    a.dacq, a.dmean, a.dvar = dacq.data_ptr(), dmean.data_ptr(), dvar.data_ptr()
+    check(lib().bo_analytic_backward_v(ctypes.byref(a), _stream(dev)), "analytic_backward")
+    return dmean, dvar
+
+
 NIPV_DMAX = 128  # bo_nipv_gram: d is a runtime loop up to here
 NIPV_QMAX = 16   # t-batches are packed into 16-row tiles
 NIPV_MAX_SPLIT = 1024

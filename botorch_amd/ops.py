@@ -47,6 +47,10 @@ Ops (reference computation each replaces):
   bo::bald            mixture entropy minus component entropies of an ensemble's Gaussian
                       posteriors at every t-batch, the M x S x M log-densities in registers
                       (+ autograd in mean, L; acquisition/bayesian_active_learning.py:52-126)
+  bo::analytic        LogEI / EI / LogPI / PI / UCB / posterior standard deviation of R rows,
+                      with up to 15 outcome constraints, from the members' posterior means
+                      and variances in one launch (+ analytic autograd in mean, var;
+                      acquisition/analytic.py:357-420, 528-608, 960-1053, 1182-1220)
 """
 from __future__ import annotations
 
@@ -934,9 +938,82 @@ def _bald_bwd(ctx, dout):
 bald.register_autograd(_bald_bwd, setup_context=_bald_setup)
 
 
+# ---- bo::analytic (the analytic q = 1 family on the posterior moments) ---------------------------
+def _analytic_dense(mean, var, best_f, mode, obj, w, beta, min_var, con_member, con_lower,
+                    con_upper, con_kind):
+    """The arguments of bo::analytic[_backward]_native after kernels.analytic_check's
+    limits (a ValueError before any native call)."""
+    if mean.dim() != 2 or tuple(var.shape) != tuple(mean.shape):
+        raise ValueError("analytic: mean and var must be Mt x R each")
+    cons = list(zip(con_member, con_lower, con_upper, con_kind))
+    if not len(cons) == len(con_member) == len(con_lower) == len(con_upper) == len(con_kind):
+        raise ValueError("analytic: the constraint lists must have one length")
+    kernels.analytic_check(mean.shape[0], mode, obj, cons, min_var, w, beta)
+    if mode <= kernels.AN_PI:
+        if best_f is None or best_f.numel() not in (1, mean.shape[1]):
+            raise ValueError(f"analytic: best_f must have 1 or R = {mean.shape[1]} entries")
+        best_f = best_f.reshape(-1).contiguous()
+    else:
+        best_f = None
+    return (mean.contiguous(), var.contiguous(), best_f, mode, obj, w, beta, min_var,
+            list(con_member), list(con_lower), list(con_upper), list(con_kind))
+
+
+@torch.library.custom_op("bo::analytic", mutates_args=(), device_types="cuda")
+def analytic(mean: Tensor, var: Tensor, best_f: Optional[Tensor], mode: int, obj: int, w: float,
+             beta: float, min_var: float, con_member: List[int], con_lower: List[float],
+             con_upper: List[float], con_kind: List[int]) -> Tensor:
+    """acq (R): the analytic acquisition ``mode`` (kernels.AN_*) of R rows from
+    the members' posterior means and variances (Mt x R each) with the constraint
+    table given as four lists (kernels.analytic).  Differentiable in mean and
+    var."""
+    return _lib.torch_ops().analytic_native(*_analytic_dense(
+        mean, var, best_f, mode, obj, w, beta, min_var, con_member, con_lower, con_upper, con_kind))
+
+
+@analytic.register_fake
+def _(mean, var, best_f, mode, obj, w, beta, min_var, con_member, con_lower, con_upper, con_kind):
+    return mean.new_empty((mean.shape[1],), dtype=F64)
+
+
+@torch.library.custom_op("bo::analytic_backward", mutates_args=(), device_types="cuda")
+def analytic_backward(dacq: Tensor, mean: Tensor, var: Tensor, best_f: Optional[Tensor], mode: int,
+                      obj: int, w: float, beta: float, min_var: float, con_member: List[int],
+                      con_lower: List[float], con_upper: List[float],
+                      con_kind: List[int]) -> Tuple[Tensor, Tensor]:
+    dmean, dvar = _lib.torch_ops().analytic_backward_native(dacq.contiguous(), *_analytic_dense(
+        mean, var, best_f, mode, obj, w, beta, min_var, con_member, con_lower, con_upper, con_kind))
+    return dmean, dvar
+
+
+@analytic_backward.register_fake
+def _(dacq, mean, var, best_f, mode, obj, w, beta, min_var, con_member, con_lower, con_upper,
+      con_kind):
+    return mean.new_empty(mean.shape, dtype=F64), mean.new_empty(mean.shape, dtype=F64)
+
+
+def _analytic_setup(ctx, inputs, output):
+    ctx.has_best_f = inputs[2] is not None
+    ctx.save_for_backward(*[t for t in inputs[:3] if t is not None])
+    ctx.consts = inputs[3:]
+
+
+def _analytic_bwd(ctx, dacq):
+    dmean = dvar = None
+    if any(ctx.needs_input_grad[:2]):
+        mean, var = ctx.saved_tensors[:2]
+        best_f = ctx.saved_tensors[2] if ctx.has_best_f else None
+        dmean, dvar = torch.ops.bo.analytic_backward(dacq.contiguous(), mean, var, best_f,
+                                                     *ctx.consts)
+    return (dmean, dvar) + (None,) * 10
+
+
+analytic.register_autograd(_analytic_bwd, setup_context=_analytic_setup)
+
+
 OPS: List[str] = ["sobol_normal", "gp_cache", "gp_cache_extend", "chol_jitter", "chol_backward",
                   "post_partials", "qmc_finalize", "gp_posterior", "gp_posterior_backward",
                   "qmc_acq", "qmc_acq_backward", "qehvi", "qehvi_backward", "mll", "kg",
                   "kg_backward", "paths_eval", "paths_eval_backward", "jes", "jes_backward", "mes",
                   "mes_backward", "gibbon", "gibbon_backward", "mv_quantiles", "nipv_gram",
-                  "nipv_gram_backward", "bald", "bald_backward"]
+                  "nipv_gram_backward", "bald", "bald_backward", "analytic", "analytic_backward"]

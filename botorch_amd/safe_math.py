@@ -193,3 +193,113 @@ def logdiffexp(log_a: torch.Tensor, log_b: torch.Tensor) -> torch.Tensor:
     log_a, log_b = torch.broadcast_tensors(log_a, log_b)
     is_inf = log_b == -math.inf
     return log_b + log1mexp(log_a - log_b.masked_fill(is_inf, 0.0))
+
+
+# -- the analytic family's leaf functions (utils/probability/utils.py:133-257 and
+# acquisition/analytic.py:968-1053), masked as the reference masks them so that
+# autograd meets no NaN on the branch not taken
+_INV_SQRT_2PI = 1 / math.sqrt(2 * math.pi)
+_INV_SQRT_2 = 1 / math.sqrt(2)
+_NEG_INV_SQRT_2 = -_INV_SQRT_2
+_LOG_2 = math.log(2)
+_LOG_SQRT_2PI = math.log(2 * math.pi) / 2
+_LOG_TWO_INV_SQRT_2PI = _LOG_2 - _LOG_SQRT_2PI  # log(2 / sqrt(2 pi))
+_LOG_SQRT_PI_DIV_2 = math.log(math.pi / 2) / 2
+LOG_EI_UPPER = -1.0  # analytic.py:990: above, the logarithm of phi(u) + u Phi(u) itself
+
+
+def _float_only(x: torch.Tensor, name: str) -> None:
+    if not (x.dtype == torch.float32 or x.dtype == torch.float64):
+        raise TypeError(f"{name} only supports torch.float32 and torch.float64 "
+                        f"dtypes, but received {x.dtype = }.")
+
+
+def ndtr(x: torch.Tensor) -> torch.Tensor:
+    """Standard normal CDF (utils.py:133-136)."""
+    return 0.5 * torch.erfc(_NEG_INV_SQRT_2 * x)
+
+
+def phi(x: torch.Tensor) -> torch.Tensor:
+    """Standard normal PDF (utils.py:139-142)."""
+    return _INV_SQRT_2PI * (-0.5 * x.square()).exp()
+
+
+def log_phi(x: torch.Tensor) -> torch.Tensor:
+    """log of the standard normal PDF (utils.py:145-148)."""
+    return -0.5 * x.square() - _LOG_SQRT_2PI
+
+
+def log_erfc(x: torch.Tensor) -> torch.Tensor:
+    """log erfc(x) (utils.py:170-193): log erfcx(x) - x^2 for x > 0."""
+    _float_only(x, "log_erfc")
+    is_pos = x > 0
+    x_pos = x.masked_fill(~is_pos, 0)
+    x_neg = x.masked_fill(is_pos, 0)
+    return torch.where(is_pos, torch.log(torch.special.erfcx(x_pos)) - x_pos.square(),
+                       torch.log(torch.special.erfc(x_neg)))
+
+
+def log_erfcx(x: torch.Tensor) -> torch.Tensor:
+    """log erfcx(x) (utils.py:196-214): log erfc(x) + x^2 for x <= 0."""
+    is_pos = x > 0
+    x_pos = x.masked_fill(~is_pos, 0)
+    x_neg = x.masked_fill(is_pos, 0)
+    return torch.where(is_pos, torch.special.erfcx(x_pos).log(),
+                       torch.special.erfc(x_neg).log() + x.square())
+
+
+def log_ndtr(x: torch.Tensor) -> torch.Tensor:
+    """log Phi(x) with finite gradients far into the left tail (utils.py:151-167)."""
+    _float_only(x, "log_Phi")
+    return log_erfc(_NEG_INV_SQRT_2 * x) - _LOG_2
+
+
+log_Phi = log_ndtr
+
+
+def standard_normal_log_hazard(x: torch.Tensor) -> torch.Tensor:
+    """log(phi(x) / Phi(-x)) (utils.py:217-230)."""
+    return _LOG_TWO_INV_SQRT_2PI - log_erfcx(_INV_SQRT_2 * x)
+
+
+def log_prob_normal_in(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """log(Phi(b) - Phi(a)) for a < b (utils.py:233-257), on the left tail: the
+    pair is reflected where |b| > |a|."""
+    if not (a < b).all():
+        raise ValueError("Received input tensors a, b for which not all a < b.")
+    rev_cond = b.abs() > a.abs()
+    if rev_cond.any():
+        c = torch.where(rev_cond, -b, a)
+        b = torch.where(rev_cond, -a, b)
+        a = c
+    return logdiffexp(log_a=log_ndtr(a), log_b=log_ndtr(b))
+
+
+def ei_helper(u: torch.Tensor) -> torch.Tensor:
+    """phi(u) + u Phi(u) (analytic.py:968-972)."""
+    return phi(u) + u * ndtr(u)
+
+
+def _log_abs_u_Phi_div_phi(u: torch.Tensor) -> torch.Tensor:
+    """log(|u| Phi(u) / phi(u)) for u < 0 (analytic.py:1026-1053)."""
+    return torch.log(torch.special.erfcx(_NEG_INV_SQRT_2 * u) * u.abs()) + _LOG_SQRT_PI_DIV_2
+
+
+def log_ei_helper(u: torch.Tensor) -> torch.Tensor:
+    """log(phi(u) + u Phi(u)), finite with a finite gradient for |u| <= 1e100 in
+    fp64 (analytic.py:975-1023): the logarithm of the sum above u = -1;
+    log phi(u) + log1mexp(log(|u| Phi(u) / phi(u))) down to -1 / sqrt(eps)
+    (-1e6 in fp64, -1e3 in fp32); log phi(u) - 2 log |u| below."""
+    if not (u.dtype == torch.float32 or u.dtype == torch.float64):
+        raise TypeError(f"LogExpectedImprovement only supports torch.float32 and torch.float64 "
+                        f"dtypes, but received {u.dtype = }.")
+    bound = LOG_EI_UPPER
+    u_upper = u.masked_fill(u < bound, bound)
+    log_ei_upper = ei_helper(u_upper).log()
+    neg_inv_sqrt_eps = -1e6 if u.dtype == torch.float64 else -1e3
+    u_lower = u.masked_fill(u > bound, bound)
+    u_eps = u_lower.masked_fill(u < neg_inv_sqrt_eps, neg_inv_sqrt_eps)
+    w = _log_abs_u_Phi_div_phi(u_eps)
+    log_ei_lower = log_phi(u) + torch.where(u > neg_inv_sqrt_eps, log1mexp(w),
+                                            -2 * u_lower.abs().log())
+    return torch.where(u > bound, log_ei_upper, log_ei_lower)

@@ -1256,6 +1256,61 @@ typedef struct BoBaldArgs {
 int bo_bald_v(const BoBaldArgs* a, void* stream);
 int bo_bald_backward_v(const BoBaldArgs* a, void* stream);
 
+/* The analytic q = 1 acquisition family (botorch/acquisition/analytic.py:
+ * LogExpectedImprovement 357-420, LogConstrainedExpectedImprovement 528-608,
+ * the helpers 960-1053 and 1182-1220) as one chain on the posterior moments,
+ * one t-batch per row.  mean, var (Mt x R, row stride R, outcome space):
+ * member j of row i at [j R + i].  With s2 = max(var[obj], min_var) (the floor
+ * is taken where var <= min_var), sigma = sqrt(s2), bf = best_f[i best_f_stride]
+ * and u = w (mean[obj] - bf) / sigma:
+ *   BO_AN_LOG_EI  log_ei(u) + log sigma,  log_ei(u) = log(phi(u) + u Phi(u)):
+ *                 u > -1: the logarithm of the sum; -1e6 < u <= -1:
+ *                 log phi(u) + log1mexp(log(erfcx(-u / sqrt 2) |u|) + log sqrt(pi / 2));
+ *                 u <= -1e6: log phi(u) - 2 log |u|
+ *   BO_AN_EI      sigma (phi(u) + u Phi(u))
+ *   BO_AN_LOG_PI  log Phi(u): log(erfc(-u / sqrt 2) / 2) for u >= 0,
+ *                 log erfcx(-u / sqrt 2) - u^2 / 2 - log 2 below
+ *   BO_AN_PI      Phi(u)
+ *   BO_AN_UCB     w mean[obj] + sqrt(beta) sigma
+ *   BO_AN_STD     w sigma
+ * ncon <= BO_AN_CMAX constraints, each on its own member con_member[c] != obj
+ * with standard deviation s_c (the same floor): kind BO_AN_CON_LOWER adds
+ * log Phi((mean - lower) / s_c), BO_AN_CON_UPPER log Phi((upper - mean) / s_c),
+ * BO_AN_CON_BOTH log(Phi(b) - Phi(a)), a = (lower - mean) / s_c, b = (upper -
+ * mean) / s_c, taken on the left tail (a, b -> -b, -a when |b| > |a|), without
+ * a difference of logarithms.  The sum of these log probabilities is added to the
+ * two log modes; its exponential multiplies the other four.
+ * Backward, from dacq (R): dmean, dvar (Mt x R), analytic; every element is
+ * written (members no term reads get 0); on the floor dvar is 0.  With
+ * r = Phi / phi = sqrt(pi / 2) erfcx(-u / sqrt 2): d log_ei / du = r / (1 + u r),
+ * and for u < -5 the continued fraction -u + 2 / (-u + 3 / (-u + ...)) of the
+ * same quantity, which has no cancellation; d log Phi / dx = 1 / r for x < 0.
+ * Finite for |u| <= 1e100.
+ * 1 <= Mt <= 16, 0 <= R < 2^38 (R = 0 returns at once), min_var > 0, w = +-1,
+ * beta >= 0, best_f_stride 0 or 1, upper > lower on two-sided constraints.
+ * One thread per row, 256-thread blocks, no LDS, no atomics, no workspace:
+ * repeated calls are bitwise identical.  A pure addition to the ABI:
+ * BO_ABI_VERSION stays 11. */
+#define BO_AN_CMAX 15
+enum { BO_AN_LOG_EI = 0, BO_AN_EI = 1, BO_AN_LOG_PI = 2, BO_AN_PI = 3, BO_AN_UCB = 4,
+       BO_AN_STD = 5 };
+enum { BO_AN_CON_LOWER = 0, BO_AN_CON_UPPER = 1, BO_AN_CON_BOTH = 2 };
+typedef struct BoAnalyticArgs {
+  BO_STRUCT_HEADER;
+  int32_t mode, Mt, obj, ncon;
+  int32_t best_f_stride, _pad;
+  int64_t R;
+  const double *mean, *var, *best_f;
+  double w, beta, min_var;
+  int32_t con_member[BO_AN_CMAX + 1], con_kind[BO_AN_CMAX + 1];
+  double con_lower[BO_AN_CMAX + 1], con_upper[BO_AN_CMAX + 1];
+  double* acq;               /* forward: R */
+  const double* dacq;        /* backward: R */
+  double *dmean, *dvar;      /* backward: Mt x R */
+} BoAnalyticArgs;
+int bo_analytic_v(const BoAnalyticArgs* a, void* stream);
+int bo_analytic_backward_v(const BoAnalyticArgs* a, void* stream);
+
 typedef struct BoLbfgsStepArgs { /* bo_lbfgs_step */
   BO_STRUCT_HEADER;
   int32_t B, n, m, _pad;
