@@ -21,11 +21,10 @@
 // term is taken on the left tail as log phi(b) + log(r(b) - E r(a)),
 // E = exp((b^2 - a^2) / 2) <= 1, with the derivatives 1 / (.) and -E / (.): no
 // difference of two logarithms of size b^2 / 2.
-#include "common.h"
+#include "normal.h"
 
 namespace {
 
-constexpr double INV_SQRT2 = 0.70710678118654752440, INV_SQRT2PI = 0.39894228040143267794;
 constexpr double LOG_SQRT_2PI = 0.91893853320467274178, LOG_2 = 0.69314718055994530942;
 constexpr double SQRT_PI_DIV_2 = 1.25331413731550025121, LOG_SQRT_PI_DIV_2 = 0.22579135264472743236;
 constexpr double LOG_EI_UPPER = -1.0, LOG_EI_SERIES = -1e6;  // analytic.py:990, 1001
@@ -46,8 +45,6 @@ struct AnDev {
   double *dmean, *dvar;
 };
 
-__device__ __forceinline__ double phi(double x) { return INV_SQRT2PI * exp(-0.5 * x * x); }
-__device__ __forceinline__ double Phi(double x) { return 0.5 * erfc(-x * INV_SQRT2); }
 __device__ __forceinline__ double log_phi(double x) { return -0.5 * x * x - LOG_SQRT_2PI; }
 // Phi(x) / phi(x), x <= 0
 __device__ __forceinline__ double mills(double x) { return SQRT_PI_DIV_2 * erfcx(-x * INV_SQRT2); }

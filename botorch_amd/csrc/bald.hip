@@ -66,13 +66,6 @@ __host__ __device__ constexpr int bald_ep(int QP) {
   return e;
 }
 
-// the sum of v over the wave's 64 lanes, in every lane, in a fixed order
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // the sum of v over the workgroup's 256 threads in thread 0 (red: 4 doubles)
 __device__ __forceinline__ double block_sum(double v, double* red) {
   v = wave_sum(v);

@@ -48,6 +48,13 @@ __device__ __forceinline__ double row_bcast(double v) {
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
+// the sum of v over the wave's 64 lanes, in every lane, in a fixed order
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
 __device__ __forceinline__ v4d v4d_zero() {
   v4d z = {0.0, 0.0, 0.0, 0.0};
   return z;

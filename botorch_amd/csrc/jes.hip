@@ -12,10 +12,8 @@
 //   vt_ji  = s2_ji max(1 - (z + r) r, 1e-8) + tau2_j
 //   H[i]   = (1 / P) sum_j log(vt_ji) / 2
 //
-// Tile plan (that of paths.hip's all mode).  A wave owns 16 rows of X; lane l
-// works for row l & 15 on the training points of slot l >> 4: it forms the kernel
-// value from the squared distance (a runtime loop over d against the wave's
-// scaled rows in LDS) and hands it to v_mfma_f64_16x16x4 as its own B element,
+// Tile plan (the row tile and its lane layout: rowtile.h).  A wave owns 16 rows
+// of X; a lane's kernel value against a training point is its own B element,
 // with V as the A operand: D[optimum][row] += V[optimum][t] k[t][row].  The
 // accumulator leaves lane l with the optima (l >> 4) + 4 r of its own row, so the
 // k(x_i, x*_j) term and the whole elementwise chain run on it in registers.  A
@@ -32,16 +30,16 @@
 // dX[row][:] -= q[row][t] Xt[t][:] (with sum_t q x added at the end) -- the two
 // contractions of paths.hip's backward with G in the place of dout.  dmu and
 // dvar are the row sums of the chain's other two derivatives.
-#include "common.h"
+#include "normal.h"
+#include "rowtile.h"
 
 namespace {
 
 constexpr int THREADS = 256;
-constexpr int TR = 16;   // rows of X per wave
-constexpr int NT = 4;    // 16-optimum tiles per pass
+constexpr int TR = ROWTILE;  // rows of X per wave
+constexpr int NT = 4;        // 16-optimum tiles per pass
 constexpr int PB = 16 * NT;
 constexpr double S2_FLOOR = 1e-10, PHI_FLOOR = 1e-8, INNER_FLOOR = 1e-8;
-constexpr double INV_SQRT2 = 0.70710678118654752440, INV_SQRT2PI = 0.39894228040143267794;
 
 struct Dev {
   int kind, d, P;
@@ -53,21 +51,11 @@ struct Dev {
   double *dX, *dmu, *dvar;
 };
 
-// the wave's 16 rows divided by the lengthscale -> xs (row stride ldx, odd)
-__device__ __forceinline__ void load_rows(const Dev& a, int64_t r0, int lane, int ldx, double* xs) {
-  for (int e = lane; e < TR * a.d; e += BO_WAVE) {
-    const int rr = e / a.d, t = e - rr * a.d;
-    const int64_t r = r0 + rr;
-    xs[rr * ldx + t] = r < a.R ? a.X[r * a.d + t] / a.ls[t] : 0.0;
-  }
-}
-
 // acc[q][r] = sum_t V[jb + 16 q + (l >> 4) + 4 r][t] k(x_row, Xt_t) for the nt
 // tiles of the pass at jb (nt is uniform over the workgroup)
 template <int KIND>
 __device__ __forceinline__ void contract_v(const Dev& a, const double* xr, int jb, int nt, int row,
                                            int kk, v4d* acc) {
-  const int d = a.d;
   int64_t vrow[NT];  // the A operand's row: optimum jb + 16 q + row, or -1
 #pragma unroll
   for (int q = 0; q < NT; ++q) {
@@ -79,19 +67,7 @@ __device__ __forceinline__ void contract_v(const Dev& a, const double* xr, int j
     const int64_t ib = i0 + 4 * kk;
     const double* xt[4];
     double d2[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      xt[m] = a.Xts + (ib + m < a.n ? ib + m : 0) * d;
-      d2[m] = 0.0;
-    }
-    for (int t = 0; t < d; ++t) {
-      const double x = xr[t];
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const double df = x - xt[m][t];
-        d2[m] = fma(df, df, d2[m]);
-      }
-    }
+    rowtile_dist2x4<1>(xr, a.Xts, ib, a.n, a.d, xt, d2);
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
       const int64_t i = ib + m;
@@ -106,16 +82,6 @@ __device__ __forceinline__ void contract_v(const Dev& a, const double* xr, int j
       }
     }
   }
-}
-
-// squared distance of the lane's row to optimum j (scaled coordinates)
-__device__ __forceinline__ double dist2(const double* xr, const double* xo, int d) {
-  double d2 = 0.0;
-  for (int t = 0; t < d; ++t) {
-    const double df = xr[t] - xo[t];
-    d2 = fma(df, df, d2);
-  }
-  return d2;
 }
 
 struct Chain {
@@ -133,9 +99,9 @@ __device__ __forceinline__ Chain chain(double c, double mu, double var, double g
   const double s2 = s2_free ? s2u : S2_FLOOR;
   const double rs = 1.0 / sqrt(s2);
   const double z = (wf - w * (mu + c * g)) * rs;
-  const double Phi = 0.5 * erfc(-z * INV_SQRT2);
-  const bool phi_free = Phi > PHI_FLOOR;
-  const double r = INV_SQRT2PI * exp(-0.5 * z * z) / (phi_free ? Phi : PHI_FLOOR);
+  const double Pz = Phi(z);
+  const bool phi_free = Pz > PHI_FLOOR;
+  const double r = phi(z) / (phi_free ? Pz : PHI_FLOOR);
   const double inu = 1.0 - (z + r) * r;
   const bool in_free = inu > INNER_FLOOR;
   const double inner = in_free ? inu : INNER_FLOOR;
@@ -166,7 +132,7 @@ jes_forward_kernel(const Dev a) {
   const int d = a.d, ldx = d | 1;
   double* xs = smem + wave * TR * ldx;
   const int64_t r0 = ((int64_t)blockIdx.x * nw + wave) * TR;
-  load_rows(a, r0, lane, ldx, xs);
+  rowtile_load(a.X, a.ls, r0, TR, a.R, d, ldx, xs, lane, BO_WAVE);
   __syncthreads();
   if (r0 >= a.R) return;  // (wave-uniform, and no barrier follows)
   const int row = lane & 15, kk = lane >> 4;
@@ -185,7 +151,7 @@ jes_forward_kernel(const Dev a) {
         for (int r = 0; r < 4; ++r) {
           const int j = jb + 16 * q + mfma_row(lane, r);
           if (j < a.P) {
-            const double kx = kernel_from_d2<KIND>(dist2(xr, a.Xo + (int64_t)j * d, d));
+            const double kx = kernel_from_d2<KIND>(rowtile_dist2(xr, a.Xo + (int64_t)j * d, d));
             const double c = a.o * (kx - acc[q][r]);
             hs += chain<false>(c, mu, var, a.g[j], a.sinv[j], a.wf[j], a.tau2[j], a.w).h;
           }
@@ -193,9 +159,7 @@ jes_forward_kernel(const Dev a) {
       }
     }
   }
-  // the row's four slots, in a fixed order
-  hs += __shfl_xor(hs, 16);
-  hs += __shfl_xor(hs, 32);
+  hs = rowtile_fold4(hs);
   if (kk == 0 && rok) a.out[r0 + row] = hs / a.P;
 }
 
@@ -210,7 +174,7 @@ jes_backward_kernel(const Dev a) {
   double* xs = smem + wave * (TR * ldx + PB * TR);
   double* gs = xs + TR * ldx;  // G[optimum of the pass][row], the wave's own
   const int64_t r0 = ((int64_t)blockIdx.x * nw + wave) * TR;
-  load_rows(a, r0, lane, ldx, xs);
+  rowtile_load(a.X, a.ls, r0, TR, a.R, d, ldx, xs, lane, BO_WAVE);
   __syncthreads();
   // (every wave stays for the barriers below; rows past R are computed on
   // zeros and never written)
@@ -239,7 +203,7 @@ jes_backward_kernel(const Dev a) {
             const int jl = 16 * q + mfma_row(lane, r), j = jb + jl;
             const bool ok = j < a.P;
             const double* xo = a.Xo + (int64_t)(ok ? j : 0) * d;
-            const double d2 = dist2(xr, xo, d);
+            const double d2 = rowtile_dist2(xr, xo, d);
             double G = 0.0;
             if (ok) {
               const double c = a.o * (kernel_from_d2<KIND>(d2) - acc[q][r]);
@@ -253,12 +217,7 @@ jes_backward_kernel(const Dev a) {
             // the direct term: dX[row] += G dk(x_row, x*_j)
             const double qd = G * dkernel_factor<KIND>(d2, a.o);
             sumq += qd;
-#pragma unroll
-            for (int tt = 0; tt < NDT; ++tt) {
-              const int t = 16 * tt + row;  // B[k = l >> 4][t = l & 15]: the lane's own optimum
-              const double b = ok && t < d ? xo[t] : 0.0;
-              accd[tt] = mfma_f64(-qd, b, accd[tt]);
-            }
+            rowtile_dx_acc<NDT>(qd, ok, xo, d, row, accd);
           }
         }
       }
@@ -276,62 +235,30 @@ jes_backward_kernel(const Dev a) {
       }
       const double* xt[4];
       double d2[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int64_t i = i0 + kk + 4 * r;
-        xt[r] = a.Xts + (i < a.n ? i : 0) * d;
-        d2[r] = 0.0;
-      }
-      for (int t = 0; t < d; ++t) {
-        const double x = xr[t];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const double df = x - xt[r][t];
-          d2[r] = fma(df, df, d2[r]);
-        }
-      }
+      rowtile_dist2x4<4>(xr, a.Xts, i0 + kk, a.n, d, xt, d2);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const bool ok = i0 + kk + 4 * r < a.n;
         const double q = ok ? -cf[r] * dkernel_factor<KIND>(d2[r], a.o) : 0.0;
         sumq += q;
-#pragma unroll
-        for (int tt = 0; tt < NDT; ++tt) {
-          const int t = 16 * tt + row;
-          const double b = ok && t < d ? xt[r][t] : 0.0;
-          accd[tt] = mfma_f64(-q, b, accd[tt]);
-        }
+        rowtile_dx_acc<NDT>(q, ok, xt[r], d, row, accd);
       }
     }
     __syncthreads();  // gs is rewritten by the next pass
   }
-  sumq += __shfl_xor(sumq, 16);
-  sumq += __shfl_xor(sumq, 32);  // now every lane of row l & 15 holds the row's sum
-  smu += __shfl_xor(smu, 16);
-  smu += __shfl_xor(smu, 32);
-  svar += __shfl_xor(svar, 16);
-  svar += __shfl_xor(svar, 32);
+  smu = rowtile_fold4(smu);
+  svar = rowtile_fold4(svar);
   if (kk == 0 && rok) {
     a.dmu[r0 + row] = smu;
     a.dvar[r0 + row] = svar;
   }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int ro = mfma_row(lane, r);
-    const double sq = __shfl(sumq, ro);  // (all lanes take part)
-#pragma unroll
-    for (int tt = 0; tt < NDT; ++tt) {
-      const int t = 16 * tt + row;
-      if (t < d && r0 + ro < a.R)
-        a.dX[(r0 + ro) * d + t] = (accd[tt][r] + xs[ro * ldx + t] * sq) / a.ls[t];
-    }
-  }
+  rowtile_dx_store<NDT>(a.dX, accd, xs, ldx, rowtile_fold4(sumq), 1.0, a.ls, r0, a.R, d, lane);
 }
 
 int fill(const BoJesArgs* a, const char* who, Dev* v) {
-  BO_CHECK_ARG(a->kind == BO_RBF || a->kind == BO_MATERN52, "%s: unknown kernel kind %d", who,
-               a->kind);
-  BO_CHECK_ARG(a->d >= 1 && a->d <= 128, "%s: 1 <= d <= 128 (got %d)", who, a->d);
+  if (int st = rowtile_check_common(a->kind, a->d, a->n, a->Xt_scaled, a->V, a->outputscale, who);
+      st != BO_OK)
+    return st;
   BO_CHECK_ARG(a->P >= 1, "%s: P >= 1 (got %d)", who, a->P);
   BO_CHECK_ARG(a->R >= 1 && a->n >= 0, "%s: R >= 1, n >= 0", who);
   BO_CHECK_ARG(a->R < (int64_t(1) << 34), "%s: R too large", who);
@@ -339,9 +266,6 @@ int fill(const BoJesArgs* a, const char* who, Dev* v) {
                "required", who);
   BO_CHECK_ARG(a->g && a->sinv && a->wf && a->tau2, "%s: g, sinv, wf and tau2 are required", who);
   BO_CHECK_ARG(a->mu && a->var, "%s: mu and var are required", who);
-  BO_CHECK_ARG(a->n == 0 || (a->Xt_scaled && a->V), "%s: Xt_scaled and V are required when n > 0",
-               who);
-  BO_CHECK_ARG(a->outputscale >= 0.0, "%s: outputscale >= 0", who);
   BO_CHECK_ARG(a->w == 1.0 || a->w == -1.0, "%s: w must be +1 or -1", who);
   v->kind = a->kind;
   v->d = a->d;
@@ -396,19 +320,9 @@ extern "C" int bo_jes_backward_impl(const BoJesArgs* a, void* stream) {
   const int nw = v.d > 32 ? 2 : 4;
   const unsigned blocks = (unsigned)ceil_div(v.R, (int64_t)nw * TR);
   const size_t lds = sizeof(double) * (size_t)nw * (TR * (v.d | 1) + PB * TR);
-  const bool rbf = v.kind == BO_RBF;
 #define BO_JES(KIND, NDT) \
   jes_backward_kernel<KIND, NDT><<<blocks, nw * BO_WAVE, lds, as_stream(stream)>>>(v)
-#define BO_JES_K(NDT)                 \
-  do {                                \
-    if (rbf) BO_JES(BO_RBF, NDT);     \
-    else BO_JES(BO_MATERN52, NDT);    \
-  } while (0)
-  if (v.d <= 16) BO_JES_K(1);
-  else if (v.d <= 32) BO_JES_K(2);
-  else if (v.d <= 64) BO_JES_K(4);
-  else BO_JES_K(8);
-#undef BO_JES_K
+  ROWTILE_DISPATCH(v.kind, v.d, BO_JES);
 #undef BO_JES
   BO_LAUNCH_CHECK();
   return BO_OK;

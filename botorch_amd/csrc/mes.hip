@@ -20,25 +20,14 @@
 //
 // bo_mv_quantiles: one workgroup per quantile, a bisection with one block
 // reduction per iteration (fixed order), one launch.
-#include "common.h"
+#include "normal.h"
 
 namespace {
 
 constexpr double CLAMP_LB = 1e-8;
-constexpr double INV_SQRT2 = 0.70710678118654752440, INV_SQRT2PI = 0.39894228040143267794;
 constexpr double LOG_2PI = 1.83787706640934548356;
 constexpr double VDET_EPS = (1.0 + 1e-12) - 1.0;
 constexpr int MES_SM_MAX = 1024, MES_SY_MAX = 4096, GIBBON_MMAX = 15;
-
-__device__ __forceinline__ double Phi(double x) { return 0.5 * erfc(-x * INV_SQRT2); }
-__device__ __forceinline__ double phi(double x) { return INV_SQRT2PI * exp(-0.5 * x * x); }
-
-// the sum of v over the wave's 64 lanes, in every lane, in a fixed order
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // ---- MES ---------------------------------------------------------------------------------
 struct MesDev {

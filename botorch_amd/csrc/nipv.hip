@@ -10,7 +10,8 @@
 // with k the kernel without its outputscale o.  Neither C (R x N) nor the
 // kernel rows (R x n) reach memory.
 //
-// Tile plan.  A workgroup of four waves owns one tile of 16 rows of X -- the
+// Tile plan (the row tile and its lane layout: rowtile.h; here the tile belongs
+// to the workgroup).  A workgroup of four waves owns one tile of 16 rows of X -- the
 // floor(16 / q) t-batches that fit, so no t-batch straddles a tile -- and one
 // slice of Z (blockIdx.y).  The slice is walked in passes of 128 points: wave w
 // owns the 16-point tiles w and w + 4 of the pass (four tiles per wave would
@@ -40,13 +41,13 @@
 // through LDS in wave order, the slices' through the workspace in slice order.
 #include <algorithm>
 
-#include "common.h"
+#include "rowtile.h"
 
 namespace {
 
 constexpr int THREADS = 256;
 constexpr int NW = THREADS / BO_WAVE;  // waves per workgroup
-constexpr int TR = 16;                 // rows of X per workgroup
+constexpr int TR = ROWTILE;            // rows of X per workgroup
 constexpr int NT = 2;                  // 16-point tiles of Z per wave and pass
 constexpr int PZ = 16 * NT * NW;       // integration points per pass
 constexpr int TC = 16 * NW;            // training points per shared chunk
@@ -67,26 +68,6 @@ struct Dev {
   double* part;  // split > 1: the slices' partial outputs
 };
 
-// the tile's 16 rows divided by the lengthscale -> xs (row stride ldx, odd);
-// rows past the tile's t-batches or past R are zeros
-__device__ __forceinline__ void load_rows(const Dev& a, int64_t r0, int ldx, double* xs) {
-  const int nr = a.tb * a.q;
-  for (int e = threadIdx.x; e < TR * a.d; e += THREADS) {
-    const int rr = e / a.d, t = e - rr * a.d;
-    const int64_t r = r0 + rr;
-    xs[rr * ldx + t] = rr < nr && r < a.R ? a.X[r * a.d + t] / a.ls[t] : 0.0;
-  }
-}
-
-__device__ __forceinline__ double dist2(const double* xr, const double* xo, int d) {
-  double d2 = 0.0;
-  for (int t = 0; t < d; ++t) {
-    const double df = xr[t] - xo[t];
-    d2 = fma(df, df, d2);
-  }
-  return d2;
-}
-
 // number of the wave's tiles 16 (wave + NW qq) of the pass at zp that begin
 // before zend (wave-uniform)
 __device__ __forceinline__ int wave_tiles(int64_t zp, int64_t zend, int wave) {
@@ -102,7 +83,7 @@ __device__ __forceinline__ int wave_tiles(int64_t zp, int64_t zend, int wave) {
 template <int KIND>
 __device__ __forceinline__ void contract_v(const Dev& a, const double* xr, double* ks, int64_t zp,
                                            int64_t zend, int ntw, int lane, int wave, v4d* acc) {
-  const int d = a.d, row = lane & 15, kk = lane >> 4;
+  const int row = lane & 15, kk = lane >> 4;
   const double* vp[NT];  // the A operand's row of V, or null
 #pragma unroll
   for (int qq = 0; qq < NT; ++qq) {
@@ -115,19 +96,7 @@ __device__ __forceinline__ void contract_v(const Dev& a, const double* xr, doubl
       const int64_t ib = c0 + 16 * wave + kk;
       const double* xt[4];
       double d2[4];
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        xt[m] = a.Xts + (ib + 4 * m < a.n ? ib + 4 * m : 0) * d;
-        d2[m] = 0.0;
-      }
-      for (int t = 0; t < d; ++t) {
-        const double x = xr[t];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-          const double df = x - xt[m][t];
-          d2[m] = fma(df, df, d2[m]);
-        }
-      }
+      rowtile_dist2x4<4>(xr, a.Xts, ib, a.n, a.d, xt, d2);
 #pragma unroll
       for (int m = 0; m < 4; ++m)
         ks[wave * KSLOT + (kk + 4 * m) * TR + row] =
@@ -161,7 +130,7 @@ nipv_gram_kernel(const Dev a) {
   double* ks = xs + TR * ldx;
   const int64_t tile = blockIdx.x, r0 = tile * nr;
   const int64_t z0 = (int64_t)blockIdx.y * a.zlen, zend = min(a.N, z0 + a.zlen);
-  load_rows(a, r0, ldx, xs);
+  rowtile_load(a.X, a.ls, r0, nr, a.R, d, ldx, xs, threadIdx.x, THREADS);
   __syncthreads();
   const int row = lane & 15;
   const double* xr = xs + row * ldx;
@@ -178,7 +147,7 @@ nipv_gram_kernel(const Dev a) {
           const int64_t z = zp + 16 * (wave + NW * qq) + mfma_row(lane, r);
           double c = 0.0;
           if (z < zend)
-            c = a.o * (kernel_from_d2<KIND>(dist2(xr, a.Zs + z * d, d)) - acc[qq][r]);
+            c = a.o * (kernel_from_d2<KIND>(rowtile_dist2(xr, a.Zs + z * d, d)) - acc[qq][r]);
           g = mfma_f64(c, c, g);
         }
       }
@@ -220,7 +189,7 @@ nipv_gram_backward_kernel(const Dev a) {
   double* gs = ks + KS;  // C, then dC, of the pass: [z of the pass][row], stride LDG
   const int64_t tile = blockIdx.x, r0 = tile * nr;
   const int64_t z0 = (int64_t)blockIdx.y * a.zlen, zend = min(a.N, z0 + a.zlen);
-  load_rows(a, r0, ldx, xs);
+  rowtile_load(a.X, a.ls, r0, nr, a.R, d, ldx, xs, threadIdx.x, THREADS);
   __syncthreads();
   const int row = lane & 15, kk = lane >> 4;
   const double* xr = xs + row * ldx;
@@ -259,7 +228,7 @@ nipv_gram_backward_kernel(const Dev a) {
           double c = 0.0;
           d2v[qq][r] = 0.0;
           if (ok) {
-            d2v[qq][r] = dist2(xr, a.Zs + (zp + zl) * d, d);
+            d2v[qq][r] = rowtile_dist2(xr, a.Zs + (zp + zl) * d, d);
             c = a.o * (kernel_from_d2<KIND>(d2v[qq][r]) - acc[qq][r]);
           }
           gs[zl * LDG + row] = c;
@@ -293,12 +262,7 @@ nipv_gram_backward_kernel(const Dev a) {
           const double* zo = a.Zs + (ok ? zp + zl : 0) * d;
           const double qd = G * dkernel_factor<KIND>(d2v[qq][r], a.o);
           sumq += qd;
-#pragma unroll
-          for (int tt = 0; tt < NDT; ++tt) {
-            const int t = 16 * tt + row;  // B[k = l >> 4][t = l & 15]: the lane's own point
-            const double b = ok && t < d ? zo[t] : 0.0;
-            accd[tt] = mfma_f64(-qd, b, accd[tt]);
-          }
+          rowtile_dx_acc<NDT>(qd, ok, zo, d, row, accd);
         }
       }
     }
@@ -314,37 +278,18 @@ nipv_gram_backward_kernel(const Dev a) {
       }
       const double* xt[4];
       double d2[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int64_t i = i0 + kk + 4 * r;
-        xt[r] = a.Xts + (i < a.n ? i : 0) * d;
-        d2[r] = 0.0;
-      }
-      for (int t = 0; t < d; ++t) {
-        const double x = xr[t];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const double df = x - xt[r][t];
-          d2[r] = fma(df, df, d2[r]);
-        }
-      }
+      rowtile_dist2x4<4>(xr, a.Xts, i0 + kk, a.n, d, xt, d2);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const bool ok = i0 + kk + 4 * r < a.n;
         const double q = ok ? -cf[r] * dkernel_factor<KIND>(d2[r], a.o) : 0.0;
         sumq += q;
-#pragma unroll
-        for (int tt = 0; tt < NDT; ++tt) {
-          const int t = 16 * tt + row;
-          const double b = ok && t < d ? xt[r][t] : 0.0;
-          accd[tt] = mfma_f64(-q, b, accd[tt]);
-        }
+        rowtile_dx_acc<NDT>(q, ok, xt[r], d, row, accd);
       }
     }
     __syncthreads();  // gs is rewritten by the next pass
   }
-  sumq += __shfl_xor(sumq, 16);
-  sumq += __shfl_xor(sumq, 32);  // now every lane of row l & 15 holds the wave's sum for the row
+  sumq = rowtile_fold4(sumq);  // the wave's sum for the row
   // the four waves' tiles in wave order (same lane layout in every wave)
   double* red = gs;             // NDT x 4 x 64
   double* rs = gs + NDT * 256;  // 16 row sums
@@ -378,9 +323,9 @@ nipv_gram_backward_kernel(const Dev a) {
 }
 
 int fill(const BoNipvArgs* a, const char* who, Dev* v) {
-  BO_CHECK_ARG(a->kind == BO_RBF || a->kind == BO_MATERN52, "%s: unknown kernel kind %d", who,
-               a->kind);
-  BO_CHECK_ARG(a->d >= 1 && a->d <= 128, "%s: 1 <= d <= 128 (got %d)", who, a->d);
+  if (int st = rowtile_check_common(a->kind, a->d, a->n, a->Xt_scaled, a->V, a->outputscale, who);
+      st != BO_OK)
+    return st;
   BO_CHECK_ARG(a->N >= 1, "%s: N >= 1 (got %lld)", who, (long long)a->N);
   BO_CHECK_ARG(a->R >= 1 && a->n >= 0, "%s: R >= 1, n >= 0", who);
   BO_CHECK_ARG(a->q >= 1 && a->q <= 16, "%s: 1 <= q <= 16 (got %d)", who, a->q);
@@ -393,9 +338,6 @@ int fill(const BoNipvArgs* a, const char* who, Dev* v) {
                MAX_SPLIT, a->split);
   BO_CHECK_ARG(a->X && a->lengthscale && a->Z_scaled, "%s: X, lengthscale and Z_scaled are "
                "required", who);
-  BO_CHECK_ARG(a->n == 0 || (a->Xt_scaled && a->V), "%s: Xt_scaled and V are required when n > 0",
-               who);
-  BO_CHECK_ARG(a->outputscale >= 0.0, "%s: outputscale >= 0", who);
   v->kind = a->kind;
   v->d = a->d;
   v->q = a->q;
@@ -468,18 +410,8 @@ extern "C" int bo_nipv_gram_backward_impl(const BoNipvArgs* a, void* stream) {
   const dim3 grid((unsigned)ceil_div(v.B, v.tb), (unsigned)v.split);
   // rows + kernel chunk + the pass's dC: at most 41.6 KiB of LDS
   const size_t lds = sizeof(double) * (size_t)(TR * (v.d | 1) + KS + PZ * LDG);
-  const bool rbf = v.kind == BO_RBF;
 #define BO_NIPV(KIND, NDT) nipv_gram_backward_kernel<KIND, NDT><<<grid, THREADS, lds, st>>>(v)
-#define BO_NIPV_K(NDT)               \
-  do {                               \
-    if (rbf) BO_NIPV(BO_RBF, NDT);   \
-    else BO_NIPV(BO_MATERN52, NDT);  \
-  } while (0)
-  if (v.d <= 16) BO_NIPV_K(1);
-  else if (v.d <= 32) BO_NIPV_K(2);
-  else if (v.d <= 64) BO_NIPV_K(4);
-  else BO_NIPV_K(8);
-#undef BO_NIPV_K
+  ROWTILE_DISPATCH(v.kind, v.d, BO_NIPV);
 #undef BO_NIPV
   BO_LAUNCH_CHECK();
   if (v.part) {

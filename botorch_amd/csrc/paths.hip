@@ -11,13 +11,12 @@
 //   mapped (inner >= 1): out[r]   = f_p(X_r), p = (r / inner) % S
 //   backward: dX[r][t] = sum_s dout[s][r] df_s/dx_t(X_r) over the paths of row r
 //
-// Tile plan.  A wave owns 16 rows of X for the whole feature range; a workgroup
-// is 4 such waves (2 when d > 64, for the LDS), and the grid is plain tiles of
-// rows.  Lane l works for row l & 15 on the features of slot l >> 4: it forms the
-// phase (a runtime loop over d against the wave's scaled rows in LDS), takes
-// sincos, or the kernel value from the squared distance, and hands the number
-// straight to v_mfma_f64_16x16x4 as the lane's own operand element: the
-// sin / cos features and the kernel row never leave the registers.
+// Tile plan (the row tile and its lane layout: rowtile.h).  A wave owns 16 rows
+// of X for the whole feature range; a workgroup is 4 such waves (2 when d > 64,
+// for the LDS), and the grid is plain tiles of rows.  A lane's number per
+// feature is sincos of the phase (a runtime loop over d, like the squared
+// distance), or the kernel value: the sin / cos features and the kernel row
+// never leave the registers.
 //   forward, all:  D[s][row] += W[s][k] feat[k][row]   (A = W, B = features),
 //                  16 features per step, a lane's four at 4 (l >> 4) + m so
 //                  that its W elements are 32 contiguous bytes; S in tiles of
@@ -31,12 +30,12 @@
 //                  (resp. -q Xt_scaled[k][t], with sum_k q x_t added at the end).
 // No atomics and a fixed order of every sum: bitwise reproducible.  No global
 // workspace at all.
-#include "common.h"
+#include "rowtile.h"
 
 namespace {
 
 constexpr int THREADS = 256;
-constexpr int TR = 16;  // rows of X per wave
+constexpr int TR = ROWTILE;  // rows of X per wave
 
 struct Dev {
   int kind, d, S, H;
@@ -48,15 +47,6 @@ struct Dev {
   double* dX;
 };
 
-// the wave's 16 rows divided by the lengthscale -> xs (row stride ldx, odd)
-__device__ __forceinline__ void load_rows(const Dev& a, int64_t r0, int lane, int ldx, double* xs) {
-  for (int e = lane; e < TR * a.d; e += BO_WAVE) {
-    const int rr = e / a.d, t = e - rr * a.d;
-    const int64_t r = r0 + rr;
-    xs[rr * ldx + t] = r < a.R ? a.X[r * a.d + t] / a.ls[t] : 0.0;
-  }
-}
-
 // NT: 16-path tiles per workgroup (all mode); MAPPED: one path per row
 template <int KIND, int NT, bool MAPPED>
 __global__ __launch_bounds__(THREADS) void paths_forward_kernel(const Dev a) {
@@ -65,7 +55,7 @@ __global__ __launch_bounds__(THREADS) void paths_forward_kernel(const Dev a) {
   const int d = a.d, H = a.H, M = 2 * a.H, ldx = d | 1;
   double* xs = smem + wave * TR * ldx;
   const int64_t r0 = ((int64_t)blockIdx.x * nw + wave) * TR;
-  load_rows(a, r0, lane, ldx, xs);
+  rowtile_load(a.X, a.ls, r0, TR, a.R, d, ldx, xs, lane, BO_WAVE);
   __syncthreads();
   if (r0 >= a.R) return;  // (wave-uniform, and no barrier follows)
   const int row = lane & 15, kk = lane >> 4;
@@ -131,19 +121,7 @@ __global__ __launch_bounds__(THREADS) void paths_forward_kernel(const Dev a) {
     const int64_t ib = i0 + 4 * kk;
     const double* xt[4];
     double d2[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      xt[m] = a.Xts + (ib + m < a.n ? ib + m : 0) * d;
-      d2[m] = 0.0;
-    }
-    for (int t = 0; t < d; ++t) {
-      const double x = xr[t];
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const double df = x - xt[m][t];
-        d2[m] = fma(df, df, d2[m]);
-      }
-    }
+    rowtile_dist2x4<1>(xr, a.Xts, ib, a.n, d, xt, d2);
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
       const int64_t i = ib + m;
@@ -163,10 +141,8 @@ __global__ __launch_bounds__(THREADS) void paths_forward_kernel(const Dev a) {
 
   if (MAPPED) {
     // the row's four feature slots, in a fixed order
-    sp += __shfl_xor(sp, 16);
-    sp += __shfl_xor(sp, 32);
-    su += __shfl_xor(su, 16);
-    su += __shfl_xor(su, 32);
+    sp = rowtile_fold4(sp);
+    su = rowtile_fold4(su);
     if (kk == 0 && r0 + row < a.R)
       a.out[r0 + row] = a.ymean + a.ystd * (a.c + a.pscale * sp + a.o * su);
   } else {
@@ -191,7 +167,7 @@ __global__ __launch_bounds__(THREADS) void paths_backward_kernel(const Dev a) {
   const int d = a.d, H = a.H, M = 2 * a.H, ldx = d | 1;
   double* xs = smem + wave * TR * ldx;
   const int64_t r0 = ((int64_t)blockIdx.x * nw + wave) * TR;
-  load_rows(a, r0, lane, ldx, xs);
+  rowtile_load(a.X, a.ls, r0, TR, a.R, d, ldx, xs, lane, BO_WAVE);
   __syncthreads();
   if (r0 >= a.R) return;  // (wave-uniform, and no barrier follows)
   const int row = lane & 15, kk = lane >> 4;
@@ -254,12 +230,7 @@ __global__ __launch_bounds__(THREADS) void paths_backward_kernel(const Dev a) {
       sincos(th[r], &sn, &cs);
       // d/dtheta (wa sin + wb cos); ca = cb = 0 past the end
       const double q = a.pscale * (ca[r] * cs - cb[r] * sn);
-#pragma unroll
-      for (int tt = 0; tt < NDT; ++tt) {
-        const int t = 16 * tt + row;  // B[k = l >> 4][t = l & 15]: the lane's own feature
-        const double b = ok && t < d ? om[r][t] : 0.0;
-        accd[tt] = mfma_f64(q, b, accd[tt]);
-      }
+      rowtile_dx_acc<NDT>(-q, ok, om[r], d, row, accd);  // dX[row][:] += q Omega[k][:]
     }
   }
 
@@ -269,62 +240,28 @@ __global__ __launch_bounds__(THREADS) void paths_backward_kernel(const Dev a) {
     coefs(a.V, a.n, i0, a.n, cv);
     const double* xt[4];
     double d2[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int64_t i = i0 + kk + 4 * r;
-      xt[r] = a.Xts + (i < a.n ? i : 0) * d;
-      d2[r] = 0.0;
-    }
-    for (int t = 0; t < d; ++t) {
-      const double x = xr[t];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const double df = x - xt[r][t];
-        d2[r] = fma(df, df, d2[r]);
-      }
-    }
+    rowtile_dist2x4<4>(xr, a.Xts, i0 + kk, a.n, d, xt, d2);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const bool ok = i0 + kk + 4 * r < a.n;
       const double q = ok ? cv[r] * dkernel_factor<KIND>(d2[r], a.o) : 0.0;
       sumq += q;
-#pragma unroll
-      for (int tt = 0; tt < NDT; ++tt) {
-        const int t = 16 * tt + row;
-        const double b = ok && t < d ? xt[r][t] : 0.0;
-        accd[tt] = mfma_f64(-q, b, accd[tt]);
-      }
+      rowtile_dx_acc<NDT>(q, ok, xt[r], d, row, accd);
     }
   }
-  sumq += __shfl_xor(sumq, 16);
-  sumq += __shfl_xor(sumq, 32);  // now every lane of row l & 15 holds the row's sum
-
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int ro = mfma_row(lane, r);
-    const double sq = __shfl(sumq, ro);  // (all lanes take part)
-#pragma unroll
-    for (int tt = 0; tt < NDT; ++tt) {
-      const int t = 16 * tt + row;
-      if (t < d && r0 + ro < a.R)
-        a.dX[(r0 + ro) * d + t] = a.ystd * (accd[tt][r] + xs[ro * ldx + t] * sq) / a.ls[t];
-    }
-  }
+  rowtile_dx_store<NDT>(a.dX, accd, xs, ldx, rowtile_fold4(sumq), a.ystd, a.ls, r0, a.R, d, lane);
 }
 
 int fill(const BoPathsArgs* a, const char* who, Dev* v) {
-  BO_CHECK_ARG(a->kind == BO_RBF || a->kind == BO_MATERN52, "%s: unknown kernel kind %d", who,
-               a->kind);
-  BO_CHECK_ARG(a->d >= 1 && a->d <= 128, "%s: 1 <= d <= 128 (got %d)", who, a->d);
+  if (int st = rowtile_check_common(a->kind, a->d, a->n, a->Xt_scaled, a->V, a->outputscale, who);
+      st != BO_OK)
+    return st;
   BO_CHECK_ARG(a->M >= 2 && a->M % 2 == 0, "%s: M must be even and >= 2 (got %d)", who, a->M);
   BO_CHECK_ARG(a->S >= 1 && a->R >= 0 && a->n >= 0 && a->inner >= 0,
                "%s: S >= 1, R >= 0, n >= 0, inner >= 0", who);
   BO_CHECK_ARG(a->R < (int64_t(1) << 34), "%s: R too large", who);
   BO_CHECK_ARG(a->X && a->lengthscale && a->Omega && a->W, "%s: X, lengthscale, Omega and W are required",
                who);
-  BO_CHECK_ARG(a->n == 0 || (a->Xt_scaled && a->V), "%s: Xt_scaled and V are required when n > 0",
-               who);
-  BO_CHECK_ARG(a->outputscale >= 0.0, "%s: outputscale >= 0", who);
   v->kind = a->kind;
   v->d = a->d;
   v->S = a->S;
@@ -397,21 +334,14 @@ extern "C" int bo_paths_eval_backward_impl(const BoPathsArgs* a, void* stream) {
   BO_CHECK_ARG(a->dout && a->dX, "bo_paths_eval_backward: dout and dX are required");
   if (v.R == 0) return BO_OK;
   const Geo g = geometry(v);
-  const bool rbf = v.kind == BO_RBF, mapped = v.inner > 0;
-#define BO_PATHS(KIND, NDT, MAPPED)                                                      \
+#define BO_PATHS(KIND, NDT, MAPPED) \
   paths_backward_kernel<KIND, NDT, MAPPED><<<g.blocks, g.threads, g.lds, as_stream(stream)>>>(v)
-#define BO_PATHS_K(NDT)                                      \
-  do {                                                       \
-    if (rbf && mapped) BO_PATHS(BO_RBF, NDT, true);          \
-    else if (rbf) BO_PATHS(BO_RBF, NDT, false);              \
-    else if (mapped) BO_PATHS(BO_MATERN52, NDT, true);       \
-    else BO_PATHS(BO_MATERN52, NDT, false);                  \
-  } while (0)
-  if (v.d <= 16) BO_PATHS_K(1);
-  else if (v.d <= 32) BO_PATHS_K(2);
-  else if (v.d <= 64) BO_PATHS_K(4);
-  else BO_PATHS_K(8);
-#undef BO_PATHS_K
+#define BO_PATHS_ALL(KIND, NDT) BO_PATHS(KIND, NDT, false)
+#define BO_PATHS_MAPPED(KIND, NDT) BO_PATHS(KIND, NDT, true)
+  if (v.inner > 0) ROWTILE_DISPATCH(v.kind, v.d, BO_PATHS_MAPPED);
+  else ROWTILE_DISPATCH(v.kind, v.d, BO_PATHS_ALL);
+#undef BO_PATHS_MAPPED
+#undef BO_PATHS_ALL
 #undef BO_PATHS
   BO_LAUNCH_CHECK();
   return BO_OK;
