@@ -17,7 +17,8 @@ _EXPORTS = {"FullyBayesianAcquisitionFunction": "acquisition",
             "LogConstrainedExpectedImprovement": "acquisition",
             "ConstrainedExpectedImprovement": "acquisition",
             "PosteriorStandardDeviation": "acquisition",
-            "ScalarizedPosteriorMean": "acquisition"}
+            "ScalarizedPosteriorMean": "acquisition",
+            "fit_fully_bayesian_model_nuts": "fit"}
 __all__ = sorted(_EXPORTS)
 
 

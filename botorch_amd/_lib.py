@@ -335,6 +335,12 @@ class AnalyticArgs(_Args):
                        ("dmean", _D), ("dvar", _D)]
 
 
+class SaasPotentialArgs(_Args):
+    _fields_ = _HDR + [("d", c_int32), ("_pad", c_int32), ("n", c_int64), ("C", c_int64),
+                       ("X", _D), ("y", _D), ("z", _D), ("U", _D), ("grad", _D), ("status", _D),
+                       ("work", _D), ("work_size", c_int64)]
+
+
 class LbfgsStepArgs(_Args):
     _fields_ = _HDR + [("B", c_int32), ("n", c_int32), ("m", c_int32), ("_pad", c_int32),
                        ("x", _D), ("f", _D), ("g", _D), ("xt", _D), ("ft", _D), ("gt", _D),
@@ -367,8 +373,10 @@ for _name, _cls in (("bo_post_partials_v", PostPartialsArgs), ("bo_qmc_finalize_
                     ("bo_nipv_gram_v", NipvArgs), ("bo_nipv_gram_backward_v", NipvArgs),
                     ("bo_bald_v", BaldArgs), ("bo_bald_backward_v", BaldArgs),
                     ("bo_analytic_v", AnalyticArgs), ("bo_analytic_backward_v", AnalyticArgs),
+                    ("bo_saas_potential_v", SaasPotentialArgs),
                     ("bo_lbfgs_step_v", LbfgsStepArgs), ("bo_lbfgsb_step_v", LbfgsbArgs)):
     _SIGNATURES[_name] = (c_int, [POINTER(_cls), _P])
+_SIGNATURES["bo_saas_potential_work"] = (c_int, [c_int64, c_int, c_int64, POINTER(c_int64)])
 _SIGNATURES["bo_struct_size"] = (c_int64, [ctypes.c_char_p])
 _SIGNATURES["bo_post_backward_jobs"] = (c_int, [c_int, POINTER(POINTER(PostBackwardArgs)), _P, _P])
 ARG_RECORDS = {"BoPostPartialsArgs": PostPartialsArgs, "BoQmcFinalizeArgs": QmcFinalizeArgs,
@@ -378,6 +386,7 @@ ARG_RECORDS = {"BoPostPartialsArgs": PostPartialsArgs, "BoQmcFinalizeArgs": QmcF
                "BoPathsArgs": PathsArgs, "BoJesArgs": JesArgs, "BoMesArgs": MesArgs,
                "BoGibbonArgs": GibbonArgs, "BoMvQuantilesArgs": MvQuantilesArgs,
                "BoNipvArgs": NipvArgs, "BoBaldArgs": BaldArgs, "BoAnalyticArgs": AnalyticArgs,
+               "BoSaasPotentialArgs": SaasPotentialArgs,
                "BoLbfgsStepArgs": LbfgsStepArgs, "BoLbfgsbArgs": LbfgsbArgs}
 
 _lib = None

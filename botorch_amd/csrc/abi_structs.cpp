@@ -101,6 +101,14 @@ int bo_bald_backward_impl(const BoBaldArgs* a, void* stream);
 int bo_analytic_impl(const BoAnalyticArgs* a, void* stream);
 int bo_analytic_backward_impl(const BoAnalyticArgs* a, void* stream);
 
+// the SAAS potential and its gradient for NUTS (saas_nuts.hip)
+int bo_saas_potential_impl(const BoSaasPotentialArgs* a, void* stream);
+
+int bo_saas_potential_v(const BoSaasPotentialArgs* a, void* stream) {
+  if (!header_ok(a, "bo_saas_potential_v")) return BO_ERR_ARG;
+  return bo_saas_potential_impl(a, stream);
+}
+
 int bo_post_partials_v(const BoPostPartialsArgs* a, void* stream) {
   if (!header_ok(a, "bo_post_partials_v")) return BO_ERR_ARG;
   return bo_post_partials_layout(a->kind, a->Xq, a->B, a->q, a->d, a->Xt_scaled, a->n, a->U,
@@ -298,6 +306,7 @@ extern "C" int64_t bo_struct_size(const char* name) {
   if (s == "BoNipvArgs") return sizeof(BoNipvArgs);
   if (s == "BoBaldArgs") return sizeof(BoBaldArgs);
   if (s == "BoAnalyticArgs") return sizeof(BoAnalyticArgs);
+  if (s == "BoSaasPotentialArgs") return sizeof(BoSaasPotentialArgs);
   if (s == "BoLbfgsStepArgs") return sizeof(BoLbfgsStepArgs);
   if (s == "BoLbfgsbArgs") return sizeof(BoLbfgsbArgs);
   return -1;

@@ -1176,9 +1176,51 @@ std::vector<at::Tensor> analytic_backward_native(
   return {dmean, dvar};
 }
 
+// [U (C), grad (C x (d + 4)), status (C, int32)] of the SAAS potential at the
+// rows of z (bo_saas_potential_v); work: a caller-kept workspace, or none.
+std::vector<at::Tensor> saas_potential_native(const at::Tensor& z, const at::Tensor& X,
+                                              const at::Tensor& y,
+                                              const c10::optional<at::Tensor>& work) {
+  const char* who = "bo::saas_potential_native";
+  mes_dense(who, {&z, &X, &y});
+  TORCH_CHECK(z.dim() == 2 && X.dim() == 2 && y.dim() == 1 && z.size(1) == X.size(1) + 4 &&
+                  y.size(0) == X.size(0), who, ": z must be C x (d + 4), X n x d and y n");
+  TORCH_CHECK(X.size(1) <= INT32_MAX, who, ": d out of range");
+  BoSaasPotentialArgs a{};
+  a.struct_size = sizeof(a);
+  a.abi_version = BO_ABI_VERSION;
+  a.d = static_cast<int32_t>(X.size(1));
+  a.n = X.size(0);
+  a.C = z.size(0);
+  int64_t need = 0;
+  ck(bo_saas_potential_work(a.n, a.d, a.C, &need), "saas_potential_work");
+  at::Tensor ws;
+  if (work.has_value() && work->defined()) {
+    mes_dense(who, {&*work});
+    TORCH_CHECK(work->numel() >= need, who, ": work must hold ", need, " doubles");
+    ws = *work;
+  } else {
+    ws = at::empty({std::max<int64_t>(need, 1)}, z.options());
+  }
+  at::Tensor U = at::empty({a.C}, z.options()), grad = at::empty({a.C, z.size(1)}, z.options()),
+             status = at::empty({a.C}, z.options().dtype(at::kInt));
+  a.X = cp(X);
+  a.y = cp(y);
+  a.z = cp(z);
+  a.U = mp(U);
+  a.grad = mp(grad);
+  a.status = status.data_ptr<int32_t>();
+  a.work = ws.data_ptr<double>();
+  a.work_size = ws.numel();
+  ck(bo_saas_potential_v(&a, c10::hip::getCurrentHIPStream(z.device().index()).stream()),
+     "saas_potential");
+  return {U, grad, status};
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(bo, m) {
+  m.def("saas_potential_native(Tensor z, Tensor X, Tensor y, Tensor? work) -> Tensor[]");
   m.def("analytic_native(Tensor mean, Tensor var, Tensor? best_f, int mode, int obj, float w, "
         "float beta, float min_var, int[] con_member, float[] con_lower, float[] con_upper, "
         "int[] con_kind) -> Tensor");
@@ -1242,4 +1284,5 @@ TORCH_LIBRARY_IMPL(bo, CUDA, m) {
   m.impl("mv_quantiles_native", &mv_quantiles_native);
   m.impl("analytic_native", &analytic_native);
   m.impl("analytic_backward_native", &analytic_backward_native);
+  m.impl("saas_potential_native", &saas_potential_native);
 }

@@ -581,3 +581,42 @@ def _fit_fallback(mll, *, closure=None, optimizer=fit_gpytorch_mll_scipy, closur
     if debug.off():
         msg += " For more information, try enabling botorch.settings.debug mode."
     raise ModelFittingError(msg)
+
+
+def fit_fully_bayesian_model_nuts(model, max_tree_depth: int = 6, warmup_steps: int = 512,
+                                  num_samples: int = 256, thinning: int = 16,
+                                  disable_progbar: bool = False, jit_compile: bool = False, *,
+                                  num_chains: int = 1, seed: Optional[int] = None) -> None:
+    """Fit a SaasFullyBayesianSingleTaskGP with NUTS (botorch/fit.py:335-391): the
+    reference's signature, defaults and order of work, on this package's sampler
+    (mcmc.run_nuts, dense mass matrix) and the fused SAAS potential
+    (torch.ops.bo.saas_potential) for device data.  ``disable_progbar`` and
+    ``jit_compile`` are accepted and ignored.  ``num_chains`` chains run in one
+    batch and are concatenated chain-major before thinning; chain k draws from
+    its own generator seeded ``seed + k``.  As in the reference,
+    ``mcmc_samples["noise"]`` is the raw Gamma draw and ``load_mcmc_samples``
+    loads max(noise, 1e-4).  The sampler's record of every chain is kept as
+    ``model.nuts_info``.  Draws are not comparable with pyro's (DESIGN.md
+    section 22)."""
+    from .mcmc import run_nuts, saas_potential_fn
+    if getattr(model, "pyro_model", None) is not None:
+        raise UnsupportedError("custom pyro models have no meaning here: the SAAS density of "
+                               "SaasPyroModel is built in")
+    if not getattr(model, "_is_fully_bayesian", False) or not hasattr(model, "load_mcmc_samples"):
+        raise UnsupportedError("fit_fully_bayesian_model_nuts fits a SaasFullyBayesianSingleTaskGP")
+    if thinning < 1 or num_chains < 1:
+        raise ValueError("thinning and num_chains must be at least 1")
+    model.train()
+    X, y = model.train_inputs[0], model.train_targets
+    d = X.shape[-1]
+    samples, info = run_nuts(saas_potential_fn(X, y), (num_chains, d + 4),
+                             warmup_steps=warmup_steps, num_samples=num_samples,
+                             max_tree_depth=max_tree_depth, full_mass=True, seed=seed)
+    z = samples.reshape(-1, d + 4).to(X)  # chain-major
+    mcmc_samples = {"mean": z[:, 1], "outputscale": z[:, 0].exp(), "noise": z[:, 2].exp(),
+                    "lengthscale": (z[:, 3].exp().unsqueeze(-1) * z[:, 4:].exp()).rsqrt()}
+    for k, v in mcmc_samples.items():
+        mcmc_samples[k] = v[::thinning]
+    model.load_mcmc_samples(mcmc_samples)
+    model.eval()
+    model.nuts_info = info

@@ -2700,6 +2700,66 @@ def bald_backward(dout: torch.Tensor, mean: torch.Tensor, L: torch.Tensor, Z: to
     return dmean, dL
 
 
+SAAS_NMAX = 1024     # bo_saas_potential: one workgroup per row of z, its panel in LDS
+SAAS_DMAX = 256
+
+
+def saas_potential_check(n: int, d: int, C: int = 1) -> None:
+    """The argument limits of :func:`saas_potential`, raised on the host before
+    any native call."""
+    if not 0 <= n <= SAAS_NMAX:
+        raise ValueError(f"saas_potential: 0 <= n <= {SAAS_NMAX} (got {n})")
+    if not 1 <= d <= SAAS_DMAX:
+        raise ValueError(f"saas_potential: 1 <= d <= {SAAS_DMAX} (got {d})")
+    if C < 1 or C * n * n >= 1 << 31:
+        raise ValueError(f"saas_potential: C >= 1 and C n^2 < 2^31 (got C = {C}, n = {n})")
+
+
+def saas_potential_work(n: int, d: int, C: int) -> int:
+    """Doubles of workspace of a C-row :func:`saas_potential` call."""
+    saas_potential_check(n, d, C)
+    elems = ctypes.c_int64()
+    check(lib().bo_saas_potential_work(n, d, C, ctypes.byref(elems)), "saas_potential_work")
+    return elems.value
+
+
+def saas_potential(z: torch.Tensor, X: torch.Tensor, y: torch.Tensor,
+                   work: Optional[torch.Tensor] = None):
+    """(U (C), grad (C x (d + 4)), status (C, int32)): the SAAS potential
+    U = -log p(z, Y) and its gradient at the C rows of z over the training data
+    X (n x d), y (n) (bo_saas_potential_v, the record's comment in
+    include/botorch_amd.h).  A row with status != 0 has U = +inf and a zero
+    gradient.  ``work``: a workspace of at least :func:`saas_potential_work`
+    doubles to reuse between calls (taken from the allocator otherwise)."""
+    if z.dim() != 2 or X.dim() != 2 or y.dim() != 1:
+        raise ValueError(f"saas_potential: z must be C x (d + 4), X n x d and y n, got "
+                         f"{tuple(z.shape)}, {tuple(X.shape)} and {tuple(y.shape)}")
+    n, d = X.shape
+    C = z.shape[0]
+    saas_potential_check(n, d, C)
+    if z.shape[1] != d + 4 or y.shape[0] != n:
+        raise ValueError(f"saas_potential: z must be C x {d + 4} and y {n}, got "
+                         f"{tuple(z.shape)} and {tuple(y.shape)}")
+    for t in (z, X, y):
+        if t.dtype != torch.float64:
+            raise ValueError("saas_potential: every tensor must be fp64")
+    dev = _dev(z, X, y)
+    need = saas_potential_work(n, d, C)
+    if work is None:
+        work = torch.empty(max(need, 1), dtype=torch.float64, device=dev)
+    elif work.dtype != torch.float64 or work.numel() < need or not work.is_contiguous():
+        raise ValueError(f"saas_potential: work must be {need} contiguous fp64 values")
+    _dev(work)
+    U = torch.empty(C, dtype=torch.float64, device=dev)
+    grad = torch.empty(C, d + 4, dtype=torch.float64, device=dev)
+    status = torch.empty(C, dtype=torch.int32, device=dev)
+    a = _lib.SaasPotentialArgs(d=d, n=n, C=C, X=X.contiguous(), y=y.contiguous(),
+                               z=z.contiguous(), U=U, grad=grad, status=status, work=work,
+                               work_size=work.numel())
+    check(lib().bo_saas_potential_v(ctypes.byref(a), _stream(dev)), "saas_potential")
+    return U, grad, status
+
+
 def kernel_grad(X: torch.Tensor, Y: torch.Tensor, dK: torch.Tensor, lengthscale: torch.Tensor,
                 kind: int, outputscale: float = 1.0, group: int = 0,
                 dX: Optional[torch.Tensor] = None) -> torch.Tensor:

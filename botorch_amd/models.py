@@ -784,7 +784,7 @@ def sample_saas_prior(d: int, num_samples: int, seed: int = 0, dtype=torch.float
     """Hyperparameter sets from the SAAS prior (models/fully_bayesian.py:168-247):
     outputscale ~ Gamma(2, 0.15), mean ~ N(0, 1), noise = 1e-4 + Gamma(0.9, 10),
     tau^2 ~ HalfCauchy(0.1), inv_len^2 ~ HalfCauchy(1)^d, lengthscale =
-    (tau^2 inv_len^2)^{-1/2}.  (NUTS itself is out of scope: pyro is absent.)"""
+    (tau^2 inv_len^2)^{-1/2}.  (Posterior draws: fit.fit_fully_bayesian_model_nuts.)"""
     g = torch.Generator().manual_seed(seed)
     M = num_samples
 
@@ -837,6 +837,7 @@ class SaasFullyBayesianSingleTaskGP(Model):
             self.outcome_transform = outcome_transform
         self.train_inputs = (train_X,)
         self.train_targets = train_Y.squeeze(-1)
+        self.pyro_model = pyro_model  # (fit_fully_bayesian_model_nuts refuses any but None)
         self._members = None
         self._ens = None
         self._ens_key = None
@@ -931,7 +932,10 @@ class SaasFullyBayesianSingleTaskGP(Model):
         return post if posterior_transform is None else posterior_transform(post)
 
 
-def fit_fully_bayesian_model_nuts(model, **kwargs):
-    """botorch/fit.py:335-391 -- NUTS over the SAAS prior needs pyro, which is not
-    available (out of scope); load hyperparameters with ``load_mcmc_samples``."""
-    raise UnsupportedError("NUTS fitting (pyro) is out of scope; use load_mcmc_samples")
+def __getattr__(name):
+    # fit_fully_bayesian_model_nuts lives in fit.py, where the reference has it
+    # (fit.py imports this module, so the re-export resolves on first use)
+    if name == "fit_fully_bayesian_model_nuts":
+        from .fit import fit_fully_bayesian_model_nuts
+        return fit_fully_bayesian_model_nuts
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

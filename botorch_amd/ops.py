@@ -51,6 +51,9 @@ Ops (reference computation each replaces):
                       with up to 15 outcome constraints, from the members' posterior means
                       and variances in one launch (+ analytic autograd in mean, var;
                       acquisition/analytic.py:357-420, 528-608, 960-1053, 1182-1220)
+  bo::saas_potential  U = -log p(z, Y) of the SAAS GP and its closed-form gradient for a batch
+                      of NUTS chains, one workgroup per chain (models/fully_bayesian.py:168-247;
+                      its launch goes through bo::saas_potential_native in C++)
 """
 from __future__ import annotations
 
@@ -1011,9 +1014,30 @@ def _analytic_bwd(ctx, dacq):
 analytic.register_autograd(_analytic_bwd, setup_context=_analytic_setup)
 
 
+# ---- bo::saas_potential (the SAAS log-density and its gradient, for NUTS) -------------------------
+@torch.library.custom_op("bo::saas_potential", mutates_args=(), device_types="cuda")
+def saas_potential(z: Tensor, X: Tensor, y: Tensor,
+                   work: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """(U (C), grad (C x (d + 4)), status (C, int32)) of the SAAS potential at
+    the rows of z over X (n x d), y (n) (kernels.saas_potential).  It returns its
+    own gradient: no autograd."""
+    kernels.saas_potential_check(X.shape[0], X.shape[1], z.shape[0])
+    U, grad, status = _lib.torch_ops().saas_potential_native(
+        z.contiguous(), X.contiguous(), y.contiguous(), work)
+    return U, grad, status
+
+
+@saas_potential.register_fake
+def _(z, X, y, work=None):
+    C = z.shape[0]
+    return (z.new_empty((C,), dtype=F64), z.new_empty(z.shape, dtype=F64),
+            z.new_empty((C,), dtype=torch.int32))
+
+
 OPS: List[str] = ["sobol_normal", "gp_cache", "gp_cache_extend", "chol_jitter", "chol_backward",
                   "post_partials", "qmc_finalize", "gp_posterior", "gp_posterior_backward",
                   "qmc_acq", "qmc_acq_backward", "qehvi", "qehvi_backward", "mll", "kg",
                   "kg_backward", "paths_eval", "paths_eval_backward", "jes", "jes_backward", "mes",
                   "mes_backward", "gibbon", "gibbon_backward", "mv_quantiles", "nipv_gram",
-                  "nipv_gram_backward", "bald", "bald_backward", "analytic", "analytic_backward"]
+                  "nipv_gram_backward", "bald", "bald_backward", "analytic", "analytic_backward",
+                  "saas_potential"]

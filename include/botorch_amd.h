@@ -1311,6 +1311,45 @@ typedef struct BoAnalyticArgs {
 int bo_analytic_v(const BoAnalyticArgs* a, void* stream);
 int bo_analytic_backward_v(const BoAnalyticArgs* a, void* stream);
 
+/* The potential of the SAAS GP for NUTS (botorch/models/fully_bayesian.py:168-247,
+ * SaasPyroModel.sample): U = -log p(z, Y) and dU/dz for C unconstrained vectors
+ *   z = [log outputscale, mean, log g, log tau, log iota_1 .. log iota_d]   (C x (d + 4))
+ * over the training data X (n x d, row-major) and y (n).  With os = e^z0, c = z1,
+ * sigma^2 = 1e-4 + e^z2, w_j = e^z3 e^z(4+j) (inverse squared lengthscales),
+ * r^2_ik = sum_j w_j (x_ij - x_kj)^2 and A = os Matern-5/2(r) + sigma^2 I:
+ *   log p = log N(y | c 1, A) + Gamma(2, 0.15)(os) + N(0, 1)(c) + Gamma(0.9, 10)(e^z2)
+ *           + HalfCauchy(0.1)(e^z3) + sum_j HalfCauchy(1)(e^z(4+j))
+ *           + z0 + z2 + z3 + sum_j z(4+j)                     (the exp Jacobians)
+ * n = 0 leaves the priors.  The gradient is closed-form: with alpha = A^{-1}(y - c),
+ * W = alpha alpha^T - A^{-1}, Kbar the unit-outputscale kernel and
+ * Kbar' = dKbar/dr^2 = -(5/6)(1 + sqrt5 r) e^{-sqrt5 r}:
+ *   d ll/d z0 = os sum W Kbar / 2, d ll/d c = sum alpha, d ll/d z2 = e^z2 tr W / 2,
+ *   d ll/d w_j = os sum_ik W_ik Kbar'_ik (x_ij - x_kj)^2 / 2, d/d z(4+j) = w_j times
+ *   that and d/d z3 their sum; the priors' terms are added.
+ * One workgroup per row of z: A, a blocked Cholesky (16 x 16 blocks, the
+ * trailing updates on v_mfma_f64_16x16x4), L^{-1}, A^{-1} and the sums, in the
+ * row's slice of work (bo_saas_potential_work doubles for the whole call).
+ * status (C): 0 ok; 1 a non-finite input or a non-finite os, sigma^2, w_j or
+ * result; 2 a non-positive or non-finite Cholesky pivot.  A row with status != 0
+ * returns U = +inf and a zero gradient; the other rows are unaffected.
+ * 0 <= n <= 1024, 1 <= d <= 256, C >= 1 with C n^2 < 2^31, fp64.  No atomics,
+ * nothing shared between workgroups: repeated calls are bitwise identical and
+ * row c of a C-row call equals the one-row call on that row.
+ * A pure addition to the ABI: BO_ABI_VERSION stays 11. */
+typedef struct BoSaasPotentialArgs {
+  BO_STRUCT_HEADER;
+  int32_t d, _pad;
+  int64_t n, C;
+  const double *X, *y, *z;
+  double *U, *grad;      /* C, C x (d + 4) */
+  int32_t* status;       /* C */
+  double* work;
+  int64_t work_size;
+} BoSaasPotentialArgs;
+int bo_saas_potential_v(const BoSaasPotentialArgs* a, void* stream);
+/* HOST: doubles of work for a call of C rows. */
+int bo_saas_potential_work(int64_t n, int d, int64_t C, int64_t* elems);
+
 typedef struct BoLbfgsStepArgs { /* bo_lbfgs_step */
   BO_STRUCT_HEADER;
   int32_t B, n, m, _pad;
