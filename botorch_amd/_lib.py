@@ -22,7 +22,7 @@ QMC_QSR, QMC_QPI, QMC_QUCB = 6, 7, 8  # qSimpleRegret, qProbabilityOfImprovement
 LOG_MODES = (QMC_QLOGEI, QMC_QLOGNEI)
 # every mode with an acquisition value (the rest return moments / roots only)
 MC_MODES = (QMC_QEI, QMC_QNEI) + LOG_MODES + (QMC_QSR, QMC_QPI, QMC_QUCB)
-ABI_VERSION = 11
+ABI_VERSION = 12
 RT_ROWMAJOR, RT_BLOCKED = 0, 1  # BoPostPartialsArgs.rt_layout (include/botorch_amd.h)
 
 _P = c_void_p  # device pointers travel as void*
@@ -72,9 +72,6 @@ _SIGNATURES = {
     "bo_post_geometry": (c_int, [c_int64, c_int, c_int64, POINTER(c_int), POINTER(c_int),
                                  POINTER(c_int)]),
     "bo_prepare_rows": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P]),
-    "bo_post_partials": (c_int, [c_int, _P, c_int, c_int, c_int, _P, c_int64, _P, c_int64, _P,
-                                 c_double, _P, _P, _P, c_int, _P, _P, c_int, c_int64, _P, _P,
-                                 _P]),
     "bo_post_kxt": (c_int, [c_int, _P, c_int, c_int, c_int, _P, c_int64, c_double, _P, _P]),
     "bo_post_w": (c_int, [_P, c_int64, _P, c_int, c_int, c_int64, _P, _P]),
     "bo_post_split_plan": (c_int, [c_int64, c_int, c_int64, c_int, POINTER(c_int),
@@ -114,14 +111,6 @@ _SIGNATURES = {
     "bo_post_quad": (c_int, [_P, _P, c_int64, _P, c_int64, c_int, c_int64, _P, _P, _P]),
     "bo_post_split_table": (c_int, [c_int64, c_int, c_int64, c_int, _P, c_int, _P, c_int,
                                     POINTER(c_int), POINTER(c_int)]),
-    "bo_qmc_finalize": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, c_int64, c_double,
-                                c_double, c_double, c_double, _P, c_int, c_double, _P, c_int,
-                                c_double, _P, _P, _P, _P, _P, _P, _P, c_int, c_int64, _P,
-                                c_int64, c_int, c_double, c_double, _P]),
-    "bo_qehvi": (c_int, [c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, c_int, c_int64, _P,
-                         c_int64, c_int64, c_int, _P, _P]),
-    "bo_qehvi_backward": (c_int, [c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, c_int, c_int64,
-                                  _P, c_int64, c_int64, c_int, _P, _P, _P, _P, _P]),
     "bo_chol_backward": (c_int, [c_int, c_int, _P, _P, _P, _P]),
     "bo_chol_dag_tasks": (c_int, [c_int, _P, c_int]),
     "bo_kernel_grad": (c_int, [c_int, _P, c_int64, _P, c_int64, c_int, _P, c_double, _P, c_int64,
@@ -129,10 +118,6 @@ _SIGNATURES = {
     "bo_mc_reduce": (c_int, [c_int, c_int, c_int, _P, c_double, _P, _P, _P]),
     "bo_sobol_normal": (c_int, [_P, _P, c_int, c_int64, c_int64, c_int, _P, _P]),
     "bo_sobol_scramble": (c_int, [c_int, _P, _P, _P, _P, _P]),
-    "bo_lbfgs_step": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                              _P, _P, _P, _P, _P, _P, c_double, c_double, c_double, c_double, _P]),
-    "bo_lbfgsb_step": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_double, _P,
-                               _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "bo_lbfgsb_layout": (c_int, [_P]),
     "bo_lbfgsb_set_profile": (c_int, [_P, c_int]),
     "bo_lbfgsb_set_staging": (c_int, [c_int]),
@@ -147,11 +132,6 @@ _SIGNATURES = {
     "bo_sobol_box": (c_int, [_P, _P, c_int, c_int64, c_int64, c_int, _P, _P, c_int, _P, _P]),
     "bo_mll_terms": (c_int, [c_int, _P, c_int64, c_int, _P, c_double, _P, _P, c_int64, _P, _P, _P,
                              _P]),
-    "bo_qmc_backward": (c_int, [c_int, c_int, c_int, _P, _P, _P, c_int, c_double, _P, _P,
-                                c_int64, _P, _P, _P, _P, _P, c_int, c_double, c_double, _P]),
-    "bo_post_backward": (c_int, [c_int, c_int, c_int, c_int, _P, _P, c_int64, _P, c_int64, _P,
-                                 _P, _P, _P, c_int64, _P, c_double, c_double, c_int, _P, c_int,
-                                 _P]),
 }
 
 
@@ -358,23 +338,28 @@ class LbfgsbArgs(_Args):
                        ("ds", _D), ("is_", _D)]
 
 
-for _name, _cls in (("bo_post_partials_v", PostPartialsArgs), ("bo_qmc_finalize_v", QmcFinalizeArgs),
-                    ("bo_qmc_backward_v", QmcBackwardArgs), ("bo_post_backward_v", PostBackwardArgs),
-                    ("bo_qehvi_v", QehviArgs), ("bo_qehvi_backward_v", QehviArgs),
-                    ("bo_qehvi_feas_v", QehviFeasArgs), ("bo_qehvi_feas_backward_v", QehviFeasArgs),
-                    ("bo_qlogehvi_v", QlogehviArgs), ("bo_qlogehvi_backward_v", QlogehviArgs),
-                    ("bo_qmc_feas_v", QmcFeasArgs), ("bo_qmc_feas_backward_v", QmcFeasArgs),
-                    ("bo_kg_v", KgArgs), ("bo_kg_backward_v", KgArgs),
-                    ("bo_paths_eval_v", PathsArgs), ("bo_paths_eval_backward_v", PathsArgs),
-                    ("bo_jes_v", JesArgs), ("bo_jes_backward_v", JesArgs),
-                    ("bo_mes_v", MesArgs), ("bo_mes_backward_v", MesArgs),
-                    ("bo_gibbon_v", GibbonArgs), ("bo_gibbon_backward_v", GibbonArgs),
-                    ("bo_mv_quantiles_v", MvQuantilesArgs),
-                    ("bo_nipv_gram_v", NipvArgs), ("bo_nipv_gram_backward_v", NipvArgs),
-                    ("bo_bald_v", BaldArgs), ("bo_bald_backward_v", BaldArgs),
-                    ("bo_analytic_v", AnalyticArgs), ("bo_analytic_backward_v", AnalyticArgs),
-                    ("bo_saas_potential_v", SaasPotentialArgs),
-                    ("bo_lbfgs_step_v", LbfgsStepArgs), ("bo_lbfgsb_step_v", LbfgsbArgs)):
+# every record entry point, int bo_<name>_v(const Bo<Record>Args*, void* stream):
+# entry name -> the ctypes mirror of its record
+RECORD_ENTRIES = {
+    "bo_post_partials_v": PostPartialsArgs, "bo_qmc_finalize_v": QmcFinalizeArgs,
+    "bo_qmc_backward_v": QmcBackwardArgs, "bo_post_backward_v": PostBackwardArgs,
+    "bo_qehvi_v": QehviArgs, "bo_qehvi_backward_v": QehviArgs,
+    "bo_qehvi_feas_v": QehviFeasArgs, "bo_qehvi_feas_backward_v": QehviFeasArgs,
+    "bo_qlogehvi_v": QlogehviArgs, "bo_qlogehvi_backward_v": QlogehviArgs,
+    "bo_qmc_feas_v": QmcFeasArgs, "bo_qmc_feas_backward_v": QmcFeasArgs,
+    "bo_kg_v": KgArgs, "bo_kg_backward_v": KgArgs,
+    "bo_paths_eval_v": PathsArgs, "bo_paths_eval_backward_v": PathsArgs,
+    "bo_jes_v": JesArgs, "bo_jes_backward_v": JesArgs,
+    "bo_mes_v": MesArgs, "bo_mes_backward_v": MesArgs,
+    "bo_gibbon_v": GibbonArgs, "bo_gibbon_backward_v": GibbonArgs,
+    "bo_mv_quantiles_v": MvQuantilesArgs,
+    "bo_nipv_gram_v": NipvArgs, "bo_nipv_gram_backward_v": NipvArgs,
+    "bo_bald_v": BaldArgs, "bo_bald_backward_v": BaldArgs,
+    "bo_analytic_v": AnalyticArgs, "bo_analytic_backward_v": AnalyticArgs,
+    "bo_saas_potential_v": SaasPotentialArgs,
+    "bo_lbfgs_step_v": LbfgsStepArgs, "bo_lbfgsb_step_v": LbfgsbArgs,
+}
+for _name, _cls in RECORD_ENTRIES.items():
     _SIGNATURES[_name] = (c_int, [POINTER(_cls), _P])
 _SIGNATURES["bo_saas_potential_work"] = (c_int, [c_int64, c_int, c_int64, POINTER(c_int64)])
 _SIGNATURES["bo_struct_size"] = (c_int64, [ctypes.c_char_p])

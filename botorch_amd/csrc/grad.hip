@@ -695,44 +695,43 @@ extern "C" int bo_kernel_grad(int kind, const double* X, int64_t rows, const dou
   return BO_OK;
 }
 
-extern "C" int bo_qmc_backward(int mode, int B, int q, const double* mean, const double* Lq,
-                               const double* Z, int S, double best_f, const double* best_f_s,
-                               const double* F, int64_t ldF, const double* dacq, double* dmean,
-                               double* dcov, double* dF, const double* acq_fwd, int fat,
-                               double tau_relu, double tau_max, void* stream) {
+// bo_qmc_backward_v behind its header check (abi_structs.cpp).
+extern "C" int bo_qmc_backward_impl(const BoQmcBackwardArgs* a, void* stream) {
+  const int mode = a->mode, B = a->B, q = a->q, S = a->S;
   BO_CHECK_ARG(q >= 1 && q <= QMAX, "bo_qmc_backward: q=%d out of range", q);
   BO_CHECK_ARG(mode == MODE_QEI || mode == MODE_QNEI || mode == MODE_QLOGEI ||
                    mode == MODE_QLOGNEI || plain_max_mode(mode),
                "bo_qmc_backward: bad mode %d", mode);
-  BO_CHECK_ARG(mode != MODE_QPI || tau_relu > 0.0, "bo_qmc_backward: qPI needs tau > 0 (tau_relu)");
-  BO_CHECK_ARG(mode != MODE_QUCB || best_f_s,
+  BO_CHECK_ARG(mode != MODE_QPI || a->tau_relu > 0.0,
+               "bo_qmc_backward: qPI needs tau > 0 (tau_relu)");
+  BO_CHECK_ARG(mode != MODE_QUCB || a->best_f_s,
                "bo_qmc_backward: qUCB needs the base samples' mean zbar (best_f_s)");
   const bool per_sample = mode == MODE_QNEI || mode == MODE_QLOGNEI;
   const bool logm = mode == MODE_QLOGEI || mode == MODE_QLOGNEI;
-  BO_CHECK_ARG(!per_sample || (best_f_s && F && dF),
+  BO_CHECK_ARG(!per_sample || (a->best_f_s && a->F && a->dF),
                "bo_qmc_backward: qNEI / qLogNEI need best_f_s, F, dF");
-  BO_CHECK_ARG(!logm || (acq_fwd && tau_relu > 0.0 && tau_max > 0.0),
+  BO_CHECK_ARG(!logm || (a->acq_fwd && a->tau_relu > 0.0 && a->tau_max > 0.0),
                "bo_qmc_backward: log modes need the forward values and positive temperatures");
   if (B == 0) return BO_OK;
   int Qp = 1;
   while (Qp < q) Qp *= 2;
-  BO_CHECK_ARG(!per_sample || ldF >= (int64_t)B * Qp, "bo_qmc_backward: ldF too small");
+  BO_CHECK_ARG(!per_sample || a->ldF >= (int64_t)B * Qp, "bo_qmc_backward: ldF too small");
   hipStream_t st = as_stream(stream);
-  const LogRedParams lp{tau_relu, tau_max, fat};
+  const LogRedParams lp{a->tau_relu, a->tau_max, a->fat};
   if (mode == MODE_QEI)
-    qmc_backward_kernel<MODE_QEI><<<B, THREADS, 0, st>>>(q, mean, Lq, Z, S, best_f, best_f_s, dacq, dmean, dcov, nullptr, 0, Qp, nullptr, 1.0);
+    qmc_backward_kernel<MODE_QEI><<<B, THREADS, 0, st>>>(q, a->mean, a->Lq, a->Z, S, a->best_f, a->best_f_s, a->dacq, a->dmean, a->dcov, nullptr, 0, Qp, nullptr, 1.0);
   else if (mode == MODE_QNEI)
-    qmc_backward_kernel<MODE_QNEI><<<B, THREADS, 0, st>>>(q, mean, Lq, Z, S, best_f, best_f_s, dacq, dmean, dcov, F, ldF, Qp, dF, 1.0);
+    qmc_backward_kernel<MODE_QNEI><<<B, THREADS, 0, st>>>(q, a->mean, a->Lq, a->Z, S, a->best_f, a->best_f_s, a->dacq, a->dmean, a->dcov, a->F, a->ldF, Qp, a->dF, 1.0);
   else if (mode == MODE_QSR)
-    qmc_backward_kernel<MODE_QSR><<<B, THREADS, 0, st>>>(q, mean, Lq, Z, S, 0.0, nullptr, dacq, dmean, dcov, nullptr, 0, Qp, nullptr, 1.0);
+    qmc_backward_kernel<MODE_QSR><<<B, THREADS, 0, st>>>(q, a->mean, a->Lq, a->Z, S, 0.0, nullptr, a->dacq, a->dmean, a->dcov, nullptr, 0, Qp, nullptr, 1.0);
   else if (mode == MODE_QPI)
-    qmc_backward_kernel<MODE_QPI><<<B, THREADS, 0, st>>>(q, mean, Lq, Z, S, best_f, nullptr, dacq, dmean, dcov, nullptr, 0, Qp, nullptr, tau_relu);
+    qmc_backward_kernel<MODE_QPI><<<B, THREADS, 0, st>>>(q, a->mean, a->Lq, a->Z, S, a->best_f, nullptr, a->dacq, a->dmean, a->dcov, nullptr, 0, Qp, nullptr, a->tau_relu);
   else if (mode == MODE_QUCB)
-    qmc_backward_kernel<MODE_QUCB><<<B, THREADS, 0, st>>>(q, mean, Lq, Z, S, best_f, best_f_s, dacq, dmean, dcov, nullptr, 0, Qp, nullptr, 1.0);
+    qmc_backward_kernel<MODE_QUCB><<<B, THREADS, 0, st>>>(q, a->mean, a->Lq, a->Z, S, a->best_f, a->best_f_s, a->dacq, a->dmean, a->dcov, nullptr, 0, Qp, nullptr, 1.0);
   else if (mode == MODE_QLOGEI)
-    qmc_log_backward_kernel<false><<<B, THREADS, 0, st>>>(q, mean, Lq, Z, S, best_f, best_f_s, acq_fwd, lp, dacq, dmean, dcov, nullptr, 0, Qp, nullptr);
+    qmc_log_backward_kernel<false><<<B, THREADS, 0, st>>>(q, a->mean, a->Lq, a->Z, S, a->best_f, a->best_f_s, a->acq_fwd, lp, a->dacq, a->dmean, a->dcov, nullptr, 0, Qp, nullptr);
   else
-    qmc_log_backward_kernel<true><<<B, THREADS, 0, st>>>(q, mean, Lq, Z, S, best_f, best_f_s, acq_fwd, lp, dacq, dmean, dcov, F, ldF, Qp, dF);
+    qmc_log_backward_kernel<true><<<B, THREADS, 0, st>>>(q, a->mean, a->Lq, a->Z, S, a->best_f, a->best_f_s, a->acq_fwd, lp, a->dacq, a->dmean, a->dcov, a->F, a->ldF, Qp, a->dF);
   BO_LAUNCH_CHECK();
   return BO_OK;
 }
@@ -749,12 +748,10 @@ extern "C" int bo_chol_backward(int B, int q, const double* L, const double* dL,
   return BO_OK;
 }
 
-extern "C" int bo_post_backward(int kind, int B, int q, int d, const double* Xq,
-                                const double* Xt_scaled, int64_t n, const double* W, int64_t ldw,
-                                const double* alpha, const double* dmean, const double* dcov,
-                                const double* E, int64_t lde, const double* lengthscale,
-                                double outputscale, double ystd, int accumulate, double* dX,
-                                int w_kmajor, void* stream) {
+// bo_post_backward_v behind its header check (abi_structs.cpp).
+extern "C" int bo_post_backward_impl(const BoPostBackwardArgs* a, void* stream) {
+  const int B = a->B, q = a->q, d = a->d;
+  const int64_t n = a->n;
   BO_CHECK_ARG(q >= 1 && q <= QMAX && d >= 1 && d <= DP, "bo_post_backward: bad q/d");
   if (B == 0) return BO_OK;
   int Qp = 1;
@@ -775,12 +772,11 @@ extern "C" int bo_post_backward(int kind, int B, int q, int d, const double* Xq,
   }
   const dim3 grid((unsigned)B, (unsigned)ns_used);
 #define BO_PB(KIND, ND)                                                                        \
-  post_backward_kernel<KIND, ND><<<grid, THREADS, 0, st>>>(q, Qp, Xq, Xt_scaled, (int)n, W, ldw, \
-                                                           alpha, dmean, dcov, E, lde,           \
-                                                           lengthscale, outputscale, ystd, d,    \
-                                                           accumulate, dX, w_kmajor,             \
-                                                           ns_used > 1 ? chunk : (int)n, part)
-  if (kind == BO_RBF) {
+  post_backward_kernel<KIND, ND><<<grid, THREADS, 0, st>>>(                                    \
+      q, Qp, a->Xq, a->Xt_scaled, (int)n, a->W, a->ldw, a->alpha, a->dmean, a->dcov, a->E,     \
+      a->lde, a->lengthscale, a->outputscale, a->ystd, d, a->accumulate, a->dX, a->w_kmajor,   \
+      ns_used > 1 ? chunk : (int)n, part)
+  if (a->kind == BO_RBF) {
     if (d == 6) BO_PB(BO_RBF, 6); else BO_PB(BO_RBF, 8);
   } else {
     if (d == 6) BO_PB(BO_MATERN52, 6); else BO_PB(BO_MATERN52, 8);
@@ -790,7 +786,7 @@ extern "C" int bo_post_backward(int kind, int B, int q, int d, const double* Xq,
   if (part) {
     const int64_t total = (int64_t)B * q * d;
     post_backward_reduce_kernel<<<(unsigned)ceil_div(total, 256), 256, 0, st>>>(
-        ns_used, total, d, part, lengthscale, accumulate, dX);
+        ns_used, total, d, part, a->lengthscale, a->accumulate, a->dX);
     BO_LAUNCH_CHECK();
     BO_HIP(hipFreeAsync(part, st));
   }

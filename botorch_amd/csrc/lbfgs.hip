@@ -254,17 +254,15 @@ __global__ __launch_bounds__(THREADS) void lbfgs_kernel(
 
 }  // namespace
 
-extern "C" int bo_lbfgs_step(int B, int n, int m, double* x, double* f, double* g, double* xt,
-                             const double* ft, const double* gt, double* d, double* alpha,
-                             double* S, double* Y, double* rho, int* hcount, int* hhead,
-                             int* status, int* nacc, const double* lower, const double* upper,
-                             double c1, double ftol, double pgtol, double min_alpha,
-                             void* stream) {
-  BO_CHECK_ARG(n >= 1 && m >= 1 && m <= MMAX, "bo_lbfgs_step: n=%d, m=%d (1..%d)", n, m, MMAX);
-  if (B == 0) return BO_OK;
-  lbfgs_kernel<<<B, THREADS, 0, as_stream(stream)>>>(n, m, x, f, g, xt, ft, gt, d, alpha, S, Y,
-                                                      rho, hcount, hhead, status, nacc, lower,
-                                                      upper, c1, ftol, pgtol, min_alpha);
+// bo_lbfgs_step_v behind its header check (abi_structs.cpp).
+extern "C" int bo_lbfgs_step_impl(const BoLbfgsStepArgs* a, void* stream) {
+  BO_CHECK_ARG(a->n >= 1 && a->m >= 1 && a->m <= MMAX, "bo_lbfgs_step: n=%d, m=%d (1..%d)", a->n,
+               a->m, MMAX);
+  if (a->B == 0) return BO_OK;
+  lbfgs_kernel<<<a->B, THREADS, 0, as_stream(stream)>>>(
+      a->n, a->m, a->x, a->f, a->g, a->xt, a->ft, a->gt, a->d, a->alpha, a->S, a->Y, a->rho,
+      a->hcount, a->hhead, a->status, a->nacc, a->lower, a->upper, a->c1, a->ftol, a->pgtol,
+      a->min_alpha);
   BO_LAUNCH_CHECK();
   return BO_OK;
 }

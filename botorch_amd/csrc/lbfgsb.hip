@@ -303,29 +303,31 @@ extern "C" int bo_lbfgsb_layout(int* out) {
   return BO_OK;
 }
 
-extern "C" int bo_lbfgsb_step(int B, int n, int m, int maxls, int maxiter, int maxfun, double ftol,
-                              double pgtol, const double* lower, const double* upper, double* xt,
-                              const double* ft, const double* gt, double* v, int* iv, double* ws,
-                              double* wy, double* mat, double* ds, int* is, void* stream) {
-  BO_CHECK_ARG(B >= 0 && n >= 1 && m >= 1 && m <= bolb::MMAX && maxls >= 1,
-               "bo_lbfgsb_step: B=%d n=%d m=%d (1..%d) maxls=%d", B, n, m, bolb::MMAX, maxls);
-  BO_CHECK_ARG(lower && upper && xt && ft && gt && v && iv && ws && wy && mat && ds && is,
+// bo_lbfgsb_step_v behind its header check (abi_structs.cpp).
+extern "C" int bo_lbfgsb_step_impl(const BoLbfgsbArgs* a, void* stream) {
+  const int B = a->B, n = a->n, m = a->m;
+  BO_CHECK_ARG(B >= 0 && n >= 1 && m >= 1 && m <= bolb::MMAX && a->maxls >= 1,
+               "bo_lbfgsb_step: B=%d n=%d m=%d (1..%d) maxls=%d", B, n, m, bolb::MMAX, a->maxls);
+  BO_CHECK_ARG(a->lower && a->upper && a->xt && a->ft && a->gt && a->v && a->iv && a->ws &&
+                   a->wy && a->mat && a->ds && a->is,
                "bo_lbfgsb_step: null buffer");
   if (B == 0) return BO_OK;
   // profile only launches the buffer can hold (B x PROF_SLOTS clocks)
   unsigned long long* prof = lbfgsb_profile_for(B);
-  bolb::Problem P{n, m, maxls, maxiter, maxfun, ftol, pgtol, lower, upper, prof};
+  bolb::Problem P{n,       m,        a->maxls, a->maxiter, a->maxfun,
+                  a->ftol, a->pgtol, a->lower, a->upper,   prof};
   // the joint problem (one restart of b q d variables) over the chip
   const int gmode = g_lbfgsb_grid.load();
   if (B == 1 && gmode >= 0 && (gmode == 1 || n >= GRID_MIN_N) && lbfgsb_grid_fits(n, m))
-    return lbfgsb_grid_launch(P, xt, ft, gt, v, iv, ws, wy, mat, ds, is, stream);
+    return lbfgsb_grid_launch(P, a->xt, a->ft, a->gt, a->v, a->iv, a->ws, a->wy, a->mat, a->ds,
+                              a->is, stream);
   const size_t bytes = staged_bytes(n, m);
   const int staged = bytes <= STAGE_LIMIT && !g_lbfgsb_unstaged.load();
   // one wave per restart; a restart wider than the wave's working set (the
   // joint problem over all restarts, n = b q d) takes an 8-wave workgroup
   if (n <= JOINT_N)
-    lbfgsb_kernel<1><<<B, 64, staged ? bytes : 0, as_stream(stream)>>>(P, xt, ft, gt, v, iv, ws, wy,
-                                                                       mat, ds, is, staged);
+    lbfgsb_kernel<1><<<B, 64, staged ? bytes : 0, as_stream(stream)>>>(
+        P, a->xt, a->ft, a->gt, a->v, a->iv, a->ws, a->wy, a->mat, a->ds, a->is, staged);
   else {
     // an unstaged wide restart keeps the Cauchy breakpoints in LDS (staged = 2)
     const int mode = staged ? 1 : (n <= JOINT_TB_LDS ? 2 : 0);
@@ -358,11 +360,11 @@ extern "C" int bo_lbfgsb_step(int B, int n, int m, int maxls, int maxiter, int m
       }
     }
     if (w16)
-      lbfgsb_kernel<16><<<B, 64 * 16, dyn, as_stream(stream)>>>(P, xt, ft, gt, v, iv, ws, wy, mat, ds,
-                                                                 is, mode);
+      lbfgsb_kernel<16><<<B, 64 * 16, dyn, as_stream(stream)>>>(
+          P, a->xt, a->ft, a->gt, a->v, a->iv, a->ws, a->wy, a->mat, a->ds, a->is, mode);
     else
-      lbfgsb_kernel<JOINT_W><<<B, 64 * JOINT_W, dyn, as_stream(stream)>>>(P, xt, ft, gt, v, iv, ws,
-                                                                           wy, mat, ds, is, mode);
+      lbfgsb_kernel<JOINT_W><<<B, 64 * JOINT_W, dyn, as_stream(stream)>>>(
+          P, a->xt, a->ft, a->gt, a->v, a->iv, a->ws, a->wy, a->mat, a->ds, a->is, mode);
   }
   BO_LAUNCH_CHECK();
   return BO_OK;

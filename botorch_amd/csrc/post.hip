@@ -2149,46 +2149,31 @@ int bo_post_kxt_rows(int kind, const double* X, int B, int q, int d, const doubl
   return BO_OK;
 }
 
-int bo_post_partials_layout(int kind, const double* Xq, int B, int q, int d,
-                            const double* Xt_scaled, int64_t n, const double* U, int64_t ldu,
-                            const double* beta, double outputscale, double* Spart, double* mpart,
-                            double* Rt, int kc_len, double* work, const double* Qc, int rq,
-                            int64_t ldq, double* Cx, const double* Kt, int rt_layout, void* stream);
-
-int bo_post_partials(int kind, const double* Xq, int B, int q, int d,
-                     const double* Xt_scaled, int64_t n, const double* U, int64_t ldu, const double* beta,
-                     double outputscale, double* Spart, double* mpart, double* Rt,
-                     int kc_len, double* work, const double* Qc, int rq, int64_t ldq, double* Cx,
-                     const double* Kt, void* stream) {
-  return bo_post_partials_layout(kind, Xq, B, q, d, Xt_scaled, n, U, ldu, beta, outputscale, Spart,
-                                 mpart, Rt, kc_len, work, Qc, rq, ldq, Cx, Kt, BO_RT_ROWMAJOR,
-                                 stream);
-}
-
-int bo_post_partials_layout(int kind, const double* Xq, int B, int q, int d,
-                            const double* Xt_scaled, int64_t n, const double* U, int64_t ldu,
-                            const double* beta, double outputscale, double* Spart, double* mpart,
-                            double* Rt, int kc_len, double* work, const double* Qc, int rq,
-                            int64_t ldq, double* Cx, const double* Kt, int rt_layout, void* stream) {
-  BO_CHECK_ARG(rt_layout == BO_RT_ROWMAJOR || (rt_layout == BO_RT_BLOCKED && kc_len == 0 && !Qc),
+// bo_post_partials_v behind its header check (abi_structs.cpp).
+int bo_post_partials_impl(const BoPostPartialsArgs* a, void* stream) {
+  const int kc_len = a->kc_len;
+  const int64_t n = a->n;
+  const bool blocked = a->rt_layout == BO_RT_BLOCKED;
+  BO_CHECK_ARG(a->rt_layout == BO_RT_ROWMAJOR || (blocked && kc_len == 0 && !a->Qc),
                "rt_layout %d: the blocked R^T is stored by one-pass grids without a cross term",
-               rt_layout);
-  BO_CHECK_ARG(Qc == nullptr || (kc_len == 0 && rq >= 1 && rq <= 16 && ldq >= n && Cx != nullptr),
-               "cross term: one-pass only, 1 <= rq <= 16 rows (got %d), ldq >= n, Cx given", rq);
-  BO_CHECK_ARG(kind == BO_RBF || kind == BO_MATERN52, "bad kernel kind %d", kind);
-  BO_CHECK_ARG(ldu % 2 == 0 && ldu >= ceil_div(n, PC) * PC, "U leading dim %lld too small",
-               (long long)ldu);
-  if (B == 0) return BO_OK;  // no t-batches: nothing to launch
-  const bool pre = Kt != nullptr;
+               a->rt_layout);
+  BO_CHECK_ARG(a->Qc == nullptr || (kc_len == 0 && a->rq >= 1 && a->rq <= 16 && a->ldq >= n &&
+                                    a->Cx != nullptr),
+               "cross term: one-pass only, 1 <= rq <= 16 rows (got %d), ldq >= n, Cx given", a->rq);
+  BO_CHECK_ARG(a->kind == BO_RBF || a->kind == BO_MATERN52, "bad kernel kind %d", a->kind);
+  BO_CHECK_ARG(a->ldu % 2 == 0 && a->ldu >= ceil_div(n, PC) * PC, "U leading dim %lld too small",
+               (long long)a->ldu);
+  if (a->B == 0) return BO_OK;  // no t-batches: nothing to launch
+  const bool pre = a->Kt != nullptr;
   BO_CHECK_ARG(kc_len == 0 || kc_len == -1 || (kc_len > 0 && kc_len % PK == 0),
                "split chunk %d must be 0, -1 (stream-K) or a positive multiple of %d", kc_len, PK);
   int Qp, nrows_pad, nC;
-  int s = bo_post_geometry(B, q, n, &Qp, &nrows_pad, &nC);
+  int s = bo_post_geometry(a->B, a->q, n, &Qp, &nrows_pad, &nC);
   if (s) return s;
   const int nI = nrows_pad / PI;
-  const int nrows = B * Qp;
+  const int nrows = a->B * Qp;
   if (nI == 0) return BO_OK;  // no t-batches: nothing to launch
-  BO_CHECK_ARG(d >= 1 && d <= DP, "fused posterior kernel supports 1 <= d <= %d", DP);
+  BO_CHECK_ARG(a->d >= 1 && a->d <= DP, "fused posterior kernel supports 1 <= d <= %d", DP);
   // Grouped 8 x 8 super-tile schedule where the grid divides (C3: 2.68 -> 2.49 ms,
   // HBM 4.5 -> 3.7 GB per launch against the per-column-tile order).
   // Paired where the column groups pair up (nC % 16 == 0; BO_POST_PAIRED=0
@@ -2199,7 +2184,7 @@ int bo_post_partials_layout(int kind, const double* Xq, int B, int q, int d,
   if (kc_len != 0) {
     s = device_plan(nC, nI, (int)n, kc_len, &plan);
     if (s) return s;
-    BO_CHECK_ARG(plan->nchunks == 0 || work != nullptr, "split plan needs a workspace of %lld doubles",
+    BO_CHECK_ARG(plan->nchunks == 0 || a->work != nullptr, "split plan needs a workspace of %lld doubles",
                  (long long)plan->nchunks * PI * PC);
   }
   const int64_t blocks = kc_len != 0    ? plan->W
@@ -2209,10 +2194,10 @@ int bo_post_partials_layout(int kind, const double* Xq, int B, int q, int d,
   const int4* segs = plan ? plan->segs : nullptr;
   const int* wg_off = plan ? plan->wg_off : nullptr;
   hipStream_t st = as_stream(stream);
-  if (wide_applies(nC, nI, kc_len, Qc != nullptr, pre)) {
+  if (wide_applies(nC, nI, kc_len, a->Qc != nullptr, pre)) {
     const int64_t wblocks = 256 * (int64_t)ceil_div((nC / 16) * (nI / 8), 8);
     post_partials_wide_kernel<<<(unsigned)wblocks, 512, 0, st>>>(
-        (int)n, U, ldu, beta, nC, nI, Spart, mpart, Rt, Kt, rt_layout == BO_RT_BLOCKED);
+        (int)n, a->U, a->ldu, a->beta, nC, nI, a->Spart, a->mpart, a->Rt, a->Kt, blocked);
     BO_LAUNCH_CHECK();
     return BO_OK;
   }
@@ -2220,21 +2205,22 @@ int bo_post_partials_layout(int kind, const double* Xq, int B, int q, int d,
   // beyond d are zero, so fewer distance terms are exact, not approximate).
 #define BO_POST_GO(KIND, ND, SPL, CRS, PRE_)                                                \
   post_partials_kernel<KIND, ND, SPL, CRS, PRE_><<<(unsigned)blocks, 256, 0, st>>>(          \
-      Xq, nrows, Xt_scaled, (int)n, U, ldu, beta, outputscale, nC, nI, Spart, mpart, Rt,    \
-      segs, wg_off, work, Qc, rq, ldq, Cx, Kt, grouped, FusedDx{}, rt_layout == BO_RT_BLOCKED)
+      a->Xq, nrows, a->Xt_scaled, (int)n, a->U, a->ldu, a->beta, a->outputscale, nC, nI,    \
+      a->Spart, a->mpart, a->Rt, segs, wg_off, a->work, a->Qc, a->rq, a->ldq, a->Cx, a->Kt, \
+      grouped, FusedDx{}, blocked)
 #define BO_POST_LAUNCH(KIND, ND)                                                            \
   if (kc_len != 0) {                                                                        \
     if (pre) BO_POST_GO(KIND, ND, true, false, true);                                       \
     else BO_POST_GO(KIND, ND, true, false, false);                                          \
-  } else if (Qc != nullptr) {                                                               \
-    if (pre) BO_POST_GO(KIND, ND, false, true, true);                                       \
+  } else if (a->Qc != nullptr) {                                                            \
+    if (pre) BO_POST_GO(KIND, ND, false, true, true);                                     \
     else BO_POST_GO(KIND, ND, false, true, false);                                          \
   } else {                                                                                  \
     if (pre) BO_POST_GO(KIND, ND, false, false, true);                                      \
     else BO_POST_GO(KIND, ND, false, false, false);                                         \
   }
 #define BO_POST_DISPATCH_D(KIND)                   \
-  switch (d) {                                     \
+  switch (a->d) {                                  \
     case 1: BO_POST_LAUNCH(KIND, 1); break;        \
     case 2: BO_POST_LAUNCH(KIND, 2); break;        \
     case 3: BO_POST_LAUNCH(KIND, 3); break;        \
@@ -2243,7 +2229,7 @@ int bo_post_partials_layout(int kind, const double* Xq, int B, int q, int d,
     case 6: BO_POST_LAUNCH(KIND, 6); break;        \
     default: BO_POST_LAUNCH(KIND, 8); break;       \
   }
-  if (kind == BO_RBF) {
+  if (a->kind == BO_RBF) {
     BO_POST_DISPATCH_D(BO_RBF)
   } else {
     BO_POST_DISPATCH_D(BO_MATERN52)
@@ -2254,7 +2240,7 @@ int bo_post_partials_layout(int kind, const double* Xq, int B, int q, int d,
   BO_LAUNCH_CHECK();
   if (plan && plan->nred > 0) {
     post_splitk_reduce_kernel<<<(unsigned)(plan->nred * (PI / 16)), 256, 0, st>>>(
-        work, plan->red, (int)n, nI, beta, Spart, mpart, Rt);
+        a->work, plan->red, (int)n, nI, a->beta, a->Spart, a->mpart, a->Rt);
     BO_LAUNCH_CHECK();
   }
   return BO_OK;

@@ -550,57 +550,89 @@ __global__ __launch_bounds__(THREADS) void mc_reduce_kernel(
   }
 }
 
-}  // namespace
+// ---- host: one forward and one backward launch for the plain (BoQehviArgs)
+// and the weighted (BoQehviFeasArgs, which opens with the same fields) records
 
-extern "C" int bo_qehvi_ext(int B, int q, int m, const double* mean, const double* L,
-                            const double* Z, int S, const double* cell_lo, const double* cell_hi,
-                            int K, int64_t cell_stride, const double* F, int64_t ldF, int64_t sF,
-                            int Qp, double* acq, double* work, int64_t work_elems, void* stream);
-
-extern "C" int bo_qehvi(int B, int q, int m, const double* mean, const double* L, const double* Z,
-                        int S, const double* cell_lo, const double* cell_hi, int K,
-                        int64_t cell_stride, const double* F, int64_t ldF, int64_t sF, int Qp,
-                        double* acq, void* stream) {
-  return bo_qehvi_ext(B, q, m, mean, L, Z, S, cell_lo, cell_hi, K, cell_stride, F, ldF, sF, Qp, acq,
-                      nullptr, 0, stream);
+// The argument checks every launch shares, and the kernels' QehviExt.
+template <class A>
+int check_plain(const A* a, const char* who, QehviExt* ex) {
+  BO_CHECK_ARG(a->q >= 1 && a->q <= QMAX, "%s: 1 <= q <= %d (got %d)", who, QMAX, a->q);
+  BO_CHECK_ARG(a->m >= 2 && a->m <= MMAX, "%s: 2 <= m <= %d (got %d)", who, MMAX, a->m);
+  BO_CHECK_ARG(a->S > 0 && a->K >= 0 && a->cell_stride >= 0, "%s: bad S/K/cell_stride", who);
+  BO_CHECK_ARG(a->F == nullptr || (a->Qp >= a->q && a->ldF >= (int64_t)a->B * a->Qp),
+               "%s: bad F layout", who);
+  *ex = QehviExt{a->cell_stride, a->F, a->ldF, a->sF, a->Qp};
+  return BO_OK;
 }
 
-// work (>= 2 B doubles, optional): the samples of each t-batch split over H =
-// min(8, 1024 / B, work_elems / B) workgroups when B leaves CUs idle.
-extern "C" int bo_qehvi_ext(int B, int q, int m, const double* mean, const double* L,
-                            const double* Z, int S, const double* cell_lo, const double* cell_hi,
-                            int K, int64_t cell_stride, const double* F, int64_t ldF, int64_t sF,
-                            int Qp, double* acq, double* work, int64_t work_elems, void* stream) {
-  BO_CHECK_ARG(q >= 1 && q <= QMAX, "bo_qehvi: 1 <= q <= %d (got %d)", QMAX, q);
-  BO_CHECK_ARG(m >= 2 && m <= MMAX, "bo_qehvi: 2 <= m <= %d (got %d)", MMAX, m);
-  BO_CHECK_ARG(S > 0 && K >= 0 && cell_stride >= 0, "bo_qehvi: bad S/K/cell_stride");
-  BO_CHECK_ARG(F == nullptr || (Qp >= q && ldF >= (int64_t)B * Qp), "bo_qehvi: bad F layout");
+// The weighted launches' checks on top: the output map packed for the kernels.
+int check_feas(const BoQehviFeasArgs* a, const char* who, QehviExtFeas* ex) {
+  BO_CHECK_ARG(a->zld <= INT32_MAX, "%s: zld too large", who);
+  if (int st = check_plain(a, who, ex); st != BO_OK) return st;
+  BO_CHECK_ARG(a->feas != nullptr, "%s: feas is required", who);
+  BO_CHECK_ARG(a->Mt >= a->m && a->Mt <= 255, "%s: m <= Mt <= 255 (got %d)", who, a->Mt);
+  BO_CHECK_ARG(a->zm >= a->Mt && a->zld >= (int64_t)a->q * a->zm,
+               "%s: base samples need zm >= Mt and zld >= q zm", who);
+  unsigned oi = 0;
+  for (int t = 0; t < a->m; ++t) {
+    BO_CHECK_ARG(a->out_idx[t] >= 0 && a->out_idx[t] < a->Mt, "%s: out_idx[%d] = %d outside [0, %d)",
+                 who, t, a->out_idx[t], a->Mt);
+    for (int u = 0; u < t; ++u)
+      BO_CHECK_ARG(a->out_idx[u] != a->out_idx[t], "%s: out_idx must be injective", who);
+    oi |= (unsigned)a->out_idx[t] << (8 * t);
+  }
+  ex->feas = a->feas;
+  ex->dfeas = a->dfeas;
+  ex->zm = a->zm;
+  ex->zld = (int)a->zld;
+  ex->oi = oi;
+  return BO_OK;
+}
+
+// An A/B knob: the sample split's target workgroup count from the environment.
+int env_target(const char* name, int dflt) {
+  const char* e = std::getenv(name);
+  const int v = e ? std::atoi(e) : dflt;
+  return v >= 1 && v <= 4096 ? v : dflt;
+}
+
+// H: the workgroups the samples of each t-batch split over when B leaves CUs
+// idle -- min(8, target / B, S), given a workspace of >= 2 B per_h doubles
+// (per_h per t-batch and workgroup); 1 without one.
+int sample_split(int B, int S, int target, const double* work, int64_t work_elems, int64_t per_h) {
+  if (work == nullptr || work_elems < 2 * (int64_t)B * per_h) return 1;
+  const int H = (int)std::min<int64_t>(std::min(8, std::max(1, target / B)),
+                                       work_elems / ((int64_t)B * per_h));
+  return std::max(1, std::min(H, S));
+}
+
+// Hypercells shared by all samples and small enough for the LDS stage
+template <class A>
+bool cells_in_lds(const A* a) {
+  return a->cell_stride == 0 && (int64_t)a->K * a->m <= LDS_CELL_DOUBLES / 2;
+}
+
+// work (>= 2 B doubles, optional): the sample split of the forward.
+template <bool FEAS, class A>
+int launch_forward(const A* a, const QehviExtOf<FEAS>& ex, void* stream) {
+  const int B = a->B, q = a->q, m = a->m;
   if (B == 0) return BO_OK;
   hipStream_t st = as_stream(stream);
-  const QehviExt ex{cell_stride, F, ldF, sF, Qp};
-  const bool cl = cell_stride == 0 && (int64_t)K * m <= LDS_CELL_DOUBLES / 2;
-  int H = 1;
+  const bool cl = cells_in_lds(a);
   // Sample split toward ~1024 workgroups (4 per CU): C4 (B = 128, H = 8) step
   // 0.395 -> 0.380-0.383 ms against a 256-workgroup target (one per CU; 512:
   // 0.386-0.391; tools/ab_qehvi_wg.sh) -- more resident waves hide the
   // inclusion-exclusion's latency.  BO_QEHVI_WG overrides (A/B knob).
-  static const int target = [] {
-    const char* e = std::getenv("BO_QEHVI_WG");
-    const int v = e ? std::atoi(e) : 1024;
-    return v >= 1 && v <= 4096 ? v : 1024;
-  }();
-  if (work != nullptr && work_elems >= 2 * (int64_t)B) {
-    H = (int)std::min<int64_t>(std::min(8, std::max(1, target / B)), work_elems / B);
-    H = std::max(1, std::min(H, S));
-  }
+  static const int target = env_target("BO_QEHVI_WG", 1024);
+  const int H = sample_split(B, a->S, target, a->work, a->work_elems, 1);
   const unsigned grid = (unsigned)((int64_t)B * H);
 #define BO_QF(MM, QQ)                                                                          \
   if (cl)                                                                                      \
-    qehvi_kernel<MM, FWD_THREADS, true, QQ><<<grid, FWD_THREADS, 0, st>>>(                     \
-        B, q, mean, L, Z, S, cell_lo, cell_hi, K, ex, acq, H, work);                           \
+    qehvi_kernel<MM, FWD_THREADS, true, QQ, FEAS><<<grid, FWD_THREADS, 0, st>>>(               \
+        B, q, a->mean, a->L, a->Z, a->S, a->cell_lo, a->cell_hi, a->K, ex, a->acq, H, a->work); \
   else                                                                                         \
-    qehvi_kernel<MM, FWD_THREADS, false, QQ><<<grid, FWD_THREADS, 0, st>>>(                    \
-        B, q, mean, L, Z, S, cell_lo, cell_hi, K, ex, acq, H, work)
+    qehvi_kernel<MM, FWD_THREADS, false, QQ, FEAS><<<grid, FWD_THREADS, 0, st>>>(              \
+        B, q, a->mean, a->L, a->Z, a->S, a->cell_lo, a->cell_hi, a->K, ex, a->acq, H, a->work)
 #define BO_QFM(MM)          \
   if (q <= 4) {             \
     BO_QF(MM, 4);           \
@@ -620,66 +652,35 @@ extern "C" int bo_qehvi_ext(int B, int q, int m, const double* mean, const doubl
 #undef BO_QF
   BO_LAUNCH_CHECK();
   if (H > 1) {
-    qehvi_part_reduce_kernel<<<(unsigned)ceil_div(B, 64), 64, 0, st>>>(work, B, H, S, acq);
+    qehvi_part_reduce_kernel<<<(unsigned)ceil_div(B, 64), 64, 0, st>>>(a->work, B, H, a->S, a->acq);
     BO_LAUNCH_CHECK();
   }
   return BO_OK;
 }
 
-extern "C" int bo_qehvi_backward_ext(int B, int q, int m, const double* mean, const double* L,
-                                     const double* Z, int S, const double* cell_lo,
-                                     const double* cell_hi, int K, int64_t cell_stride,
-                                     const double* F, int64_t ldF, int64_t sF, int Qp,
-                                     const double* dacq, double* dmean, double* dL, double* dF,
-                                     double* work, int64_t work_elems, void* stream);
-
-extern "C" int bo_qehvi_backward(int B, int q, int m, const double* mean, const double* L,
-                                 const double* Z, int S, const double* cell_lo,
-                                 const double* cell_hi, int K, int64_t cell_stride,
-                                 const double* F, int64_t ldF, int64_t sF, int Qp,
-                                 const double* dacq, double* dmean, double* dL, double* dF,
-                                 void* stream) {
-  return bo_qehvi_backward_ext(B, q, m, mean, L, Z, S, cell_lo, cell_hi, K, cell_stride, F, ldF, sF,
-                               Qp, dacq, dmean, dL, dF, nullptr, 0, stream);
-}
-
 // work (>= 2 B nent doubles, nent = m q (q + 3) / 2, optional): the sample
-// split of bo_qehvi_ext for the backward.
-extern "C" int bo_qehvi_backward_ext(int B, int q, int m, const double* mean, const double* L,
-                                 const double* Z, int S, const double* cell_lo,
-                                 const double* cell_hi, int K, int64_t cell_stride,
-                                 const double* F, int64_t ldF, int64_t sF, int Qp,
-                                 const double* dacq, double* dmean, double* dL, double* dF,
-                                 double* work, int64_t work_elems, void* stream) {
-  BO_CHECK_ARG(q >= 1 && q <= QMAX, "bo_qehvi_backward: 1 <= q <= %d (got %d)", QMAX, q);
-  BO_CHECK_ARG(m >= 2 && m <= MMAX, "bo_qehvi_backward: 2 <= m <= %d (got %d)", MMAX, m);
-  BO_CHECK_ARG(S > 0 && K >= 0 && cell_stride >= 0, "bo_qehvi_backward: bad S/K/cell_stride");
-  BO_CHECK_ARG((F == nullptr) == (dF == nullptr), "bo_qehvi_backward: F and dF go together");
-  BO_CHECK_ARG(F == nullptr || (Qp >= q && ldF >= (int64_t)B * Qp), "bo_qehvi_backward: bad F layout");
+// split of the backward.
+template <bool FEAS, class A>
+int launch_backward(const A* a, const QehviExtOf<FEAS>& ex, const char* who, void* stream) {
+  BO_CHECK_ARG((a->F == nullptr) == (a->dF == nullptr), "%s: F and dF go together", who);
+  const int B = a->B, q = a->q, m = a->m;
   if (B == 0) return BO_OK;
   hipStream_t st = as_stream(stream);
-  const QehviExt ex{cell_stride, F, ldF, sF, Qp};
   const int64_t nent = (int64_t)m * q * (q + 3) / 2;
-  int H = 1;
   // BO_QEHVI_BWD_WG: target workgroups of the backward's sample split (A/B knob)
-  static const int target = [] {
-    const char* e = std::getenv("BO_QEHVI_BWD_WG");
-    const int v = e ? std::atoi(e) : 256;
-    return v >= 1 && v <= 4096 ? v : 256;
-  }();
-  if (work != nullptr && work_elems >= 2 * (int64_t)B * nent) {
-    H = (int)std::min<int64_t>(std::min(8, std::max(1, target / B)), work_elems / ((int64_t)B * nent));
-    H = std::max(1, std::min(H, S));
-  }
+  static const int target = env_target("BO_QEHVI_BWD_WG", 256);
+  const int H = sample_split(B, a->S, target, a->work, a->work_elems, nent);
   const unsigned grid = (unsigned)((int64_t)B * H);
-  const bool cl = cell_stride == 0 && (int64_t)K * m <= LDS_CELL_DOUBLES / 2;
+  const bool cl = cells_in_lds(a);
 #define BO_QB(MM, NT, QQ)                                                                      \
   if (cl)                                                                                      \
-    qehvi_backward_kernel<MM, NT, QQ, true><<<grid, NT, 0, st>>>(                              \
-        B, q, mean, L, Z, S, cell_lo, cell_hi, K, ex, dacq, dmean, dL, dF, H, work);           \
+    qehvi_backward_kernel<MM, NT, QQ, true, FEAS><<<grid, NT, 0, st>>>(                        \
+        B, q, a->mean, a->L, a->Z, a->S, a->cell_lo, a->cell_hi, a->K, ex, a->dacq, a->dmean,  \
+        a->dL, a->dF, H, a->work);                                                             \
   else                                                                                         \
-    qehvi_backward_kernel<MM, NT, QQ, false><<<grid, NT, 0, st>>>(                             \
-        B, q, mean, L, Z, S, cell_lo, cell_hi, K, ex, dacq, dmean, dL, dF, H, work)
+    qehvi_backward_kernel<MM, NT, QQ, false, FEAS><<<grid, NT, 0, st>>>(                       \
+        B, q, a->mean, a->L, a->Z, a->S, a->cell_lo, a->cell_hi, a->K, ex, a->dacq, a->dmean,  \
+        a->dL, a->dF, H, a->work)
 #define BO_QBM(MM, NT)        \
   if (q <= 4) {               \
     BO_QB(MM, NT, 4);         \
@@ -699,142 +700,44 @@ extern "C" int bo_qehvi_backward_ext(int B, int q, int m, const double* mean, co
 #undef BO_QB
   BO_LAUNCH_CHECK();
   if (H > 1) {
-    qehvi_backward_reduce_kernel<<<(unsigned)B, 256, 0, st>>>(work, B, q, m, H, dmean, dL);
+    if constexpr (FEAS)
+      qehvi_backward_reduce_kernel<<<(unsigned)B, 256, 0, st>>>(a->work, B, q, m, H, a->dmean, a->dL,
+                                                                ex.oi);
+    else
+      qehvi_backward_reduce_kernel<<<(unsigned)B, 256, 0, st>>>(a->work, B, q, m, H, a->dmean, a->dL);
     BO_LAUNCH_CHECK();
   }
-  return BO_OK;
-}
-
-namespace {
-
-// Arguments shared by the weighted forward and backward: the output map packed
-// for the kernels, or BO_ERR_ARG.
-int feas_ext(const BoQehviFeasArgs* a, const char* who, QehviExtFeas* ex) {
-  BO_CHECK_ARG(a->q >= 1 && a->q <= QMAX, "%s: 1 <= q <= %d (got %d)", who, QMAX, a->q);
-  BO_CHECK_ARG(a->m >= 2 && a->m <= MMAX, "%s: 2 <= m <= %d (got %d)", who, MMAX, a->m);
-  BO_CHECK_ARG(a->S > 0 && a->K >= 0 && a->cell_stride >= 0, "%s: bad S/K/cell_stride", who);
-  BO_CHECK_ARG(a->F == nullptr || (a->Qp >= a->q && a->ldF >= (int64_t)a->B * a->Qp),
-               "%s: bad F layout", who);
-  BO_CHECK_ARG(a->feas != nullptr, "%s: feas is required", who);
-  BO_CHECK_ARG(a->Mt >= a->m && a->Mt <= 255, "%s: m <= Mt <= 255 (got %d)", who, a->Mt);
-  BO_CHECK_ARG(a->zm >= a->Mt && a->zld >= (int64_t)a->q * a->zm,
-               "%s: base samples need zm >= Mt and zld >= q zm", who);
-  unsigned oi = 0;
-  for (int t = 0; t < a->m; ++t) {
-    BO_CHECK_ARG(a->out_idx[t] >= 0 && a->out_idx[t] < a->Mt, "%s: out_idx[%d] = %d outside [0, %d)",
-                 who, t, a->out_idx[t], a->Mt);
-    for (int u = 0; u < t; ++u)
-      BO_CHECK_ARG(a->out_idx[u] != a->out_idx[t], "%s: out_idx must be injective", who);
-    oi |= (unsigned)a->out_idx[t] << (8 * t);
-  }
-  *ex = QehviExtFeas{{a->cell_stride, a->F, a->ldF, a->sF, a->Qp}, a->feas, a->dfeas, a->zm,
-                     (int)a->zld, oi};
   return BO_OK;
 }
 
 }  // namespace
 
-// bo_qehvi_feas_v / bo_qehvi_feas_backward_v behind their header checks
-// (abi_structs.cpp): the launches of bo_qehvi_ext / bo_qehvi_backward_ext on
-// the weighted instantiations, with the same sample split and buckets.
+// The record entry points behind their header checks (abi_structs.cpp).
+extern "C" int bo_qehvi_impl(const BoQehviArgs* a, void* stream) {
+  QehviExt ex;
+  if (int st = check_plain(a, "bo_qehvi", &ex); st != BO_OK) return st;
+  return launch_forward<false>(a, ex, stream);
+}
+
+extern "C" int bo_qehvi_backward_impl(const BoQehviArgs* a, void* stream) {
+  QehviExt ex;
+  if (int st = check_plain(a, "bo_qehvi_backward", &ex); st != BO_OK) return st;
+  return launch_backward<false>(a, ex, "bo_qehvi_backward", stream);
+}
+
 extern "C" int bo_qehvi_feas_impl(const BoQehviFeasArgs* a, void* stream) {
   QehviExtFeas ex;
-  BO_CHECK_ARG(a->zld <= INT32_MAX, "bo_qehvi_feas: zld too large");
-  if (int st = feas_ext(a, "bo_qehvi_feas", &ex); st != BO_OK) return st;
+  if (int st = check_feas(a, "bo_qehvi_feas", &ex); st != BO_OK) return st;
   BO_CHECK_ARG(a->acq != nullptr, "bo_qehvi_feas: acq is required");
-  const int B = a->B, q = a->q, m = a->m, S = a->S, K = a->K;
-  if (B == 0) return BO_OK;
-  hipStream_t st = as_stream(stream);
-  const bool cl = a->cell_stride == 0 && (int64_t)K * m <= LDS_CELL_DOUBLES / 2;
-  int H = 1;
-  if (a->work != nullptr && a->work_elems >= 2 * (int64_t)B) {
-    H = (int)std::min<int64_t>(std::min(8, std::max(1, 1024 / B)), a->work_elems / B);
-    H = std::max(1, std::min(H, S));
-  }
-  const unsigned grid = (unsigned)((int64_t)B * H);
-#define BO_QF(MM, QQ)                                                                          \
-  if (cl)                                                                                      \
-    qehvi_kernel<MM, FWD_THREADS, true, QQ, true><<<grid, FWD_THREADS, 0, st>>>(               \
-        B, q, a->mean, a->L, a->Z, S, a->cell_lo, a->cell_hi, K, ex, a->acq, H, a->work);      \
-  else                                                                                         \
-    qehvi_kernel<MM, FWD_THREADS, false, QQ, true><<<grid, FWD_THREADS, 0, st>>>(              \
-        B, q, a->mean, a->L, a->Z, S, a->cell_lo, a->cell_hi, K, ex, a->acq, H, a->work)
-#define BO_QFM(MM)          \
-  if (q <= 4) {             \
-    BO_QF(MM, 4);           \
-  } else if (q <= 8) {      \
-    BO_QF(MM, 8);           \
-  } else {                  \
-    BO_QF(MM, QMAX);        \
-  }
-  if (m == 2) {
-    BO_QFM(2);
-  } else if (m == 3) {
-    BO_QFM(3);
-  } else {
-    BO_QFM(4);
-  }
-#undef BO_QFM
-#undef BO_QF
-  BO_LAUNCH_CHECK();
-  if (H > 1) {
-    qehvi_part_reduce_kernel<<<(unsigned)ceil_div(B, 64), 64, 0, st>>>(a->work, B, H, S, a->acq);
-    BO_LAUNCH_CHECK();
-  }
-  return BO_OK;
+  return launch_forward<true>(a, ex, stream);
 }
 
 extern "C" int bo_qehvi_feas_backward_impl(const BoQehviFeasArgs* a, void* stream) {
   QehviExtFeas ex;
-  BO_CHECK_ARG(a->zld <= INT32_MAX, "bo_qehvi_feas_backward: zld too large");
-  if (int st = feas_ext(a, "bo_qehvi_feas_backward", &ex); st != BO_OK) return st;
+  if (int st = check_feas(a, "bo_qehvi_feas_backward", &ex); st != BO_OK) return st;
   BO_CHECK_ARG(a->dfeas != nullptr && a->dacq != nullptr && a->dmean != nullptr && a->dL != nullptr,
                "bo_qehvi_feas_backward: dacq, dmean, dL and dfeas are required");
-  BO_CHECK_ARG((a->F == nullptr) == (a->dF == nullptr), "bo_qehvi_feas_backward: F and dF go together");
-  const int B = a->B, q = a->q, m = a->m, S = a->S, K = a->K;
-  if (B == 0) return BO_OK;
-  hipStream_t st = as_stream(stream);
-  const int64_t nent = (int64_t)m * q * (q + 3) / 2;
-  int H = 1;
-  if (a->work != nullptr && a->work_elems >= 2 * (int64_t)B * nent) {
-    H = (int)std::min<int64_t>(std::min(8, std::max(1, 256 / B)), a->work_elems / ((int64_t)B * nent));
-    H = std::max(1, std::min(H, S));
-  }
-  const unsigned grid = (unsigned)((int64_t)B * H);
-  const bool cl = a->cell_stride == 0 && (int64_t)K * m <= LDS_CELL_DOUBLES / 2;
-#define BO_QB(MM, NT, QQ)                                                                      \
-  if (cl)                                                                                      \
-    qehvi_backward_kernel<MM, NT, QQ, true, true><<<grid, NT, 0, st>>>(                        \
-        B, q, a->mean, a->L, a->Z, S, a->cell_lo, a->cell_hi, K, ex, a->dacq, a->dmean, a->dL, \
-        a->dF, H, a->work);                                                                    \
-  else                                                                                         \
-    qehvi_backward_kernel<MM, NT, QQ, false, true><<<grid, NT, 0, st>>>(                       \
-        B, q, a->mean, a->L, a->Z, S, a->cell_lo, a->cell_hi, K, ex, a->dacq, a->dmean, a->dL, \
-        a->dF, H, a->work)
-#define BO_QBM(MM, NT)        \
-  if (q <= 4) {               \
-    BO_QB(MM, NT, 4);         \
-  } else if (q <= 8) {        \
-    BO_QB(MM, NT, 8);         \
-  } else {                    \
-    BO_QB(MM, NT, QMAX);      \
-  }
-  if (m == 2) {
-    BO_QBM(2, BWD_THREADS);
-  } else if (m == 3) {
-    BO_QBM(3, BWD_THREADS);
-  } else {
-    BO_QBM(4, 256);
-  }
-#undef BO_QBM
-#undef BO_QB
-  BO_LAUNCH_CHECK();
-  if (H > 1) {
-    qehvi_backward_reduce_kernel<<<(unsigned)B, 256, 0, st>>>(a->work, B, q, m, H, a->dmean, a->dL,
-                                                              ex.oi);
-    BO_LAUNCH_CHECK();
-  }
-  return BO_OK;
+  return launch_backward<true>(a, ex, "bo_qehvi_feas_backward", stream);
 }
 
 extern "C" int bo_mc_reduce(int S, int B, int q, const double* samples, double best_f,

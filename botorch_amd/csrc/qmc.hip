@@ -706,82 +706,51 @@ void launch_qmc(int mode, int B, const QmcArgs& a, hipStream_t st) {
 
 extern "C" int bo_post_geometry(int64_t B, int q, int64_t n, int* Qp, int* nrows_pad, int* nC);
 
-extern "C" int bo_qmc_finalize_ext(int kind, int mode, int B, int q, const double* Xq,
-                                   const double* Spart, const double* mpart, int64_t n,
-                                   double outputscale, double constant, double ymean,
-                                   double ystd, const double* Z, int S, double best_f,
-                                   const double* best_f_s, int max_tries, double jitter0,
-                                   double* acq, double* mean_out, double* cov_out, double* L_out,
-                                   int* info_out, double* jitter_out, const double* Tm, int r,
-                                   int64_t ldT, const double* F, int64_t ldF, int fat,
-                                   double tau_relu, double tau_max, int nparts, int sym_parts,
-                                   double* status_out, int* status_count, void* stream);
-
-extern "C" int bo_qmc_finalize(int kind, int mode, int B, int q, const double* Xq,
-                               const double* Spart, const double* mpart, int64_t n,
-                               double outputscale, double constant, double ymean, double ystd,
-                               const double* Z, int S, double best_f, const double* best_f_s,
-                               int max_tries, double jitter0, double* acq, double* mean_out,
-                               double* cov_out, double* L_out, int* info_out,
-                               double* jitter_out, const double* Tm, int r, int64_t ldT,
-                               const double* F, int64_t ldF, int fat, double tau_relu,
-                               double tau_max, void* stream) {
-  return bo_qmc_finalize_ext(kind, mode, B, q, Xq, Spart, mpart, n, outputscale, constant, ymean,
-                             ystd, Z, S, best_f, best_f_s, max_tries, jitter0, acq, mean_out,
-                             cov_out, L_out, info_out, jitter_out, Tm, r, ldT, F, ldF, fat,
-                             tau_relu, tau_max, 0, 0, nullptr, nullptr, stream);
-}
-
-extern "C" int bo_qmc_finalize_ext(int kind, int mode, int B, int q, const double* Xq,
-                               const double* Spart, const double* mpart, int64_t n,
-                               double outputscale, double constant, double ymean, double ystd,
-                               const double* Z, int S, double best_f, const double* best_f_s,
-                               int max_tries, double jitter0, double* acq, double* mean_out,
-                               double* cov_out, double* L_out, int* info_out,
-                               double* jitter_out, const double* Tm, int r, int64_t ldT,
-                               const double* F, int64_t ldF, int fat, double tau_relu,
-                               double tau_max, int nparts, int sym_parts, double* status_out,
-                               int* status_count, void* stream) {
+// bo_qmc_finalize_v behind its header check (abi_structs.cpp).
+extern "C" int bo_qmc_finalize_impl(const BoQmcFinalizeArgs* a, void* stream) {
+  const int mode = a->mode;
   BO_CHECK_ARG(mode >= 0 && mode <= QMC_QUCB, "bo_qmc_finalize: bad mode %d", mode);
-  BO_CHECK_ARG(nparts >= 0 && (sym_parts == 0 || nparts > 0),
-               "bo_qmc_finalize: nparts %d / sym_parts %d", nparts, sym_parts);
-  BO_CHECK_ARG(status_out == nullptr ||
-                   (status_count && info_out && jitter_out && mode != QMC_POSTERIOR),
+  BO_CHECK_ARG(a->nparts >= 0 && (a->sym_parts == 0 || a->nparts > 0),
+               "bo_qmc_finalize: nparts %d / sym_parts %d", a->nparts, a->sym_parts);
+  BO_CHECK_ARG(a->status_out == nullptr ||
+                   (a->status_count && a->info_out && a->jitter_out && mode != QMC_POSTERIOR),
                "bo_qmc_finalize: the fused ladder status needs a counter, info and jitter outputs");
-  if (B == 0) return BO_OK;  // no t-batches (empty outputs may carry null pointers)
-  BO_CHECK_ARG(!log_mode(mode) || (tau_relu > 0.0 && tau_max > 0.0),
+  if (a->B == 0) return BO_OK;  // no t-batches (empty outputs may carry null pointers)
+  BO_CHECK_ARG(!log_mode(mode) || (a->tau_relu > 0.0 && a->tau_max > 0.0),
                "bo_qmc_finalize: tau_relu and tau_max must be positive");
-  BO_CHECK_ARG(mode == QMC_POSTERIOR || mode == QMC_CHOL || (acq && Z && S > 0),
+  BO_CHECK_ARG(mode == QMC_POSTERIOR || mode == QMC_CHOL || (a->acq && a->Z && a->S > 0),
                "bo_qmc_finalize: missing MC args");
-  BO_CHECK_ARG(!per_sample_best(mode) || best_f_s,
+  BO_CHECK_ARG(!per_sample_best(mode) || a->best_f_s,
                "bo_qmc_finalize: qNEI / qLogNEI need per-sample best_f");
-  BO_CHECK_ARG(mode != QMC_QPI || tau_relu > 0.0, "bo_qmc_finalize: qPI needs tau > 0 (tau_relu)");
-  BO_CHECK_ARG(mode != QMC_QUCB || best_f_s,
+  BO_CHECK_ARG(mode != QMC_QPI || a->tau_relu > 0.0,
+               "bo_qmc_finalize: qPI needs tau > 0 (tau_relu)");
+  BO_CHECK_ARG(mode != QMC_QUCB || a->best_f_s,
                "bo_qmc_finalize: qUCB needs the base samples' mean zbar (best_f_s)");
-  BO_CHECK_ARG(!plain_max_mode(mode) || (Tm == nullptr && F == nullptr),
+  BO_CHECK_ARG(!plain_max_mode(mode) || (a->Tm == nullptr && a->F == nullptr),
                "bo_qmc_finalize: qSR / qPI / qUCB take no cached-root terms");
-  BO_CHECK_ARG((Tm == nullptr) == (F == nullptr) && (Tm == nullptr || r > 0),
+  BO_CHECK_ARG((a->Tm == nullptr) == (a->F == nullptr) && (a->Tm == nullptr || a->r > 0),
                "bo_qmc_finalize: cached-root qNEI needs both T and F");
   int Qp, nrows_pad, nC;
-  int s = bo_post_geometry(B, q, n, &Qp, &nrows_pad, &nC);
+  int s = bo_post_geometry(a->B, a->q, a->n, &Qp, &nrows_pad, &nC);
   if (s) return s;
-  if (B == 0) return BO_OK;
-  if (nparts > 0) nC = nparts;
-  QmcArgs a{q,      Qp,     Xq,       Spart,     mpart,     nC,      nrows_pad, outputscale,
-            constant, ymean, ystd,   Z,        S,         best_f,  best_f_s,  max_tries,
-            jitter0, acq,    mean_out, cov_out,  L_out,     info_out, jitter_out, Tm,
-            r,       ldT,    F,        ldF,      LogRedParams{tau_relu, tau_max, fat},
-            sym_parts, status_out, status_count};
+  if (a->nparts > 0) nC = a->nparts;
+  QmcArgs k{a->q,        Qp,         a->Xq,          a->Spart,     a->mpart,    nC,
+            nrows_pad,   a->outputscale, a->constant, a->ymean,     a->ystd,     a->Z,
+            a->S,        a->best_f,  a->best_f_s,    a->max_tries, a->jitter0,  a->acq,
+            a->mean_out, a->cov_out, a->L_out,       a->info_out,  a->jitter_out, a->Tm,
+            a->r,        a->ldT,     a->F,           a->ldF,
+            LogRedParams{a->tau_relu, a->tau_max, a->fat},
+            a->sym_parts, a->status_out, a->status_count};
   hipStream_t st = as_stream(stream);
-  if (kind == BO_RBF) launch_qmc<BO_RBF>(mode, B, a, st);
-  else launch_qmc<BO_MATERN52>(mode, B, a, st);
+  if (a->kind == BO_RBF) launch_qmc<BO_RBF>(mode, a->B, k, st);
+  else launch_qmc<BO_MATERN52>(mode, a->B, k, st);
   BO_LAUNCH_CHECK();
   return BO_OK;
 }
 
 // The root-only finalisation (BO_QMC_CHOL: mean + jittered q x q Cholesky) of
 // nm <= 8 models of one shape and kernel kind in ONE launch (grid B x nm):
-// per member its rows, partials (nparts as bo_qmc_finalize_ext), scalars,
+// per member its rows, partials (nparts as BoQmcFinalizeArgs.nparts), scalars,
 // outputs and optional fused-status words.
 extern "C" int bo_qmc_finalize_members(int nm, int kind, int B, int q, const double* const* Xq,
                                        const double* const* Spart, const double* const* mpart,

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define BO_ABI_VERSION 11
+#define BO_ABI_VERSION 12
 
 /* status codes */
 #define BO_OK 0
@@ -63,7 +63,7 @@ extern "C" {
 #define BO_QMC_QLOGEI 4  /* qLogExpectedImprovement (acquisition/logei.py:137-234) */
 #define BO_QMC_QLOGNEI 5 /* qLogNoisyExpectedImprovement, cached root (logei.py:236-507) */
 /* The rest of the sample-reducing family (acquisition/monte_carlo.py:648-871).
- * They reuse the parameter slots of bo_qmc_finalize / bo_qmc_backward:
+ * They reuse the parameter slots of bo_qmc_finalize_v / bo_qmc_backward_v:
  *   mode      best_f           tau_relu   best_f_s
  *   QSR       ignored          ignored    ignored
  *   QPI       best_f           tau (> 0)  ignored
@@ -87,7 +87,6 @@ int bo_probe_mfma_f64_layout(double* out, void* stream);
 /* Peak-rate probe: `blocks` x 256 threads, each wave issuing iters x 8
  * independent fp64 MFMAs (2048 flop each).  out: 1 double (kept live). */
 int bo_probe_mfma_f64_rate(int blocks, int iters, double* out, void* stream);
-
 
 
 /* Queue of the Cholesky task DAG for T = np/64 tile rows (HOST function, no
@@ -169,20 +168,20 @@ int bo_cholesky_jitter(const double* A, int64_t n, double* L, double* Linv, doub
                        void* stream);
 
 /* Outcome of a batched jitter ladder (info, jitter: B entries from
- * bo_qmc_finalize / bo_chol_small): out[0] = max info (0: all factored),
+ * bo_qmc_finalize_v / bo_chol_small): out[0] = max info (0: all factored),
  * out[1] = max jitter added.  One launch; the caller reads 16 bytes back, as
  * [G] psd_safe_cholesky's torch.any(info) check does. */
 int bo_ladder_status(const int* info, const double* jitter, int64_t B, double* out, void* stream);
 
 /* Pinned, device-mapped, coherent host memory (zeroed): *host for the CPU,
- * *dev for kernels -- the status words bo_qmc_finalize folds a ladder's
+ * *dev for kernels -- the status words bo_qmc_finalize_v folds a ladder's
  * outcome into (BoQmcFinalizeArgs.status_out), read by the host after a
  * stream sync without a status launch or copy (a ModelListGP's members in
  * the qEHVI forward).  bo_pinned_free releases it. */
 int bo_pinned_alloc(int64_t bytes, void** host, void** dev);
-/* bo_qmc_finalize_ext in BO_QMC_CHOL mode (mean + jittered q x q root) for
+/* bo_qmc_finalize_v in BO_QMC_CHOL mode (mean + jittered q x q root) for
  * nm <= 8 models of one shape and kernel kind in ONE launch: per member its
- * rows Xq[m], partials Spart[m] / mpart[m] (nparts as bo_qmc_finalize_ext),
+ * rows Xq[m], partials Spart[m] / mpart[m] (nparts as BoQmcFinalizeArgs.nparts),
  * scalars and outputs; status_out (optional, with status_count) per member as
  * BoQmcFinalizeArgs.status_out; Tm / F (optional, with r, ldT, ldF): each
  * member's cached-root qNEHVI terms as BoQmcFinalizeArgs.Tm / F.  A
@@ -290,8 +289,7 @@ int bo_gp_cache_build_fixed(int kind, const double* Xt, int64_t n, int d,
  * the caller then rebuilds with bo_gp_cache_build, and also when the old
  * caches were built with jitter).  Enqueue only.  L, Linv, their outputs,
  * U_out and work 16-B aligned, ld and ld_out even.  BO_ERR_ARG (nothing
- * launched) on k < 1, ld_out < np', a NULL or misaligned buffer, d > 8.
- * A pure addition to the ABI: BO_ABI_VERSION stays 11. */
+ * launched) on k < 1, ld_out < np', a NULL or misaligned buffer, d > 8. */
 int bo_gp_cache_extend_work(int64_t n, int k, int64_t* work_elems);
 int bo_gp_cache_extend(int kind, const double* Xt_scaled, const double* L, const double* Linv,
                        const double* beta, const double* alpha, int64_t ld, int64_t n, int d,
@@ -312,44 +310,10 @@ int bo_post_geometry(int64_t B, int q, int64_t n, int* Qp, int* nrows_pad, int* 
 int bo_prepare_rows(const double* X, int B, int q, int d, const double* lengthscale,
                     double* Xq, void* stream);
 
-/* Fused K*x build + R^T = U^T K*x^T GEMM + R R^T / R beta epilogue
- * ([G] exact_predictive_mean / exact_predictive_covar under fast_pred_var,
- * botorch/models/gpytorch.py:446).  Xt_scaled: n x 8 lengthscale-scaled
- * training inputs; U: >= np x np with leading dim ldu; beta: n.
- * Spart: nC x (nrows_pad/16) x 16 x 16,  mpart: nC x nrows_pad.
- * Rt (nullable, gradient path): R^T, (nC*128) x nrows_pad.
- * kc_len = 0: one workgroup per (column tile, row tile), work unused;
- * kc_len > 0: split (every tile cut into chunks of kc_len training rows);
- * kc_len = -1: stream-K (the tiles' k-steps cut into one equal share per
- * resident slot).  Split plans reduce each cut tile's chunks in k order, with
- * `work` >= the work_elems of bo_post_split_plan / bo_post_split_work.
- * Qc (nullable, one-pass only): rq <= 16 rows (leading dim ldq >= n) whose
- * products with K*x are returned as nC column-tile partials
- * Cx[ci] (nC x rq x nrows_pad; sum over ci = Qc K*x^T) -- the
- * qNEI cross-covariance P_b R^T = Q_b K*x^T, Q_b = P_b U^T
- * (acquisition/cached_cholesky.py:94-120), without storing R.
- * Kt (nullable): K*x^T from bo_post_kxt (read instead of evaluated).
- *
- * The triangular operand (every entry point on the posterior kernel's 128 x
- * 128 tiles: bo_post_partials*, bo_post_partials_members with U = L^{-T}
- * upper; bo_post_w*, bo_post_w_dx, bo_ainv with L^{-1} lower).  Column tile c
- * reads rows [0, 128 c + 128) of U (rows [128 c, n) of L^{-1}) and nothing
- * beyond.  Inside the tile's diagonal 128 x 128 block it multiplies only the
- * 16 x 16 blocks on or above the block diagonal (on or below, L^{-1}): the
- * 16 x 16 blocks on the zero side are loaded but never multiplied, so their
- * contents do not reach the result.  What the caller owes: the zero triangle
- * INSIDE the 16 x 16 diagonal blocks holds exact zeros, and rows / columns
- * >= n hold the identity pad.  bo_gp_cache_build*, bo_cholesky_inverse* and
- * bo_gp_cache_extend leave the whole opposite triangle zero. */
-int bo_post_partials(int kind, const double* Xq, int B, int q, int d,
-                     const double* Xt_scaled, int64_t n, const double* U, int64_t ldu, const double* beta,
-                     double outputscale, double* Spart, double* mpart, double* Rt,
-                     int kc_len, double* work, const double* Qc, int rq, int64_t ldq, double* Cx,
-                     const double* Kt, void* stream);
 
 /* K*x^T of the same call, np x nrows_pad (np = 128 nC): Kt[k][i] =
  * outputscale k(x_i, x_k), zero for k >= n and padding rows.  Passed to
- * bo_post_partials as Kt, the posterior kernel reads these values instead of
+ * bo_post_partials_v as Kt, the posterior kernel reads these values instead of
  * evaluating each one again for every column tile that covers it. */
 int bo_post_kxt(int kind, const double* Xq, int B, int q, int d, const double* Xt_scaled,
                 int64_t n, double outputscale, double* Kt, void* stream);
@@ -361,7 +325,7 @@ int bo_post_kxt_rows(int kind, const double* X, int B, int q, int d, const doubl
                      void* stream);
 
 /* W^T = L^{-T} R^T = (K*x (K + s2 I)^{-1})^T for the posterior backward, np x
- * nrows_pad, from bo_post_partials' stored R^T (np x nrows_pad) and L^{-1}
+ * nrows_pad, from bo_post_partials_v's stored R^T (np x nrows_pad) and L^{-1}
  * (lower, ld ldl): the posterior kernel's MFMA tiles over the lower k-range
  * k >= c of each column (the second forward-size contraction of the gradient,
  * SURVEY.md 8(a) a14).  BO_ERR_ARG when the tile grid does not form 8 x 8
@@ -385,7 +349,7 @@ int bo_post_w_split_members(int nm, const double* const* Linv, int64_t ldl, cons
 
 /* The posterior backward without W: dX (B x q x d) of the posterior moments'
  * cotangents (dmean B x q, dcov B x q x q, standardised by ystd as in
- * bo_post_backward) from bo_post_partials' stored R^T and L^{-1}: the one-pass
+ * bo_post_backward_v) from bo_post_partials_v's stored R^T and L^{-1}: the one-pass
  * W^T = L^{-T} R^T tiles of bo_post_w with the reduction dK*x = s dmean alpha^T
  * - G W (G_b = s^2 (dcov_b + dcov_b^T)) -> dX fused into their epilogue, W
  * never written; then the K** term and 1 / lengthscale (generation/gen.py:
@@ -393,20 +357,20 @@ int bo_post_w_split_members(int nm, const double* const* Linv, int64_t ldl, cons
  * Rt in the BO_RT_BLOCKED layout (bo_post_partials_v with rt_layout =
  * BO_RT_BLOCKED).  work >= bo_post_w_dx_work doubles (nC x nrows_pad x 8 partials); a zero
  * size means the one-pass grid does not apply (stream-K plans: use
- * bo_post_w_split + bo_post_backward) and bo_post_w_dx returns BO_ERR_ARG. */
+ * bo_post_w_split + bo_post_backward_v) and bo_post_w_dx returns BO_ERR_ARG. */
 int bo_post_w_dx_work(int B, int q, int64_t n, int64_t* work_elems);
 int bo_post_w_dx(int kind, const double* Linv, int64_t ldl, const double* Rt, int B, int q, int d,
                  int64_t n, const double* Xq, const double* Xt_scaled, const double* alpha,
                  const double* dmean, const double* dcov, const double* lengthscale,
                  double outputscale, double ystd, double* work, double* dX, void* stream);
 
-/* Plan of bo_post_partials (host pointers): kc_len = 0 (one pass) or -1
+/* Plan of bo_post_partials_v (host pointers): kc_len = 0 (one pass) or -1
  * (stream-K), whichever a k-step cost model of the triangular grid over
  * `slots` resident workgroups (slots <= 0: 512 = 256 CUs x 2) rates faster,
  * and the workspace size in doubles. */
 int bo_post_split_plan(int64_t B, int q, int64_t n, int slots, int* kc_len,
                        int64_t* work_elems);
-/* Workspace doubles of bo_post_partials under a given kc_len (0, -1 or a
+/* Workspace doubles of bo_post_partials_v under a given kc_len (0, -1 or a
  * chunk length). */
 int bo_post_split_work(int64_t B, int q, int64_t n, int kc_len, int64_t* work_elems);
 /* Route of the one-pass paired forward that reads K*x^T (kc_len = 0, Kt given,
@@ -415,7 +379,7 @@ int bo_post_split_work(int64_t B, int q, int64_t n, int kc_len, int64_t* work_el
  * kernel (one 512-thread workgroup per 256 x 128 tile, U staged through LDS
  * two k-steps per barrier).  Every output is bit for bit the same on
  * both routes; every other shape and flag runs the 256-thread kernel.
- * bo_post_wide_applies: *out = 1 where a bo_post_partials call of that shape
+ * bo_post_wide_applies: *out = 1 where a bo_post_partials_v call of that shape
  * would take the 8-wave kernel under the current mode (tests assert the route).
  * bo_post_wide_schedule (host): the 8-wave kernel's LDS schedule for one half
  * (0: waves 0-3, 1: waves 4-7) of a segment of nsteps k-steps walked ascending
@@ -442,7 +406,7 @@ int bo_post_wide_schedule(int nsteps, int half, int rev, int cap, int* n_barrier
  * the 128-tile plan would be stream-K), else 0.  bo_post_small: Kt = K*x^T
  * (np x nrows_pad, bo_post_kxt), U (ld ldu >= np), beta (n); writes Spart
  * (nparts x nrows_pad/16 x 16 x 16) and mpart (nparts x nrows_pad), the
- * bo_qmc_finalize inputs with nparts = *nparts, sym_parts = 0, and with Rt
+ * bo_qmc_finalize_v inputs with nparts = *nparts, sym_parts = 0, and with Rt
  * non-null R^T row-major (np x nrows_pad) for the gradient's W^T routes. */
 int bo_post_small_plan(int64_t B, int q, int64_t n, int* nparts);
 int bo_post_small(const double* Kt, int64_t B, int q, int64_t n, const double* U, int64_t ldu,
@@ -459,9 +423,9 @@ int bo_post_small_batched(int nm, const double* const* Kt, const double* const* 
 /* The same nm <= 8 models' partials where the one-model plan is stream-K
  * (C4: ModelListGP(3), n = 2048, q = 8, b = 128): ONE stream-K launch over
  * every member's 128 x 128 tiles plus one split-k reduction, replacing one
- * bo_post_partials per member (models/model_list_gp.py -> [G]
+ * bo_post_partials_v per member (models/model_list_gp.py -> [G]
  * ModelListGP.posterior's per-model loop).  Spart[m] / mpart[m] hold nC
- * column-tile partials (bo_post_partials' layout); Rt[m] (optional) R^T
+ * column-tile partials (bo_post_partials_v's layout); Rt[m] (optional) R^T
  * row-major; Xq0 any member's padded rows (bo_post_kxt_rows).
  * bo_post_members_work: the shared workspace in doubles, -1 where the
  * one-model plan is not stream-K (one launch per model then). */
@@ -493,7 +457,7 @@ int bo_sym_lower(double* A, int64_t ld, int64_t n, void* stream);
  * plan, csrc/quad.hip): Sigma_b = K**_b - sum_{kb <= lb} (P + P^T) over 64 x 64
  * block pairs of the full symmetric A^{-1} = (K + s2 I)^{-1} (bo_ainv +
  * bo_sym_lower), mu_b = c + K*x alpha -- the same [G] exact_predictive_mean /
- * covar as bo_post_partials (models/gpytorch.py:405-466), linear in the blocks
+ * covar as bo_post_partials_v (models/gpytorch.py:405-466), linear in the blocks
  * of A^{-1}, so the units' partials are 16 x 16 blocks and no split-k
  * reduction runs; the pairs of one block row are taken in chunks of G (one
  * partial per chunk and row tile).  bo_post_quad_plan: *npairs = the partial
@@ -514,79 +478,6 @@ int bo_post_quad(const double* Kt, const double* Ainv, int64_t lda, const double
 int bo_post_split_table(int64_t B, int q, int64_t n, int kc_len, int* segs, int cap, int* wg_off,
                         int wcap, int* nseg, int* nwg);
 
-/* Finalise the posterior of each t-batch and (mode != POSTERIOR) run the
- * fused q x q psd_safe_cholesky + reparameterised sampling + MC reduction:
- *   mean_out (B x q) = ymean + ystd (constant + R beta)
- *   cov_out (B x q x q) = ystd^2 (K** - R R^T)       [Standardize.untransform_posterior,
- *                                                     botorch/models/transforms/outcome.py:373-447]
- *   L_out (B x q x q), info_out (B), jitter_out (B)  [posteriors/gpytorch.py:85-126]
- *   acq (B): qEI  mean_s max_a relu(f - best_f)      [acquisition/monte_carlo.py:405-414]
- *            qNEI mean_s max_a relu(f - best_f_s[s])  [acquisition/monte_carlo.py:580-589]
- *            qLogEI / qLogNEI (best_f / best_f_s[s]):
- *              logmeanexp_s fatmax_a log_fatplus(f - best_f, tau_relu)   (fat != 0)
- *              logmeanexp_s smooth_amax_a log_softplus(f - best_f, tau_relu) (fat == 0)
- *              with the q-reduction at temperature tau_max
- *              [acquisition/logei.py:122, 219-234, 347-362, 509-534;
- *               utils/safe_math.py:209-352]; fat/tau_* are ignored by other modes
- *            qSR  mean_s max_a f                      [acquisition/monte_carlo.py:789-798]
- *            qPI  mean_s max_a sigmoid((f - best_f) / tau), tau in tau_relu   [:721-731]
- *            qUCB mean_s max_a (fbar_a + beta' |f_a - fbar_a|), fbar = mean_s f =
- *                 mean' + L_q zbar; beta' in best_f, zbar (q) in best_f_s       [:861-871]
- *            (the slots per mode: see BO_QMC_QSR above)
- * Z: S x q base samples (SobolQMCNormalSampler, sampling/normal.py:178-209).
- * Output pointers may be NULL when not needed (acq required for QEI/QNEI).
- * Cached-root qNEI (utils/low_rank.py:85-173, acquisition/cached_cholesky.py):
- * Tm (r x ldT) = L_rr^{-1} Sigma'(X_baseline, X) columns per padded test row,
- * F (S x ldF) = Z_baseline Tm; then Sigma'_qq <- Sigma'_qq - Tm^T Tm and
- * f = mean' + F + chol(.) Z (Z: the q new Sobol columns).  NULL otherwise. */
-int bo_qmc_finalize(int kind, int mode, int B, int q, const double* Xq, const double* Spart,
-                    const double* mpart, int64_t n, double outputscale, double constant,
-                    double ymean, double ystd, const double* Z, int S, double best_f,
-                    const double* best_f_s, int max_tries, double jitter0, double* acq,
-                    double* mean_out, double* cov_out, double* L_out, int* info_out,
-                    double* jitter_out, const double* Tm, int r, int64_t ldT, const double* F,
-                    int64_t ldF, int fat, double tau_relu, double tau_max, void* stream);
-
-/* Backward of the MC reduction + q x q Cholesky (gen_candidates_scipy's
- * autograd.grad, botorch/generation/gen.py:194-222):
- * dacq (B) -> dmean (B x q), dcov (B x q x q, symmetric) w.r.t. the outcome-
- * space posterior (mean', Sigma'), given mean' and L_q from bo_qmc_finalize.
- * mode: BO_QMC_QEI or BO_QMC_QNEI (best_f_s per sample).  torch semantics:
- * amax splits ties evenly, clamp_min(0) passes the gradient at >= 0.
- * qNEI (cached root, utils/low_rank.py:85-173): the forward samples include
- * F = Z_base T (S x ldF, rows b*Qp + a, as passed to bo_qmc_finalize); dF (same
- * layout) receives its cotangent, from which dT = Z_base^T dF.  F/dF may be
- * NULL for qEI.  Log modes (BO_QMC_QLOGEI / BO_QMC_QLOGNEI) also take the
- * forward values acq_fwd (B) and the forward's fat / tau_relu / tau_max; their
- * weights are dense over (sample, q) rather than one-hot.
- * BO_QMC_QSR / BO_QMC_QPI / BO_QMC_QUCB: one-hot weights as qEI (amax ties
- * split evenly; qPI's scaled by sigma (1 - sigma) / tau at the winning value,
- * ties taken among the sigmoid values as torch.amax sees them); qUCB also
- * carries the gradient through the sample mean,
- *   dL[a][j] = zbar[j] sum_s w + beta' sum_s w sgn(e) (Z[s][j] - zbar[j]),
- *   e = (L_q (z_s - zbar))[a], sgn(0) = 0.  Parameter slots as the forward's. */
-int bo_qmc_backward(int mode, int B, int q, const double* mean, const double* Lq,
-                    const double* Z, int S, double best_f, const double* best_f_s,
-                    const double* F, int64_t ldF, const double* dacq, double* dmean,
-                    double* dcov, double* dF, const double* acq_fwd, int fat, double tau_relu,
-                    double tau_max, void* stream);
-
-/* Backward of the batched exact posterior w.r.t. the candidates X (B x q x d):
- *   dK*x = ystd dmean alpha^T - G W,  G = ystd^2 (dcov + dcov^T),
- *   W = R L^{-1} (nrows_pad x ldw, rows b*Qp + a; w_kmajor != 0: W^T as
- *   bo_post_w writes it, np x ldw), dK** = ystd^2 dcov,
- *   + E (optional extra dK*x, nrows_pad x lde, same rows: the qNEI cross-
- *     covariance terms),
- * reduced through dk/dx.  Xq / Xt_scaled as for bo_post_partials.  W, alpha,
- * dmean, dcov and E may each be NULL (term absent); accumulate != 0 adds into
- * dX.  With Xt_scaled = the qNEI baseline points and only E, this is the
- * gradient through K(X_baseline, X).  Caches carry no gradient ([G]
- * detach_test_caches, botorch/models/utils/assorted.py:286-298). */
-int bo_post_backward(int kind, int B, int q, int d, const double* Xq, const double* Xt_scaled,
-                     int64_t n, const double* W, int64_t ldw, const double* alpha,
-                     const double* dmean, const double* dcov, const double* E, int64_t lde,
-                     const double* lengthscale, double outputscale, double ystd, int accumulate,
-                     double* dX, int w_kmajor, void* stream);
 
 /* Kernel-matrix gradient for any d <= 128 (inputs in the original scale):
  *   dX[i][t] (+)= sum_k dK[i][k] d k(X_i, Y_k) / d X_it,
@@ -610,29 +501,6 @@ int bo_mll_terms(int kind, const double* X, int64_t n, int d, const double* leng
                  double outputscale, const double* L, const double* Ainv, int64_t ld,
                  const double* alpha, const double* beta, double* partial, void* stream);
 
-/* qEHVI over hypercells ([lo, hi] K x m from the non-dominated partitioning,
- * botorch/acquisition/multi_objective/monte_carlo.py:230-317) for B t-batches of
- * q points of an m-output independent model (ModelListGP):
- *   f[s][p][t] = mean[t][b][p] + sum_j L[t][b][p][j] Z[s][j m + t]
- *   acq[b] = mean_s sum_k inclusion-exclusion volume.
- * mean: m x B x q, L: m x B x q x q, Z: S x (q m).  2 <= m <= 4, q <= 12.
- * cell_stride 0: one set of K cells for every sample; > 0 (qNEHVI,
- * NoisyExpectedHypervolumeMixin, botorch/utils/multi_objective/hypervolume.py:
- * 507-835): sample s reads its own cells at cell_lo/hi + s * cell_stride (padded
- * with empty cells as BoxDecompositionList does).  F (nullable): the cached-root
- * baseline term added to f (m x S x ldF, output stride sF, row b * Qp + p). */
-int bo_qehvi(int B, int q, int m, const double* mean, const double* L, const double* Z, int S,
-             const double* cell_lo, const double* cell_hi, int K, int64_t cell_stride,
-             const double* F, int64_t ldF, int64_t sF, int Qp, double* acq, void* stream);
-
-/* Backward of bo_qehvi (autograd through _compute_qehvi,
- * multi_objective/monte_carlo.py:230-317): dacq (B) -> dmean (m x B x q) and
- * dL (m x B x q x q, lower) of the per-output posterior roots, and (with F)
- * dF (the cotangent of F, same layout) from which dT = Z_base^T dF. */
-int bo_qehvi_backward(int B, int q, int m, const double* mean, const double* L, const double* Z,
-                      int S, const double* cell_lo, const double* cell_hi, int K,
-                      int64_t cell_stride, const double* F, int64_t ldF, int64_t sF, int Qp,
-                      const double* dacq, double* dmean, double* dL, double* dF, void* stream);
 
 /* Batched Cholesky backward (torch linalg.cholesky backward): L, dL (B x q x q,
  * lower) -> dA (B x q x q, symmetric), q <= 64. */
@@ -662,44 +530,10 @@ int bo_sobol_normal(const int64_t* state, const int64_t* shift, int dim, int64_t
 int bo_sobol_scramble(int dim, const int64_t* state0, const uint8_t* bits, int64_t* state,
                       int64_t* shift, void* stream);
 
-/* One function evaluation of the device-resident multi-start projected L-BFGS
- * (replaces scipy L-BFGS-B in gen_candidates_scipy, botorch/generation/gen.py:
- * 194-267).  B restarts of dimension n, history m (<= 32).  The caller fills
- * ft (B) / gt (B x n) with the objective (-acq) and its gradient at the trial
- * points xt; the step accepts (Armijo, c1) or backtracks, updates x / f / g
- * and the (S, Y, rho) ring, tests convergence (status: 1 projected gradient
- * <= pgtol, 2 relative decrease <= ftol, 3 step below min_alpha; -1 on the first
- * call = take xt as the start), and writes the next trial points to xt.
- * x, g, xt, gt, d: B x n; S, Y: B x m x n; f, alpha: B; rho: B x m;
- * hcount, hhead, status, nacc (accepted steps): B int32; lower, upper: n. */
-int bo_lbfgs_step(int B, int n, int m, double* x, double* f, double* g, double* xt,
-                  const double* ft, const double* gt, double* d, double* alpha, double* S,
-                  double* Y, double* rho, int* hcount, int* hhead, int* status, int* nacc,
-                  const double* lower, const double* upper, double c1, double ftol,
-                  double pgtol, double min_alpha, void* stream);
 
-/* One function evaluation of the device-resident multi-start L-BFGS-B: scipy
- * 1.15's L-BFGS-B (generalized Cauchy point, subspace minimisation with the
- * v3.0 projection, More-Thuente line search; the optimiser of
- * gen_candidates_scipy, botorch/generation/gen.py:252-267) as a reverse-
- * communication state machine, one 64-lane wave per restart.  The caller
- * writes ft (B) / gt (B x n) = objective and gradient at the trial points xt
- * (B x n); the call advances every restart to its next evaluation and
- * overwrites xt.  Zeroed state (v, iv, ws, wy, mat, ds, is) means "start at
- * xt".  ftol / pgtol / maxls / maxiter / maxfun are scipy's options of the same
- * names (m = maxcor <= 20).  Per restart: v = V x n doubles, iv = IV x n ints,
- * ws / wy = m x n, mat = MAT doubles, ds = DS doubles, is = IS ints, with
- * (V, IV, MAT, DS, IS) from bo_lbfgsb_layout; is[1] is the status (0 running,
- * 1 projected gradient <= pgtol, 2 relative reduction <= ftol, 3 abnormal line
- * search, 4 maxiter, 5 maxfun, 6 error), is[10] the iterations, ds[0] f and
- * v[0..n) x. */
-int bo_lbfgsb_step(int B, int n, int m, int maxls, int maxiter, int maxfun, double ftol,
-                   double pgtol, const double* lower, const double* upper, double* xt,
-                   const double* ft, const double* gt, double* v, int* iv, double* ws, double* wy,
-                   double* mat, double* ds, int* is, void* stream);
 /* HOST: out[0..5] = V, IV, MAT, DS, IS, maximum m. */
 int bo_lbfgsb_layout(int* out);
-/* Profiling aid: subsequent bo_lbfgsb_step launches of at most `capacity`
+/* Profiling aid: subsequent bo_lbfgsb_step_v launches of at most `capacity`
  * restarts add each restart's phase times (wall-clock ticks: load, Cauchy
  * point, free set, formk, cmprlb, subsm, line search + update, store) into prof
  * (capacity x 8, device memory); larger launches are not profiled; NULL stops. */
@@ -764,18 +598,48 @@ int bo_sobol_box(const int64_t* state, const int64_t* shift, int dim, int64_t n,
                  void* stream);
 
 /* ---- Parameter-struct entry points (ABI 9; ABI 10 adds rt_layout, ABI 11 the
- * quad-plan and fused-status fields of BoQmcFinalizeArgs) ------------------------
- * The widest calls above also take one struct of named fields, so a binding
- * declares a record instead of a positional list of 20-33 arguments.  Every
- * struct opens with struct_size = sizeof(struct) and abi_version =
- * BO_ABI_VERSION; a mismatch returns BO_ERR_ARG (never a misread field).  Field
- * meanings are those of the positional function named in each comment; each
- * _v function forwards to it. */
+ * quad-plan and fused-status fields of BoQmcFinalizeArgs; ABI 12 retires the
+ * positional twins of the eight oldest launches) ------------------------------
+ * The widest calls take one struct of named fields, so a binding declares a
+ * record instead of a positional list of 20-33 arguments; the bo_<name>_v
+ * function is the only entry point of such a launch.  Every struct opens with
+ * struct_size = sizeof(struct) and abi_version = BO_ABI_VERSION; a mismatch
+ * returns BO_ERR_ARG (never a misread field) before anything else runs.  The
+ * comment on each record documents the launch and its fields. */
 #define BO_STRUCT_HEADER \
   uint32_t struct_size;  \
   uint32_t abi_version
 
-typedef struct BoPostPartialsArgs { /* bo_post_partials */
+/* Fused K*x build + R^T = U^T K*x^T GEMM + R R^T / R beta epilogue
+ * ([G] exact_predictive_mean / exact_predictive_covar under fast_pred_var,
+ * botorch/models/gpytorch.py:446).  Xt_scaled: n x 8 lengthscale-scaled
+ * training inputs; U: >= np x np with leading dim ldu; beta: n.
+ * Spart: nC x (nrows_pad/16) x 16 x 16,  mpart: nC x nrows_pad.
+ * Rt (nullable, gradient path): R^T, (nC*128) x nrows_pad.
+ * kc_len = 0: one workgroup per (column tile, row tile), work unused;
+ * kc_len > 0: split (every tile cut into chunks of kc_len training rows);
+ * kc_len = -1: stream-K (the tiles' k-steps cut into one equal share per
+ * resident slot).  Split plans reduce each cut tile's chunks in k order, with
+ * `work` >= the work_elems of bo_post_split_plan / bo_post_split_work.
+ * Qc (nullable, one-pass only): rq <= 16 rows (leading dim ldq >= n) whose
+ * products with K*x are returned as nC column-tile partials
+ * Cx[ci] (nC x rq x nrows_pad; sum over ci = Qc K*x^T) -- the
+ * qNEI cross-covariance P_b R^T = Q_b K*x^T, Q_b = P_b U^T
+ * (acquisition/cached_cholesky.py:94-120), without storing R.
+ * Kt (nullable): K*x^T from bo_post_kxt (read instead of evaluated).
+ *
+ * The triangular operand (every entry point on the posterior kernel's 128 x
+ * 128 tiles: bo_post_partials_v, bo_post_partials_members with U = L^{-T}
+ * upper; bo_post_w*, bo_post_w_dx, bo_ainv with L^{-1} lower).  Column tile c
+ * reads rows [0, 128 c + 128) of U (rows [128 c, n) of L^{-1}) and nothing
+ * beyond.  Inside the tile's diagonal 128 x 128 block it multiplies only the
+ * 16 x 16 blocks on or above the block diagonal (on or below, L^{-1}): the
+ * 16 x 16 blocks on the zero side are loaded but never multiplied, so their
+ * contents do not reach the result.  What the caller owes: the zero triangle
+ * INSIDE the 16 x 16 diagonal blocks holds exact zeros, and rows / columns
+ * >= n hold the identity pad.  bo_gp_cache_build*, bo_cholesky_inverse* and
+ * bo_gp_cache_extend leave the whole opposite triangle zero. */
+typedef struct BoPostPartialsArgs {
   BO_STRUCT_HEADER;
   int32_t kind, B, q, d;
   const double* Xq;
@@ -796,7 +660,32 @@ typedef struct BoPostPartialsArgs { /* bo_post_partials */
 } BoPostPartialsArgs;
 int bo_post_partials_v(const BoPostPartialsArgs* a, void* stream);
 
-typedef struct BoQmcFinalizeArgs { /* bo_qmc_finalize */
+/* Finalise the posterior of each t-batch and (mode != POSTERIOR) run the
+ * fused q x q psd_safe_cholesky + reparameterised sampling + MC reduction:
+ *   mean_out (B x q) = ymean + ystd (constant + R beta)
+ *   cov_out (B x q x q) = ystd^2 (K** - R R^T)       [Standardize.untransform_posterior,
+ *                                                     botorch/models/transforms/outcome.py:373-447]
+ *   L_out (B x q x q), info_out (B), jitter_out (B)  [posteriors/gpytorch.py:85-126]
+ *   acq (B): qEI  mean_s max_a relu(f - best_f)      [acquisition/monte_carlo.py:405-414]
+ *            qNEI mean_s max_a relu(f - best_f_s[s])  [acquisition/monte_carlo.py:580-589]
+ *            qLogEI / qLogNEI (best_f / best_f_s[s]):
+ *              logmeanexp_s fatmax_a log_fatplus(f - best_f, tau_relu)   (fat != 0)
+ *              logmeanexp_s smooth_amax_a log_softplus(f - best_f, tau_relu) (fat == 0)
+ *              with the q-reduction at temperature tau_max
+ *              [acquisition/logei.py:122, 219-234, 347-362, 509-534;
+ *               utils/safe_math.py:209-352]; fat/tau_* are ignored by other modes
+ *            qSR  mean_s max_a f                      [acquisition/monte_carlo.py:789-798]
+ *            qPI  mean_s max_a sigmoid((f - best_f) / tau), tau in tau_relu   [:721-731]
+ *            qUCB mean_s max_a (fbar_a + beta' |f_a - fbar_a|), fbar = mean_s f =
+ *                 mean' + L_q zbar; beta' in best_f, zbar (q) in best_f_s       [:861-871]
+ *            (the slots per mode: see BO_QMC_QSR above)
+ * Z: S x q base samples (SobolQMCNormalSampler, sampling/normal.py:178-209).
+ * Output pointers may be NULL when not needed (acq required for QEI/QNEI).
+ * Cached-root qNEI (utils/low_rank.py:85-173, acquisition/cached_cholesky.py):
+ * Tm (r x ldT) = L_rr^{-1} Sigma'(X_baseline, X) columns per padded test row,
+ * F (S x ldF) = Z_baseline Tm; then Sigma'_qq <- Sigma'_qq - Tm^T Tm and
+ * f = mean' + F + chol(.) Z (Z: the q new Sobol columns).  NULL otherwise. */
+typedef struct BoQmcFinalizeArgs {
   BO_STRUCT_HEADER;
   int32_t kind, mode, B, q;
   const double *Xq, *Spart, *mpart;
@@ -828,7 +717,25 @@ typedef struct BoQmcFinalizeArgs { /* bo_qmc_finalize */
 } BoQmcFinalizeArgs;
 int bo_qmc_finalize_v(const BoQmcFinalizeArgs* a, void* stream);
 
-typedef struct BoQmcBackwardArgs { /* bo_qmc_backward */
+/* Backward of the MC reduction + q x q Cholesky (gen_candidates_scipy's
+ * autograd.grad, botorch/generation/gen.py:194-222):
+ * dacq (B) -> dmean (B x q), dcov (B x q x q, symmetric) w.r.t. the outcome-
+ * space posterior (mean', Sigma'), given mean' and L_q from bo_qmc_finalize_v.
+ * mode: BO_QMC_QEI or BO_QMC_QNEI (best_f_s per sample).  torch semantics:
+ * amax splits ties evenly, clamp_min(0) passes the gradient at >= 0.
+ * qNEI (cached root, utils/low_rank.py:85-173): the forward samples include
+ * F = Z_base T (S x ldF, rows b*Qp + a, as passed to bo_qmc_finalize_v); dF (same
+ * layout) receives its cotangent, from which dT = Z_base^T dF.  F/dF may be
+ * NULL for qEI.  Log modes (BO_QMC_QLOGEI / BO_QMC_QLOGNEI) also take the
+ * forward values acq_fwd (B) and the forward's fat / tau_relu / tau_max; their
+ * weights are dense over (sample, q) rather than one-hot.
+ * BO_QMC_QSR / BO_QMC_QPI / BO_QMC_QUCB: one-hot weights as qEI (amax ties
+ * split evenly; qPI's scaled by sigma (1 - sigma) / tau at the winning value,
+ * ties taken among the sigmoid values as torch.amax sees them); qUCB also
+ * carries the gradient through the sample mean,
+ *   dL[a][j] = zbar[j] sum_s w + beta' sum_s w sgn(e) (Z[s][j] - zbar[j]),
+ *   e = (L_q (z_s - zbar))[a], sgn(0) = 0.  Parameter slots as the forward's. */
+typedef struct BoQmcBackwardArgs {
   BO_STRUCT_HEADER;
   int32_t mode, B, q, S;
   const double *mean, *Lq, *Z;
@@ -843,7 +750,18 @@ typedef struct BoQmcBackwardArgs { /* bo_qmc_backward */
 } BoQmcBackwardArgs;
 int bo_qmc_backward_v(const BoQmcBackwardArgs* a, void* stream);
 
-typedef struct BoPostBackwardArgs { /* bo_post_backward */
+/* Backward of the batched exact posterior w.r.t. the candidates X (B x q x d):
+ *   dK*x = ystd dmean alpha^T - G W,  G = ystd^2 (dcov + dcov^T),
+ *   W = R L^{-1} (nrows_pad x ldw, rows b*Qp + a; w_kmajor != 0: W^T as
+ *   bo_post_w writes it, np x ldw), dK** = ystd^2 dcov,
+ *   + E (optional extra dK*x, nrows_pad x lde, same rows: the qNEI cross-
+ *     covariance terms),
+ * reduced through dk/dx.  Xq / Xt_scaled as for bo_post_partials_v.  W, alpha,
+ * dmean, dcov and E may each be NULL (term absent); accumulate != 0 adds into
+ * dX.  With Xt_scaled = the qNEI baseline points and only E, this is the
+ * gradient through K(X_baseline, X).  Caches carry no gradient ([G]
+ * detach_test_caches, botorch/models/utils/assorted.py:286-298). */
+typedef struct BoPostBackwardArgs {
   BO_STRUCT_HEADER;
   int32_t kind, B, q, d;
   const double *Xq, *Xt_scaled;
@@ -865,7 +783,22 @@ int bo_post_backward_v(const BoPostBackwardArgs* a, void* stream);
 int bo_post_backward_jobs(int njobs, const BoPostBackwardArgs* const* jobs, double* dX_parts,
                           void* stream);
 
-typedef struct BoQehviArgs { /* bo_qehvi and bo_qehvi_backward (d* fields: backward only) */
+/* qEHVI over hypercells ([lo, hi] K x m from the non-dominated partitioning,
+ * botorch/acquisition/multi_objective/monte_carlo.py:230-317) for B t-batches of
+ * q points of an m-output independent model (ModelListGP):
+ *   f[s][p][t] = mean[t][b][p] + sum_j L[t][b][p][j] Z[s][j m + t]
+ *   acq[b] = mean_s sum_k inclusion-exclusion volume.
+ * mean: m x B x q, L: m x B x q x q, Z: S x (q m).  2 <= m <= 4, q <= 12.
+ * cell_stride 0: one set of K cells for every sample; > 0 (qNEHVI,
+ * NoisyExpectedHypervolumeMixin, botorch/utils/multi_objective/hypervolume.py:
+ * 507-835): sample s reads its own cells at cell_lo/hi + s * cell_stride (padded
+ * with empty cells as BoxDecompositionList does).  F (nullable): the cached-root
+ * baseline term added to f (m x S x ldF, output stride sF, row b * Qp + p).
+ * The backward (autograd through _compute_qehvi,
+ * multi_objective/monte_carlo.py:230-317): dacq (B) -> dmean (m x B x q) and
+ * dL (m x B x q x q, lower) of the per-output posterior roots, and (with F)
+ * dF (the cotangent of F, same layout) from which dT = Z_base^T dF. */
+typedef struct BoQehviArgs { /* forward and backward (d* fields: backward only) */
   BO_STRUCT_HEADER;
   int32_t B, q, m, S;
   const double *mean, *L, *Z, *cell_lo, *cell_hi;
@@ -888,7 +821,7 @@ int bo_qehvi_backward_v(const BoQehviArgs* a, void* stream);
 /* Feasibility-weighted qEHVI (outcome constraints: botorch/acquisition/
  * multi_objective/monte_carlo.py:245-251, 303-309; qNEHVI,
  * botorch/utils/multi_objective/hypervolume.py:725-767): every
- * inclusion-exclusion term of bo_qehvi is multiplied by prod_{p in T}
+ * inclusion-exclusion term of bo_qehvi_v is multiplied by prod_{p in T}
  * feas[s][b][p] (feas: S x B x q, the smoothed feasibility indicator of the
  * samples).  The model list has Mt >= m members, of which objective t is member
  * out_idx[t] (injective, any order): mean is Mt x B x q, L is Mt x B x q x q, F is
@@ -935,8 +868,7 @@ int bo_qehvi_feas_backward_v(const BoQehviFeasArgs* a, void* stream);
  * Forward: writes acq (B) and hvi (S x B).  Backward: reads both, and dacq;
  * writes dmean / dL / dF at the objective members' slices only and, with logw,
  * dlogw (S x B x q).  work (optional, the sample split over workgroups):
- * forward >= 4 B doubles, backward >= 2 B m q (q + 3) / 2.
- * A pure addition to the ABI: BO_ABI_VERSION stays 11. */
+ * forward >= 4 B doubles, backward >= 2 B m q (q + 3) / 2. */
 typedef struct BoQlogehviArgs {
   BO_STRUCT_HEADER;
   int32_t B, q, m, S;
@@ -981,8 +913,7 @@ int bo_qlogehvi_backward_v(const BoQlogehviArgs* a, void* stream);
  * log mode the forward's acq, writes dmean, dL (full q x q, upper zero), dF
  * (with F; entries of rows a < q) following torch autograd: amax shares the
  * cotangent evenly among all maximal entries (ties at 0 included), clamp_min
- * passes it where obj - bf >= 0.  No atomics; fixed summation order.
- * A pure addition to the ABI: BO_ABI_VERSION stays 11. */
+ * passes it where obj - bf >= 0.  No atomics; fixed summation order. */
 typedef struct BoQmcFeasArgs {
   BO_STRUCT_HEADER;
   int32_t B, q, Mt, S;
@@ -1021,7 +952,7 @@ int bo_qmc_feas_backward_v(const BoQmcFeasArgs* a, void* stream);
  * dcov[row_i][j] = c_i w_ij, the tile-0 q_a x q_a block the (symmetric)
  * Cholesky backward of dL = -tril(sum_i c_i w_i u_i^T), u_i = L^{-1} cov[row_i][:q_a],
  * and every other entry zero.  One workgroup per restart, one launch each way,
- * no atomics.  A pure addition to the ABI: BO_ABI_VERSION stays 11. */
+ * no atomics. */
 typedef struct BoKgArgs {
   BO_STRUCT_HEADER;
   int32_t B, T, q_a, slots, N_f, max_tries;
@@ -1055,7 +986,7 @@ int bo_kg_backward_v(const BoKgArgs* a, void* stream);
  * d <= 128 (a runtime loop), M even, fp64 throughout, sincos on the unreduced
  * phase.  The features and the kernel row of a 16-row tile live in registers:
  * no workspace, one launch each way, no atomics (repeated calls are bitwise
- * identical).  A pure addition to the ABI: BO_ABI_VERSION stays 11. */
+ * identical). */
 typedef struct BoPathsArgs {
   BO_STRUCT_HEADER;
   int32_t kind, d, S, M;
@@ -1088,8 +1019,7 @@ int bo_paths_eval_backward_v(const BoPathsArgs* a, void* stream);
  * every entry is written, the caller clears nothing.
  * d <= 128 (a runtime loop), P >= 1, R >= 1, fp64 throughout.  c_ij lives in
  * the MFMA accumulators: no R x P array, no workspace, one launch each way, no
- * atomics (repeated calls are bitwise identical).  A pure addition to the ABI:
- * BO_ABI_VERSION stays 11. */
+ * atomics (repeated calls are bitwise identical). */
 typedef struct BoJesArgs {
   BO_STRUCT_HEADER;
   int32_t kind, d, P, _pad;
@@ -1130,7 +1060,7 @@ int bo_jes_backward_v(const BoJesArgs* a, void* stream);
  * 1 <= S_M <= 1024, 2 <= S_m <= 4096, 1 <= R < 2^31.  One wave per row, the
  * pairs spread over its lanes; sums folded in a fixed order by lane exchanges:
  * no atomics, no workspace, no R x S_M x S_m array; repeated calls are bitwise
- * identical.  A pure addition to the ABI: BO_ABI_VERSION stays 11. */
+ * identical. */
 typedef struct BoMesArgs {
   BO_STRUCT_HEADER;
   int32_t S_M, S_m;
@@ -1207,7 +1137,7 @@ int bo_mv_quantiles_v(const BoMvQuantilesArgs* a, void* stream);
  * Neither C (R x N) nor the kernel rows (R x n) reach memory; with more than
  * one slice a stream-ordered workspace of split x B q q (forward) or split x
  * R d (backward) doubles is taken and returned.  No atomics (repeated calls
- * are bitwise identical).  A pure addition to the ABI: BO_ABI_VERSION stays 11. */
+ * are bitwise identical). */
 typedef struct BoNipvArgs {
   BO_STRUCT_HEADER;
   int32_t kind, d, q, split;
@@ -1240,8 +1170,7 @@ int bo_nipv_gram_backward_v(const BoNipvArgs* a, void* stream);
  * work: scratch of work_size doubles, at least B M (forward) or B M S
  * (backward: the per-sample log-sum-exp).
  * 1 <= M <= 64, 1 <= q <= 16, 1 <= S <= 2^20, B >= 1 with B M < 2^31, fp64.
- * Sums fold in a fixed order, no atomics: repeated calls are bitwise identical.
- * A pure addition to the ABI: BO_ABI_VERSION stays 11. */
+ * Sums fold in a fixed order, no atomics: repeated calls are bitwise identical. */
 typedef struct BoBaldArgs {
   BO_STRUCT_HEADER;
   int32_t M, q, S, _pad;
@@ -1289,8 +1218,7 @@ int bo_bald_backward_v(const BoBaldArgs* a, void* stream);
  * 1 <= Mt <= 16, 0 <= R < 2^38 (R = 0 returns at once), min_var > 0, w = +-1,
  * beta >= 0, best_f_stride 0 or 1, upper > lower on two-sided constraints.
  * One thread per row, 256-thread blocks, no LDS, no atomics, no workspace:
- * repeated calls are bitwise identical.  A pure addition to the ABI:
- * BO_ABI_VERSION stays 11. */
+ * repeated calls are bitwise identical. */
 #define BO_AN_CMAX 15
 enum { BO_AN_LOG_EI = 0, BO_AN_EI = 1, BO_AN_LOG_PI = 2, BO_AN_PI = 3, BO_AN_UCB = 4,
        BO_AN_STD = 5 };
@@ -1334,8 +1262,7 @@ int bo_analytic_backward_v(const BoAnalyticArgs* a, void* stream);
  * returns U = +inf and a zero gradient; the other rows are unaffected.
  * 0 <= n <= 1024, 1 <= d <= 256, C >= 1 with C n^2 < 2^31, fp64.  No atomics,
  * nothing shared between workgroups: repeated calls are bitwise identical and
- * row c of a C-row call equals the one-row call on that row.
- * A pure addition to the ABI: BO_ABI_VERSION stays 11. */
+ * row c of a C-row call equals the one-row call on that row. */
 typedef struct BoSaasPotentialArgs {
   BO_STRUCT_HEADER;
   int32_t d, _pad;
@@ -1350,7 +1277,17 @@ int bo_saas_potential_v(const BoSaasPotentialArgs* a, void* stream);
 /* HOST: doubles of work for a call of C rows. */
 int bo_saas_potential_work(int64_t n, int d, int64_t C, int64_t* elems);
 
-typedef struct BoLbfgsStepArgs { /* bo_lbfgs_step */
+/* One function evaluation of the device-resident multi-start projected L-BFGS
+ * (replaces scipy L-BFGS-B in gen_candidates_scipy, botorch/generation/gen.py:
+ * 194-267).  B restarts of dimension n, history m (<= 32).  The caller fills
+ * ft (B) / gt (B x n) with the objective (-acq) and its gradient at the trial
+ * points xt; the step accepts (Armijo, c1) or backtracks, updates x / f / g
+ * and the (S, Y, rho) ring, tests convergence (status: 1 projected gradient
+ * <= pgtol, 2 relative decrease <= ftol, 3 step below min_alpha; -1 on the first
+ * call = take xt as the start), and writes the next trial points to xt.
+ * x, g, xt, gt, d: B x n; S, Y: B x m x n; f, alpha: B; rho: B x m;
+ * hcount, hhead, status, nacc (accepted steps): B int32; lower, upper: n. */
+typedef struct BoLbfgsStepArgs {
   BO_STRUCT_HEADER;
   int32_t B, n, m, _pad;
   double *x, *f, *g, *xt;
@@ -1362,7 +1299,22 @@ typedef struct BoLbfgsStepArgs { /* bo_lbfgs_step */
 } BoLbfgsStepArgs;
 int bo_lbfgs_step_v(const BoLbfgsStepArgs* a, void* stream);
 
-typedef struct BoLbfgsbArgs { /* bo_lbfgsb_step */
+/* One function evaluation of the device-resident multi-start L-BFGS-B: scipy
+ * 1.15's L-BFGS-B (generalized Cauchy point, subspace minimisation with the
+ * v3.0 projection, More-Thuente line search; the optimiser of
+ * gen_candidates_scipy, botorch/generation/gen.py:252-267) as a reverse-
+ * communication state machine, one 64-lane wave per restart.  The caller
+ * writes ft (B) / gt (B x n) = objective and gradient at the trial points xt
+ * (B x n); the call advances every restart to its next evaluation and
+ * overwrites xt.  Zeroed state (v, iv, ws, wy, mat, ds, is) means "start at
+ * xt".  ftol / pgtol / maxls / maxiter / maxfun are scipy's options of the same
+ * names (m = maxcor <= 20).  Per restart: v = V x n doubles, iv = IV x n ints,
+ * ws / wy = m x n, mat = MAT doubles, ds = DS doubles, is = IS ints, with
+ * (V, IV, MAT, DS, IS) from bo_lbfgsb_layout; is[1] is the status (0 running,
+ * 1 projected gradient <= pgtol, 2 relative reduction <= ftol, 3 abnormal line
+ * search, 4 maxiter, 5 maxfun, 6 error), is[10] the iterations, ds[0] f and
+ * v[0..n) x. */
+typedef struct BoLbfgsbArgs {
   BO_STRUCT_HEADER;
   int32_t B, n, m, maxls, maxiter, maxfun;
   double ftol, pgtol;

@@ -31,7 +31,7 @@ def test_analytic_record_symbols_and_ops():
     for sym in ("bo_analytic_v", "bo_analytic_backward_v"):
         assert sym in _lib.exported_symbols() and hasattr(ctypes.CDLL(_lib.LIB_PATH), sym)
     assert "analytic" in ops.OPS and "analytic_backward" in ops.OPS
-    assert lib.bo_version() == _lib.ABI_VERSION == 11  # a pure addition
+    assert lib.bo_version() == _lib.ABI_VERSION == 12  # a pure addition
     assert kernels.AN_CMAX == _lib.AN_CMAX == 15 and kernels.AN_MT_MAX == 16
     assert (kernels.AN_LOG_EI, kernels.AN_EI, kernels.AN_LOG_PI, kernels.AN_PI, kernels.AN_UCB,
             kernels.AN_STD) == (ar.LOG_EI, ar.EI, ar.LOG_PI, ar.PI, ar.UCB, ar.STD)

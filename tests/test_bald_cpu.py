@@ -25,7 +25,7 @@ def test_bald_record_and_symbols():
         assert sym in _lib.exported_symbols()
         assert hasattr(ctypes.CDLL(_lib.LIB_PATH), sym)
     assert "bald" in ops.OPS and "bald_backward" in ops.OPS
-    assert lib.bo_version() == _lib.ABI_VERSION == 11  # a pure addition
+    assert lib.bo_version() == _lib.ABI_VERSION == 12  # a pure addition
 
 
 def test_bald_abi_refusals():

@@ -40,7 +40,7 @@ def test_library_exports_every_header_symbol():
         assert hasattr(handle, s), s
     assert set(syms) == set(_lib.exported_symbols()), set(syms) ^ set(_lib.exported_symbols())
     lib = _lib.lib()
-    assert lib.bo_version() == _lib.ABI_VERSION == 11
+    assert lib.bo_version() == _lib.ABI_VERSION == 12
     assert lib.bo_padded_order(4096) == 4096 and lib.bo_padded_order(20) == 128
 
 
@@ -154,6 +154,54 @@ def test_arg_records_match_c_layout():
     a = _lib.LbfgsStepArgs(B=1, n=1, m=1)
     a.struct_size = 8
     assert lib.bo_lbfgs_step_v(ctypes.byref(a), None) != 0
+
+
+# the positional twins of the eight oldest launches and the longer positional
+# functions behind them, retired at ABI 12
+_RETIRED = ("bo_post_partials", "bo_qmc_finalize", "bo_qmc_backward", "bo_post_backward",
+            "bo_qehvi", "bo_qehvi_backward", "bo_lbfgs_step", "bo_lbfgsb_step",
+            "bo_qmc_finalize_ext", "bo_qehvi_ext", "bo_qehvi_backward_ext",
+            "bo_post_partials_layout")
+
+
+def test_no_retired_symbol_survives():
+    """Each of those launches has one entry point, its record's _v function:
+    the library exports no retired name and the header names none, in a
+    declaration or in prose."""
+    from botorch_amd import _lib
+    handle = ctypes.CDLL(_lib.LIB_PATH)  # a fresh handle: no attribute cached by a binding
+    header = open(os.path.join(ROOT, "include", "botorch_amd.h")).read()
+    declared = _header_symbols()
+    for name in _RETIRED:
+        assert not hasattr(handle, name), name
+        assert name not in declared and name not in _lib.exported_symbols(), name
+        assert re.search(r"\b%s\b" % name, header) is None, name
+        if not name.endswith(("_ext", "_layout")):  # the record form stays
+            assert hasattr(handle, name + "_v") and name + "_v" in declared, name
+
+
+def test_every_record_entry_refuses_a_bad_header():
+    """Every bo_*_v checks the record's header first: a default-constructed
+    record (null pointers, zero sizes) of another ABI version or a short
+    struct_size is BO_ERR_ARG with a message, and nothing is read or launched."""
+    from botorch_amd import _lib
+    lib = _lib.lib()
+    assert len(_lib.RECORD_ENTRIES) == 32
+    assert set(_lib.RECORD_ENTRIES) == {s for s in _header_symbols() if s.endswith("_v")}
+    assert set(_lib.RECORD_ENTRIES.values()) == set(_lib.ARG_RECORDS.values())
+    for name, rec in _lib.RECORD_ENTRIES.items():
+        fn = getattr(lib, name)
+        a = rec()
+        a.abi_version = _lib.ABI_VERSION + 1
+        assert fn(ctypes.byref(a), None) == _lib.BO_ERR_ARG, name
+        msg = lib.bo_last_error()
+        assert msg and name.encode() in msg, (name, msg)
+        a = rec()
+        a.struct_size = ctypes.sizeof(rec) - 8
+        assert fn(ctypes.byref(a), None) == _lib.BO_ERR_ARG, name
+        msg = lib.bo_last_error()
+        assert msg and name.encode() in msg, (name, msg)
+        assert fn(None, None) == _lib.BO_ERR_ARG, name  # a null record
 
 
 def test_settings_flags_mirror_reference():

@@ -223,7 +223,10 @@ def test_output_map_writes_objective_slices_only():
     _check_case("Mt=5 out_idx=(3,0)", c, acq, res)
 
 
-@pytest.mark.parametrize("m,q,S,B,K", [(3, 4, 16, 5, 30), (2, 12, 16, 2, 16)])
+# The plain and the weighted launches share one launcher.  B = 2: every launch
+# splits the samples (forward: B <= 512, backward: B <= 128); B = 600: none does.
+@pytest.mark.parametrize("m,q,S,B,K", [(3, 4, 16, 5, 30), (2, 12, 16, 2, 16), (2, 2, 16, 2, 3),
+                                       (2, 2, 16, 600, 3)])
 def test_unit_weights_match_unweighted_kernels(m, q, S, B, K):
     """(a) all weights exactly 1.0: the unweighted kernels' acq, dmean, dL."""
     from botorch_amd import kernels

@@ -22,7 +22,7 @@ def test_jes_record_and_symbols():
         assert sym in _lib.exported_symbols()
         assert hasattr(ctypes.CDLL(_lib.LIB_PATH), sym)
     assert "jes" in ops.OPS and "jes_backward" in ops.OPS
-    assert lib.bo_version() == _lib.ABI_VERSION == 11  # a pure addition
+    assert lib.bo_version() == _lib.ABI_VERSION == 12  # a pure addition
 
 
 def test_jes_abi_refusals():

@@ -28,7 +28,7 @@ def test_mes_records_and_symbols():
         assert hasattr(ctypes.CDLL(_lib.LIB_PATH), sym)
     for op in ("mes", "mes_backward", "gibbon", "gibbon_backward", "mv_quantiles"):
         assert op in ops.OPS
-    assert lib.bo_version() == _lib.ABI_VERSION == 11  # a pure addition
+    assert lib.bo_version() == _lib.ABI_VERSION == 12  # a pure addition
 
 
 def test_mes_abi_refusals():

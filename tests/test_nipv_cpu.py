@@ -24,7 +24,7 @@ def test_nipv_record_and_symbols():
         assert sym in _lib.exported_symbols()
         assert hasattr(ctypes.CDLL(_lib.LIB_PATH), sym)
     assert "nipv_gram" in ops.OPS and "nipv_gram_backward" in ops.OPS
-    assert lib.bo_version() == _lib.ABI_VERSION == 11  # a pure addition
+    assert lib.bo_version() == _lib.ABI_VERSION == 12  # a pure addition
 
 
 def test_nipv_abi_refusals():

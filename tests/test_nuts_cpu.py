@@ -245,7 +245,7 @@ def test_saas_record_symbols_and_limits():
     assert lib.bo_struct_size(b"BoSaasPotentialArgs") == ctypes.sizeof(_lib.SaasPotentialArgs)
     for sym in ("bo_saas_potential_v", "bo_saas_potential_work"):
         assert sym in _lib.exported_symbols() and hasattr(ctypes.CDLL(_lib.LIB_PATH), sym)
-    assert "saas_potential" in ops.OPS and lib.bo_version() == _lib.ABI_VERSION == 11
+    assert "saas_potential" in ops.OPS and lib.bo_version() == _lib.ABI_VERSION == 12
     # the header and the limits are refused before any launch
     a = _lib.SaasPotentialArgs(d=3, n=4, C=1)
     a.abi_version += 1
