@@ -54,9 +54,32 @@ constexpr int PLD = 144;  // LDS row pitch (doubles): 2 x 144 dwords = 32 mod 64
 constexpr int DP = 8;     // padded input dimension held in registers
 constexpr int kSlots = 512;            // resident workgroups: 256 CUs x 2 (launch bounds)
 constexpr int kTileDoubles = 32 * 64;  // one 16-row x 128-column R^T tile
+// kxt_build_kernel where the grid fills the chip: KXT_K training points and
+// KXT_ROWS adjacent test rows per thread, KXT_UNROLL points in flight
 #ifndef KXT_K
-#define KXT_K 16  // training points per thread of kxt_build_kernel
+#define KXT_K 32
 #endif
+#ifndef KXT_ROWS
+#define KXT_ROWS 2
+#endif
+#ifndef KXT_UNROLL
+#define KXT_UNROLL 2
+#endif
+#ifndef KXT_STAGE_LDS
+#define KXT_STAGE_LDS 1  // the workgroup's training rows staged in LDS (0: a measurement arm)
+#endif
+constexpr int kKxtSmallUnit = 16;  // the small-grid rule counts workgroups of 256 rows x 16 points
+typedef double v2d __attribute__((ext_vector_type(2)));
+
+// outputscale k(d2): the one expression every K*x value of this file comes from.
+template <int KIND>
+__device__ __forceinline__ double scaled_kernel_value(double d2, double outputscale) {
+#ifdef BO_PROBE_CHEAP_KERNEL  // timing probe only (tools): no exp, wrong values
+  return outputscale * d2 * 0.0;  // keeps the distance FMAs, drops the exp
+#else
+  return outputscale * kernel_from_d2<KIND>(d2);
+#endif
+}
 
 // One kernel value k(x_i, x_k) from scaled coordinates (0 beyond n / invalid rows).
 template <int KIND, int ND>
@@ -70,11 +93,7 @@ __device__ __forceinline__ double eval_kernel_row(const double (&xi)[ND], const 
     const double df = xi[t] - xt[t];
     d2 = fma(df, df, d2);
   }
-#ifdef BO_PROBE_CHEAP_KERNEL  // timing probe only (tools): no exp, wrong values
-  return outputscale * d2 * 0.0;  // keeps the distance FMAs, drops the exp
-#else
-  return outputscale * kernel_from_d2<KIND>(d2);
-#endif
+  return scaled_kernel_value<KIND>(d2, outputscale);
 }
 
 // Number of k-chunks of column tile ci, and the chunks of all tiles before it
@@ -1008,10 +1027,18 @@ __global__ __launch_bounds__(512, 2) void post_partials_wide_kernel(
 // K*x^T once per call: Kt[k][i] = outputscale k(x_i, x_k), zero for k >= n
 // or padding rows; np x nrows_pad.  The one-pass grid re-reads each K*x tile
 // from L2/HBM for every column tile whose k-range covers it (nC / 2 times on
-// average) instead of re-evaluating its exponentials each time: at C3 the
-// posterior kernel runs 3.0 ms from precomputed values against 3.7 ms with
-// the exponentials between its MFMAs, for 0.08 ms of build.
-// RowsFromX (bo_post_kxt_rows): the thread takes its test row straight from
+// average) instead of re-evaluating its exponentials each time.
+// A workgroup is 256 x ROWS test rows by KK training points.  Its KK rows of
+// Xt are fetched once into LDS ahead of the arithmetic (k clamped to n - 1),
+// the value loop has no branch and no global load (rows k >= n and invalid
+// test rows are selected to 0.0 after the evaluation), and with ROWS = 2 a
+// thread's two adjacent rows leave as one 16-byte store per training point.
+// C3 (8192 rows x 4096 points, 268 MB; HIP events around the call,
+// tools/time_kxt.py): 56.7 us with 512 x 32 workgroups, against 83.4 us for the
+// round-8 kernel (a load, a wait and a branch per value) and 45.8 us for a
+// plain device fill of the same bytes; 256 x 32 60.1, 512 x 16 61.5, 512 x 64
+// 57.8, the rows read from global memory inside the loop 63.4.
+// RowsFromX (bo_post_kxt_rows): the thread takes its test rows straight from
 // X (B x q x d) divided by the lengthscale, and the blockIdx.y == 0 threads
 // write the padded row layout Xq (prepare_rows_kernel's output) on the way --
 // one launch instead of two.
@@ -1033,13 +1060,17 @@ struct KxtMembers {
   int nm;  // 0: the kernel's own arguments
 };
 
-template <int KIND, int ND, int KK = KXT_K, bool FROMX = false>
+template <int KIND, int ND, int KK, bool FROMX, int ROWS>
 __global__ __launch_bounds__(256) void kxt_build_kernel(const double* __restrict__ Xq, int nrows,
                                                         const double* __restrict__ Xt, int n,
-                                                        int np, int nrows_pad, double outputscale,
+                                                        int nrows_pad, double outputscale,
                                                         double* __restrict__ Kt,
                                                         RowsFromX rx = RowsFromX{},
                                                         KxtMembers km = KxtMembers{}) {
+  static_assert(PC % KK == 0, "np = nC * PC is a whole number of k-chunks: no k < np test");
+  static_assert(ROWS == 1 || ROWS == 2, "one row, or two adjacent rows and 16-byte stores");
+  constexpr int NST = (KK * DP + 255) / 256;  // staged doubles per thread
+  __shared__ double xts[KK * DP];
   if (km.nm > 0) {
     const int m = blockIdx.z;
     rx.ls = km.ls[m];
@@ -1048,31 +1079,172 @@ __global__ __launch_bounds__(256) void kxt_build_kernel(const double* __restrict
     outputscale = km.os[m];
     Kt = km.Kt[m];
   }
-  const int i = blockIdx.x * 256 + threadIdx.x;
   const int k0 = blockIdx.y * KK;
-  const bool iv = i < nrows;
-  double xi[ND];
+  // the workgroup's KK training rows: in flight under the row preparation
+  double stage[NST];
+#pragma unroll
+  for (int s = 0; s < NST; ++s) {
+    const int e = s * 256 + threadIdx.x;
+    const int k = min(k0 + e / DP, n - 1);
+    stage[s] = (NST * 256 == KK * DP || e < KK * DP) ? Xt[(int64_t)k * DP + e % DP] : 0.0;
+  }
+  const int i0 = (blockIdx.x * 256 + threadIdx.x) * ROWS;
+  bool iv[ROWS];
+  double xi[ROWS][ND];
   if constexpr (FROMX) {
-    const int b = i / rx.Qp, a = i - (i / rx.Qp) * rx.Qp;
-    const bool real = iv && b < rx.B && a < rx.q;
+    const int sh = __ffs(rx.Qp) - 1;  // Qp is a power of two
+    // every load of X and ls is issued (addresses clamped) before the first
+    // division waits for one; the compiler barrier keeps the loads from
+    // sinking back under the selects
+    double xr[ROWS][ND], lsv[ND];
+    bool real[ROWS];
 #pragma unroll
-    for (int t = 0; t < ND; ++t)
-      xi[t] = (real && t < rx.d) ? rx.X[((int64_t)b * rx.q + a) * rx.d + t] / rx.ls[t] : 0.0;
-    if (blockIdx.y == 0 && i < nrows_pad) {
+    for (int r = 0; r < ROWS; ++r) {
+      const int i = i0 + r;
+      iv[r] = i < nrows;
+      const int b = i >> sh, a = i & (rx.Qp - 1);
+      real[r] = iv[r] && b < rx.B && a < rx.q;
+      const double* xrow = rx.X + (real[r] ? ((int64_t)b * rx.q + a) * rx.d : 0);
 #pragma unroll
-      for (int t = 0; t < DP; ++t)
-        rx.Xq_out[(int64_t)i * DP + t] =
-            (real && t < rx.d) ? rx.X[((int64_t)b * rx.q + a) * rx.d + t] / rx.ls[t] : 0.0;
+      for (int t = 0; t < ND; ++t) xr[r][t] = xrow[t < rx.d ? t : 0];
+    }
+#pragma unroll
+    for (int t = 0; t < ND; ++t) lsv[t] = rx.ls[t < rx.d ? t : 0];
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+      for (int t = 0; t < ND; ++t) xi[r][t] = (real[r] && t < rx.d) ? xr[r][t] / lsv[t] : 0.0;
+    if (blockIdx.y == 0) {
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r)
+        if (i0 + r < nrows_pad) {
+#pragma unroll
+          for (int t = 0; t < DP; ++t)
+            rx.Xq_out[(int64_t)(i0 + r) * DP + t] = t < ND ? xi[r][t < ND ? t : 0] : 0.0;
+        }
     }
   } else {
 #pragma unroll
-    for (int t = 0; t < ND; ++t) xi[t] = iv ? Xq[(int64_t)i * DP + t] : 0.0;
+    for (int r = 0; r < ROWS; ++r) {
+      iv[r] = i0 + r < nrows;
+#pragma unroll
+      for (int t = 0; t < ND; ++t) xi[r][t] = iv[r] ? Xq[(int64_t)(i0 + r) * DP + t] : 0.0;
+    }
   }
-  if (i >= nrows_pad) return;
-#pragma unroll 4
+#pragma unroll
+  for (int s = 0; s < NST; ++s) {
+    const int e = s * 256 + threadIdx.x;
+    if (NST * 256 == KK * DP || e < KK * DP) xts[e] = stage[s];
+  }
+  __syncthreads();
+  // nrows_pad is a multiple of 128: a thread's ROWS rows are inside or outside together
+  if (i0 >= nrows_pad) return;
+  double* out = Kt + (int64_t)k0 * nrows_pad + i0;
+#pragma unroll KXT_UNROLL
   for (int kk = 0; kk < KK; ++kk) {
-    const int k = k0 + kk;
-    if (k < np) Kt[(int64_t)k * nrows_pad + i] = eval_kernel_row<KIND, ND>(xi, Xt, n, k, outputscale, iv);
+    const bool kv = k0 + kk < n;
+    double v[ROWS];
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+      double d2 = 0.0;
+#pragma unroll
+      for (int t = 0; t < ND; ++t) {
+#if KXT_STAGE_LDS
+        const double df = xi[r][t] - xts[kk * DP + t];
+#else  // measurement arm: the row straight from global memory (uniform address) inside the loop
+        const double df = xi[r][t] - Xt[(int64_t)min(k0 + kk, n - 1) * DP + t];
+#endif
+        d2 = fma(df, df, d2);
+      }
+      const double val = scaled_kernel_value<KIND>(d2, outputscale);
+      v[r] = (kv && iv[r]) ? val : 0.0;
+    }
+    if constexpr (ROWS == 2) {
+      v2d w;
+      w.x = v[0];
+      w.y = v[1];
+      *reinterpret_cast<v2d*>(out) = w;
+    } else {
+      *out = v[0];
+    }
+    out += nrows_pad;
+  }
+}
+
+// Points per thread of the small-grid K*x^T build: BO_KXT_SMALL (1, 2, 4 or
+// 8; default 2), read once -- an A/B knob for tools/time_kxt.py.
+static int kxt_small_k() {
+  static const int k = [] {
+    const char* e = std::getenv("BO_KXT_SMALL");
+    const int v = e ? std::atoi(e) : 2;
+    return (v == 1 || v == 2 || v == 4 || v == 8) ? v : 2;
+  }();
+  return k;
+}
+
+// One kxt_build_kernel launch: the geometry, and the workgroup shape chosen
+// for it.  Where the grid fills the chip (1024 workgroups or more of 256 rows
+// x 16 points, C3: 4096) a thread takes KXT_K points of one row or of
+// KXT_ROWS adjacent rows; small grids (C2: 128) take small_k points of one
+// row.  A Kt that is not 16-byte aligned keeps one row per thread (8-byte
+// stores).
+struct KxtLaunch {
+  int nrows_pad, np, nrows, n;
+  hipStream_t st;
+};
+struct KxtShape {
+  int kk, rows;
+};
+static bool kxt_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static KxtShape kxt_shape(const KxtLaunch& L, int nm, int small_k, bool aligned16) {
+  const bool small = ceil_div(L.nrows_pad, 256) * ceil_div(L.np, kKxtSmallUnit) * nm < 1024;
+  if (small) return KxtShape{small_k, 1};
+  // two rows per thread only while every CU still gets its 8 workgroups (C3:
+  // exactly 2048); below that the halved grid costs more than the wider
+  // stores save (C4, three members: 384 workgroups 20.1 us, 768 of one row 17.2)
+  const bool two = aligned16 && KXT_ROWS == 2 &&
+                   ceil_div(L.nrows_pad, 512) * (L.np / KXT_K) * nm >= 2048;
+  return KxtShape{KXT_K, two ? 2 : 1};
+}
+
+template <int KIND, int ND, bool FROMX>
+static void kxt_launch(KxtShape sh, const KxtLaunch& L, const double* Xq, const double* Xt,
+                       double outputscale, double* Kt, const RowsFromX& rx, const KxtMembers& km) {
+  const dim3 grid((unsigned)ceil_div(L.nrows_pad, 256 * sh.rows), (unsigned)(L.np / sh.kk),
+                  (unsigned)(km.nm > 0 ? km.nm : 1));
+#define BO_KXT_LAUNCH(K, R)                                                              \
+  kxt_build_kernel<KIND, ND, K, FROMX, R><<<grid, 256, 0, L.st>>>(Xq, L.nrows, Xt, L.n, \
+                                                                  L.nrows_pad, outputscale, Kt, rx, km)
+  if (sh.rows == 2) {
+    BO_KXT_LAUNCH(KXT_K, 2);
+  } else if (sh.kk == 2) {
+    BO_KXT_LAUNCH(2, 1);
+  } else if (sh.kk == KXT_K) {
+    BO_KXT_LAUNCH(KXT_K, 1);
+  } else if constexpr (FROMX) {  // BO_KXT_SMALL's other values: the rows routes only
+    if (sh.kk == 1) {
+      BO_KXT_LAUNCH(1, 1);
+    } else if (sh.kk == 4) {
+      BO_KXT_LAUNCH(4, 1);
+    } else {
+      BO_KXT_LAUNCH(8, 1);
+    }
+  }
+#undef BO_KXT_LAUNCH
+}
+
+template <int KIND, bool FROMX>
+static void kxt_launch_d(int d, KxtShape sh, const KxtLaunch& L, const double* Xq, const double* Xt,
+                         double outputscale, double* Kt, const RowsFromX& rx, const KxtMembers& km) {
+  switch (d) {
+    case 1: kxt_launch<KIND, 1, FROMX>(sh, L, Xq, Xt, outputscale, Kt, rx, km); break;
+    case 2: kxt_launch<KIND, 2, FROMX>(sh, L, Xq, Xt, outputscale, Kt, rx, km); break;
+    case 3: kxt_launch<KIND, 3, FROMX>(sh, L, Xq, Xt, outputscale, Kt, rx, km); break;
+    case 4: kxt_launch<KIND, 4, FROMX>(sh, L, Xq, Xt, outputscale, Kt, rx, km); break;
+    case 5: kxt_launch<KIND, 5, FROMX>(sh, L, Xq, Xt, outputscale, Kt, rx, km); break;
+    case 6: kxt_launch<KIND, 6, FROMX>(sh, L, Xq, Xt, outputscale, Kt, rx, km); break;
+    default: kxt_launch<KIND, 8, FROMX>(sh, L, Xq, Xt, outputscale, Kt, rx, km); break;
   }
 }
 
@@ -1986,50 +2158,14 @@ int bo_post_kxt(int kind, const double* Xq, int B, int q, int d, const double* X
   int s = bo_post_geometry(B, q, n, &Qp, &nrows_pad, &nC);
   if (s) return s;
   if (nrows_pad == 0) return BO_OK;
-  const int np = nC * PC;
-  const int nrows = B * Qp;
-  hipStream_t st = as_stream(stream);
-  // 16 training points per thread where the grid fills the chip (C3: 4096
-  // workgroups); small grids (C2: 128 workgroups at 16) take 2 per thread
-  const bool small = ceil_div(nrows_pad, 256) * ceil_div(np, KXT_K) < 1024;
-  const dim3 grid((unsigned)ceil_div(nrows_pad, 256), (unsigned)ceil_div(np, small ? 2 : KXT_K));
-#define BO_KXT(KIND, ND)                                                                        \
-  if (small)                                                                                    \
-    kxt_build_kernel<KIND, ND, 2><<<grid, 256, 0, st>>>(Xq, nrows, Xt_scaled, (int)n, np,       \
-                                                        nrows_pad, outputscale, Kt);            \
-  else                                                                                          \
-    kxt_build_kernel<KIND, ND><<<grid, 256, 0, st>>>(Xq, nrows, Xt_scaled, (int)n, np, nrows_pad, \
-                                                     outputscale, Kt)
-#define BO_KXT_D(KIND)                       \
-  switch (d) {                               \
-    case 1: BO_KXT(KIND, 1); break;          \
-    case 2: BO_KXT(KIND, 2); break;          \
-    case 3: BO_KXT(KIND, 3); break;          \
-    case 4: BO_KXT(KIND, 4); break;          \
-    case 5: BO_KXT(KIND, 5); break;          \
-    case 6: BO_KXT(KIND, 6); break;          \
-    default: BO_KXT(KIND, 8); break;         \
-  }
-  if (kind == BO_RBF) {
-    BO_KXT_D(BO_RBF)
-  } else {
-    BO_KXT_D(BO_MATERN52)
-  }
-#undef BO_KXT_D
-#undef BO_KXT
+  const KxtLaunch L{nrows_pad, nC * PC, B * Qp, (int)n, as_stream(stream)};
+  const KxtShape sh = kxt_shape(L, 1, 2, kxt_aligned16(Kt));
+  if (kind == BO_RBF)
+    kxt_launch_d<BO_RBF, false>(d, sh, L, Xq, Xt_scaled, outputscale, Kt, RowsFromX{}, KxtMembers{});
+  else
+    kxt_launch_d<BO_MATERN52, false>(d, sh, L, Xq, Xt_scaled, outputscale, Kt, RowsFromX{}, KxtMembers{});
   BO_LAUNCH_CHECK();
   return BO_OK;
-}
-
-// Points per thread of the small-grid K*x^T build: BO_KXT_SMALL (1, 2, 4 or
-// 8; default 2), read once -- an A/B knob for tools/time_kxt.py.
-static int kxt_small_k() {
-  static const int k = [] {
-    const char* e = std::getenv("BO_KXT_SMALL");
-    const int v = e ? std::atoi(e) : 2;
-    return (v == 1 || v == 2 || v == 4 || v == 8) ? v : 2;
-  }();
-  return k;
 }
 
 // bo_post_kxt_rows for nm <= 8 models of one shape and kernel kind (a
@@ -2057,43 +2193,16 @@ int bo_post_kxt_rows_members(int nm, int kind, const double* X, int B, int q, in
     km.Xq[m] = Xq[m];
     km.Kt[m] = Kt[m];
   }
-  const int np = nC * PC;
-  const int nrows = B * Qp;
-  hipStream_t st = as_stream(stream);
+  const KxtLaunch L{nrows_pad, nC * PC, B * Qp, (int)n, as_stream(stream)};
   const RowsFromX rx{X, lengthscale[0], B, q, d, Qp, Xq[0]};
-  // points per thread: the one-model rule over the whole (z-stacked) grid
-  const bool small = ceil_div(nrows_pad, 256) * ceil_div(np, KXT_K) * nm < 1024;
-  const int kk = small ? kxt_small_k() : KXT_K;
-  const dim3 grid((unsigned)ceil_div(nrows_pad, 256), (unsigned)ceil_div(np, kk), (unsigned)nm);
-#define BO_KXTM_K(KIND, ND, K)                                                                 \
-  kxt_build_kernel<KIND, ND, K, true><<<grid, 256, 0, st>>>(nullptr, nrows, Xt_scaled[0], (int)n, \
-                                                            np, nrows_pad, outputscale[0], Kt[0], rx, km)
-#define BO_KXTM(KIND, ND)                  \
-  switch (kk) {                            \
-    case 1: BO_KXTM_K(KIND, ND, 1); break; \
-    case 2: BO_KXTM_K(KIND, ND, 2); break; \
-    case 4: BO_KXTM_K(KIND, ND, 4); break; \
-    case 8: BO_KXTM_K(KIND, ND, 8); break; \
-    default: BO_KXTM_K(KIND, ND, KXT_K); break; \
-  }
-#define BO_KXTM_D(KIND)                      \
-  switch (d) {                               \
-    case 1: BO_KXTM(KIND, 1); break;         \
-    case 2: BO_KXTM(KIND, 2); break;         \
-    case 3: BO_KXTM(KIND, 3); break;         \
-    case 4: BO_KXTM(KIND, 4); break;         \
-    case 5: BO_KXTM(KIND, 5); break;         \
-    case 6: BO_KXTM(KIND, 6); break;         \
-    default: BO_KXTM(KIND, 8); break;        \
-  }
-  if (kind == BO_RBF) {
-    BO_KXTM_D(BO_RBF)
-  } else {
-    BO_KXTM_D(BO_MATERN52)
-  }
-#undef BO_KXTM_D
-#undef BO_KXTM
-#undef BO_KXTM_K
+  // the one-model rule over the whole (z-stacked) grid; 16-byte stores where every member's Kt allows
+  bool aligned16 = true;
+  for (int m = 0; m < nm; ++m) aligned16 = aligned16 && kxt_aligned16(Kt[m]);
+  const KxtShape sh = kxt_shape(L, nm, kxt_small_k(), aligned16);
+  if (kind == BO_RBF)
+    kxt_launch_d<BO_RBF, true>(d, sh, L, nullptr, Xt_scaled[0], outputscale[0], Kt[0], rx, km);
+  else
+    kxt_launch_d<BO_MATERN52, true>(d, sh, L, nullptr, Xt_scaled[0], outputscale[0], Kt[0], rx, km);
   BO_LAUNCH_CHECK();
   return BO_OK;
 }
@@ -2109,42 +2218,13 @@ int bo_post_kxt_rows(int kind, const double* X, int B, int q, int d, const doubl
   if (s) return s;
   if (nrows_pad == 0) return BO_OK;  // no t-batches (empty outputs may carry null pointers)
   BO_CHECK_ARG(X && lengthscale && Xt_scaled && Xq && Kt, "bo_post_kxt_rows: null buffer");
-  const int np = nC * PC;
-  const int nrows = B * Qp;
-  hipStream_t st = as_stream(stream);
+  const KxtLaunch L{nrows_pad, nC * PC, B * Qp, (int)n, as_stream(stream)};
   const RowsFromX rx{X, lengthscale, B, q, d, Qp, Xq};
-  const bool small = ceil_div(nrows_pad, 256) * ceil_div(np, KXT_K) < 1024;
-  const int kk = small ? kxt_small_k() : KXT_K;
-  const dim3 grid((unsigned)ceil_div(nrows_pad, 256), (unsigned)ceil_div(np, kk));
-#define BO_KXTR_K(KIND, ND, K)                                                                 \
-  kxt_build_kernel<KIND, ND, K, true><<<grid, 256, 0, st>>>(nullptr, nrows, Xt_scaled, (int)n,  \
-                                                            np, nrows_pad, outputscale, Kt, rx)
-#define BO_KXTR(KIND, ND)                  \
-  switch (kk) {                            \
-    case 1: BO_KXTR_K(KIND, ND, 1); break; \
-    case 2: BO_KXTR_K(KIND, ND, 2); break; \
-    case 4: BO_KXTR_K(KIND, ND, 4); break; \
-    case 8: BO_KXTR_K(KIND, ND, 8); break; \
-    default: BO_KXTR_K(KIND, ND, KXT_K); break; \
-  }
-#define BO_KXTR_D(KIND)                      \
-  switch (d) {                               \
-    case 1: BO_KXTR(KIND, 1); break;         \
-    case 2: BO_KXTR(KIND, 2); break;         \
-    case 3: BO_KXTR(KIND, 3); break;         \
-    case 4: BO_KXTR(KIND, 4); break;         \
-    case 5: BO_KXTR(KIND, 5); break;         \
-    case 6: BO_KXTR(KIND, 6); break;         \
-    default: BO_KXTR(KIND, 8); break;        \
-  }
-  if (kind == BO_RBF) {
-    BO_KXTR_D(BO_RBF)
-  } else {
-    BO_KXTR_D(BO_MATERN52)
-  }
-#undef BO_KXTR_D
-#undef BO_KXTR
-#undef BO_KXTR_K
+  const KxtShape sh = kxt_shape(L, 1, kxt_small_k(), kxt_aligned16(Kt));
+  if (kind == BO_RBF)
+    kxt_launch_d<BO_RBF, true>(d, sh, L, nullptr, Xt_scaled, outputscale, Kt, rx, KxtMembers{});
+  else
+    kxt_launch_d<BO_MATERN52, true>(d, sh, L, nullptr, Xt_scaled, outputscale, Kt, rx, KxtMembers{});
   BO_LAUNCH_CHECK();
   return BO_OK;
 }
