@@ -18,7 +18,8 @@ _EXPORTS = {"FullyBayesianAcquisitionFunction": "acquisition",
             "ConstrainedExpectedImprovement": "acquisition",
             "PosteriorStandardDeviation": "acquisition",
             "ScalarizedPosteriorMean": "acquisition",
-            "fit_fully_bayesian_model_nuts": "fit"}
+            "fit_fully_bayesian_model_nuts": "fit",
+            "FantasizedGP": "models"}
 __all__ = sorted(_EXPORTS)
 
 

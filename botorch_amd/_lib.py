@@ -247,6 +247,16 @@ class KgArgs(_Args):
                        ("dacq", _D), ("dvalues", _D), ("dmean", _D), ("dcov", _D)]
 
 
+class FantasyArgs(_Args):
+    _fields_ = _HDR + [("B", c_int32), ("T", c_int32), ("q_a", c_int32), ("q", c_int32),
+                       ("slots", c_int32), ("N_f", c_int32), ("shared", c_int32),
+                       ("max_tries", c_int32), ("jitter0", c_double), ("noise_stride", c_int64),
+                       ("mean", _D), ("cov", _D), ("Z", _D), ("noise", _D), ("mean_out", _D),
+                       ("cov_out", _D), ("L", _D), ("V", _D), ("info", _D), ("jitter", _D),
+                       ("dmean_out", _D), ("dcov_out", _D), ("dmean", _D), ("dcov", _D),
+                       ("dZ", _D)]
+
+
 class PathsArgs(_Args):
     _fields_ = _HDR + [("kind", c_int32), ("d", c_int32), ("S", c_int32), ("M", c_int32),
                        ("R", c_int64), ("n", c_int64), ("inner", c_int64), ("X", _D),
@@ -363,6 +373,13 @@ for _name, _cls in RECORD_ENTRIES.items():
     _SIGNATURES[_name] = (c_int, [POINTER(_cls), _P])
 _SIGNATURES["bo_saas_potential_work"] = (c_int, [c_int64, c_int, c_int64, POINTER(c_int64)])
 _SIGNATURES["bo_struct_size"] = (c_int64, [ctypes.c_char_p])
+# record entry points added within ABI 12 (plain names: the _v table above is that version's
+# closed set); their records' layouts are verified on load like ARG_RECORDS'
+PLAIN_RECORD_ENTRIES = {"bo_fantasy_posterior": FantasyArgs,
+                        "bo_fantasy_posterior_backward": FantasyArgs}
+PLAIN_ARG_RECORDS = {"BoFantasyArgs": FantasyArgs}
+for _name, _cls in PLAIN_RECORD_ENTRIES.items():
+    _SIGNATURES[_name] = (c_int, [POINTER(_cls), _P])
 _SIGNATURES["bo_post_backward_jobs"] = (c_int, [c_int, POINTER(POINTER(PostBackwardArgs)), _P, _P])
 ARG_RECORDS = {"BoPostPartialsArgs": PostPartialsArgs, "BoQmcFinalizeArgs": QmcFinalizeArgs,
                "BoQmcBackwardArgs": QmcBackwardArgs, "BoPostBackwardArgs": PostBackwardArgs,
@@ -397,7 +414,7 @@ def lib():
         if handle.bo_version() != ABI_VERSION:
             raise NativeLibraryMissing(
                 f"{LIB_PATH} has ABI {handle.bo_version()}, expected {ABI_VERSION}: rebuild with `make`")
-        for cname, rec in ARG_RECORDS.items():  # record layouts agree with the C header
+        for cname, rec in {**ARG_RECORDS, **PLAIN_ARG_RECORDS}.items():  # layouts agree with the C header
             if handle.bo_struct_size(cname.encode()) != sizeof(rec):
                 raise NativeLibraryMissing(f"{cname}: ctypes layout differs from the library's")
         _lib = handle

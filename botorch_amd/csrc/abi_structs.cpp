@@ -67,7 +67,7 @@ bool header_ok(const T* a, const char* name) {
 #define BO_RECORDS(X)                                                                          \
   X(PostPartials) X(QmcFinalize) X(QmcBackward) X(PostBackward) X(Qehvi) X(QehviFeas)          \
   X(Qlogehvi) X(QmcFeas) X(Kg) X(Paths) X(Jes) X(Mes) X(Gibbon) X(MvQuantiles) X(Nipv) X(Bald) \
-  X(Analytic) X(SaasPotential) X(LbfgsStep) X(Lbfgsb)
+  X(Analytic) X(SaasPotential) X(LbfgsStep) X(Lbfgsb) X(Fantasy)
 
 extern "C" {
 
@@ -79,6 +79,18 @@ extern "C" {
   }
 BO_RECORD_ENTRIES(BO_ENTRY)
 #undef BO_ENTRY
+
+// fantasy.hip: record entry points added within ABI 12.  The _v names above are
+// that version's closed set, so these carry plain names; the header check is the same.
+#define BO_ENTRY_PLAIN(entry, record)                                   \
+  int bo_##entry##_impl(const Bo##record##Args* a, void* stream);       \
+  int bo_##entry(const Bo##record##Args* a, void* stream) {             \
+    if (!header_ok(a, "bo_" #entry)) return BO_ERR_ARG;                 \
+    return bo_##entry##_impl(a, stream);                                \
+  }
+BO_ENTRY_PLAIN(fantasy_posterior, Fantasy)
+BO_ENTRY_PLAIN(fantasy_posterior_backward, Fantasy)
+#undef BO_ENTRY_PLAIN
 
 // sizeof of each argument record (HOST, for bindings to verify their layouts).
 int64_t bo_struct_size(const char* name) {

@@ -17,6 +17,11 @@ class InputDataError(BotorchError):
     pass
 
 
+class DeprecationError(BotorchError):
+    """botorch/exceptions/errors.py DeprecationError: a removed way of calling
+    (``fantasize`` with a boolean ``observation_noise``)."""
+
+
 class BotorchTensorDimensionError(BotorchError, ValueError):
     """botorch/exceptions/errors.py BotorchTensorDimensionError (also a
     ValueError here: the shape checks of this package raise ValueError)."""

@@ -2075,6 +2075,100 @@ def kg_backward(cov: torch.Tensor, L: torch.Tensor, W: torch.Tensor, dacq: torch
     return dmean, dcov
 
 
+FANTASY_ROWS = 16  # rows of a packed tile: q_a + slots q <= 16 (bo_fantasy_posterior, the fused posterior)
+
+
+def fantasy_tile_plan(q_a: int, q: int, F: int):
+    """(T, slots) of the fantasy-model packing (kg_tile_plan with groups of q
+    rows): each t-batch's q_a fantasised points and F groups of q evaluation
+    points go into T tiles of q_a + slots q <= 16 rows (the fantasised points,
+    then ``slots`` groups); group g sits in tile g // slots at rows q_a +
+    (g % slots) q ..., the last tile's T slots - F spare groups repeat the last
+    group.  F = N_f for one set of evaluation points per fantasy, F = 1 for a
+    set shared by all fantasies."""
+    if q_a < 1 or q < 1 or q_a + q > FANTASY_ROWS:
+        raise ValueError(f"fantasy_tile_plan: q_a >= 1, q >= 1 and q_a + q <= {FANTASY_ROWS} "
+                         f"(got {q_a} + {q})")
+    if F < 1:
+        raise ValueError(f"fantasy_tile_plan: F >= 1 (got {F})")
+    T = -(-F // ((FANTASY_ROWS - q_a) // q))
+    return T, -(-F // T)
+
+
+def _fantasy_dims(who, Z, q_a, q, slots, shared):
+    N_f = Z.shape[0] if Z.dim() == 2 else 0
+    qp = q_a + slots * q
+    if q_a < 1 or q < 1 or slots < 1 or qp > FANTASY_ROWS:
+        raise ValueError(f"{who}: q_a >= 1, q >= 1, slots >= 1 and q_a + slots q <= "
+                         f"{FANTASY_ROWS} (got {q_a} + {slots} x {q})")
+    if Z.dim() != 2 or Z.shape[1] != q_a or N_f < 1:
+        raise ValueError(f"{who}: Z must be N_f x q_a = N_f x {q_a}, got {tuple(Z.shape)}")
+    F = 1 if shared else N_f
+    return N_f, F, -(-F // slots), qp
+
+
+def fantasy_posterior(mean: torch.Tensor, cov: torch.Tensor, Z: torch.Tensor, noise: torch.Tensor,
+                      q_a: int, q: int, slots: int, shared: bool,
+                      max_tries: int = CHOLESKY_MAX_TRIES, jitter0: float = CHOLESKY_JITTER_F64):
+    """Moments of the fantasy models from the packed moments (bo_fantasy_posterior): A =
+    Sigma(X, X) + diag(noise) of tile 0, L = psd_safe_cholesky(A), V_g = C_g
+    L^{-T}, mean_out[b][f] = mu(X'_f) + V_f z_f, cov_out[b][g] = D_g - V_g V_g^T
+    -> dict(mean_out B x N_f x q, cov_out B x F x q x q, L B x q_a x q_a, V B x F
+    x q x q_a, info B, jitter B).  mean (B T) x q', cov (B T) x q' x q' (q' = q_a
+    + slots q, fantasy_tile_plan), Z N_f x q_a, noise q_a (all t-batches) or B x
+    q_a; F = 1 with ``shared``, else N_f.  Nothing else of mean / cov is read."""
+    dev = _dev(mean, cov, Z, noise)
+    N_f, F, T, qp = _fantasy_dims("fantasy_posterior", Z, q_a, q, slots, shared)
+    if mean.dim() != 2 or mean.shape[1] != qp or tuple(cov.shape) != (mean.shape[0], qp, qp):
+        raise ValueError(f"fantasy_posterior: mean must be (B T) x {qp} and cov (B T) x {qp} x "
+                         f"{qp}, got {tuple(mean.shape)} and {tuple(cov.shape)}")
+    if mean.shape[0] % T:
+        raise ValueError(f"fantasy_posterior: {mean.shape[0]} tiles are no multiple of T = {T}")
+    B = mean.shape[0] // T
+    if tuple(noise.shape) not in ((q_a,), (B, q_a)):
+        raise ValueError(f"fantasy_posterior: noise must be {q_a} or {B} x {q_a}, got "
+                         f"{tuple(noise.shape)}")
+    f64 = dict(dtype=torch.float64, device=dev)
+    out = dict(mean_out=torch.empty(B, N_f, q, **f64), cov_out=torch.empty(B, F, q, q, **f64),
+               L=torch.empty(B, q_a, q_a, **f64), V=torch.empty(B, F, q, q_a, **f64),
+               info=torch.empty(B, dtype=torch.int32, device=dev), jitter=torch.empty(B, **f64))
+    a = _lib.FantasyArgs(B=B, T=T, q_a=q_a, q=q, slots=slots, N_f=N_f, shared=int(bool(shared)),
+                         max_tries=int(max_tries), jitter0=float(jitter0),
+                         noise_stride=q_a if noise.dim() == 2 else 0, mean=mean.contiguous(),
+                         cov=cov.contiguous(), Z=Z.contiguous(), noise=noise.contiguous(), **out)
+    check(lib().bo_fantasy_posterior(ctypes.byref(a), _stream(dev)), "fantasy_posterior")
+    return out
+
+
+def fantasy_posterior_backward(Z: torch.Tensor, L: torch.Tensor, V: torch.Tensor,
+                               dmean_out: torch.Tensor, dcov_out: torch.Tensor, slots: int,
+                               shared: bool, need_dZ: bool = False):
+    """Backward of :func:`fantasy_posterior` from its saved L and V -> (dmean,
+    dcov, dZ) with the forward's packed shapes, every entry written: the
+    cotangent of each entry the forward read (the tile-0 X x X block symmetric,
+    as torch's Cholesky backward leaves it), zero elsewhere.  dZ (N_f x q_a,
+    the t-batches' parts summed in order) only with ``need_dZ``, else None."""
+    dev = _dev(Z, L, V, dmean_out, dcov_out)
+    B, F, q, q_a = V.shape
+    N_f, F_, T, qp = _fantasy_dims("fantasy_posterior_backward", Z, q_a, q, slots, shared)
+    if F != F_ or tuple(L.shape) != (B, q_a, q_a):
+        raise ValueError(f"fantasy_posterior_backward: V must be {B} x {F_} x {q} x {q_a} and L "
+                         f"{B} x {q_a} x {q_a}")
+    if tuple(dmean_out.shape) != (B, N_f, q) or tuple(dcov_out.shape) != (B, F, q, q):
+        raise ValueError(f"fantasy_posterior_backward: dmean_out must be {B} x {N_f} x {q} and "
+                         f"dcov_out {B} x {F} x {q} x {q}")
+    f64 = dict(dtype=torch.float64, device=dev)
+    dmean = torch.empty(B * T, qp, **f64)
+    dcov = torch.empty(B * T, qp, qp, **f64)
+    dZb = torch.empty(B, N_f, q_a, **f64) if need_dZ else None
+    a = _lib.FantasyArgs(B=B, T=T, q_a=q_a, q=q, slots=slots, N_f=N_f, shared=int(bool(shared)),
+                         Z=Z.contiguous(), L=L.contiguous(), V=V.contiguous(),
+                         dmean_out=dmean_out.contiguous(), dcov_out=dcov_out.contiguous(),
+                         dmean=dmean, dcov=dcov, dZ=dZb)
+    check(lib().bo_fantasy_posterior_backward(ctypes.byref(a), _stream(dev)), "fantasy_posterior_backward")
+    return dmean, dcov, (dZb.sum(dim=0) if need_dZ else None)
+
+
 PATHS_DMAX = 128  # bo_paths_eval: d is a runtime loop up to here
 
 

@@ -277,6 +277,13 @@ class Model(_TrackedModule):
         raise NotImplementedError(
             f"`condition_on_observations` not implemented for {type(self).__name__}")
 
+    def fantasize(self, X, sampler, observation_noise=None, **kwargs):
+        """models/model.py:328-407.  Only a single-output SingleTaskGP builds
+        fantasy models here (SingleTaskGP.fantasize)."""
+        raise UnsupportedError(
+            f"fantasize: {type(self).__name__} is not on the accelerated path (fantasy models "
+            "are built from a single-output SingleTaskGP only)")
+
     def outcome_stats(self):
         """(mean, std) of the Standardize transform as host floats, read back once
         per change of the buffers (not per acquisition call: each read is a
@@ -499,6 +506,55 @@ class SingleTaskGP(Model):
             return posterior_transform(post)
         return post
 
+    # -- fantasy models -----------------------------------------------------------
+    def fantasize(self, X: torch.Tensor, sampler, observation_noise=None, **kwargs):
+        """botorch/models/model.py:328-407: the batch of N_f fantasy models that
+        condition this model on (X, Y_f), Y_f = mu(X) + L z_f drawn from the
+        posterior at X under observation noise (L L^T = Sigma(X, X) + diag(s'^2),
+        z_f row f of ``sampler.base_samples_2d(q_a, device)``: the sampler fixes
+        the fantasies across calls, as in qKnowledgeGradient).
+
+        X: q_a x d or b x q_a x d (promoted to fp64).  ``sampler``: an MCSampler
+        with a one-dimensional ``sample_shape`` [N_f].  ``observation_noise``:
+        None -- the likelihood's noise (a fixed-noise likelihood: the mean
+        training noise) -- or a 1 x 1 / q_a x 1 tensor in the transformed
+        (standardised) space; a bool raises DeprecationError as in the reference.
+
+        Returns a :class:`FantasizedGP` with ``batch_shape`` (N_f, *X.shape[:-2]).
+        It keeps a reference to this model (not a copy) and X with its graph:
+        every ``posterior`` call recomputes the joint moments at [X; X'], so the
+        result is differentiable in X' and in X whenever either requires a
+        gradient, a later change of this model's hyperparameters is seen, and
+        nothing stale is kept between calls.  ``propagate_grads`` is accepted
+        and has no further effect: the derivative with respect to X is the one
+        qKnowledgeGradient returns for its candidates."""
+        from .exceptions import DeprecationError
+        if observation_noise is not None and not torch.is_tensor(observation_noise):
+            raise DeprecationError(
+                "`fantasize` no longer accepts a boolean for `observation_noise`.")
+        if self._is_multi_output:
+            raise UnsupportedError("fantasize: a multi-output SingleTaskGP is not on the "
+                                   "accelerated path (single-output SingleTaskGP only)")
+        kwargs.pop("propagate_grads", None)
+        if kwargs:
+            raise UnsupportedError(f"fantasize: unsupported arguments {sorted(kwargs)}")
+        shape = getattr(sampler, "sample_shape", None)
+        if shape is None or len(shape) != 1 or shape[0] < 1:
+            raise ValueError("fantasize: the sampler's sample_shape must be one-dimensional "
+                             f"([N_f]), got {tuple(shape) if shape is not None else None}")
+        d = self.train_inputs[0].shape[-1]
+        if X.dim() < 2 or X.shape[-1] != d:
+            raise ValueError(f"fantasize: X must be (b x) q_a x {d}, got {tuple(X.shape)}")
+        if X.shape[-2] == 0:
+            raise UnsupportedError("fantasize: q_a = 0 (a fantasy model without fantasised "
+                                   "points) is not on the accelerated path")
+        if observation_noise is not None:
+            q_a = X.shape[-2]
+            if tuple(observation_noise.shape) not in ((1, 1), (q_a, 1)):
+                raise ValueError(f"fantasize: observation_noise must be 1 x 1 or {q_a} x 1, got "
+                                 f"{tuple(observation_noise.shape)}")
+        return FantasizedGP(self, X.to(torch.float64), sampler, observation_noise)
+
     # -- conditioning on new observations ------------------------------------------
     def _blank_copy(self, train_X):
         """A SingleTaskGP shell with the new inputs and no modules yet (the
@@ -633,6 +689,193 @@ class SingleTaskGP(Model):
         new.train_targets = torch.stack([mm.train_targets for mm in members])  # m x (n + k)
         new.eval()
         return new
+
+
+class FantasizedGP(Model):
+    """The batch of fantasy models of ``SingleTaskGP.fantasize`` (the reference's
+    batched model after models/model.py:328-407): N_f x b exact GPs on the n +
+    q_a points [train_X; X_b] with targets [y; Y_f], never built -- with all
+    moments of the source model's joint posterior at [X; X'] in outcome space,
+
+        A     = Sigma(X, X) + diag(s'^2)         L = psd_safe_cholesky(A)
+        V_f   = Sigma(X'_f, X) L^{-T}
+        mu'_f = mu(X'_f) + V_f z_f               (Y_f - mu(X) = L z_f)
+        S'_f  = Sigma(X'_f, X'_f) - V_f V_f^T
+
+    so conditioning is a rank-q_a correction that needs no new n x n work and
+    all fantasies of a t-batch share L.  For q_a + q <= FUSED_ROWS, d <=
+    kernels.DP and X on the device the points are packed into tiles of at most
+    16 rows (kernels.fantasy_tile_plan), the fused posterior runs once over all
+    tiles and bo::fantasy_posterior conditions them; otherwise the generic
+    posterior kernels give the joint moments and the formula runs in torch.
+
+    There is no ``prediction_cache``: acquisition functions on a fantasy model
+    take their generic routes through :meth:`posterior`."""
+
+    FUSED_ROWS = 16  # largest q_a + q on the fused route (one 16-row tile holds X and one group)
+
+    def __init__(self, source: "SingleTaskGP", X: torch.Tensor, sampler, observation_noise=None):
+        super().__init__()
+        # references, not submodules: the source model is neither copied nor trained through this
+        self.__dict__["source"] = source
+        self.__dict__["_sampler"] = sampler
+        self._X = X
+        self._obs_noise = observation_noise
+        self.num_fantasies = int(sampler.sample_shape[0])
+        self._tile_index = {}
+
+    @property
+    def batch_shape(self) -> torch.Size:
+        return torch.Size([self.num_fantasies]) + self._X.shape[:-2]
+
+    def outcome_stats(self):
+        return self.source.outcome_stats()
+
+    # -- the pieces every call recomputes -------------------------------------------
+    def _base_samples(self) -> torch.Tensor:
+        return self._sampler.base_samples_2d(self._X.shape[-2], self._X.device)
+
+    def _noise(self) -> torch.Tensor:
+        """s'^2 of the fantasy observations in outcome space (q_a)."""
+        q_a = self._X.shape[-2]
+        ystd = self.source.outcome_stats()[1]
+        if self._obs_noise is None:  # qKnowledgeGradient._noise
+            s2 = self.source.prediction_cache().noise * ystd * ystd
+            return torch.full((q_a,), s2, dtype=torch.float64, device=self._X.device)
+        s2 = self._obs_noise.detach().to(self._X).reshape(-1) * (ystd * ystd)
+        return s2.expand(q_a).contiguous()
+
+    def _fantasy_targets(self) -> torch.Tensor:
+        """Y_f = mu(X) + L z_f in outcome space, N_f x b x q_a (detached)."""
+        from . import kernels
+        from .posteriors import posterior_moments
+        with torch.no_grad():
+            mean, cov = posterior_moments(self.source, self._X.detach())
+            L = kernels.chol_jitter(cov + torch.diag_embed(self._noise()))
+            Z = self._base_samples()
+            return mean + torch.einsum("...ij,fj->f...i", L, Z)
+
+    @property
+    def train_inputs(self):
+        """(N_f x b x (n + q_a) x d,), as the reference's batched model holds them."""
+        Xt = self.source.train_inputs[0].detach()
+        X = self._X.detach()
+        both = torch.cat([Xt.expand(*X.shape[:-2], *Xt.shape), X], dim=-2)
+        return (both.expand(self.num_fantasies, *both.shape),)
+
+    @property
+    def train_targets(self) -> torch.Tensor:
+        """N_f x b x (n + q_a), in the source model's transformed space."""
+        ymean, ystd = self.source.outcome_stats()
+        Yf = (self._fantasy_targets() - ymean) / ystd
+        y = self.source.train_targets.detach()
+        return torch.cat([y.expand(*Yf.shape[:-1], y.shape[-1]), Yf], dim=-1)
+
+    def fantasize(self, X, sampler, observation_noise=None, **kwargs):
+        raise UnsupportedError("fantasize: nested fantasies (a fantasy model of a FantasizedGP) "
+                               "are not on the accelerated path")
+
+    def condition_on_observations(self, X, Y, **kwargs):
+        raise UnsupportedError("condition_on_observations of a FantasizedGP (nested "
+                               "conditioning) is not on the accelerated path")
+
+    # -- posterior -----------------------------------------------------------------
+    def _broadcast(self, Xp: torch.Tensor):
+        """(X B x q_a x d, X' B x F x q x d, shared, batch): X' broadcast against
+        (N_f, b); F = 1 when one set of points serves every fantasy."""
+        N_f, X = self.num_fantasies, self._X
+        d, bshape = X.shape[-1], X.shape[:-2]
+        if Xp.dim() < 2 or Xp.shape[-1] != d:
+            raise ValueError(f"FantasizedGP.posterior: X must be ... x q x {d}, got "
+                             f"{tuple(Xp.shape)}")
+        pb = Xp.shape[:-2]
+        lead = 1
+        if len(pb) > len(bshape) + 1:
+            raise ValueError(f"FantasizedGP.posterior: X of batch shape {tuple(pb)} does not "
+                             f"broadcast against {tuple(self.batch_shape)}")
+        if len(pb) == len(bshape) + 1:
+            lead, pb = pb[0], pb[1:]
+        try:
+            if lead not in (1, N_f):
+                raise RuntimeError
+            batch = torch.broadcast_shapes(bshape, pb)
+        except RuntimeError:
+            raise ValueError(f"FantasizedGP.posterior: X of batch shape {tuple(Xp.shape[:-2])} "
+                             f"does not broadcast against {tuple(self.batch_shape)}") from None
+        q = Xp.shape[-2]
+        shared = lead == 1
+        F = 1 if shared else N_f
+        Xp = Xp.reshape(F, *([1] * (len(batch) - len(pb))), *pb, q, d)
+        Xp = Xp.expand(F, *batch, q, d).reshape(F, -1, q, d)
+        Xa = X.expand(*batch, *X.shape[-2:]).reshape(-1, X.shape[-2], d)
+        return Xa, Xp.transpose(0, 1), shared, batch
+
+    def _fused(self, Xa, Xp, Z, noise, shared):
+        from . import kernels, ops  # noqa: F401  (torch.ops.bo registration)
+        from .posteriors import _fused_moments
+        B, q_a, d = Xa.shape
+        F, q = Xp.shape[1], Xp.shape[2]
+        T, slots = kernels.fantasy_tile_plan(q_a, q, F)
+        key = (F, T, slots, Xa.device)
+        idx = self._tile_index.get(key)
+        if idx is None:  # group of each slot; the spare slots repeat the last one
+            idx = torch.arange(T * slots, device=Xa.device).clamp_max(F - 1)
+            self._tile_index[key] = idx
+        groups = Xp[:, idx].reshape(B, T, slots * q, d)
+        tiles = torch.cat([Xa.unsqueeze(1).expand(B, T, q_a, d), groups], dim=2)
+        mean, cov = _fused_moments(tiles.reshape(B * T, q_a + slots * q, d), self.source)
+        mean_f, cov_f, _, _, jit, info = torch.ops.bo.fantasy_posterior(
+            mean, cov, Z, noise, q_a, q, slots, shared)
+        kernels.raise_not_psd_deferred(info, jit, type(self).__name__)
+        return mean_f, cov_f
+
+    def _generic(self, Xa, Xp, Z, noise):
+        """posterior_moments on cat([X, X']) and the same formula in torch
+        (qKnowledgeGradient._generic's shape of it); also the in-library
+        cross-check of the fused route."""
+        from .posteriors import _CholJitter, posterior_moments
+        B, q_a, d = Xa.shape
+        F = Xp.shape[1]
+        mean, cov = posterior_moments(
+            self.source, torch.cat([Xa.unsqueeze(1).expand(B, F, q_a, d), Xp], dim=-2))
+        L = _CholJitter.apply(cov[:, 0, :q_a, :q_a] + torch.diag_embed(noise))      # B x q_a x q_a
+        C = cov[:, :, q_a:, :q_a]                                                     # B x F x q x q_a
+        V = torch.linalg.solve_triangular(L.unsqueeze(1), C.mT, upper=False).mT      # C L^{-T}
+        # F = 1: the one group (g) serves every fantasy
+        mean_f = mean[:, :, q_a:] + torch.einsum("bgrj,fj->bfr" if F == 1 else "bfrj,fj->bfr", V, Z)
+        return mean_f, cov[:, :, q_a:, q_a:] - V @ V.mT
+
+    def posterior(self, X: torch.Tensor, output_indices=None, observation_noise=False,
+                  posterior_transform=None):
+        """The fantasy models' posterior at X: q x d or b x q x d (shared by all
+        fantasies), N_f x b x q x d (one set per fantasy), a 1 in place of b or
+        N_f broadcasting -> GPyTorchPosterior with mean N_f x b x q x 1 and
+        covariance N_f x b x q x q (for a shared X an expanded view: it does not
+        depend on the fantasy).  ``observation_noise=True`` adds the fantasy
+        noise s'^2 (its mean, if per row) to the diagonal."""
+        from . import kernels
+        from .posteriors import GPyTorchPosterior, MultivariateNormal
+        if output_indices not in (None, [0]):
+            raise UnsupportedError("single-output model")
+        if not isinstance(observation_noise, bool):
+            raise UnsupportedError("FantasizedGP.posterior: observation_noise is True or False "
+                                   "here (the fantasy noise), not a tensor")
+        if X.dtype != torch.float64:
+            X = X.to(torch.float64)
+        self.source.eval()
+        Xa, Xp, shared, batch = self._broadcast(X)
+        N_f, q_a, q, d = self.num_fantasies, Xa.shape[-2], Xp.shape[-2], Xa.shape[-1]
+        Z, noise = self._base_samples(), self._noise()
+        if q_a + q <= self.FUSED_ROWS and d <= kernels.DP and Xa.is_cuda:
+            mean, cov = self._fused(Xa, Xp, Z, noise, shared)
+        else:
+            mean, cov = self._generic(Xa, Xp, Z, noise)
+        mean = mean.transpose(0, 1).reshape(N_f, *batch, q)
+        cov = cov.transpose(0, 1).reshape(-1, *batch, q, q).expand(N_f, *batch, q, q)
+        if observation_noise:
+            cov = cov + noise.mean() * torch.eye(q, dtype=cov.dtype, device=cov.device)
+        post = GPyTorchPosterior(MultivariateNormal(mean, cov), model=self, X=X)
+        return post if posterior_transform is None else posterior_transform(post)
 
 
 def prime_prediction_caches(models):

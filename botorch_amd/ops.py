@@ -28,6 +28,8 @@ Ops (reference computation each replaces):
                       (optim/closures/model_closures.py:171-184)
   bo::kg              one-shot qKnowledgeGradient value of packed posterior moments
                       (+ autograd, acquisition/knowledge_gradient.py:151-207)
+  bo::fantasy_posterior  mean and covariance of N_f fantasy models per t-batch from
+                      packed posterior moments (+ autograd, models/model.py:328-407)
   bo::paths_eval      S Matheron paths at R points, features and kernel rows fused
                       (+ autograd in X, sampling/pathwise/posterior_samplers.py:198-224)
   bo::jes             mean conditional entropy of R points over P optima, the
@@ -599,6 +601,63 @@ def _kg_bwd(ctx, dacq, dvalues, *_):
 kg.register_autograd(_kg_bwd, setup_context=_kg_setup)
 
 
+# ---- bo::fantasy_posterior (batched fantasy models from packed posterior moments) --------------
+@torch.library.custom_op("bo::fantasy_posterior", mutates_args=(), device_types="cuda")
+def fantasy_posterior(mean: Tensor, cov: Tensor, Z: Tensor, noise: Tensor, q_a: int, q: int,
+                      slots: int, shared: bool
+                      ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """(mean_out B x N_f x q, cov_out B x F x q x q) of the fantasy models from
+    the packed moments mean (B T) x q', cov (B T) x q' x q' (kernels.
+    fantasy_tile_plan, q' = q_a + slots q), the fantasy base samples Z (N_f x
+    q_a) and the fantasy noise (q_a or B x q_a), plus (L, V) for the backward
+    and the ladder's (jitter, info) per t-batch.  F = 1 with ``shared``."""
+    o = kernels.fantasy_posterior(mean, cov, Z, noise, q_a, q, slots, shared)
+    return o["mean_out"], o["cov_out"], o["L"], o["V"], o["jitter"], o["info"]
+
+
+@fantasy_posterior.register_fake
+def _(mean, cov, Z, noise, q_a, q, slots, shared):
+    N_f = Z.shape[0]
+    F = 1 if shared else N_f
+    B = mean.shape[0] // ((F + slots - 1) // slots)
+    mk = lambda *s: mean.new_empty(*s, dtype=F64)  # noqa: E731
+    return (mk(B, N_f, q), mk(B, F, q, q), mk(B, q_a, q_a), mk(B, F, q, q_a), mk(B),
+            mean.new_empty(B, dtype=torch.int32))
+
+
+@torch.library.custom_op("bo::fantasy_posterior_backward", mutates_args=(), device_types="cuda")
+def fantasy_posterior_backward(dmean_out: Tensor, dcov_out: Tensor, Z: Tensor, L: Tensor,
+                               V: Tensor, slots: int, shared: bool
+                               ) -> Tuple[Tensor, Tensor, Tensor]:
+    return kernels.fantasy_posterior_backward(Z, L, V, dmean_out, dcov_out, slots, shared,
+                                              need_dZ=True)
+
+
+@fantasy_posterior_backward.register_fake
+def _(dmean_out, dcov_out, Z, L, V, slots, shared):
+    B, F, q, q_a = V.shape
+    T, qp = (F + slots - 1) // slots, q_a + slots * q
+    return V.new_empty(B * T, qp), V.new_empty(B * T, qp, qp), torch.empty_like(Z)
+
+
+def _fantasy_setup(ctx, inputs, output):
+    mean, cov, Z, noise, q_a, q, slots, shared = inputs
+    _, _, L, V, jitter, info = output
+    ctx.mark_non_differentiable(L, V, jitter, info)
+    ctx.save_for_backward(Z, L, V)
+    ctx.slots, ctx.shared = slots, shared
+
+
+def _fantasy_bwd(ctx, dmean_out, dcov_out, *_):
+    Z, L, V = ctx.saved_tensors
+    dmean, dcov, dZ = torch.ops.bo.fantasy_posterior_backward(
+        dmean_out, dcov_out, Z, L, V, ctx.slots, ctx.shared)
+    return dmean, dcov, (dZ if ctx.needs_input_grad[2] else None), None, None, None, None, None
+
+
+fantasy_posterior.register_autograd(_fantasy_bwd, setup_context=_fantasy_setup)
+
+
 # ---- bo::paths_eval (Matheron paths at R points, fused features + kernel rows) -----------------
 @torch.library.custom_op("bo::paths_eval", mutates_args=(), device_types="cuda")
 def paths_eval(X: Tensor, lengthscale: Tensor, Omega: Tensor, W: Tensor,
@@ -1040,4 +1099,4 @@ OPS: List[str] = ["sobol_normal", "gp_cache", "gp_cache_extend", "chol_jitter", 
                   "kg_backward", "paths_eval", "paths_eval_backward", "jes", "jes_backward", "mes",
                   "mes_backward", "gibbon", "gibbon_backward", "mv_quantiles", "nipv_gram",
                   "nipv_gram_backward", "bald", "bald_backward", "analytic", "analytic_backward",
-                  "saas_potential"]
+                  "saas_potential", "fantasy_posterior", "fantasy_posterior_backward"]

@@ -967,6 +967,47 @@ typedef struct BoKgArgs {
 int bo_kg_v(const BoKgArgs* a, void* stream);
 int bo_kg_backward_v(const BoKgArgs* a, void* stream);
 
+/* Batched fantasy models (botorch/models/model.py:328-407 fantasize, then the
+ * conditioned model's posterior) from packed posterior moments.  T-batch b owns
+ * T tiles of q' = q_a + slots q rows: the q_a fantasised points, then `slots`
+ * groups of q evaluation points; group g sits in tile g / slots at rows
+ * q_a + (g % slots) q ... + q.  F = N_f groups (one per fantasy), or F = 1 with
+ * `shared` (one group for all fantasies).  mean: B T q', cov: B T q' q'.
+ *   A = cov[tile 0][:q_a, :q_a] + diag(noise_b),   L = psd_safe_cholesky(A)
+ *   V_g = C_g L^{-T}            (C_g: the rows of group g, columns < q_a;  q x q_a)
+ *   mean_out[b][f] = mean[rows of g_f] + V_{g_f} z_f   (g_f = f, or 0 when shared;
+ *                                                       z_f: row f of Z, N_f x q_a)
+ *   cov_out[b][g]  = D_g - V_g V_g^T                   (D_g: the group's own q x q
+ *                                                       diagonal block, both triangles)
+ * noise: q_a doubles per t-batch at stride noise_stride (0: one vector for all,
+ * or q_a).  Only the lower triangle of tile 0's X x X block, each C_g and D_g
+ * and the mean at the groups' rows are read.  The ladder is plain first, then
+ * jitter0 10^k (k < max_tries) on the diagonal; info[b] (0: factored) and
+ * jitter[b] (total added) are nullable; a failed t-batch's outputs are NaN.
+ * mean_out: B N_f q, cov_out: B F q q; L (B q_a q_a, upper zero) and V (B F q
+ * q_a) are kept for the backward, which from dmean_out and dcov_out (the
+ * forward's shapes) writes every entry of dmean and dcov -- the groups' rows,
+ * cross and diagonal blocks, the tile-0 X x X block the (symmetric) Cholesky
+ * backward of dL = -tril(sum_rows dC_row^T V_row), dC = dV L^{-1}, dV_g =
+ * sum_{f: g_f = g} dmean_out_f z_f^T - (dcov_out_g + dcov_out_g^T) V_g; zero
+ * elsewhere -- and, when dZ is given, dZ[b][f] = V_{g_f}^T dmean_out[b][f] (B N_f
+ * q_a; the caller sums over b).  One workgroup per t-batch, one launch each
+ * way, sums in a fixed order, no atomics. */
+typedef struct BoFantasyArgs {
+  BO_STRUCT_HEADER;
+  int32_t B, T, q_a, q, slots, N_f, shared, max_tries;
+  double jitter0;
+  int64_t noise_stride;
+  const double *mean, *cov, *Z, *noise;
+  double *mean_out, *cov_out, *L, *V; /* forward: outputs; backward: L, V are inputs */
+  int32_t* info;
+  double* jitter;
+  const double *dmean_out, *dcov_out; /* backward only */
+  double *dmean, *dcov, *dZ;          /* backward only; dZ nullable */
+} BoFantasyArgs;
+int bo_fantasy_posterior(const BoFantasyArgs* a, void* stream);
+int bo_fantasy_posterior_backward(const BoFantasyArgs* a, void* stream);
+
 /* Pathwise posterior samples (Matheron paths) of one single-output exact GP
  * (botorch/sampling/pathwise: features/generators.py:66-193, prior_samplers.py:
  * 52-106, update_strategies.py:72-135, posterior_samplers.py:198-224), S paths
