@@ -19,7 +19,11 @@ _EXPORTS = {"FullyBayesianAcquisitionFunction": "acquisition",
             "PosteriorStandardDeviation": "acquisition",
             "ScalarizedPosteriorMean": "acquisition",
             "fit_fully_bayesian_model_nuts": "fit",
-            "FantasizedGP": "models"}
+            "FantasizedGP": "models",
+            "MultiTaskGP": "models", "IndexKernel": "models", "GammaPrior": "models",
+            "get_matern_kernel_with_gamma_prior": "models",
+            "get_gaussian_likelihood_with_gamma_prior": "models",
+            "icm_mll_terms": "fit", "icm_mll_terms_torch": "fit"}
 __all__ = sorted(_EXPORTS)
 
 

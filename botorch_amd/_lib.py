@@ -257,6 +257,29 @@ class FantasyArgs(_Args):
                        ("dZ", _D)]
 
 
+ICM_MAX_TASKS, ICM_MAX_DIM = 16, 64  # BO_ICM_MAX_TASKS, BO_ICM_MAX_DIM
+
+
+class IcmCovarArgs(_Args):
+    _fields_ = _HDR + [("kind", c_int32), ("d", c_int32), ("T", c_int32), ("_pad", c_int32),
+                       ("n", c_int64), ("np", c_int64), ("X", _D), ("lengthscale", _D), ("B", _D),
+                       ("task", _D), ("noise_vec", _D), ("outputscale", c_double),
+                       ("noise", c_double), ("A", _D)]
+
+
+class IcmMllArgs(_Args):
+    _fields_ = _HDR + [("kind", c_int32), ("d", c_int32), ("T", c_int32), ("_pad", c_int32),
+                       ("n", c_int64), ("ld", c_int64), ("X", _D), ("lengthscale", _D), ("B", _D),
+                       ("task", _D), ("outputscale", c_double), ("L", _D), ("Ainv", _D),
+                       ("alpha", _D), ("beta", _D), ("partial", _D)]
+
+
+class IcmTaskViewArgs(_Args):
+    _fields_ = _HDR + [("T", c_int32), ("t", c_int32), ("n", c_int64), ("np", c_int64),
+                       ("B", _D), ("task", _D), ("U", _D), ("alpha", _D), ("U_out", _D),
+                       ("Linv_out", _D), ("alpha_out", _D)]
+
+
 class PathsArgs(_Args):
     _fields_ = _HDR + [("kind", c_int32), ("d", c_int32), ("S", c_int32), ("M", c_int32),
                        ("R", c_int64), ("n", c_int64), ("inner", c_int64), ("X", _D),
@@ -378,7 +401,12 @@ _SIGNATURES["bo_struct_size"] = (c_int64, [ctypes.c_char_p])
 PLAIN_RECORD_ENTRIES = {"bo_fantasy_posterior": FantasyArgs,
                         "bo_fantasy_posterior_backward": FantasyArgs}
 PLAIN_ARG_RECORDS = {"BoFantasyArgs": FantasyArgs}
-for _name, _cls in PLAIN_RECORD_ENTRIES.items():
+# the multi-task (ICM) kernels of icm.hip, added within ABI 12 the same way
+ICM_RECORD_ENTRIES = {"bo_icm_covar": IcmCovarArgs, "bo_icm_mll_terms": IcmMllArgs,
+                      "bo_icm_task_view": IcmTaskViewArgs}
+ICM_ARG_RECORDS = {"BoIcmCovarArgs": IcmCovarArgs, "BoIcmMllArgs": IcmMllArgs,
+                   "BoIcmTaskViewArgs": IcmTaskViewArgs}
+for _name, _cls in {**PLAIN_RECORD_ENTRIES, **ICM_RECORD_ENTRIES}.items():
     _SIGNATURES[_name] = (c_int, [POINTER(_cls), _P])
 _SIGNATURES["bo_post_backward_jobs"] = (c_int, [c_int, POINTER(POINTER(PostBackwardArgs)), _P, _P])
 ARG_RECORDS = {"BoPostPartialsArgs": PostPartialsArgs, "BoQmcFinalizeArgs": QmcFinalizeArgs,
@@ -414,7 +442,7 @@ def lib():
         if handle.bo_version() != ABI_VERSION:
             raise NativeLibraryMissing(
                 f"{LIB_PATH} has ABI {handle.bo_version()}, expected {ABI_VERSION}: rebuild with `make`")
-        for cname, rec in {**ARG_RECORDS, **PLAIN_ARG_RECORDS}.items():  # layouts agree with the C header
+        for cname, rec in {**ARG_RECORDS, **PLAIN_ARG_RECORDS, **ICM_ARG_RECORDS}.items():  # layouts agree with the C header
             if handle.bo_struct_size(cname.encode()) != sizeof(rec):
                 raise NativeLibraryMissing(f"{cname}: ctypes layout differs from the library's")
         _lib = handle

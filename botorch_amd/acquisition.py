@@ -48,11 +48,29 @@ def t_batch_mode(X: torch.Tensor, expected_q: Optional[int] = None) -> torch.Ten
     return X
 
 
+def _cache_dim_ok(model, X: torch.Tensor) -> bool:
+    """A MultiTaskGP's prediction cache is the task view of its one output task
+    over the d non-task columns: X that carries the task column (d + 1 columns)
+    keeps the generic route, which goes through ``model.posterior``."""
+    return not model.__dict__.get("_is_multitask") or X.shape[-1] == model._d
+
+
 class AcquisitionFunction(nn.Module):
     """acquisition/acquisition.py:33-74."""
 
+    # whether the class's routes have been audited for a MultiTaskGP (its task view
+    # carries no Cholesky factor and its caches are those of one output task)
+    _admits_multitask = False
+
     def __init__(self, model):
         super().__init__()
+        if getattr(model, "_is_multitask", False) and not self._admits_multitask:
+            raise UnsupportedError(
+                f"{type(self).__name__}: MultiTaskGP is not on the accelerated path of this "
+                "acquisition function (admitted: qExpectedImprovement, qLogExpectedImprovement, "
+                "qNoisyExpectedImprovement, qLogNoisyExpectedImprovement, qUpperConfidenceBound, "
+                "ExpectedImprovement, LogExpectedImprovement, UpperConfidenceBound, "
+                "PosteriorMean)")
         self.model = model
         self.X_pending = None
 
@@ -121,7 +139,7 @@ class MCAcquisitionFunction(AcquisitionFunction):
         return (hasattr(m, "prediction_cache") and type(self.objective) is IdentityMCObjective
                 and self.posterior_transform is None and self._constraints is None
                 and X.shape[-2] <= FUSED_QMAX and X.shape[-1] <= kernels.DP and X.is_cuda
-                and len(self.sample_shape) == 1)
+                and len(self.sample_shape) == 1 and _cache_dim_ok(m, X))
 
     # -- generic route (monte_carlo.py:253-330) -----------------------------------------
     def _sample_forward(self, obj: torch.Tensor) -> torch.Tensor:
@@ -244,6 +262,8 @@ class qExpectedImprovement(MCAcquisitionFunction):
     """MC batch EI (acquisition/monte_carlo.py:332-414):
     qEI(X) = E[max_j max(Y_j - best_f, 0)], optionally weighted by smoothed
     outcome constraints (``constraints``, ``eta``)."""
+
+    _admits_multitask = True
 
     def __init__(self, model, best_f: Union[float, torch.Tensor], sampler=None, objective=None,
                  posterior_transform=None, X_pending=None, constraints=None, eta=1e-3):
@@ -421,6 +441,8 @@ class qUpperConfidenceBound(_PlainMaxMCAcquisitionFunction):
     beta' = sqrt(beta pi / 2) and mu the mean of the samples (not of the
     posterior), as the reference computes it."""
 
+    _admits_multitask = True
+
     _fused_mode = _lib.QMC_QUCB
 
     def __init__(self, model, beta: float, sampler=None, objective=None, posterior_transform=None,
@@ -475,6 +497,8 @@ class AnalyticAcquisitionFunction(AcquisitionFunction):
 class ExpectedImprovement(AnalyticAcquisitionFunction):
     """acquisition/analytic.py:298-354: sigma (phi(u) + u Phi(u)), u = (mu - best_f)/sigma."""
 
+    _admits_multitask = True
+
     def __init__(self, model, best_f, posterior_transform=None, maximize=True):
         super().__init__(model, posterior_transform)
         self.register_buffer("best_f", torch.as_tensor(best_f, dtype=torch.float64))
@@ -507,6 +531,8 @@ class ProbabilityOfImprovement(AnalyticAcquisitionFunction):
 class UpperConfidenceBound(AnalyticAcquisitionFunction):
     """acquisition/analytic.py (UCB): mu + sqrt(beta) sigma."""
 
+    _admits_multitask = True
+
     def __init__(self, model, beta, posterior_transform=None, maximize=True):
         super().__init__(model, posterior_transform)
         self.register_buffer("beta", torch.as_tensor(beta, dtype=torch.float64))
@@ -520,6 +546,8 @@ class UpperConfidenceBound(AnalyticAcquisitionFunction):
 
 class PosteriorMean(AnalyticAcquisitionFunction):
     """acquisition/analytic.py (PosteriorMean): mu, or -mu with ``maximize=False``."""
+
+    _admits_multitask = True
 
     def __init__(self, model, posterior_transform=None, maximize=True):
         super().__init__(model, posterior_transform)
@@ -544,6 +572,8 @@ def _exact_members(model) -> Optional[list]:
         members = [model]
     if all(isinstance(mm, SingleTaskGP) and not mm._is_multi_output for mm in members):
         return members
+    if getattr(model, "_is_multitask", False) and model.num_outputs == 1:
+        return members  # its prediction cache is the one output task's view
     return None
 
 
@@ -587,7 +617,7 @@ class _MomentChainAcquisition(AnalyticAcquisitionFunction):
             return False
         idx = self._an_members()
         return (len(idx) <= kernels.AN_MT_MAX and len(self._an_constraints()) <= kernels.AN_CMAX
-                and max(idx) < len(members))
+                and max(idx) < len(members) and _cache_dim_ok(self.model, X3))
 
     def _best_f_rows(self, batch: torch.Size, like: torch.Tensor) -> Optional[torch.Tensor]:
         best_f = getattr(self, "best_f", None)
@@ -647,6 +677,8 @@ class LogExpectedImprovement(_MomentChainAcquisition):
     """acquisition/analytic.py:356-416: log EI(x) = log_ei(u) + log sigma with
     u = (mu - best_f) / sigma; finite, with a usable gradient, where EI itself
     underflows to 0."""
+
+    _admits_multitask = True
 
     _log: bool = True
     _an_mode = kernels.AN_LOG_EI
@@ -1848,7 +1880,8 @@ class _CachedBaselineRoot:
             self.L = L_rr.contiguous()
             self.Linv = Linv_rr.contiguous()
             self.fused_ready = False
-            if hasattr(model, "prediction_cache") and X_baseline.shape[-1] <= kernels.DP:
+            if (hasattr(model, "prediction_cache") and X_baseline.shape[-1] <= kernels.DP
+                    and _cache_dim_ok(model, X_baseline)):
                 cache = model.prediction_cache()
                 Kb = kernels.covar_matrix(X_baseline.contiguous(), cache.Xt, cache.lengthscale,
                                           cache.kind, cache.outputscale)
@@ -1911,6 +1944,8 @@ class qNoisyExpectedImprovement(MCAcquisitionFunction):
     the joint (r + q) posterior and takes the baseline best from those samples.
     """
 
+    _admits_multitask = True
+
     _fused_mode = _lib.QMC_QNEI
 
     def __init__(self, model, X_baseline, sampler=None, objective=None, posterior_transform=None,
@@ -1956,7 +1991,8 @@ class qNoisyExpectedImprovement(MCAcquisitionFunction):
         fusable = (hasattr(model, "prediction_cache") and type(self.objective) is IdentityMCObjective
                    and self.posterior_transform is None and self._constraints is None
                    and X_baseline.ndim == 2 and X_baseline.shape[-1] <= kernels.DP
-                   and X_baseline.is_cuda and len(self.sample_shape) == 1)
+                   and X_baseline.is_cuda and len(self.sample_shape) == 1
+                   and _cache_dim_ok(model, X_baseline))
         with torch.no_grad():
             if wplan is not None:
                 # qNEHVI's convention: member t's baseline base samples are the

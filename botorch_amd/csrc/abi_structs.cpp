@@ -67,7 +67,8 @@ bool header_ok(const T* a, const char* name) {
 #define BO_RECORDS(X)                                                                          \
   X(PostPartials) X(QmcFinalize) X(QmcBackward) X(PostBackward) X(Qehvi) X(QehviFeas)          \
   X(Qlogehvi) X(QmcFeas) X(Kg) X(Paths) X(Jes) X(Mes) X(Gibbon) X(MvQuantiles) X(Nipv) X(Bald) \
-  X(Analytic) X(SaasPotential) X(LbfgsStep) X(Lbfgsb) X(Fantasy)
+  X(Analytic) X(SaasPotential) X(LbfgsStep) X(Lbfgsb) X(Fantasy) X(IcmCovar) X(IcmMll)          \
+  X(IcmTaskView)
 
 extern "C" {
 
@@ -80,7 +81,7 @@ extern "C" {
 BO_RECORD_ENTRIES(BO_ENTRY)
 #undef BO_ENTRY
 
-// fantasy.hip: record entry points added within ABI 12.  The _v names above are
+// fantasy.hip, icm.hip: record entry points added within ABI 12.  The _v names above are
 // that version's closed set, so these carry plain names; the header check is the same.
 #define BO_ENTRY_PLAIN(entry, record)                                   \
   int bo_##entry##_impl(const Bo##record##Args* a, void* stream);       \
@@ -90,6 +91,9 @@ BO_RECORD_ENTRIES(BO_ENTRY)
   }
 BO_ENTRY_PLAIN(fantasy_posterior, Fantasy)
 BO_ENTRY_PLAIN(fantasy_posterior_backward, Fantasy)
+BO_ENTRY_PLAIN(icm_covar, IcmCovar)
+BO_ENTRY_PLAIN(icm_mll_terms, IcmMll)
+BO_ENTRY_PLAIN(icm_task_view, IcmTaskView)
 #undef BO_ENTRY_PLAIN
 
 // sizeof of each argument record (HOST, for bindings to verify their layouts).

@@ -29,7 +29,8 @@ from scipy.optimize import minimize
 from . import _lib, kernels
 from ._lib import check, lib
 from .exceptions import NotPSDError, OptimizationWarning, UnsupportedError
-from .models import FixedNoiseGaussianLikelihood, LogNormalPrior, ScaleKernel, SingleTaskGP
+from .models import (ICM_VAR_LOWER, FixedNoiseGaussianLikelihood, GammaPrior, LogNormalPrior,
+                     ScaleKernel, SingleTaskGP)
 
 logger = logging.getLogger("botorch_amd")
 
@@ -54,9 +55,15 @@ class ExactMarginalLogLikelihood:
         return self.model.training
 
 
-def _prior_terms(prior: Optional[LogNormalPrior], x: np.ndarray):
+def _prior_terms(prior, x: np.ndarray):
+    """Sum of the prior's log density over x and its gradient (LogNormalPrior or
+    GammaPrior; None: no prior)."""
     if prior is None:
         return 0.0, np.zeros_like(x)
+    if isinstance(prior, GammaPrior):
+        a, b = prior.concentration, prior.rate
+        val = np.sum(a * math.log(b) + (a - 1.0) * np.log(x) - b * x - math.lgamma(a))
+        return float(val), (a - 1.0) / x - b
     lx = np.log(x)
     val = np.sum(-((lx - prior.loc) ** 2) / (2 * prior.scale ** 2) - math.log(prior.scale)
                  - 0.5 * math.log(2 * math.pi) - lx)
@@ -170,6 +177,8 @@ class _MultiLayout:
 
 
 def _layout(model):
+    if getattr(model, "_is_multitask", False):
+        return _ICMLayout(model)
     return _MultiLayout(model) if getattr(model, "_is_multi_output", False) else _Layout(model)
 
 
@@ -284,6 +293,233 @@ def mll_value_and_grad(model: SingleTaskGP, x: np.ndarray, layout: _Layout, cach
     pv, pg = _prior_terms(layout.base.lengthscale_prior, ls)
     ll += pv
     g[o + 1:o + 1 + d] += pg
+    return -ll / n, -g / n
+
+
+# ---- MultiTaskGP: the ICM marginal log likelihood ------------------------------------------------
+# None: by kernels.icm_fused_ok (T <= 16, d <= 64 take icm.hip); "fused" / "generic": forced
+# (tests, tools/bench_mtgp.py)
+ICM_ROUTE = None
+
+
+def _icm_grad(s, G, d, T, ls, F, n):
+    """(ll, gradient) from the summed row terms s (d + 5) and the folded,
+    symmetrised task sums G (T x T): d ll / d [noise, constant, lengthscale_1..d,
+    outputscale, F (row-major), v]."""
+    quad, logdet_half, sum_alpha = s[d + 3], s[d + 2], s[d + 4]
+    ll = -0.5 * quad - logdet_half - 0.5 * n * math.log(2 * math.pi)
+    g = np.zeros(d + 3 + F.size + T)
+    g[0] = 0.5 * s[d]
+    g[1] = sum_alpha
+    g[2:2 + d] = 0.5 * s[:d] / ls ** 3
+    g[2 + d] = 0.5 * s[d + 1]
+    g[3 + d:3 + d + F.size] = (G @ F).reshape(-1)      # d ll / d F = 1/2 (G + G^T) F
+    g[3 + d + F.size:] = 0.5 * np.diag(G)              # d ll / d v
+    return float(ll), g
+
+
+def icm_mll_terms(Xd: torch.Tensor, task: torch.Tensor, y: torch.Tensor, ls, noise, const: float,
+                  os_: float, F, v, kind: int):
+    """Data term of the exact MLL of the ICM multi-task GP, ll = log N(y | c, A) with
+    A = os kbar(Xd, Xd) * B[task, task] + diag(noise), B = F F^T + diag(v), and
+    d ll / d [noise, constant, lengthscale_1..d, outputscale, F (row-major), v]
+    on the fused route: bo_icm_covar, the optimistic (jitter-free) factorisation
+    and everything after it enqueued at once, A^{-1}, one bo_icm_mll_terms pass;
+    the row terms are summed and the task bins folded on the device, and one
+    device-to-host transfer brings the sums and the factorisation's status.
+    Xd: n x d without the task column, task: n int32 indices, ``noise`` a float or
+    an n-vector (fixed noise: the first gradient entry is then meaningless);
+    ls, F (T x rank), v (T): host arrays.  T <= 16, d <= 64."""
+    from . import ops  # noqa: F401  (registers torch.ops.bo)
+    n, d = Xd.shape
+    dev = Xd.device
+    ls = np.asarray(ls, dtype=np.float64).reshape(-1)
+    F = np.asarray(F, dtype=np.float64)
+    v = np.asarray(v, dtype=np.float64).reshape(-1)
+    T = F.shape[0]
+    Bm = torch.as_tensor(F @ F.T + np.diag(v), dtype=torch.float64).to(dev)
+    ls_t = torch.as_tensor(ls, dtype=torch.float64).to(dev)
+    onehot = _icm_onehot(task, T)
+    fixed = torch.is_tensor(noise) and noise.numel() > 1
+
+    def _sums(cache, info):
+        Ainv = cache.Ainv if cache.Ainv is not None else kernels.ainv(cache)
+        part = torch.ops.bo.icm_mll_terms(cache.Xt, task, ls_t, Bm, int(kind), float(os_), cache.L,
+                                          Ainv, cache.alpha, cache.beta)
+        # rows -> Gl[task_i][b]: a one-hot product (no atomics: repeated calls agree bit for bit)
+        Gl = kernels.gemm(onehot, part[:, d + 5:].contiguous())
+        sums = torch.cat([part[:, :d + 5].sum(dim=0), Gl.reshape(-1)]
+                         + ([info.to(torch.float64)] if info is not None else []))
+        return sums.cpu().numpy()
+
+    cache, info = kernels.build_icm_cache(Xd, task, y, ls_t, Bm, noise, const, kind=kind,
+                                          outputscale=os_, optimistic=True)
+    s = _sums(cache, info)
+    status, s = int(s[-1]), s[:-1]
+    if status < 0:
+        raise RuntimeError("bo_cholesky_inverse: the Cholesky task DAG timed out")
+    if status != 0:  # not p.d. without jitter: the ladder, then the sums again
+        cache, _ = kernels.build_icm_cache(Xd, task, y, ls_t, Bm, noise, const, kind=kind,
+                                           outputscale=os_)
+        s = _sums(cache, None)
+    Gl = s[d + 5:].reshape(T, T)
+    return _icm_grad(s, 0.5 * (Gl + Gl.T), d, T, ls, F, n)
+
+
+def _icm_onehot(task: torch.Tensor, T: int) -> torch.Tensor:
+    """T x n fp64 indicator of the training points' tasks."""
+    return (task.to(torch.long).unsqueeze(0)
+            == torch.arange(T, device=task.device).unsqueeze(1)).to(torch.float64).contiguous()
+
+
+def icm_mll_terms_torch(Xd: torch.Tensor, task: torch.Tensor, y: torch.Tensor, ls, noise,
+                        const: float, os_: float, F, v, kind: int):
+    """icm_mll_terms as a torch composition on the device (the generic route: any
+    T and d; the comparator of tools/bench_mtgp.py): the same sums with
+    W = alpha alpha^T - A^{-1} from torch.linalg's Cholesky (jitter ladder of
+    psd_safe_cholesky on failure) and one device-to-host transfer."""
+    n, d = Xd.shape
+    dev = Xd.device
+    ls = np.asarray(ls, dtype=np.float64).reshape(-1)
+    F = np.asarray(F, dtype=np.float64)
+    v = np.asarray(v, dtype=np.float64).reshape(-1)
+    T = F.shape[0]
+    f64 = dict(dtype=torch.float64, device=dev)
+    Bm = torch.as_tensor(F @ F.T + np.diag(v), dtype=torch.float64).to(dev)
+    ls_t = torch.as_tensor(ls, dtype=torch.float64).to(dev)
+    tl = task.to(torch.long)
+    D2 = (Xd.unsqueeze(1) - Xd.unsqueeze(0)).pow(2)                  # n x n x d
+    r2 = (D2 / ls_t.pow(2)).sum(-1)
+    if kind == _lib.RBF:
+        kbar = torch.exp(-0.5 * r2)
+        g = kbar
+    else:
+        r = r2.sqrt()
+        e = torch.exp(-math.sqrt(5.0) * r)
+        kbar = (1.0 + math.sqrt(5.0) * r + (5.0 / 3.0) * r2) * e
+        g = (5.0 / 3.0) * (1.0 + math.sqrt(5.0) * r) * e
+    Bik = Bm[tl][:, tl]
+    nz = noise.to(**f64).reshape(-1) if torch.is_tensor(noise) else torch.full((n,), float(noise), **f64)
+    A0 = os_ * kbar * Bik + torch.diag(nz.expand(n))
+    jitter, L = 0.0, None
+    for attempt in range(kernels.CHOLESKY_MAX_TRIES + 1):
+        if attempt > 0:
+            jitter = kernels.CHOLESKY_JITTER_F64 * 10.0 ** (attempt - 1)
+        L, info = torch.linalg.cholesky_ex(A0 + jitter * torch.eye(n, **f64))
+        if int(info) == 0:
+            break
+    else:
+        raise NotPSDError("Matrix not positive definite after repeatedly adding jitter up to "
+                          f"{jitter:.1e}")
+    res = (y - const).unsqueeze(-1)
+    beta = torch.linalg.solve_triangular(L, res, upper=False)
+    Ainv = torch.cholesky_inverse(L)
+    alpha = (Ainv @ res).squeeze(-1)
+    W = torch.outer(alpha, alpha) - Ainv
+    WK = W * kbar
+    onehot = _icm_onehot(task, T)
+    G = os_ * (onehot @ WK @ onehot.T)
+    sums = torch.cat([
+        os_ * torch.einsum("ik,ikj->j", W * g * Bik, D2),
+        torch.stack([torch.trace(W), (WK * Bik).sum(), torch.log(torch.diagonal(L)).sum(),
+                     (beta * beta).sum(), alpha.sum()]),
+        G.reshape(-1)])
+    s = sums.cpu().numpy()
+    G = s[d + 5:].reshape(T, T)
+    return _icm_grad(s, 0.5 * (G + G.T), d, T, ls, F, n)
+
+
+class _ICMLayout:
+    """Flat parameter vector <-> hyperparameters of a MultiTaskGP, in the order
+    noise (unless fixed), constant, lengthscale_1..d, outputscale (under a
+    ScaleKernel), covar_factor (row-major), var.  The parameters are the natural
+    values, as in _Layout; ``var`` is bounded below by ICM_VAR_LOWER, which keeps
+    B[t][t] > 0 for the task view's division (anything small against the unit
+    scale of standardised outputs serves), the factor is free."""
+
+    def __init__(self, model):
+        self.model = model
+        self.d = model._d
+        self.T, self.rank = model.num_tasks, model._rank
+        self.fixed = isinstance(model.likelihood, FixedNoiseGaussianLikelihood)
+        self.o = 0 if self.fixed else 1
+        self.has_os = isinstance(model.covar_module, ScaleKernel)
+        self.base = model.covar_module.base_kernel if self.has_os else model.covar_module
+        d, o, nF = self.d, self.o, self.T * self.rank
+        self.f0 = o + 1 + d + (1 if self.has_os else 0)   # start of covar_factor
+        self.v0 = self.f0 + nF                            # start of var
+        self.size = self.v0 + self.T
+        lo = ([] if self.fixed else [model.likelihood.noise_lower]) + [-np.inf]
+        lo += [self.base.lengthscale_lower] * d + ([0.0] if self.has_os else [])
+        lo += [-np.inf] * nF + [ICM_VAR_LOWER] * self.T
+        self.bounds = [(None if not np.isfinite(l) else l, None) for l in lo]
+        self.segments = ([] if self.fixed else [("noise", 0, 1)]) + [
+            ("constant", o, 1), ("lengthscale", o + 1, d)] + (
+            [("outputscale", o + 1 + d, 1)] if self.has_os else []) + [
+            ("covar_factor", self.f0, nF), ("var", self.v0, self.T)]
+
+    def get(self) -> np.ndarray:
+        m = self.model
+        v = [] if self.fixed else [float(m.likelihood.noise.detach())]
+        v.append(float(m.mean_module.constant.detach()))
+        v += self.base.lengthscale.detach().reshape(-1).cpu().tolist()
+        if self.has_os:
+            v.append(float(m.covar_module.outputscale.detach()))
+        v += m.task_covar_module.covar_factor.detach().reshape(-1).cpu().tolist()
+        v += m.task_covar_module.var.detach().reshape(-1).cpu().tolist()
+        return np.asarray(v, dtype=np.float64)
+
+    def set(self, x: np.ndarray) -> None:
+        m, o, d = self.model, self.o, self.d
+        if not self.fixed:
+            m.likelihood.noise = torch.tensor([float(x[0])], dtype=torch.float64)
+        m.mean_module.constant = float(x[o])
+        self.base.lengthscale = torch.as_tensor(x[o + 1:o + 1 + d]).reshape(1, -1)
+        if self.has_os:
+            m.covar_module.outputscale = float(x[o + 1 + d])
+        tk = m.task_covar_module
+        with torch.no_grad():
+            tk.covar_factor.copy_(torch.as_tensor(np.asarray(x[self.f0:self.v0]),
+                                                  dtype=torch.float64).reshape(self.T, self.rank))
+        tk.var = np.asarray(x[self.v0:])
+
+    def value_and_grad(self, x: np.ndarray):
+        return icm_mll_value_and_grad(self.model, x, self)
+
+
+def icm_mll_value_and_grad(model, x: np.ndarray, layout: "_ICMLayout"):
+    """Loss = -(log N(y | c, A) + log priors) / n of a MultiTaskGP at the flat vector
+    x and its gradient: the data term from icm_mll_terms (T <= 16, d <= 64) or
+    icm_mll_terms_torch, the noise / lengthscale / outputscale priors on the
+    host.  Reads x, not the module (the parameters are written at the optimum)."""
+    x = np.asarray(x, dtype=np.float64)
+    d, o, T = layout.d, layout.o, layout.T
+    n = model._Xd.shape[0]
+    noise = model.likelihood.noise if layout.fixed else float(x[0])
+    ls = x[o + 1:o + 1 + d]
+    os_ = float(x[o + 1 + d]) if layout.has_os else 1.0
+    F = x[layout.f0:layout.v0].reshape(T, layout.rank)
+    v = x[layout.v0:]
+    fused = kernels.icm_fused_ok(T, d) if ICM_ROUTE is None else ICM_ROUTE == "fused"
+    terms = icm_mll_terms if fused else icm_mll_terms_torch
+    ll, gall = terms(model._Xd, model._task_i32, model.train_targets, ls, noise, float(x[o]), os_,
+                     F, v, int(model.kind))
+    g = np.zeros_like(x)
+    if not layout.fixed:
+        g[0] = gall[0]
+        pv, pg = _prior_terms(model.likelihood.noise_prior, np.array([x[0]]))
+        ll += pv
+        g[0] += pg[0]
+    g[o:o + 1 + d] = gall[1:2 + d]
+    pv, pg = _prior_terms(layout.base.lengthscale_prior, ls)
+    ll += pv
+    g[o + 1:o + 1 + d] += pg
+    if layout.has_os:
+        g[o + 1 + d] = gall[2 + d]
+        pv, pg = _prior_terms(model.covar_module.outputscale_prior, np.array([os_]))
+        ll += pv
+        g[o + 1 + d] += pg[0]
+    g[layout.f0:] = gall[3 + d:]
     return -ll / n, -g / n
 
 
@@ -404,6 +640,10 @@ def fit_gpytorch_mll_scipy(mll: ExactMarginalLogLikelihood, parameters=None, bou
 def _sample_prior_values(prior: LogNormalPrior, shape, device) -> torch.Tensor:
     """[G] LogNormalPrior.sample(shape) in fp64 on the model's device:
     exp(torch.normal(loc, scale)) from the global generator of that device."""
+    if isinstance(prior, GammaPrior):  # torch Gamma's sampler: standard_gamma(concentration) / rate
+        conc = torch.full(shape, prior.concentration, dtype=torch.float64, device=device)
+        with torch.no_grad():
+            return torch._standard_gamma(conc) / prior.rate
     loc = torch.full(shape, prior.loc, dtype=torch.float64, device=device)
     scale = torch.full(shape, prior.scale, dtype=torch.float64, device=device)
     with torch.no_grad():

@@ -421,6 +421,165 @@ def build_gp_cache_optimistic(Xt, y, lengthscale, noise: float, constant: float,
     return cache, info
 
 
+# ---- multi-task GP, intrinsic coregionalisation model (icm.hip) -----------------------------
+ICM_MAX_TASKS = _lib.ICM_MAX_TASKS  # bo_icm_*: tasks of one launch (B staged in LDS, bins in registers)
+ICM_MAX_DIM = _lib.ICM_MAX_DIM      # and non-task input dimensions
+
+
+def icm_fused_ok(T: int, d: int) -> bool:
+    """The route rule of the ICM kernels: T <= 16 tasks and d <= 64 non-task
+    dimensions take icm.hip, anything else the torch composition."""
+    return 1 <= T <= ICM_MAX_TASKS and 1 <= d <= ICM_MAX_DIM
+
+
+def icm_covar(X, task, lengthscale, B, kind=_lib.RBF, outputscale=1.0, noise=0.0, noise_vec=None,
+              out=None):
+    """The ICM training covariance outputscale kbar(X, X) * B[task, task] +
+    diag(noise + noise_vec) as the padded np x np lower Cholesky input (strict
+    upper zero, identity pad) of bo_cholesky_inverse*.  X: n x d without the task
+    column, task: n int32 in [0, T), B: T x T."""
+    dev = _dev(X, lengthscale, B)
+    n, d = X.shape
+    T = B.shape[0]
+    np_ = padded_order(n)
+    A = out if out is not None else torch.empty(np_, np_, dtype=torch.float64, device=dev)
+    if task.dtype != torch.int32 or task.numel() != n or tuple(B.shape) != (T, T):
+        raise ValueError("icm_covar: task must be n int32 indices and B a T x T matrix")
+    a = _lib.IcmCovarArgs(kind=int(kind), d=d, T=T, n=n, np=np_, X=X.contiguous(),
+                          lengthscale=lengthscale.reshape(-1).contiguous(), B=B.contiguous(),
+                          task=task.contiguous(), noise_vec=noise_vec,
+                          outputscale=float(outputscale), noise=float(noise), A=A)
+    _KEEPALIVE.append(a)
+    check(lib().bo_icm_covar(ctypes.byref(a), _stream(dev)), "icm_covar")
+    return A
+
+
+def build_icm_cache(X, task, y, lengthscale, B, noise, constant, kind=_lib.RBF, outputscale=1.0,
+                    optimistic: bool = False, max_tries=CHOLESKY_MAX_TRIES,
+                    jitter0=CHOLESKY_JITTER_F64):
+    """GPCache of the long-format ICM model: L, L^{-1}, beta, alpha of A =
+    outputscale kbar * B[task, task] + noise (a float, or an n-vector of observed
+    variances), factorised by the existing ladder entry (bo_cholesky_inverse, or
+    its _ainv variant under AINV_IN_DAG).  ``optimistic``: the jitter-free
+    attempt only, enqueued without a status read-back, no U -- returns (cache,
+    info) as build_gp_cache_optimistic does (the MLL closure).  Otherwise the
+    jitter ladder with U = L^{-T}, returns (cache, None).  The cache's ``Xt`` /
+    ``Xt_scaled`` hold the non-task columns."""
+    dev = _dev(X, y, lengthscale, B)
+    X = X.contiguous()
+    y = y.contiguous()
+    n, d = X.shape
+    np_ = padded_order(n)
+    f64 = dict(dtype=torch.float64, device=dev)
+    ls = lengthscale.detach().reshape(-1).to(**f64).contiguous()
+    fixed = torch.is_tensor(noise) and noise.numel() > 1
+    nv = noise.detach().reshape(-1).to(**f64).contiguous() if fixed else None
+    if fixed and nv.numel() != n:
+        raise ValueError(f"fixed noise has {nv.numel()} entries for {n} training points")
+    s2 = 0.0 if fixed else float(noise)
+    L = torch.empty(np_, np_, **f64)
+    Linv = torch.empty(np_, np_, **f64)
+    Ainv = torch.empty(np_, np_, **f64) if (optimistic and AINV_IN_DAG) else None
+    T_ = np_ // 64
+    we = ctypes.c_int64()
+    check(lib().bo_gemv_lt_work(n, ctypes.byref(we)), "gemv_lt_work")
+    work = torch.empty(max((16 + 5 * T_ * T_ + 1) // 2, we.value), **f64)
+    info = torch.zeros(1, dtype=torch.int32, device=dev)
+    st = _stream(dev)
+    jitter = 0.0
+    for attempt in range(1 if optimistic else max_tries + 1):
+        if attempt > 0:
+            jitter = jitter0 * 10.0 ** (attempt - 1)
+        icm_covar(X, task, ls, B, kind, outputscale, s2 + jitter, nv, out=L)
+        if Ainv is not None:
+            check(lib().bo_cholesky_inverse_ainv(_p(L), _p(Linv), _p(Ainv), _p(work), np_,
+                                                 _p(info), st), "cholesky_inverse_ainv")
+        else:
+            check(lib().bo_cholesky_inverse(_p(L), _p(Linv), _p(work), np_, _p(info), st),
+                  "cholesky_inverse")
+        if optimistic:
+            break
+        status = int(info.item())
+        if status < 0:
+            raise RuntimeError("bo_cholesky_inverse: the Cholesky task DAG timed out")
+        if status == 0:
+            break
+    else:
+        from .exceptions import NotPSDError
+        raise NotPSDError("Matrix not positive definite after repeatedly adding jitter up to "
+                          f"{jitter:.1e}")
+    if jitter > 0:
+        import warnings
+        from .exceptions import NumericalWarning
+        warnings.warn(f"A not p.d., added jitter of {jitter:.1e} to the diagonal", NumericalWarning)
+    beta = torch.empty(n, **f64)
+    alpha = torch.empty(n, **f64)
+    check(lib().bo_gemv_tri(_p(Linv), np_, n, _p(y), float(constant), _p(beta), 1, st), "gemv_tri")
+    check(lib().bo_gemv_lt(_p(Linv), np_, n, _p(beta), 0.0, _p(alpha), _p(work), st), "gemv_lt")
+    if optimistic:
+        U = Linv.new_empty(0)  # not formed (no posterior is taken from this cache)
+    else:
+        U = torch.empty(np_, np_, **f64)
+        check(lib().bo_transpose(_p(Linv), _p(U), np_, np_, st), "transpose")
+    Xs = torch.empty(n, DP, **f64)
+    if d <= DP:
+        check(lib().bo_scale_inputs(_p(X), n, d, _p(ls), ctypes.c_void_p(0), DP, _p(Xs), st),
+              "scale_inputs")
+    cache = GPCache(kind, n, d, np_, X, Xs, ls, float(outputscale),
+                    float(nv.mean()) if fixed else s2, float(constant), L, Linv, U, beta, alpha,
+                    jitter, Ainv)
+    return cache, (info if optimistic else None)
+
+
+def icm_mll_partials(X, task, lengthscale, B, kind, outputscale, L, Ainv, alpha, beta):
+    """The row terms of the ICM marginal log likelihood (bo_icm_mll_terms): n x
+    (d + 5 + T), the d + 5 columns of bo_mll_terms (with B[task_i, task_k] as a
+    factor of every pair) and row i's T task bins.  L, Ainv: np x np."""
+    dev = _dev(X, lengthscale, B, L, Ainv, alpha, beta)
+    n, d = X.shape
+    T = B.shape[0]
+    part = torch.empty(n, d + 5 + T, dtype=torch.float64, device=dev)
+    a = _lib.IcmMllArgs(kind=int(kind), d=d, T=T, n=n, ld=L.shape[-1], X=X.contiguous(),
+                        lengthscale=lengthscale.reshape(-1).contiguous(), B=B.contiguous(),
+                        task=task.contiguous(), outputscale=float(outputscale), L=L, Ainv=Ainv,
+                        alpha=alpha, beta=beta, partial=part)
+    _KEEPALIVE.append(a)
+    check(lib().bo_icm_mll_terms(ctypes.byref(a), _stream(dev)), "icm_mll_terms")
+    return part
+
+
+def icm_task_view_arrays(U, alpha, task, B, t: int):
+    """(U' = D U, L^{-1}' = U'^T, alpha' = D alpha), D = diag(B[t, task] / B[t, t])
+    with 1 on the padding (bo_icm_task_view).  U: np x np, alpha: n."""
+    dev = _dev(U, alpha, B)
+    np_, n = U.shape[0], alpha.shape[0]
+    U_out = torch.empty_like(U)
+    Linv_out = torch.empty_like(U)
+    alpha_out = torch.empty_like(alpha)
+    a = _lib.IcmTaskViewArgs(T=B.shape[0], t=int(t), n=n, np=np_, B=B.contiguous(),
+                             task=task.contiguous(), U=U, alpha=alpha, U_out=U_out,
+                             Linv_out=Linv_out, alpha_out=alpha_out)
+    _KEEPALIVE.append(a)
+    check(lib().bo_icm_task_view(ctypes.byref(a), _stream(dev)), "icm_task_view")
+    return U_out, Linv_out, alpha_out
+
+
+def icm_task_view(cache: GPCache, task, B, t: int, Btt: float) -> GPCache:
+    """The caches of output task t of an ICM model as a single-task GPCache:
+    U' = D U, L^{-1}' = U'^T, alpha' = D alpha with D = diag(B[t, task] / B[t, t])
+    (bo_icm_task_view), outputscale' = outputscale B[t, t] (``Btt``: B[t, t] on
+    the host); beta, the constant, the inputs and the lengthscales are shared
+    with ``cache``.  There is no factor for the view (D may hold zeros and
+    negative entries): ``L`` is None, so a consumer of it fails loudly."""
+    from . import ops  # noqa: F401  (torch.ops.bo registration)
+    if not Btt > 0.0:
+        raise ValueError(f"icm_task_view: B[{t}, {t}] = {Btt} is not positive")
+    U, Linv, alpha = torch.ops.bo.icm_task_view(cache.U, cache.alpha, task, B, int(t))
+    return GPCache(cache.kind, cache.n, cache.d, cache.np, cache.Xt, cache.Xt_scaled,
+                   cache.lengthscale, cache.outputscale * float(Btt), cache.noise, cache.constant,
+                   None, Linv, U, cache.beta, alpha, cache.jitter)
+
+
 def build_gp_caches(specs, check_nan: bool = True):
     """GPCaches of several exact GPs whose training sets pad to one order (the
     outputs of a batched multi-output SingleTaskGP, a ModelListGP's members):

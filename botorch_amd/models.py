@@ -75,6 +75,21 @@ class LogNormalPrior:
                 - 0.5 * math.log(2 * math.pi) - lx)
 
 
+class GammaPrior:
+    """[G] GammaPrior(concentration, rate) (torch Gamma)."""
+
+    def __init__(self, concentration: float, rate: float):
+        self.concentration, self.rate = float(concentration), float(rate)
+
+    @property
+    def mode(self) -> float:
+        return max(self.concentration - 1.0, 0.0) / self.rate
+
+    def log_prob(self, x: torch.Tensor) -> torch.Tensor:
+        a, b = self.concentration, self.rate
+        return a * math.log(b) + (a - 1.0) * torch.log(x) - b * x - math.lgamma(a)
+
+
 class _Kernel(_TrackedModule):
     kind = _lib.RBF
 
@@ -204,6 +219,63 @@ def get_covar_module_with_dim_scaled_prior(ard_num_dims: int, use_rbf_kernel: bo
 def get_gaussian_likelihood_with_lognormal_prior():
     """gpytorch_modules.py:74-97."""
     return GaussianLikelihood(noise_prior=LogNormalPrior(-4.0, 1.0))
+
+
+def get_matern_kernel_with_gamma_prior(ard_num_dims: int):
+    """gpytorch_modules.py:34-50: ScaleKernel(Matern-5/2) with a Gamma(3, 6) prior on
+    the lengthscales and a Gamma(2, 0.15) prior on the outputscale, both starting
+    at the reference's initial value softplus(0) = ln 2.  The lengthscales keep
+    this package's lower bound (the parameters are the natural values, so
+    L-BFGS-B needs one above zero)."""
+    base = MaternKernel(ard_num_dims=ard_num_dims, lengthscale_prior=GammaPrior(3.0, 6.0),
+                        initial=math.log(2.0))
+    return ScaleKernel(base, outputscale=math.log(2.0), outputscale_prior=GammaPrior(2.0, 0.15))
+
+
+def get_gaussian_likelihood_with_gamma_prior():
+    """gpytorch_modules.py:53-71: Gamma(1.1, 0.05) noise prior, noise >=
+    MIN_INFERRED_NOISE_LEVEL, initialised at the prior's mode."""
+    prior = GammaPrior(1.1, 0.05)
+    return GaussianLikelihood(noise_prior=prior, noise_lower=MIN_INFERRED_NOISE_LEVEL,
+                              initial=prior.mode)
+
+
+ICM_VAR_LOWER = 1e-6  # floor of IndexKernel.var in the fit: B[t][t] > 0 for the task view
+
+
+class IndexKernel(_TrackedModule):
+    """[G] IndexKernel(num_tasks, rank): the task covariance B = F F^T + diag(v) of
+    the intrinsic coregionalisation model, ``covar_factor`` F (T x rank) and
+    ``var`` v (T, the natural values).  Initialised from the global torch
+    generator as the reference's is: F ~ randn(T, rank), then v = softplus of
+    randn(T) (its Positive constraint at a standard-normal raw value)."""
+
+    def __init__(self, num_tasks: int, rank: int = 1, prior=None):
+        super().__init__()
+        if prior is not None:
+            raise UnsupportedError("IndexKernel: a prior on the task covariance (LKJ) is not "
+                                   "on the accelerated path")
+        if rank > num_tasks:
+            raise RuntimeError("Cannot create a task covariance matrix larger than the number "
+                               "of tasks")
+        self.num_tasks, self.rank = int(num_tasks), int(rank)
+        F = torch.randn(num_tasks, rank).to(torch.float64)
+        v = torch.nn.functional.softplus(torch.randn(num_tasks).to(torch.float64))
+        self.covar_factor = nn.Parameter(F)
+        self.raw_var = nn.Parameter(v.clamp_min(ICM_VAR_LOWER))
+
+    @property
+    def var(self) -> torch.Tensor:
+        return self.raw_var
+
+    @var.setter
+    def var(self, value):
+        with torch.no_grad():
+            self.raw_var.copy_(torch.as_tensor(value, dtype=torch.float64).reshape(-1))
+
+    @property
+    def covar_matrix(self) -> torch.Tensor:
+        return self.covar_factor @ self.covar_factor.mT + torch.diag(self.raw_var)
 
 
 class Standardize(_TrackedModule):
@@ -1173,6 +1245,371 @@ class SaasFullyBayesianSingleTaskGP(Model):
         cov = torch.stack(covs, dim=1).reshape(*batch, M, q, q)
         post = GaussianMixturePosterior(MultivariateNormal(mean, cov), model=self, X=X)
         return post if posterior_transform is None else posterior_transform(post)
+
+
+class _TaskView:
+    """One output task of a MultiTaskGP as the posterior kernels see a
+    single-output exact GP: ``prediction_cache`` (the task view of the base
+    caches) and ``outcome_stats``."""
+
+    def __init__(self, model: "MultiTaskGP", t: int):
+        self.model, self.t = model, t
+
+    def prediction_cache(self, key=None):
+        return self.model._task_view(self.t)
+
+    def outcome_stats(self):
+        return self.model.outcome_stats()
+
+
+class MultiTaskGP(Model):
+    """Long-format multi-task exact GP with the intrinsic coregionalisation
+    kernel k((x, a), (x', b)) = k_x(x, x') B[a, b], B = F F^T + diag(v)
+    (botorch/models/multitask.py:123-333, models/gpytorch.py:732-918).
+
+    train_X: n x (d + 1) with the task values in column ``task_feature``;
+    train_Y: n x 1; ``train_Yvar`` (n x 1) gives a fixed-noise likelihood.
+    ``all_tasks`` defaults to the task values in the data (a superset may be
+    given: tasks without data); raw task values are remapped to 0..T-1 in sorted
+    order.  Defaults as the reference's: ScaleKernel(Matern-5/2) with Gamma
+    priors, Gamma(1.1, 0.05) noise prior, full-rank IndexKernel, no outcome
+    transform (``Standardize(m=1)`` is accepted), one noise level shared by the
+    tasks.  ``task_covar_prior`` and ``input_transform`` raise UnsupportedError.
+
+    ``posterior(X)``: X with d columns gives the one output task (``output_tasks``
+    or ``output_indices`` of length 1); X with d + 1 columns gives each point's
+    own task and is single-output.  One task throughout takes that task's view
+    of the caches (kernels.icm_task_view) through the single-task posterior
+    kernels; mixed tasks inside a q-batch take posteriors._ICMGeneralMoments.
+    Several output tasks with X lacking the task column (the multi-output
+    posterior with cross-task covariance) raise UnsupportedError.
+
+    With one output task ``prediction_cache()`` returns that task's view, which
+    is what admits the model to the fused acquisition routes; the view's ``L``
+    is None."""
+
+    _is_multitask = True
+
+    def __init__(self, train_X: torch.Tensor, train_Y: torch.Tensor, task_feature: int,
+                 train_Yvar: Optional[torch.Tensor] = None, mean_module=None, covar_module=None,
+                 likelihood=None, task_covar_prior=None, output_tasks: Optional[List[int]] = None,
+                 rank: Optional[int] = None, all_tasks: Optional[List[int]] = None,
+                 input_transform=None, outcome_transform=None):
+        super().__init__()
+        from .exceptions import InputDataError
+        if input_transform is not None:
+            raise UnsupportedError("MultiTaskGP: input transforms are not on the accelerated path")
+        if task_covar_prior is not None:
+            raise UnsupportedError("MultiTaskGP: a `task_covar_prior` (LKJ) is not on the "
+                                   "accelerated path")
+        if train_X.ndim != 2:
+            raise ValueError(f"Unsupported shape {train_X.shape} for train_X.")
+        if train_Y.dim() != 2 or train_Y.shape != (train_X.shape[0], 1):
+            raise UnsupportedError("MultiTaskGP takes train_X n x (d + 1) and train_Y n x 1")
+        if train_Yvar is not None and train_Yvar.shape != train_Y.shape:
+            raise ValueError(f"train_Yvar of shape {tuple(train_Yvar.shape)} does not match "
+                             f"train_Y of shape {tuple(train_Y.shape)}")
+        d = train_X.shape[-1] - 1
+        if not (-d <= task_feature <= d):
+            raise ValueError(f"Must have that -{d} <= task_feature <= {d}")
+        task_feature = task_feature % (d + 1)
+        train_X = train_X.to(torch.float64)
+        train_Y = train_Y.to(torch.float64)
+        if torch.isnan(train_X).any() or torch.isnan(train_Y).any():
+            raise InputDataError("Input data contains NaN values.")
+        if train_Yvar is not None:
+            train_Yvar = train_Yvar.to(torch.float64)
+            if torch.isnan(train_Yvar).any():
+                raise InputDataError("Input data contains NaN values.")
+            if (train_Yvar < 0).any():
+                raise InputDataError("Input data contains negative variances.")
+        all_tasks_inferred = train_X[:, task_feature].unique(sorted=True).to(torch.long).tolist()
+        if all_tasks is not None and not set(all_tasks_inferred).issubset(all_tasks):
+            raise UnsupportedError(
+                f"The provided {all_tasks=} does not contain all the task features "
+                f"inferred from the training data {all_tasks_inferred=}. "
+                "This is not allowed as it will lead to errors during model training.")
+        all_tasks = sorted(all_tasks) if all_tasks else all_tasks_inferred
+        self.num_tasks = len(all_tasks)
+        self.num_non_task_features = d
+        if outcome_transform is not None:
+            if not (isinstance(outcome_transform, Standardize) and outcome_transform._m == 1):
+                raise UnsupportedError("MultiTaskGP takes Standardize(m=1) or no outcome "
+                                       "transform here")
+            outcome_transform.train()
+            train_Y_tf, train_Yvar_tf = outcome_transform(train_Y, train_Yvar)
+            self.outcome_transform = outcome_transform
+        else:
+            train_Y_tf, train_Yvar_tf = train_Y, train_Yvar
+        if output_tasks is None:
+            output_tasks = list(all_tasks)
+        elif set(output_tasks) - set(all_tasks):
+            raise RuntimeError("All output tasks must be present in input data.")
+        self._output_tasks = list(output_tasks)
+        self._num_outputs = len(output_tasks)
+        self._task_feature = task_feature
+        self._d = d
+        self._all_tasks = list(all_tasks)
+        self._expected_task_values = set(all_tasks)
+        self._task_index = {int(v): i for i, v in enumerate(all_tasks)}
+        # raw task value -> index (NaN where the value is no task), None when the values
+        # are already 0..T-1 (get_task_value_remapping)
+        if list(all_tasks) == list(range(len(all_tasks))):
+            self._task_mapper = None
+        else:
+            if min(all_tasks) < 0:
+                raise ValueError(f"task values must be non-negative integers, got {all_tasks}")
+            mapper = torch.full((max(all_tasks) + 1,), float("nan"), dtype=torch.float64)
+            mapper[torch.tensor(all_tasks, dtype=torch.long)] = torch.arange(
+                len(all_tasks), dtype=torch.float64)
+            self.register_buffer("_task_mapper", mapper)
+        self._base_idxr = [j for j in range(d + 1) if j != task_feature]
+        Xd = train_X[:, self._base_idxr].contiguous()
+        self._check_scaling(Xd, train_Y_tf)
+        self.train_inputs = (train_X,)
+        self.train_targets = train_Y_tf.squeeze(-1)
+        self._raw_train_Y = train_Y
+        self._Xd = Xd
+        if likelihood is None:
+            likelihood = (get_gaussian_likelihood_with_gamma_prior() if train_Yvar_tf is None
+                          else FixedNoiseGaussianLikelihood(train_Yvar_tf.squeeze(-1)))
+        self.likelihood = likelihood
+        self.mean_module = mean_module if mean_module is not None else ConstantMean()
+        self.covar_module = (covar_module if covar_module is not None
+                             else get_matern_kernel_with_gamma_prior(ard_num_dims=d))
+        self._rank = rank if rank is not None else self.num_tasks
+        self.task_covar_module = IndexKernel(num_tasks=self.num_tasks, rank=self._rank)
+        self.to(train_X.device)
+        self._is_multitask = True  # (an instance attribute: read from __dict__ on hot paths)
+        self._task_long = self._map_tasks(train_X[:, task_feature].to(torch.long)).contiguous()
+        self._task_i32 = self._task_long.to(torch.int32).contiguous()
+        self._cache = None
+        self._cache_key = None
+        self._views = {}
+        self._view_models = {}
+        self._noise_by_task = None
+
+    _check_scaling = staticmethod(SingleTaskGP._check_scaling)
+
+    # -- tasks ------------------------------------------------------------------------
+    def _map_tasks(self, task_values: torch.Tensor) -> torch.Tensor:
+        """models/gpytorch.py:739-770: raw task values (long) -> task indices."""
+        mapper = self._buffers.get("_task_mapper")
+        if mapper is None:
+            if not (torch.all(0 <= task_values) and torch.all(task_values < self.num_tasks)):
+                raise ValueError("Expected all task features in `X` to be between 0 and "
+                                 f"self.num_tasks - 1. Got {task_values}.")
+            return task_values.long()
+        task_values = task_values.long()
+        unexpected = set(task_values.unique().tolist()).difference(self._expected_task_values)
+        if len(unexpected) > 0:
+            raise ValueError("Received invalid raw task values. Expected raw value to be in"
+                             f" {self._expected_task_values}, but got unexpected task values:"
+                             f" {unexpected}.")
+        return mapper[task_values].long()
+
+    def _split_inputs(self, X: torch.Tensor):
+        """The d non-task columns and the task indices (long) of X (... x (d + 1))."""
+        return X[..., self._base_idxr], self._map_tasks(X[..., self._task_feature].long())
+
+    # -- hyperparameters and caches -----------------------------------------------------
+    @property
+    def kind(self) -> int:
+        return self.covar_module.kind
+
+    @property
+    def batch_shape(self) -> torch.Size:
+        return torch.Size([])
+
+    def hyper(self):
+        ls = self.covar_module.lengthscale.detach().reshape(-1)
+        os_ = float(self.covar_module.outputscale.detach()) if isinstance(self.covar_module, ScaleKernel) else 1.0
+        return ls, os_, float(self.likelihood.noise.detach().mean()), float(self.mean_module.constant.detach())
+
+    def train(self, mode: bool = True):
+        if mode:
+            self._drop_caches()
+        return super().train(mode)
+
+    def _drop_caches(self):
+        self._cache = None
+        self._cache_key = None
+        self._views = {}
+
+    def _key(self):
+        d = self.__dict__
+        if d.get("_plist_gen") != _STRUCTURE[0]:
+            d["_plist"] = list(self.parameters())
+            d["_plist_gen"] = _STRUCTURE[0]
+        ps = [self.train_inputs[0], self.train_targets] + d["_plist"]
+        return tuple((p.data_ptr(), p._version) for p in ps)
+
+    def _base_cache(self):
+        """The caches of the ICM training covariance (its L, L^{-1}, U, beta,
+        alpha) over the non-task columns; rebuilt, and every task view dropped,
+        on any change of a parameter or training tensor (SingleTaskGP._key)."""
+        from . import kernels
+        from .settings import propagate_grads
+        if propagate_grads.on() and (self.train_inputs[0].requires_grad or self.train_targets.requires_grad):
+            raise UnsupportedError(
+                "settings.propagate_grads: posterior gradients to the training data are not "
+                "supported (the prediction caches are built without a backward to them)")
+        key = self._key()
+        if self._cache is None or self._cache_key != key:
+            ls, os_, noise, c = self.hyper()
+            fixed = isinstance(self.likelihood, FixedNoiseGaussianLikelihood)
+            Bm = self.task_covar_module.covar_matrix.detach().contiguous()
+            if kernels.icm_fused_ok(self.num_tasks, self._d):
+                cache, _ = kernels.build_icm_cache(
+                    self._Xd, self._task_i32, self.train_targets, ls, Bm,
+                    self.likelihood.noise if fixed else noise, c, kind=int(self.kind),
+                    outputscale=os_)
+            else:
+                cache = self._base_cache_generic(ls, os_, noise, c, Bm, fixed)
+            self._drop_caches()
+            self._cache, self._cache_key = cache, key
+            self._B_dev, self._B_host = Bm, Bm.cpu()
+        return self._cache
+
+    def _base_cache_generic(self, ls, os_, noise, c, Bm, fixed):
+        """T > 16 or d > 64: the covariance as a torch composition on the device
+        (covar_matrix, a gather of B), factorised by kernels.cholesky_with_inverse."""
+        from . import kernels
+        Xd, n = self._Xd, self._Xd.shape[0]
+        K = kernels.covar_matrix(Xd, Xd, ls.contiguous(), int(self.kind), os_)
+        A = K * Bm[self._task_long][:, self._task_long]
+        A = A + torch.diag(self.likelihood.noise if fixed else torch.full_like(self.train_targets, noise))
+        L, Linv, jit = kernels.cholesky_with_inverse(A)
+        np_ = kernels.padded_order(n)
+
+        def pad(M):  # the caches' layout: np x np with the identity pad
+            P = torch.eye(np_, dtype=torch.float64, device=Xd.device)
+            P[:n, :n] = M
+            return P
+
+        Lp, Lip = pad(L), pad(Linv)
+        U = Lip.mT.contiguous()
+        beta = Linv @ (self.train_targets - c)
+        alpha = Linv.mT @ beta
+        Xs = torch.zeros(n, kernels.DP, dtype=torch.float64, device=Xd.device)
+        if self._d <= kernels.DP:
+            Xs[:, :self._d] = Xd / ls
+        return kernels.GPCache(int(self.kind), n, self._d, np_, Xd, Xs, ls.contiguous(), os_,
+                               noise, c, Lp, Lip, U, beta.contiguous(), alpha.contiguous(), jit)
+
+    def _task_view(self, t: int):
+        """The GPCache view of output task index t (cached until the base caches change)."""
+        from . import kernels
+        base = self._base_cache()
+        view = self._views.get(t)
+        if view is None:
+            Btt = float(self._B_host[t, t])
+            if kernels.icm_fused_ok(self.num_tasks, self._d):
+                view = kernels.icm_task_view(base, self._task_i32, self._B_dev, t, Btt)
+            else:
+                D = torch.ones(base.np, dtype=torch.float64, device=base.U.device)
+                D[:base.n] = self._B_dev[t][self._task_long] / Btt
+                U = (D.unsqueeze(-1) * base.U).contiguous()
+                view = kernels.GPCache(base.kind, base.n, base.d, base.np, base.Xt, base.Xt_scaled,
+                                       base.lengthscale, base.outputscale * Btt, base.noise,
+                                       base.constant, None, U.mT.contiguous(), U, base.beta,
+                                       (D[:base.n] * base.alpha).contiguous(), base.jitter)
+            self._views[t] = view
+        return view
+
+    def _view_model(self, t: int) -> _TaskView:
+        vm = self._view_models.get(t)
+        if vm is None:
+            vm = self._view_models[t] = _TaskView(self, t)
+        return vm
+
+    def prediction_cache(self, key=None):
+        """The task view of the one output task (what the fused acquisition routes
+        read); a model with several output tasks has no single cache."""
+        if self._num_outputs != 1:
+            raise UnsupportedError(
+                "MultiTaskGP.prediction_cache: the model has several output tasks; the fused "
+                "routes take a model with exactly one (output_tasks=[t])")
+        return self._task_view(self._task_index[int(self._output_tasks[0])])
+
+    # -- posterior -----------------------------------------------------------------------
+    def _observation_noise(self, tq: torch.Tensor) -> torch.Tensor:
+        """The noise variance of each test point's task in the model's (transformed)
+        space: the inferred noise, or with fixed noise the mean observed noise of
+        the task's training points (models/gpytorch.py:772-832)."""
+        if not isinstance(self.likelihood, FixedNoiseGaussianLikelihood):
+            return self.likelihood.noise.detach().reshape(()).expand(tq.shape)
+        nz = self.likelihood.noise
+        key = (nz.data_ptr(), nz._version)
+        if self._noise_by_task is None or self._noise_by_task[0] != key:
+            nbt = torch.zeros(self.num_tasks, dtype=torch.float64, device=tq.device)
+            for t in self._task_long.unique().tolist():
+                nbt[t] = nz[self._task_long == t].mean()
+            self._noise_by_task = (key, nbt)
+        return self._noise_by_task[1][tq]
+
+    def posterior(self, X: torch.Tensor, output_indices=None, observation_noise=False,
+                  posterior_transform=None):
+        """models/gpytorch.py:834-918, computing in fp64."""
+        from .posteriors import (GPyTorchPosterior, MultivariateNormal, _ICMGeneralMoments,
+                                 posterior_moments)
+        if torch.is_tensor(observation_noise):
+            raise NotImplementedError(
+                "Passing a tensor of observations is not supported by MultiTaskGP.")
+        if X.dtype != torch.float64:
+            X = X.to(torch.float64)
+        d = self._d
+        if X.shape[-1] == d + 1:
+            if output_indices is not None:
+                raise ValueError("`output_indices` must be None when `X` includes task features.")
+            Xd, tq = self._split_inputs(X)
+            tasks = tq.unique().tolist()
+        elif X.shape[-1] == d:
+            raw = self._output_tasks if output_indices is None else list(output_indices)
+            bad = set(raw).difference(self._expected_task_values)
+            if bad:
+                raise ValueError("Received invalid raw task values. Expected raw value to be in"
+                                 f" {self._expected_task_values}, but got unexpected task values:"
+                                 f" {bad}.")
+            if len(raw) != 1:
+                raise UnsupportedError(
+                    "MultiTaskGP.posterior: several output tasks for X without the task column "
+                    "(the multi-output posterior with cross-task covariance) are not on the "
+                    "accelerated path.  Supported: X with d columns and exactly one output task "
+                    "(output_tasks=[t] or output_indices=[t]), or X with the task column "
+                    "(d + 1 columns), which is single-output.")
+            Xd, tq = X, None
+            tasks = [self._task_index[int(raw[0])]]
+        else:
+            raise ValueError(f"MultiTaskGP.posterior: X has {X.shape[-1]} columns, expected {d} "
+                             f"or {d + 1}")
+        self.eval()
+        batch, q = Xd.shape[:-2], Xd.shape[-2]
+        if len(tasks) == 1:
+            mean, cov = posterior_moments(self._view_model(int(tasks[0])), Xd)
+            if observation_noise is True and tq is None:
+                tq = torch.full(Xd.shape[:-1], int(tasks[0]), dtype=torch.long, device=Xd.device)
+        else:
+            X3 = Xd.reshape(-1, q, d).contiguous()
+            mean, cov = _ICMGeneralMoments.apply(X3, tq.reshape(-1, q), self)
+            mean, cov = mean.reshape(*batch, q), cov.reshape(*batch, q, q)
+        if observation_noise is True:
+            _, ystd = self.outcome_stats()
+            cov = cov + torch.diag_embed(self._observation_noise(tq) * (ystd * ystd))
+        post = GPyTorchPosterior(MultivariateNormal(mean, cov), model=self, X=X)
+        return post if posterior_transform is None else posterior_transform(post)
+
+    # -- what stays off the accelerated path -----------------------------------------------
+    def condition_on_observations(self, X, Y, **kwargs):
+        raise UnsupportedError("condition_on_observations: MultiTaskGP is not on the accelerated "
+                               "path (conditioning of multi-task models)")
+
+    def fantasize(self, X, sampler, observation_noise=None, **kwargs):
+        raise UnsupportedError("fantasize: MultiTaskGP is not on the accelerated path (fantasy "
+                               "models of multi-task models)")
+
+    def subset_output(self, idcs):
+        raise UnsupportedError("Subsetting outputs is not supported by `MultiTaskGPyTorchModel`.")
 
 
 def __getattr__(name):

@@ -56,6 +56,12 @@ Ops (reference computation each replaces):
   bo::saas_potential  U = -log p(z, Y) of the SAAS GP and its closed-form gradient for a batch
                       of NUTS chains, one workgroup per chain (models/fully_bayesian.py:168-247;
                       its launch goes through bo::saas_potential_native in C++)
+  bo::icm_covar       training covariance of the ICM multi-task GP as the padded Cholesky
+                      input (models/multitask.py:301-312)
+  bo::icm_mll_terms   row terms of its marginal log likelihood with T task bins per row for
+                      d ll / d B (the closure of fit_gpytorch_mll on a MultiTaskGP)
+  bo::icm_task_view   the prediction caches of one output task, scaled so that the
+                      single-task posterior kernels compute that task's posterior
 """
 from __future__ import annotations
 
@@ -1093,10 +1099,54 @@ def _(z, X, y, work=None):
             z.new_empty((C,), dtype=torch.int32))
 
 
+# ---- bo::icm_* (multi-task GP, intrinsic coregionalisation model: icm.hip) ---------------------
+@torch.library.custom_op("bo::icm_covar", mutates_args=(), device_types="cuda")
+def icm_covar(X: Tensor, task: Tensor, lengthscale: Tensor, B: Tensor, kind: int,
+              outputscale: float, noise: float, noise_vec: Optional[Tensor] = None) -> Tensor:
+    """The ICM training covariance outputscale kbar(X, X) * B[task, task] + diag(noise
+    + noise_vec) as the padded np x np lower Cholesky input (identity pad)."""
+    return kernels.icm_covar(X, task, lengthscale, B, kind, outputscale, noise, noise_vec)
+
+
+@icm_covar.register_fake
+def _(X, task, lengthscale, B, kind, outputscale, noise, noise_vec=None):
+    np_ = _padded(X.shape[0])
+    return X.new_empty(np_, np_, dtype=F64)
+
+
+@torch.library.custom_op("bo::icm_mll_terms", mutates_args=(), device_types="cuda")
+def icm_mll_terms(X: Tensor, task: Tensor, lengthscale: Tensor, B: Tensor, kind: int,
+                  outputscale: float, L: Tensor, Ainv: Tensor, alpha: Tensor,
+                  beta: Tensor) -> Tensor:
+    """Row terms of the ICM marginal log likelihood, n x (d + 5 + T): bo_mll_terms'
+    columns with the task covariance as a factor of every pair, then T task bins."""
+    return kernels.icm_mll_partials(X, task, lengthscale, B, kind, outputscale, L, Ainv, alpha,
+                                    beta)
+
+
+@icm_mll_terms.register_fake
+def _(X, task, lengthscale, B, kind, outputscale, L, Ainv, alpha, beta):
+    return X.new_empty(X.shape[0], X.shape[1] + 5 + B.shape[0], dtype=F64)
+
+
+@torch.library.custom_op("bo::icm_task_view", mutates_args=(), device_types="cuda")
+def icm_task_view(U: Tensor, alpha: Tensor, task: Tensor, B: Tensor, t: int
+                  ) -> Tuple[Tensor, Tensor, Tensor]:
+    """(D U, (D U)^T, D alpha) with D = diag(B[t, task] / B[t, t]): the caches of
+    output task t of a MultiTaskGP as the single-task posterior kernels read them."""
+    return kernels.icm_task_view_arrays(U, alpha, task, B, t)
+
+
+@icm_task_view.register_fake
+def _(U, alpha, task, B, t):
+    return U.new_empty(U.shape), U.new_empty(U.shape), alpha.new_empty(alpha.shape)
+
+
 OPS: List[str] = ["sobol_normal", "gp_cache", "gp_cache_extend", "chol_jitter", "chol_backward",
                   "post_partials", "qmc_finalize", "gp_posterior", "gp_posterior_backward",
                   "qmc_acq", "qmc_acq_backward", "qehvi", "qehvi_backward", "mll", "kg",
                   "kg_backward", "paths_eval", "paths_eval_backward", "jes", "jes_backward", "mes",
                   "mes_backward", "gibbon", "gibbon_backward", "mv_quantiles", "nipv_gram",
                   "nipv_gram_backward", "bald", "bald_backward", "analytic", "analytic_backward",
-                  "saas_potential", "fantasy_posterior", "fantasy_posterior_backward"]
+                  "saas_potential", "fantasy_posterior", "fantasy_posterior_backward", "icm_covar",
+                  "icm_mll_terms", "icm_task_view"]

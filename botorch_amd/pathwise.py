@@ -56,6 +56,9 @@ def _check_model(model) -> None:
         raise NotImplementedError(
             f"Pathwise sampling is not implemented for {type(model).__name__} (fully Bayesian "
             "models are not supported).")
+    if getattr(model, "_is_multitask", False):
+        raise UnsupportedError("Pathwise sampling: MultiTaskGP is not on the accelerated path "
+                               "(the paths' prior features take a single-task kernel).")
     if not isinstance(model, (SingleTaskGP, ModelListGP)):
         raise NotImplementedError(f"Pathwise sampling is not implemented for {type(model).__name__}.")
     if model.training:

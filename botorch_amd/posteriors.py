@@ -89,6 +89,64 @@ class _GeneralMoments(torch.autograd.Function):
         return dX.reshape(B, q, d), None
 
 
+class _ICMGeneralMoments(torch.autograd.Function):
+    """(mean', Sigma') of B t-batches whose q points belong to different tasks of a
+    MultiTaskGP (the task column varies inside a t-batch), differentiable w.r.t.
+    the non-task columns X.  _GeneralMoments on the model's base caches (the
+    factor of the ICM training covariance) with the task covariance gathered
+    onto both kernel blocks:
+      K*x = outputscale kbar(X, Xt) * B[t_x, tau],   K** = outputscale kbar(X, X) * B[t_x, t_x'],
+    so the backward multiplies d K*x and d K** by the same gathers before
+    bo_kernel_grad.  ``tq``: B x q task indices (long)."""
+
+    @staticmethod
+    def forward(ctx, X3, tq, model):
+        cache = model._base_cache()
+        Bm = model.task_covar_module.covar_matrix.detach()
+        ymean, ystd = model.outcome_stats()
+        B, q, d = X3.shape
+        n, np_ = cache.n, cache.np
+        X2 = X3.detach().reshape(B * q, d).contiguous()
+        Sx = Bm[tq.reshape(-1)][:, model._task_long]                       # Bq x n
+        Sq = Bm[tq.unsqueeze(-1), tq.unsqueeze(-2)]                        # B x q x q
+        Kx = kernels.covar_matrix(X2, cache.Xt, cache.lengthscale, cache.kind, cache.outputscale)
+        Kx = (Kx * Sx).contiguous()
+        R = torch.empty(B * q, n, dtype=torch.float64, device=X2.device)
+        kernels.gemm_strided(B * q, n, n, Kx, n, 0, cache.U, np_, 0, R, n, 0, 1,
+                             flags=_lib.GEMM_B_UPPER)
+        mean = kernels.gemm(Kx, cache.alpha.reshape(n, 1)).reshape(B, q)
+        RR = kernels.gemm(R.view(B, q, n), R.view(B, q, n), transB=True)
+        Kxx = kernels.covar_blocks(X3.detach(), cache.lengthscale, cache.kind, cache.outputscale)
+        cov = (Kxx * Sq - RR) * (ystd * ystd)
+        mean = ymean + ystd * (mean + cache.constant)
+        if ctx.needs_input_grad[0]:
+            ctx.cache, ctx.ystd, ctx.X2, ctx.R, ctx.shape = cache, ystd, X2, R, (B, q, d)
+            ctx.Sx, ctx.Sq = Sx, Sq
+        return mean, cov
+
+    @staticmethod
+    def backward(ctx, dmean, dcov):
+        cache, ystd = ctx.cache, ctx.ystd
+        B, q, d = ctx.shape
+        n, np_ = cache.n, cache.np
+        dev = ctx.R.device
+        if dmean is None:
+            dmean = torch.zeros(B, q, dtype=torch.float64, device=dev)
+        if dcov is None:
+            dcov = torch.zeros(B, q, q, dtype=torch.float64, device=dev)
+        G = ((ystd * ystd) * (dcov + dcov.mT)).contiguous()
+        W = torch.empty(B * q, n, dtype=torch.float64, device=dev)      # R L^{-1} = R U^T
+        kernels.gemm_strided(B * q, n, n, ctx.R, n, 0, cache.U, np_, 0, W, n, 0, 1,
+                             transB=True, flags=_lib.GEMM_B_LOWER)
+        dK = ((ystd * dmean).reshape(B * q, 1) * cache.alpha.reshape(1, n)).contiguous()
+        kernels.gemm(G, W.view(B, q, n), alpha=-1.0, beta=1.0, C=dK.view(B, q, n))
+        dX = kernels.kernel_grad(ctx.X2, cache.Xt, (dK * ctx.Sx).contiguous(), cache.lengthscale,
+                                 cache.kind, cache.outputscale)
+        dX = kernels.kernel_grad(ctx.X2, ctx.X2, (G * ctx.Sq).reshape(B * q, q).contiguous(),
+                                 cache.lengthscale, cache.kind, cache.outputscale, group=q, dX=dX)
+        return dX.reshape(B, q, d), None, None
+
+
 class _CholJitter(torch.autograd.Function):
     """psd_safe_cholesky with its gradient ([G] MultivariateNormal
     root_decomposition under autograd): forward = the jitter ladder

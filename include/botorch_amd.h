@@ -1369,6 +1369,72 @@ typedef struct BoLbfgsbArgs {
 } BoLbfgsbArgs;
 int bo_lbfgsb_step_v(const BoLbfgsbArgs* a, void* stream);
 
+/* ---- Multi-task GP, intrinsic coregionalisation model (botorch/models/multitask.py:
+ * 123-333): k((x, a), (x', b)) = outputscale kbar(x, x') B[a][b] over T tasks, B = F F^T +
+ * diag(v) (T x T, row-major), task[i] in [0, T) the task of training point i (the
+ * caller checks the range; the kernels clamp it, so a bad index reads no other
+ * memory).  X: n x d WITHOUT the task column.  Added within ABI 12 (plain names, as
+ * bo_fantasy_posterior).  1 <= T <= BO_ICM_MAX_TASKS, 1 <= d <= BO_ICM_MAX_DIM, kind
+ * RBF or Matern-5/2; fp64; no atomics, sums in a fixed order. */
+#define BO_ICM_MAX_TASKS 16
+#define BO_ICM_MAX_DIM 64
+
+/* A[i][k] = outputscale kbar(x_i, x_k) B[task_i][task_k] + (i == k)(noise + noise_vec[i])
+ * for k <= i < n, zeros above the diagonal, the identity on rows / columns >= n:
+ * the np x np input bo_cholesky_inverse / bo_cholesky_inverse_ainv factorise in
+ * place (np = bo_padded_order(n)).  noise_vec (n) is nullable; `noise` carries the
+ * homoskedastic noise and / or a ladder's jitter. */
+typedef struct BoIcmCovarArgs {
+  BO_STRUCT_HEADER;
+  int32_t kind, d, T, _pad;
+  int64_t n, np;
+  const double *X, *lengthscale, *B;
+  const int32_t* task;
+  const double* noise_vec;
+  double outputscale, noise;
+  double* A;
+} BoIcmCovarArgs;
+int bo_icm_covar(const BoIcmCovarArgs* a, void* stream);
+
+/* bo_mll_terms for the ICM covariance: one pass over the lower triangle, one
+ * workgroup per row i, with W_ik = alpha_i alpha_k - A^{-1}_ik, w = 2 off the
+ * diagonal, B_ik = B[task_i][task_k].  partial: n x (d + 5 + T),
+ *   [0..d-1] sum_k w W_ik outputscale B_ik g_ik (x_ij - x_kj)^2   (d ll/d ls_j = 1/2 . / ls_j^3)
+ *   [d] W_ii        [d+1] sum_k w W_ik kbar_ik B_ik        [d+2] log L_ii
+ *   [d+3] beta_i^2  [d+4] alpha_i
+ *   [d+5+b] sum_{k <= i, task_k = b} w W_ik outputscale kbar_ik   (row i's bins of d ll/d B)
+ * The host folds the bins into Gl[task_i][b] and symmetrises: G = (Gl + Gl^T) / 2,
+ * d ll/d B = G / 2.  L, Ainv (lower part read): leading dimension ld. */
+typedef struct BoIcmMllArgs {
+  BO_STRUCT_HEADER;
+  int32_t kind, d, T, _pad;
+  int64_t n, ld;
+  const double *X, *lengthscale, *B;
+  const int32_t* task;
+  double outputscale;
+  const double *L, *Ainv, *alpha, *beta;
+  double* partial;
+} BoIcmMllArgs;
+int bo_icm_mll_terms(const BoIcmMllArgs* a, void* stream);
+
+/* The prediction caches of output task t as a single-task model sees them: with
+ * D = diag(B[t][task_j] / B[t][t]) (1 on the padding),
+ *   U_out = D U,  Linv_out = U_out^T,  alpha_out = D alpha;
+ * together with outputscale' = outputscale B[t][t] and the unchanged beta, constant
+ * and scaled inputs, the posterior kernels compute task t's exact posterior.  D may
+ * hold zeros and negative entries, so there is no factor L for this view.  U, U_out,
+ * Linv_out: np x np (U_out apart from U); B[t][t] > 0 is the caller's to ensure. */
+typedef struct BoIcmTaskViewArgs {
+  BO_STRUCT_HEADER;
+  int32_t T, t;
+  int64_t n, np;
+  const double* B;
+  const int32_t* task;
+  const double *U, *alpha;
+  double *U_out, *Linv_out, *alpha_out;
+} BoIcmTaskViewArgs;
+int bo_icm_task_view(const BoIcmTaskViewArgs* a, void* stream);
+
 /* HOST: sizeof the named record ("BoPostPartialsArgs", ...), -1 if unknown --
  * lets a binding check its declared layout once at load time. */
 int64_t bo_struct_size(const char* name);
