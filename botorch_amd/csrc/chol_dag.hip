@@ -861,6 +861,39 @@ __device__ __forceinline__ void crit_trsm(const Ctx& c, v4d (&t)[4], const doubl
   }
 }
 
+// One step of iterative refinement of the wave's rows of L = A D^T:
+// L += (A - L Lkk^T) D^T, with SL = Lkk, the lower triangular factor D is the
+// explicit inverse of.  A product with an explicit inverse alone leaves a
+// residual of u cond(Lkk) |L| |Lkk^T| componentwise; the refined L has the
+// u |L| |Lkk^T| of a substitution.  Lkk^T is upper
+// triangular like D^T, so both products take crit_trsm's block skipping.
+// S: scratch tile; each wave writes and reads its own 16 rows only.
+__device__ __forceinline__ void crit_refine(const Ctx& c, v4d (&t)[4], const double* SA,
+                                            const double* SD, const double* SL, double* S) {
+  const int col0 = mfma_col(c.lane);
+#pragma unroll
+  for (int C = 0; C < 4; ++C)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) S[(16 * c.wave + mfma_row(c.lane, r)) * LP + 16 * C + col0] = t[C][r];
+  __syncthreads();
+  v4d p[4];
+  crit_trsm(c, p, S, SL);  // L Lkk^T
+  __syncthreads();
+#pragma unroll
+  for (int C = 0; C < 4; ++C)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int e = (16 * c.wave + mfma_row(c.lane, r)) * LP + 16 * C + col0;
+      S[e] = SA[e] - p[C][r];
+    }
+  __syncthreads();
+  crit_trsm(c, p, S, SD);  // (A - L Lkk^T) D^T
+#pragma unroll
+  for (int C = 0; C < 4; ++C)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) t[C][r] += p[C][r];
+}
+
 // The lower blocks (I, J) of A_kk per wave: {(0,0), (3,0), (3,3)}, {(1,0),
 // (1,1), (3,1)}, {(2,0), (2,1), (2,2)}, {(3,2)}.
 __device__ __forceinline__ int syrk_blocks(int wave, int (&I)[3], int (&J)[3]) {
@@ -888,6 +921,7 @@ __device__ __forceinline__ v4d syrk_block(const Ctx& c, v4d blk, const double* S
 
 // ---- the bulk tasks: a chunk of tile rows i in [i0, i1) ----------------------------
 // KIND 0 TRSM    X0 <- A_ik,                   acc  = X0 X1^T  -> A_ik = L_ik, fL[i][k] = 1
+//                (then one step of refinement against L_kk in XL, through the scratch tile XS)
 // KIND 1 COLUPD  X0 <- L_ik (X1 if i == j),    acc  = A_ij - X0 X1^T -> A_ij, fA[i][j] = k + 1
 // KIND 2 XSTEP   X0 <- L_ik,                   acc  = acc_ij + X0 X1 -> Linv_ij, fX[i][j] = k - j + 1
 // The next tile's operands are loaded into registers while this tile's MFMAs
@@ -932,7 +966,8 @@ __device__ __forceinline__ void row_issue(const Ctx& c, int i, int j, int k, dou
 template <int KIND>
 __device__ bool row_loop(const Ctx& c, const Flags& f, int k, int j, int i0, int i1, double* X0,
                          const double* X1, int* s_ok, int* s_rdy, long long* wsum,
-                         long long* ph = nullptr) {
+                         long long* ph = nullptr, const double* XL = nullptr, double* XS = nullptr) {
+  // XL, XS (KIND 0 only): L_kk in LDS and a scratch tile, for the refinement
   long long tA = 0;
   double2 pv[8];
   double pa[16];
@@ -991,8 +1026,25 @@ __device__ bool row_loop(const Ctx& c, const Flags& f, int k, int j, int i0, int
     if (pre) row_issue<KIND>(c, i + 1, j, k, pv, pa);
     long long tB = 0;
     if (ph && c.tid == 0) { tB = wall_clock64(); ph[0] += tB - tA; }
-    if (KIND == 0) acc_mma_nt(c, acc, X0, X1, 1.0);
-    else if (KIND == 1) acc_mma_nt(c, acc, own_x0 ? X0 : X1, X1, -1.0);
+    if (KIND == 0) {
+      acc_mma_nt(c, acc, X0, X1, 1.0);
+      // one step of refinement, as crit_refine: L += (A - L Lkk^T) D^T
+      acc_to_lds(c, acc, XS);
+      Acc res;
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            res.t[a][b][q] = X0[(c.wm + 16 * a + mfma_row(c.lane, q)) * LP + c.wn + 16 * b + mfma_col(c.lane)];
+      __syncthreads();
+      acc_mma_nt(c, res, XS, XL, -1.0);  // A - L Lkk^T
+      __syncthreads();                   // every wave's reads of XS done
+      acc_to_lds(c, res, XS);
+      __syncthreads();
+      acc_mma_nt(c, acc, XS, X1, 1.0);
+    } else if (KIND == 1) acc_mma_nt(c, acc, own_x0 ? X0 : X1, X1, -1.0);
     else acc_mma_nt(c, acc, X0, X1, 1.0);  // X1 holds X_kj transposed
     long long tC = 0;
     if (ph && c.tid == 0) {
@@ -1522,9 +1574,11 @@ __global__ __launch_bounds__(256) void chol_dag_kernel(double* __restrict__ A, d
         }
         if (ok) {
           tile_to_lds(c, c.rI, k - 1, k - 1, X1);
+          tile_to_lds(c, c.rA, k - 1, k - 1, X2);  // L_{k-1,k-1}, for the refinement
           __syncthreads();
           v4d tl[4];
           crit_trsm(c, tl, X0, X1);  // rows 16 w.. of L_{k,k-1} = A_{k,k-1} D_{k-1}^T
+          crit_refine(c, tl, X0, X1, X2, X3);
           // the wave's own rows: X0 <- L (only this wave read them), and to A
 #pragma unroll
           for (int C = 0; C < 4; ++C)
@@ -1565,7 +1619,8 @@ __global__ __launch_bounds__(256) void chol_dag_kernel(double* __restrict__ A, d
     } else if (type == T_TRSM) {
       ok = wait2(c, F(fL, k, k), 1u, F(fL, k, k), 1u, abortw, &s_ok, &wsum);
       if (ok) tile_to_lds(c, c.rI, k, k, X1);  // D_k
-      if (ok) ok = row_loop<0>(c, fl, k, j, i0, i1, X0, X1, &s_ok, s_rdy, &wsum, ph);
+      if (ok) tile_to_lds(c, c.rA, k, k, X2);  // L_kk
+      if (ok) ok = row_loop<0>(c, fl, k, j, i0, i1, X0, X1, &s_ok, s_rdy, &wsum, ph, X2, X3);
     } else if (type == T_COLUPD && nk > 1) {
       ok = wait2(c, F(fL, j, k + nk - 1), 1u, F(fL, j, k + nk - 1), 1u, abortw, &s_ok, &wsum);
       if (ok) {

@@ -134,7 +134,14 @@ int bo_covar_batched(int kind, const double* X1, int64_t s1o, int64_t s1i, int n
 /* In-place blocked Cholesky of the lower-stored SPD matrix A (np x np, upper
  * triangle zero) and its explicit inverse Linv (np x np).  work: np x np
  * scratch.  *info (device int) = 0 or the 1-based order of the first failing
- * leading minor (torch.linalg.cholesky_ex convention). */
+ * leading minor (torch.linalg.cholesky_ex convention; a NaN pivot fails at its
+ * own column).
+ * Contract on the buffers (tests/test_gpu_chol_accuracy.py): the caller gives
+ * A with a zero strict upper triangle and, for an order n < np, the identity
+ * in rows and columns >= n; Linv may hold anything.  With info = 0 the call
+ * has written every entry of Linv and leaves both A and Linv lower triangular
+ * (strict upper triangle exactly zero) with the identity pad in rows and
+ * columns >= n bit for bit, so Linv^T is usable over all np columns. */
 int bo_cholesky_inverse(double* A, double* Linv, double* work, int64_t np, int* info,
                         void* stream);
 /* bo_cholesky_inverse plus A^{-1} = L^{-T} L^{-1} (the lower 64 x 64 tiles,

@@ -19,6 +19,8 @@ def _spd(n, seed, noise=1e-3, ls=0.3):
 
 @pytest.mark.parametrize("n", [128, 200, 640, 1024, 2048, 4096])
 def test_cholesky_inverse_matches_torch(n):
+    """Agreement with f64 LAPACK on a benign matrix, up to n = 4096; the accuracy
+    of the factorisation itself is held in test_gpu_chol_accuracy.py."""
     from botorch_amd import kernels
     torch.set_num_threads(16)
     A = _spd(n, n)
