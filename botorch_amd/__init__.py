@@ -23,7 +23,9 @@ _EXPORTS = {"FullyBayesianAcquisitionFunction": "acquisition",
             "MultiTaskGP": "models", "IndexKernel": "models", "GammaPrior": "models",
             "get_matern_kernel_with_gamma_prior": "models",
             "get_gaussian_likelihood_with_gamma_prior": "models",
-            "icm_mll_terms": "fit", "icm_mll_terms_torch": "fit"}
+            "icm_mll_terms": "fit", "icm_mll_terms_torch": "fit",
+            "MixedSingleTaskGP": "models", "CategoricalKernel": "models",
+            "optimize_acqf_mixed": "optim"}
 __all__ = sorted(_EXPORTS)
 
 

@@ -280,6 +280,33 @@ class IcmTaskViewArgs(_Args):
                        ("Linv_out", _D), ("alpha_out", _D)]
 
 
+MIXED_MAX_DIM, MIXED_MLL_COLS = 8, 40  # BO_MIXED_MAX_DIM, BO_MIXED_MLL_COLS
+_COLS8 = c_int32 * MIXED_MAX_DIM
+_MIXED_HEAD = [("kind", c_int32), ("d", c_int32), ("d_c", c_int32), ("d_k", c_int32),
+               ("cont_cols", _COLS8), ("cat_cols", _COLS8)]
+
+
+class MixedCovarArgs(_Args):
+    _fields_ = _HDR + _MIXED_HEAD + [("n", c_int64), ("np", c_int64), ("X", _D), ("hyper", _D),
+                                     ("noise_vec", _D), ("o_s", c_double), ("o_c", c_double),
+                                     ("o_p", c_double), ("noise", c_double), ("A", _D)]
+
+
+class MixedMllArgs(_Args):
+    _fields_ = _HDR + _MIXED_HEAD + [("n", c_int64), ("ld", c_int64), ("X", _D), ("hyper", _D),
+                                     ("o_s", c_double), ("o_c", c_double), ("o_p", c_double),
+                                     ("L", _D), ("Ainv", _D), ("alpha", _D), ("beta", _D),
+                                     ("partial", _D)]
+
+
+class MixedCrossArgs(_Args):
+    _fields_ = _HDR + _MIXED_HEAD + [("kappa_direct", c_int32), ("_pad", c_int32), ("B", c_int64),
+                                     ("q", c_int64), ("n", c_int64), ("Xq", _D), ("Xt", _D),
+                                     ("hyper", _D), ("o_s", c_double), ("o_c", c_double),
+                                     ("o_p", c_double), ("Kx", _D), ("Kxx", _D), ("dKx", _D),
+                                     ("G", _D), ("dX", _D)]
+
+
 class PathsArgs(_Args):
     _fields_ = _HDR + [("kind", c_int32), ("d", c_int32), ("S", c_int32), ("M", c_int32),
                        ("R", c_int64), ("n", c_int64), ("inner", c_int64), ("X", _D),
@@ -406,7 +433,12 @@ ICM_RECORD_ENTRIES = {"bo_icm_covar": IcmCovarArgs, "bo_icm_mll_terms": IcmMllAr
                       "bo_icm_task_view": IcmTaskViewArgs}
 ICM_ARG_RECORDS = {"BoIcmCovarArgs": IcmCovarArgs, "BoIcmMllArgs": IcmMllArgs,
                    "BoIcmTaskViewArgs": IcmTaskViewArgs}
-for _name, _cls in {**PLAIN_RECORD_ENTRIES, **ICM_RECORD_ENTRIES}.items():
+# the mixed continuous / categorical kernels of mixed.hip, likewise
+MIXED_RECORD_ENTRIES = {"bo_mixed_covar": MixedCovarArgs, "bo_mixed_mll_terms": MixedMllArgs,
+                        "bo_mixed_cross": MixedCrossArgs, "bo_mixed_cross_grad": MixedCrossArgs}
+MIXED_ARG_RECORDS = {"BoMixedCovarArgs": MixedCovarArgs, "BoMixedMllArgs": MixedMllArgs,
+                     "BoMixedCrossArgs": MixedCrossArgs}
+for _name, _cls in {**PLAIN_RECORD_ENTRIES, **ICM_RECORD_ENTRIES, **MIXED_RECORD_ENTRIES}.items():
     _SIGNATURES[_name] = (c_int, [POINTER(_cls), _P])
 _SIGNATURES["bo_post_backward_jobs"] = (c_int, [c_int, POINTER(POINTER(PostBackwardArgs)), _P, _P])
 ARG_RECORDS = {"BoPostPartialsArgs": PostPartialsArgs, "BoQmcFinalizeArgs": QmcFinalizeArgs,
@@ -442,7 +474,8 @@ def lib():
         if handle.bo_version() != ABI_VERSION:
             raise NativeLibraryMissing(
                 f"{LIB_PATH} has ABI {handle.bo_version()}, expected {ABI_VERSION}: rebuild with `make`")
-        for cname, rec in {**ARG_RECORDS, **PLAIN_ARG_RECORDS, **ICM_ARG_RECORDS}.items():  # layouts agree with the C header
+        for cname, rec in {**ARG_RECORDS, **PLAIN_ARG_RECORDS, **ICM_ARG_RECORDS,
+                           **MIXED_ARG_RECORDS}.items():  # layouts agree with the C header
             if handle.bo_struct_size(cname.encode()) != sizeof(rec):
                 raise NativeLibraryMissing(f"{cname}: ctypes layout differs from the library's")
         _lib = handle

@@ -71,6 +71,15 @@ class AcquisitionFunction(nn.Module):
                 "qNoisyExpectedImprovement, qLogNoisyExpectedImprovement, qUpperConfidenceBound, "
                 "ExpectedImprovement, LogExpectedImprovement, UpperConfidenceBound, "
                 "PosteriorMean)")
+        if getattr(model, "_is_mixed", False) and not self._admits_multitask:
+            # the same audit serves MixedSingleTaskGP: it has no prediction_cache, so the
+            # admitted classes (whose routes guard on it) go through model.posterior alone
+            raise UnsupportedError(
+                f"{type(self).__name__}: MixedSingleTaskGP is not on the accelerated path of "
+                "this acquisition function (admitted: qExpectedImprovement, "
+                "qLogExpectedImprovement, qNoisyExpectedImprovement, "
+                "qLogNoisyExpectedImprovement, qUpperConfidenceBound, ExpectedImprovement, "
+                "LogExpectedImprovement, UpperConfidenceBound, PosteriorMean)")
         self.model = model
         self.X_pending = None
 

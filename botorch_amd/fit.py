@@ -179,6 +179,8 @@ class _MultiLayout:
 def _layout(model):
     if getattr(model, "_is_multitask", False):
         return _ICMLayout(model)
+    if getattr(model, "_is_mixed", False):
+        return _MixedLayout(model)
     return _MultiLayout(model) if getattr(model, "_is_multi_output", False) else _Layout(model)
 
 
@@ -520,6 +522,151 @@ def icm_mll_value_and_grad(model, x: np.ndarray, layout: "_ICMLayout"):
         ll += pv
         g[o + 1 + d] += pg[0]
     g[layout.f0:] = gall[3 + d:]
+    return -ll / n, -g / n
+
+
+# ---- MixedSingleTaskGP: the marginal log likelihood of the mixed kernel -----------------------
+def mixed_mll_terms(model, noise, const: float, hyper: np.ndarray, scales: np.ndarray):
+    """Data term ll = log N(y | c, K + noise) of a MixedSingleTaskGP and d ll / d [noise,
+    constant, hyper (l1, lam1, l2, lam2), o_s, o_c, o_p] on the fused route:
+    bo_mixed_covar, the optimistic (jitter-free) factorisation, A^{-1} and one
+    bo_mixed_mll_terms pass enqueued at once; the row terms are summed on the
+    device and one device-to-host transfer brings the sums and the factorisation's
+    status (the ladder, then the sums again, if it failed).  ``noise``: a float or
+    the fixed n-vector (the first gradient entry is then meaningless)."""
+    from . import ops  # noqa: F401  (registers torch.ops.bo)
+    X, y = model.train_inputs[0], model.train_targets
+    n = X.shape[0]
+    dc, dk = len(model.cont_dims), len(model.cat_dims)
+    spec = model.spec(torch.as_tensor(hyper, dtype=torch.float64).to(X.device),
+                      [float(v) for v in scales])
+
+    def _sums(cache, info):
+        Ainv = cache.Ainv if cache.Ainv is not None else kernels.ainv(cache)
+        part = torch.ops.bo.mixed_mll_terms(cache.Xt, spec.hyper, list(spec.cont), list(spec.cat),
+                                            spec.kind, spec.o_s, spec.o_c, spec.o_p, cache.L, Ainv,
+                                            cache.alpha, cache.beta)
+        sums = part.sum(dim=0)
+        if info is not None:
+            sums = torch.cat([sums, info.to(torch.float64)])
+        return sums.cpu().numpy()
+
+    cache, info = kernels.build_mixed_cache(X, y, spec, noise, const, optimistic=True)
+    s = _sums(cache, info)
+    status, s = int(s[-1]), s[:-1]
+    if status < 0:
+        raise RuntimeError("bo_cholesky_inverse: the Cholesky task DAG timed out")
+    if status != 0:  # not p.d. without jitter: the ladder, then the sums again
+        cache, _ = kernels.build_mixed_cache(X, y, spec, noise, const)
+        s = _sums(cache, None)
+    ll = -0.5 * s[37] - s[36] - 0.5 * n * math.log(2 * math.pi)
+    l1, m1, l2, m2 = np.split(np.asarray(hyper, dtype=np.float64), [dc, dc + dk, 2 * dc + dk])
+    g = np.concatenate([[0.5 * s[35], s[38]], 0.5 * s[0:dc] / l1 ** 3,
+                        0.5 * s[8:8 + dk] / (dk * m1 ** 2), 0.5 * s[16:16 + dc] / l2 ** 3,
+                        0.5 * s[24:24 + dk] / (dk * m2 ** 2), 0.5 * s[32:35]])
+    return float(ll), g
+
+
+def mixed_mll_terms_torch(model, noise, const: float, hyper: np.ndarray, scales: np.ndarray):
+    """mixed_mll_terms in plain torch with autograd (the torch route: CPU tensors, any
+    d_c and d_k, categorical columns only; the comparator of tools/bench_mixed.py)."""
+    from .models import _cholesky_ladder, mixed_covar_torch
+    X, y = model.train_inputs[0], model.train_targets
+    n = X.shape[0]
+    dc, dk = len(model.cont_dims), len(model.cat_dims)
+    fixed = torch.is_tensor(noise)
+    theta = torch.as_tensor(np.concatenate([[0.0 if fixed else float(noise), const], hyper, scales]),
+                            dtype=torch.float64).to(X.device).requires_grad_(True)
+    h, sc = theta[2:2 + len(hyper)], theta[2 + len(hyper):]
+    if dc:
+        l1, m1, l2, m2 = h[:dc], h[dc:dc + dk], h[dc + dk:2 * dc + dk], h[2 * dc + dk:]
+        K = mixed_covar_torch(X, X, model.cont_dims, model.cat_dims, model.kind, l1, m1, l2, m2,
+                              sc[0], sc[1], sc[2])
+    else:
+        K = mixed_covar_torch(X, X, [], model.cat_dims, model.kind, None, h, None, None, sc[0],
+                              None, None)
+    A = K + (torch.diag(noise.to(K)) if fixed else theta[0] * torch.eye(n, dtype=K.dtype, device=K.device))
+    L = _cholesky_ladder(A)  # (cholesky_ex is differentiable: the ladder stays in the graph)
+    res = (y - theta[1]).unsqueeze(-1)
+    beta = torch.linalg.solve_triangular(L, res, upper=False)
+    ll = -0.5 * (beta * beta).sum() - torch.log(torch.diagonal(L)).sum() - 0.5 * n * math.log(2 * math.pi)
+    (g,) = torch.autograd.grad(ll, theta)
+    return float(ll.detach()), g.cpu().numpy()
+
+
+class _MixedLayout:
+    """Flat parameter vector <-> hyperparameters of a MixedSingleTaskGP, in the order
+    noise (unless fixed), constant, l1 (d_c), lam1 (d_k), l2 (d_c), lam2 (d_k), o_s,
+    o_c, o_p (categorical columns only: noise, constant, lam1, o_s).  The
+    parameters are the natural values, as in _Layout: lengthscales bounded below by
+    their kernels' ``lengthscale_lower`` (the reference's 1e-4 / 1e-6), the noise by
+    the likelihood's, the outputscales by 0."""
+
+    def __init__(self, model):
+        self.model = model
+        self.fixed = isinstance(model.likelihood, FixedNoiseGaussianLikelihood)
+        self.o = 0 if self.fixed else 1
+        self.mods = model.lengthscale_modules()
+        self.nh = sum(m.ard_num_dims for m in self.mods)
+        self.ns = model.raw_outputscales.numel()
+        self.h0 = self.o + 1
+        self.s0 = self.h0 + self.nh
+        self.size = self.s0 + self.ns
+        lo = ([] if self.fixed else [model.likelihood.noise_lower]) + [-np.inf]
+        for m in self.mods:
+            lo += [m.lengthscale_lower] * m.ard_num_dims
+        lo += [0.0] * self.ns
+        self.bounds = [(None if not np.isfinite(l) else l, None) for l in lo]
+        self.segments = ([] if self.fixed else [("noise", 0, 1)]) + [
+            ("constant", self.o, 1), ("lengthscale", self.h0, self.nh),
+            ("outputscale", self.s0, self.ns)]
+
+    def get(self) -> np.ndarray:
+        m = self.model
+        v = [] if self.fixed else [float(m.likelihood.noise.detach())]
+        v.append(float(m.mean_module.constant.detach()))
+        v += m.hyper_vector().cpu().tolist()
+        v += m.raw_outputscales.detach().cpu().tolist()
+        return np.asarray(v, dtype=np.float64)
+
+    def set(self, x: np.ndarray) -> None:
+        m = self.model
+        if not self.fixed:
+            m.likelihood.noise = torch.tensor([float(x[0])], dtype=torch.float64)
+        m.mean_module.constant = float(x[self.o])
+        at = self.h0
+        for mod in self.mods:
+            mod.lengthscale = torch.as_tensor(x[at:at + mod.ard_num_dims]).reshape(1, -1)
+            at += mod.ard_num_dims
+        with torch.no_grad():
+            m.raw_outputscales.copy_(torch.as_tensor(np.asarray(x[self.s0:]), dtype=torch.float64))
+
+    def value_and_grad(self, x: np.ndarray):
+        return mixed_mll_value_and_grad(self.model, x, self)
+
+
+def mixed_mll_value_and_grad(model, x: np.ndarray, layout: "_MixedLayout"):
+    """Loss = -(log N(y | c, A) + log priors) / n of a MixedSingleTaskGP at the flat
+    vector x and its gradient: the data term from mixed_mll_terms (the fused route)
+    or mixed_mll_terms_torch, the noise prior (and lengthscale priors of a custom
+    continuous kernel) on the host.  Reads x, not the module."""
+    x = np.asarray(x, dtype=np.float64)
+    o, h0, s0 = layout.o, layout.h0, layout.s0
+    n = model.train_inputs[0].shape[0]
+    noise = model.likelihood.noise if layout.fixed else float(x[0])
+    terms = mixed_mll_terms if model.fused() else mixed_mll_terms_torch
+    ll, gall = terms(model, noise, float(x[o]), x[h0:s0], x[s0:])
+    g = np.array(gall[1 - o:], dtype=np.float64)
+    if not layout.fixed:
+        pv, pg = _prior_terms(model.likelihood.noise_prior, np.array([x[0]]))
+        ll += pv
+        g[0] += pg[0]
+    at = h0
+    for mod in layout.mods:
+        pv, pg = _prior_terms(mod.lengthscale_prior, x[at:at + mod.ard_num_dims])
+        ll += pv
+        g[at:at + mod.ard_num_dims] += pg
+        at += mod.ard_num_dims
     return -ll / n, -g / n
 
 

@@ -456,7 +456,7 @@ def icm_covar(X, task, lengthscale, B, kind=_lib.RBF, outputscale=1.0, noise=0.0
 
 def build_icm_cache(X, task, y, lengthscale, B, noise, constant, kind=_lib.RBF, outputscale=1.0,
                     optimistic: bool = False, max_tries=CHOLESKY_MAX_TRIES,
-                    jitter0=CHOLESKY_JITTER_F64):
+                    jitter0=CHOLESKY_JITTER_F64, fill=None):
     """GPCache of the long-format ICM model: L, L^{-1}, beta, alpha of A =
     outputscale kbar * B[task, task] + noise (a float, or an n-vector of observed
     variances), factorised by the existing ladder entry (bo_cholesky_inverse, or
@@ -464,7 +464,10 @@ def build_icm_cache(X, task, y, lengthscale, B, noise, constant, kind=_lib.RBF, 
     attempt only, enqueued without a status read-back, no U -- returns (cache,
     info) as build_gp_cache_optimistic does (the MLL closure).  Otherwise the
     jitter ladder with U = L^{-T}, returns (cache, None).  The cache's ``Xt`` /
-    ``Xt_scaled`` hold the non-task columns."""
+    ``Xt_scaled`` hold the non-task columns.  ``fill(noise, noise_vec, out)``
+    writes another model's padded covariance in place of icm_covar
+    (build_mixed_cache: ``task`` and ``B`` are then unused, ``Xt_scaled`` is None
+    and ``lengthscale`` is stored as given)."""
     dev = _dev(X, y, lengthscale, B)
     X = X.contiguous()
     y = y.contiguous()
@@ -490,7 +493,10 @@ def build_icm_cache(X, task, y, lengthscale, B, noise, constant, kind=_lib.RBF, 
     for attempt in range(1 if optimistic else max_tries + 1):
         if attempt > 0:
             jitter = jitter0 * 10.0 ** (attempt - 1)
-        icm_covar(X, task, ls, B, kind, outputscale, s2 + jitter, nv, out=L)
+        if fill is not None:
+            fill(s2 + jitter, nv, L)
+        else:
+            icm_covar(X, task, ls, B, kind, outputscale, s2 + jitter, nv, out=L)
         if Ainv is not None:
             check(lib().bo_cholesky_inverse_ainv(_p(L), _p(Linv), _p(Ainv), _p(work), np_,
                                                  _p(info), st), "cholesky_inverse_ainv")
@@ -521,8 +527,8 @@ def build_icm_cache(X, task, y, lengthscale, B, noise, constant, kind=_lib.RBF, 
     else:
         U = torch.empty(np_, np_, **f64)
         check(lib().bo_transpose(_p(Linv), _p(U), np_, np_, st), "transpose")
-    Xs = torch.empty(n, DP, **f64)
-    if d <= DP:
+    Xs = torch.empty(n, DP, **f64) if fill is None else None  # (no consumer of it with ``fill``)
+    if d <= DP and fill is None:
         check(lib().bo_scale_inputs(_p(X), n, d, _p(ls), ctypes.c_void_p(0), DP, _p(Xs), st),
               "scale_inputs")
     cache = GPCache(kind, n, d, np_, X, Xs, ls, float(outputscale),
@@ -578,6 +584,122 @@ def icm_task_view(cache: GPCache, task, B, t: int, Btt: float) -> GPCache:
     return GPCache(cache.kind, cache.n, cache.d, cache.np, cache.Xt, cache.Xt_scaled,
                    cache.lengthscale, cache.outputscale * float(Btt), cache.noise, cache.constant,
                    None, Linv, U, cache.beta, alpha, cache.jitter)
+
+
+# ---- mixed continuous / categorical GP (mixed.hip) ---------------------------------------------
+MIXED_MAX_DIM = _lib.MIXED_MAX_DIM  # bo_mixed_*: continuous and categorical columns, each
+
+
+def mixed_fused_ok(d_c: int, d_k: int) -> bool:
+    """The route rule of the mixed kernels: 1 <= d_c <= 8 continuous and 1 <= d_k <= 8
+    categorical columns take mixed.hip, anything else the torch route."""
+    return 1 <= d_c <= MIXED_MAX_DIM and 1 <= d_k <= MIXED_MAX_DIM
+
+
+@dataclass
+class MixedSpec:
+    """What every bo_mixed_* launch needs beside its arrays: the column lists, the
+    kernel kind, ``hyper`` = [l1 (d_c), lam1 (d_k), l2 (d_c), lam2 (d_k)] on the
+    device and the three outputscales (o_s: sum term, o_c: its categorical part,
+    o_p: product term)."""
+    kind: int
+    cont: tuple
+    cat: tuple
+    hyper: torch.Tensor
+    o_s: float
+    o_c: float
+    o_p: float
+
+    def head(self) -> dict:
+        dc, dk = len(self.cont), len(self.cat)
+        return dict(kind=int(self.kind), d=dc + dk, d_c=dc, d_k=dk,
+                    cont_cols=_lib._COLS8(*self.cont), cat_cols=_lib._COLS8(*self.cat),
+                    hyper=self.hyper, o_s=float(self.o_s), o_p=float(self.o_p))
+
+
+def _mixed_check(spec: MixedSpec, *rows) -> None:
+    d = len(spec.cont) + len(spec.cat)
+    if spec.hyper.numel() != 2 * d or not spec.hyper.is_contiguous():
+        raise ValueError("bo_mixed: hyper must hold 2 (d_c + d_k) contiguous values")
+    for X in rows:
+        if X.shape[-1] != d or not X.is_contiguous():
+            raise ValueError(f"bo_mixed: rows must be contiguous with {d} columns")
+
+
+def mixed_covar(X, spec: MixedSpec, noise=0.0, noise_vec=None, out=None):
+    """The mixed training covariance K(Z, Z) + diag(noise + noise_vec) as the padded
+    np x np lower Cholesky input (strict upper zero, identity pad) of
+    bo_cholesky_inverse*.  X: n x d in the model's column layout."""
+    dev = _dev(X, spec.hyper)
+    _mixed_check(spec, X)
+    n = X.shape[0]
+    np_ = padded_order(n)
+    A = out if out is not None else torch.empty(np_, np_, dtype=torch.float64, device=dev)
+    a = _lib.MixedCovarArgs(n=n, np=np_, X=X, noise_vec=noise_vec, o_c=float(spec.o_c),
+                            noise=float(noise), A=A, **spec.head())
+    _KEEPALIVE.append(a)
+    check(lib().bo_mixed_covar(ctypes.byref(a), _stream(dev)), "mixed_covar")
+    return A
+
+
+def build_mixed_cache(X, y, spec: MixedSpec, noise, constant, optimistic: bool = False):
+    """GPCache of the mixed model (build_icm_cache's ladder and status contract with
+    bo_mixed_covar as the covariance).  Only L, Linv, U, beta, alpha, Ainv, Xt, n, np
+    and the constant describe the model: ``lengthscale`` holds spec.hyper (2 d values),
+    ``d`` counts all columns and ``Xt_scaled`` is None, so a single-task consumer of
+    those fields fails instead of reading something else."""
+    return build_icm_cache(X, None, y, spec.hyper, None, noise, constant, kind=spec.kind,
+                           outputscale=spec.o_s, optimistic=optimistic,
+                           fill=lambda s2, nv, L: mixed_covar(X, spec, s2, nv, out=L))
+
+
+def mixed_mll_partials(X, spec: MixedSpec, L, Ainv, alpha, beta):
+    """Row terms of the mixed model's marginal log likelihood (bo_mixed_mll_terms):
+    n x 40, the 35 padded kernel-hyperparameter sums, then W_ii, log L_ii, beta_i^2,
+    alpha_i (include/botorch_amd.h)."""
+    dev = _dev(X, spec.hyper, L, Ainv, alpha, beta)
+    _mixed_check(spec, X)
+    n = X.shape[0]
+    part = torch.empty(n, _lib.MIXED_MLL_COLS, dtype=torch.float64, device=dev)
+    a = _lib.MixedMllArgs(n=n, ld=L.shape[-1], X=X, o_c=float(spec.o_c), L=L, Ainv=Ainv,
+                          alpha=alpha, beta=beta, partial=part, **spec.head())
+    _KEEPALIVE.append(a)
+    check(lib().bo_mixed_mll_terms(ctypes.byref(a), _stream(dev)), "mixed_mll_terms")
+    return part
+
+
+def mixed_cross(Xq, Xt, spec: MixedSpec, kappa_direct: bool = False):
+    """(K*x, K**) of B t-batches (bo_mixed_cross): Xq B x q x d, Xt n x d; returns
+    Bq x n and B x q x q."""
+    dev = _dev(Xq, Xt, spec.hyper)
+    _mixed_check(spec, Xq, Xt)
+    B, q, _ = Xq.shape
+    n = Xt.shape[0]
+    Kx = torch.empty(B * q, n, dtype=torch.float64, device=dev)
+    Kxx = torch.empty(B, q, q, dtype=torch.float64, device=dev)
+    a = _lib.MixedCrossArgs(kappa_direct=int(kappa_direct), B=B, q=q, n=n, Xq=Xq, Xt=Xt,
+                            o_c=float(spec.o_c), Kx=Kx, Kxx=Kxx, **spec.head())
+    _KEEPALIVE.append(a)
+    check(lib().bo_mixed_cross(ctypes.byref(a), _stream(dev)), "mixed_cross")
+    return Kx, Kxx
+
+
+def mixed_cross_grad(Xq, Xt, spec: MixedSpec, dKx, G):
+    """dX (B x q x d, exact zeros in the categorical columns) from dK*x (Bq x n) and
+    the symmetric G (B x q x q) of each t-batch's own block (bo_mixed_cross_grad)."""
+    dev = _dev(Xq, Xt, spec.hyper, dKx, G)
+    _mixed_check(spec, Xq, Xt)
+    B, q, d = Xq.shape
+    n = Xt.shape[0]
+    if tuple(dKx.shape) != (B * q, n) or tuple(G.shape) != (B, q, q) or not (
+            dKx.is_contiguous() and G.is_contiguous()):
+        raise ValueError("mixed_cross_grad: dKx must be contiguous Bq x n and G B x q x q")
+    dX = torch.empty(B, q, d, dtype=torch.float64, device=dev)
+    a = _lib.MixedCrossArgs(B=B, q=q, n=n, Xq=Xq, Xt=Xt, o_c=float(spec.o_c), dKx=dKx, G=G,
+                            dX=dX, **spec.head())
+    _KEEPALIVE.append(a)
+    check(lib().bo_mixed_cross_grad(ctypes.byref(a), _stream(dev)), "mixed_cross_grad")
+    return dX
 
 
 def build_gp_caches(specs, check_nan: bool = True):

@@ -1612,6 +1612,292 @@ class MultiTaskGP(Model):
         raise UnsupportedError("Subsetting outputs is not supported by `MultiTaskGPyTorchModel`.")
 
 
+class CategoricalKernel(_TrackedModule):
+    """models/kernels/categorical.py: exp(-mean_j [c_j != c'_j] / lengthscale_j), the
+    parameter holder (``ard_num_dims`` lengthscales, the natural values, starting at
+    softplus(0) = ln 2, bounded below by the reference's 1e-6)."""
+
+    def __init__(self, ard_num_dims: int, lengthscale_lower: float = 1e-6,
+                 initial: float = math.log(2.0)):
+        super().__init__()
+        self.ard_num_dims = ard_num_dims
+        self.lengthscale_prior = None
+        self.lengthscale_lower = lengthscale_lower
+        self.raw_lengthscale = nn.Parameter(torch.full((1, ard_num_dims), initial, dtype=torch.float64))
+
+    lengthscale = _Kernel.lengthscale
+
+
+def mixed_covar_torch(X1, X2, cont, cat, kind, ls1, lam1, ls2, lam2, o_s, o_c, o_p):
+    """The mixed covariance K(X1, X2) in plain torch (the torch route; autograd
+    carries its gradients): o_s (kbar(l1) + o_c kap(lam1)) + o_p kbar(l2) kap(lam2),
+    or o_s kap(lam1) without continuous columns.  X1: ... x a x d, X2: ... x b x d."""
+    c1, c2 = X1[..., cat], X2[..., cat]
+    ne = (c1.unsqueeze(-2) != c2.unsqueeze(-3)).to(X1.dtype)
+
+    def kap(lam):
+        return torch.exp(-(ne / lam).mean(-1))
+
+    if len(cont) == 0:
+        return o_s * kap(lam1)
+    diff = X1[..., cont].unsqueeze(-2) - X2[..., cont].unsqueeze(-3)
+
+    def kbar(ls):
+        r2 = (diff / ls).pow(2).sum(-1)
+        if kind == _lib.RBF:
+            return torch.exp(-0.5 * r2)
+        s5r = math.sqrt(5.0) * (r2 + 1e-300).sqrt()  # (the offset keeps autograd finite at r = 0)
+        return (1.0 + s5r + (5.0 / 3.0) * r2) * torch.exp(-s5r)
+
+    return o_s * (kbar(ls1) + o_c * kap(lam1)) + o_p * kbar(ls2) * kap(lam2)
+
+
+class MixedSingleTaskGP(Model):
+    """Single-output exact GP over continuous and categorical columns
+    (botorch/models/gp_regression_mixed.py:32-182):
+      K = o_s (k_cont(l1) + o_c k_cat(lam1)) + o_p k_cont(l2) k_cat(lam2),
+    k_cat the CategoricalKernel; with categorical columns only, K = o_s k_cat(lam1).
+    Defaults as the reference's: Matern-5/2 continuous kernels (lengthscale >= 1e-4,
+    no priors), Gamma(0.9, 10) noise prior with noise >= 1e-6 starting at 1e-3, every
+    lengthscale and outputscale starting at softplus(0) = ln 2, no outcome transform
+    (``Standardize(m=1)`` is accepted).  ``cont_kernel_factory(batch_shape,
+    ard_num_dims, active_dims)`` may return this package's RBFKernel or MaternKernel.
+
+    1 <= d_c, d_k <= 8 on a ROCm device take the fused kernels of mixed.hip
+    (kernels.mixed_fused_ok); CPU tensors and every other shape take the torch
+    route (``_route``: None by that rule, "fused" / "torch" forced).  There is no
+    ``prediction_cache``: acquisition functions reach the model through
+    ``posterior`` alone."""
+
+    _is_mixed = True
+
+    def __init__(self, train_X: torch.Tensor, train_Y: torch.Tensor, cat_dims: List[int],
+                 train_Yvar: Optional[torch.Tensor] = None, cont_kernel_factory=None,
+                 likelihood=None, outcome_transform=None, input_transform=None):
+        super().__init__()
+        from .exceptions import InputDataError
+        if len(cat_dims) == 0:
+            raise ValueError("Must specify categorical dimensions for MixedSingleTaskGP")
+        if input_transform is not None:
+            raise UnsupportedError("MixedSingleTaskGP: input transforms (`input_transform`) are "
+                                   "not on the accelerated path")
+        if train_X.dim() != 2 or train_Y.dim() != 2:
+            raise UnsupportedError("MixedSingleTaskGP: batched training data is not on the "
+                                   "accelerated path (train_X n x d, train_Y n x 1)")
+        if train_Y.shape[-1] != 1 or train_Y.shape[0] != train_X.shape[0]:
+            raise UnsupportedError("MixedSingleTaskGP: several outputs (m > 1) are not on the "
+                                   "accelerated path (train_Y n x 1)")
+        if train_Yvar is not None and train_Yvar.shape != train_Y.shape:
+            raise ValueError(f"train_Yvar of shape {tuple(train_Yvar.shape)} does not match "
+                             f"train_Y of shape {tuple(train_Y.shape)}")
+        d = train_X.shape[-1]
+        if any(not (-d <= int(j) < d) for j in cat_dims):
+            raise ValueError(f"cat_dims {list(cat_dims)} out of range for d = {d}")
+        cat = sorted({int(j) % d for j in cat_dims})  # normalize_indices
+        cont = sorted(set(range(d)) - set(cat))
+        train_X = train_X.to(torch.float64).contiguous()
+        train_Y = train_Y.to(torch.float64)
+        if torch.isnan(train_X).any() or torch.isnan(train_Y).any():
+            raise InputDataError("Input data contains NaN values.")
+        if train_Yvar is not None:
+            train_Yvar = train_Yvar.to(torch.float64)
+            if torch.isnan(train_Yvar).any():
+                raise InputDataError("Input data contains NaN values.")
+            if (train_Yvar < 0).any():
+                raise InputDataError("Input data contains negative variances.")
+        if outcome_transform is not None:
+            if not (isinstance(outcome_transform, Standardize) and outcome_transform._m == 1):
+                raise UnsupportedError("MixedSingleTaskGP takes Standardize(m=1) or no outcome "
+                                       "transform here")
+            outcome_transform.train()
+            train_Y_tf, train_Yvar_tf = outcome_transform(train_Y, train_Yvar)
+            self.outcome_transform = outcome_transform
+        else:
+            train_Y_tf, train_Yvar_tf = train_Y, train_Yvar
+        SingleTaskGP._check_scaling(train_X[:, cont], train_Y_tf)
+        self.train_inputs = (train_X,)
+        self.train_targets = train_Y_tf.squeeze(-1).contiguous()
+        self._raw_train_Y = train_Y
+        self.cat_dims, self.cont_dims = cat, cont
+        ln2 = math.log(2.0)
+        if cont_kernel_factory is None:
+            def cont_kernel_factory(batch_shape, ard_num_dims, active_dims):
+                return MaternKernel(ard_num_dims=ard_num_dims, lengthscale_lower=1e-4, initial=ln2)
+        if likelihood is None:
+            likelihood = (GaussianLikelihood(noise_prior=GammaPrior(0.9, 10.0), noise_lower=1e-6,
+                                             initial=1e-3) if train_Yvar_tf is None
+                          else FixedNoiseGaussianLikelihood(train_Yvar_tf.squeeze(-1)))
+        self.likelihood = likelihood
+        self.mean_module = ConstantMean()
+        self.cat_kernel_sum = CategoricalKernel(len(cat))
+        scales = ["sum"]
+        if cont:
+            self.cont_kernel_sum = cont_kernel_factory(torch.Size([]), len(cont), cont)
+            self.cont_kernel_prod = cont_kernel_factory(torch.Size([]), len(cont), cont)
+            self.cat_kernel_prod = CategoricalKernel(len(cat))
+            for k in (self.cont_kernel_sum, self.cont_kernel_prod):
+                if not isinstance(k, (RBFKernel, MaternKernel)):
+                    raise UnsupportedError("MixedSingleTaskGP: cont_kernel_factory must return "
+                                           "this package's RBFKernel or MaternKernel")
+            if self.cont_kernel_sum.kind != self.cont_kernel_prod.kind:
+                raise UnsupportedError("MixedSingleTaskGP: both continuous kernels must be of "
+                                       "one kind")
+            scales += ["cat", "prod"]
+        # o_s, o_c, o_p: the three ScaleKernels' outputscales (natural values)
+        self._scale_names = scales
+        self.raw_outputscales = nn.Parameter(torch.full((len(scales),), ln2, dtype=torch.float64))
+        self.to(train_X.device)
+        self._route = None
+        self._cache = None
+        self._cache_key = None
+
+    # -- hyperparameters ----------------------------------------------------------------
+    @property
+    def kind(self) -> int:
+        return self.cont_kernel_sum.kind if self.cont_dims else _lib.MATERN52
+
+    @property
+    def batch_shape(self) -> torch.Size:
+        return torch.Size([])
+
+    @property
+    def outputscales(self) -> torch.Tensor:
+        return self.raw_outputscales
+
+    def lengthscale_modules(self) -> list:
+        """The lengthscale holders in the flat order l1, lam1, l2, lam2."""
+        if not self.cont_dims:
+            return [self.cat_kernel_sum]
+        return [self.cont_kernel_sum, self.cat_kernel_sum, self.cont_kernel_prod,
+                self.cat_kernel_prod]
+
+    def hyper_vector(self) -> torch.Tensor:
+        """[l1, lam1, l2, lam2] on the model's device (bo_mixed_*'s ``hyper``)."""
+        return torch.cat([m.lengthscale.detach().reshape(-1) for m in self.lengthscale_modules()])
+
+    def fused(self) -> bool:
+        from . import kernels
+        if self._route is not None:
+            return self._route == "fused"
+        return (self.train_inputs[0].is_cuda
+                and kernels.mixed_fused_ok(len(self.cont_dims), len(self.cat_dims)))
+
+    def spec(self, hyper=None, scales=None):
+        """kernels.MixedSpec of the current (or the given host) hyperparameters."""
+        from . import kernels
+        if hyper is None:
+            hyper = self.hyper_vector()
+        if scales is None:
+            scales = self.raw_outputscales.detach().cpu().tolist()
+        return kernels.MixedSpec(int(self.kind), tuple(self.cont_dims), tuple(self.cat_dims),
+                                 hyper.contiguous(), *scales)
+
+    def _covar_torch(self, X1, X2):
+        ls = [m.lengthscale.detach().reshape(-1) for m in self.lengthscale_modules()]
+        sc = self.raw_outputscales.detach()
+        if not self.cont_dims:
+            return mixed_covar_torch(X1, X2, [], self.cat_dims, self.kind, None, ls[0], None, None,
+                                     sc[0], None, None)
+        return mixed_covar_torch(X1, X2, self.cont_dims, self.cat_dims, self.kind, ls[0], ls[1],
+                                 ls[2], ls[3], sc[0], sc[1], sc[2])
+
+    def train(self, mode: bool = True):
+        if mode:
+            self._cache = None
+            self._cache_key = None
+        return super().train(mode)
+
+    _key = MultiTaskGP._key
+
+    def _noise(self):
+        fixed = isinstance(self.likelihood, FixedNoiseGaussianLikelihood)
+        return self.likelihood.noise.detach() if fixed else float(self.likelihood.noise.detach())
+
+    def _caches(self):
+        """The prediction caches, rebuilt on any change of a parameter or training
+        tensor: a kernels.GPCache from bo_mixed_covar and the Cholesky ladder on the
+        fused route, (L, alpha) from torch.linalg on the torch route."""
+        from . import kernels
+        from .settings import propagate_grads
+        if propagate_grads.on() and (self.train_inputs[0].requires_grad or self.train_targets.requires_grad):
+            raise UnsupportedError(
+                "settings.propagate_grads: posterior gradients to the training data are not "
+                "supported (the prediction caches are built without a backward to them)")
+        key = (self._key(), self.fused())
+        if self._cache is None or self._cache_key != key:
+            X, y = self.train_inputs[0], self.train_targets
+            c = float(self.mean_module.constant.detach())
+            if self.fused():
+                spec = self.spec()
+                cache, _ = kernels.build_mixed_cache(X, y, spec, self._noise(), c)
+                self._cache = (spec, cache)
+            else:
+                noise = self._noise()
+                K = self._covar_torch(X, X)
+                K = K + (torch.diag(noise) if torch.is_tensor(noise)
+                         else noise * torch.eye(X.shape[0], dtype=K.dtype, device=K.device))
+                L = _cholesky_ladder(K)
+                alpha = torch.cholesky_solve((y - c).unsqueeze(-1), L).squeeze(-1)
+                self._cache = (L, alpha, c)
+            self._cache_key = key
+        return self._cache
+
+    # -- posterior ---------------------------------------------------------------------------
+    def posterior(self, X: torch.Tensor, output_indices=None, observation_noise=False,
+                  posterior_transform=None):
+        """models/gpytorch.py:127-199 for the mixed kernel, computing in fp64."""
+        from .posteriors import GPyTorchPosterior, MultivariateNormal, _MixedMoments
+        if torch.is_tensor(observation_noise):
+            raise UnsupportedError("MixedSingleTaskGP.posterior: a tensor of observation noise "
+                                   "is not on the accelerated path")
+        d = self.train_inputs[0].shape[-1]
+        if X.shape[-1] != d:
+            raise ValueError(f"MixedSingleTaskGP.posterior: X has {X.shape[-1]} columns, expected {d}")
+        if X.dtype != torch.float64:
+            X = X.to(torch.float64)
+        self.eval()
+        batch, q = X.shape[:-2], X.shape[-2]
+        ymean, ystd = self.outcome_stats()
+        if self.fused():
+            mean, cov = _MixedMoments.apply(X.reshape(-1, q, d).contiguous(), self)
+            mean, cov = mean.reshape(*batch, q), cov.reshape(*batch, q, q)
+        else:
+            L, alpha, c = self._caches()
+            Kx = self._covar_torch(X, self.train_inputs[0])
+            V = torch.linalg.solve_triangular(L, Kx.mT, upper=False)
+            mean = ymean + ystd * (Kx @ alpha + c)
+            cov = (self._covar_torch(X, X) - V.mT @ V) * (ystd * ystd)
+        if observation_noise is True:
+            nz = self.likelihood.noise.detach().mean()
+            cov = cov + torch.diag_embed((nz * (ystd * ystd)).expand(*batch, q))
+        post = GPyTorchPosterior(MultivariateNormal(mean, cov), model=self, X=X)
+        return post if posterior_transform is None else posterior_transform(post)
+
+    # -- what stays off the accelerated path ---------------------------------------------------
+    def condition_on_observations(self, X, Y, **kwargs):
+        raise UnsupportedError("condition_on_observations: MixedSingleTaskGP is not on the "
+                               "accelerated path (conditioning of mixed models)")
+
+    def fantasize(self, X, sampler, observation_noise=None, **kwargs):
+        raise UnsupportedError("fantasize: MixedSingleTaskGP is not on the accelerated path "
+                               "(fantasy models of mixed models)")
+
+
+def _cholesky_ladder(K: torch.Tensor) -> torch.Tensor:
+    """psd_safe_cholesky: the lower factor of K, with the jitter ladder on failure."""
+    from . import kernels
+    from .exceptions import NotPSDError
+    jitter = 0.0
+    for attempt in range(kernels.CHOLESKY_MAX_TRIES + 1):
+        if attempt > 0:
+            jitter = kernels.CHOLESKY_JITTER_F64 * 10.0 ** (attempt - 1)
+        L, info = torch.linalg.cholesky_ex(
+            K + jitter * torch.eye(K.shape[-1], dtype=K.dtype, device=K.device))
+        if int(info) == 0:
+            return L
+    raise NotPSDError(f"Matrix not positive definite after repeatedly adding jitter up to {jitter:.1e}")
+
+
 def __getattr__(name):
     # fit_fully_bayesian_model_nuts lives in fit.py, where the reference has it
     # (fit.py imports this module, so the re-export resolves on first use)

@@ -62,6 +62,11 @@ Ops (reference computation each replaces):
                       d ll / d B (the closure of fit_gpytorch_mll on a MultiTaskGP)
   bo::icm_task_view   the prediction caches of one output task, scaled so that the
                       single-task posterior kernels compute that task's posterior
+  bo::mixed_covar     training covariance of the mixed continuous / categorical GP as the
+                      padded Cholesky input (models/gp_regression_mixed.py:133-173)
+  bo::mixed_mll_terms row terms of its marginal log likelihood: 35 kernel-hyperparameter sums
+  bo::mixed_cross     K*x and the t-batches' K** blocks of MixedSingleTaskGP.posterior
+  bo::mixed_cross_grad  their gradient in the continuous columns of X
 """
 from __future__ import annotations
 
@@ -1142,6 +1147,69 @@ def _(U, alpha, task, B, t):
     return U.new_empty(U.shape), U.new_empty(U.shape), alpha.new_empty(alpha.shape)
 
 
+# ---- bo::mixed_* (mixed continuous / categorical GP: mixed.hip) ----------------------------------
+def _mixed_spec(hyper, cont, cat, kind, o_s, o_c, o_p):
+    return kernels.MixedSpec(int(kind), tuple(cont), tuple(cat), hyper, o_s, o_c, o_p)
+
+
+@torch.library.custom_op("bo::mixed_covar", mutates_args=(), device_types="cuda")
+def mixed_covar(X: Tensor, hyper: Tensor, cont: List[int], cat: List[int], kind: int, o_s: float,
+                o_c: float, o_p: float, noise: float, noise_vec: Optional[Tensor] = None) -> Tensor:
+    """K(Z, Z) + diag(noise + noise_vec) of the mixed kernel as the padded np x np
+    lower Cholesky input (identity pad)."""
+    return kernels.mixed_covar(X, _mixed_spec(hyper, cont, cat, kind, o_s, o_c, o_p), noise,
+                               noise_vec)
+
+
+@mixed_covar.register_fake
+def _(X, hyper, cont, cat, kind, o_s, o_c, o_p, noise, noise_vec=None):
+    np_ = _padded(X.shape[0])
+    return X.new_empty(np_, np_, dtype=F64)
+
+
+@torch.library.custom_op("bo::mixed_mll_terms", mutates_args=(), device_types="cuda")
+def mixed_mll_terms(X: Tensor, hyper: Tensor, cont: List[int], cat: List[int], kind: int,
+                    o_s: float, o_c: float, o_p: float, L: Tensor, Ainv: Tensor, alpha: Tensor,
+                    beta: Tensor) -> Tensor:
+    """Row terms of the mixed model's marginal log likelihood, n x 40."""
+    return kernels.mixed_mll_partials(X, _mixed_spec(hyper, cont, cat, kind, o_s, o_c, o_p), L,
+                                      Ainv, alpha, beta)
+
+
+@mixed_mll_terms.register_fake
+def _(X, hyper, cont, cat, kind, o_s, o_c, o_p, L, Ainv, alpha, beta):
+    return X.new_empty(X.shape[0], _lib.MIXED_MLL_COLS, dtype=F64)
+
+
+@torch.library.custom_op("bo::mixed_cross", mutates_args=(), device_types="cuda")
+def mixed_cross(Xq: Tensor, Xt: Tensor, hyper: Tensor, cont: List[int], cat: List[int], kind: int,
+                o_s: float, o_c: float, o_p: float,
+                kappa_direct: bool = False) -> Tuple[Tensor, Tensor]:
+    """(K*x: Bq x n, K**: B x q x q) of the mixed kernel for Xq B x q x d."""
+    return kernels.mixed_cross(Xq, Xt, _mixed_spec(hyper, cont, cat, kind, o_s, o_c, o_p),
+                               kappa_direct)
+
+
+@mixed_cross.register_fake
+def _(Xq, Xt, hyper, cont, cat, kind, o_s, o_c, o_p, kappa_direct=False):
+    B, q, _ = Xq.shape
+    return Xq.new_empty(B * q, Xt.shape[0], dtype=F64), Xq.new_empty(B, q, q, dtype=F64)
+
+
+@torch.library.custom_op("bo::mixed_cross_grad", mutates_args=(), device_types="cuda")
+def mixed_cross_grad(Xq: Tensor, Xt: Tensor, hyper: Tensor, cont: List[int], cat: List[int],
+                     kind: int, o_s: float, o_c: float, o_p: float, dKx: Tensor,
+                     G: Tensor) -> Tensor:
+    """dX (B x q x d, zeros in the categorical columns) from dK*x and the symmetric G."""
+    return kernels.mixed_cross_grad(Xq, Xt, _mixed_spec(hyper, cont, cat, kind, o_s, o_c, o_p),
+                                    dKx, G)
+
+
+@mixed_cross_grad.register_fake
+def _(Xq, Xt, hyper, cont, cat, kind, o_s, o_c, o_p, dKx, G):
+    return Xq.new_empty(Xq.shape, dtype=F64)
+
+
 OPS: List[str] = ["sobol_normal", "gp_cache", "gp_cache_extend", "chol_jitter", "chol_backward",
                   "post_partials", "qmc_finalize", "gp_posterior", "gp_posterior_backward",
                   "qmc_acq", "qmc_acq_backward", "qehvi", "qehvi_backward", "mll", "kg",
@@ -1149,4 +1217,5 @@ OPS: List[str] = ["sobol_normal", "gp_cache", "gp_cache_extend", "chol_jitter", 
                   "mes_backward", "gibbon", "gibbon_backward", "mv_quantiles", "nipv_gram",
                   "nipv_gram_backward", "bald", "bald_backward", "analytic", "analytic_backward",
                   "saas_potential", "fantasy_posterior", "fantasy_posterior_backward", "icm_covar",
-                  "icm_mll_terms", "icm_task_view"]
+                  "icm_mll_terms", "icm_task_view", "mixed_covar", "mixed_mll_terms", "mixed_cross",
+                  "mixed_cross_grad"]

@@ -1267,3 +1267,60 @@ def optimize_acqf_driver(batch_fn, acq_function, bounds, q, num_restarts, raw_sa
                                    if base_pending is not None else cands)
     acq_function.set_X_pending(base_pending)
     return cands, torch.stack(values)
+
+
+def optimize_acqf_mixed(acq_function, bounds, q, num_restarts, fixed_features_list,
+                        raw_samples=None, options=None, inequality_constraints=None,
+                        equality_constraints=None, nonlinear_inequality_constraints=None,
+                        post_processing_func=None, batch_initial_conditions=None,
+                        ic_generator=None, ic_gen_kwargs=None):
+    """optim/optimize.py:835-987: optimise over a list of fixed-feature maps (the
+    categorical combinations of a mixed search space) and return the best.  q = 1:
+    one optimize_acqf per entry, the entry with the largest value wins.  q > 1:
+    sequentially greedy -- each pick is a q = 1 call with the earlier picks appended
+    to ``X_pending``; the caller's ``X_pending`` is restored and the joint value
+    re-evaluated at the q candidates.  Nonlinear constraints raise UnsupportedError,
+    as in optimize_acqf."""
+    if not fixed_features_list:
+        raise ValueError("fixed_features_list must be non-empty.")
+    _reject_constraints(None, None, nonlinear_inequality_constraints, "optimize_acqf_mixed")
+    from .acquisition import OneShotAcquisitionFunction
+    one_shot = isinstance(acq_function, OneShotAcquisitionFunction)
+    if one_shot and not hasattr(acq_function, "evaluate") and q > 1:
+        raise ValueError("`OneShotAcquisitionFunction`s that do not implement `evaluate` "
+                         "are currently not supported when `q > 1`. This is needed to "
+                         "compute the joint acquisition value.")
+    ic_gen_kwargs = ic_gen_kwargs or {}
+    if q == 1:
+        cands, values = [], []
+        for fixed_features in fixed_features_list:
+            c, v = optimize_acqf(
+                acq_function=acq_function, bounds=bounds, q=1, num_restarts=num_restarts,
+                raw_samples=raw_samples, options=options or {},
+                inequality_constraints=inequality_constraints,
+                equality_constraints=equality_constraints, fixed_features=fixed_features,
+                post_processing_func=post_processing_func,
+                batch_initial_conditions=batch_initial_conditions, ic_generator=ic_generator,
+                return_best_only=True, **ic_gen_kwargs)
+            cands.append(c)
+            values.append(v)
+        values = torch.stack(values)
+        best = int(torch.argmax(values))
+        return cands[best], values[best]
+    base_X_pending = acq_function.X_pending
+    candidates = torch.empty(0, bounds.shape[-1], device=bounds.device, dtype=bounds.dtype)
+    for _ in range(q):
+        c, _ = optimize_acqf_mixed(
+            acq_function, bounds, 1, num_restarts, fixed_features_list, raw_samples=raw_samples,
+            options=options or {}, inequality_constraints=inequality_constraints,
+            equality_constraints=equality_constraints, post_processing_func=post_processing_func,
+            batch_initial_conditions=batch_initial_conditions, ic_generator=ic_generator,
+            ic_gen_kwargs=ic_gen_kwargs)
+        candidates = torch.cat([candidates, c], dim=-2)
+        acq_function.set_X_pending(torch.cat([base_X_pending, candidates], dim=-2)
+                                   if base_X_pending is not None else candidates)
+    acq_function.set_X_pending(base_X_pending)
+    with torch.no_grad():
+        value = (acq_function.evaluate(X=candidates, bounds=bounds) if one_shot
+                 else acq_function(candidates))
+    return candidates, value

@@ -1442,6 +1442,84 @@ typedef struct BoIcmTaskViewArgs {
 } BoIcmTaskViewArgs;
 int bo_icm_task_view(const BoIcmTaskViewArgs* a, void* stream);
 
+/* ---- Mixed continuous / categorical exact GP (botorch/models/gp_regression_mixed.py:
+ * 133-173, models/kernels/categorical.py).  A row z = (x, c) has d = d_c + d_k columns:
+ * cont_cols[0..d_c) name the continuous ones, cat_cols[0..d_k) the categorical ones
+ * (together a partition of 0..d-1; the rows stay in the caller's layout).
+ *   K(z, z') = o_s (kbar(x, x'; l1) + o_c kap(c, c'; lam1)) + o_p kbar(x, x'; l2) kap(c, c'; lam2)
+ *   kap(c, c'; lam) = exp(-(1 / d_k) sum_j [c_j != c'_j] / lam_j)
+ * kbar the unit-outputscale RBF or Matern-5/2 kernel (kind), categories compared by
+ * exact equality of the stored doubles.  hyper: [l1 (d_c), lam1 (d_k), l2 (d_c),
+ * lam2 (d_k)] on the device.  1 <= d_c, d_k <= BO_MIXED_MAX_DIM; fp64; no atomics,
+ * sums in a fixed order.  Added within ABI 12 (plain names, as bo_icm_covar). */
+#define BO_MIXED_MAX_DIM 8
+#define BO_MIXED_MLL_COLS 40
+
+/* A[i][k] = K(z_i, z_k) + (i == k)(noise + noise_vec[i]) for k <= i < n, zeros above
+ * the diagonal, the identity on rows / columns >= n: the np x np input of
+ * bo_cholesky_inverse / bo_cholesky_inverse_ainv (np = bo_padded_order(n)).
+ * noise_vec (n) is nullable. */
+typedef struct BoMixedCovarArgs {
+  BO_STRUCT_HEADER;
+  int32_t kind, d, d_c, d_k;
+  int32_t cont_cols[BO_MIXED_MAX_DIM], cat_cols[BO_MIXED_MAX_DIM];
+  int64_t n, np;
+  const double *X, *hyper, *noise_vec;
+  double o_s, o_c, o_p, noise;
+  double* A;
+} BoMixedCovarArgs;
+int bo_mixed_covar(const BoMixedCovarArgs* a, void* stream);
+
+/* One pass over the lower triangle, one workgroup per row i, W_ik = alpha_i alpha_k -
+ * A^{-1}_ik, w = 2 off the diagonal, Delta = x_i - x_k, ne_j = [c_ij != c_kj], g the
+ * radial factor of dkbar/dl_j = g Delta_j^2 / l_j^3.  partial: n x BO_MIXED_MLL_COLS
+ * (column groups padded to 8, padded slots exactly 0):
+ *   [0..7]   sum_k w W o_s g1 Delta_j^2        d ll/d l1_j   = 1/2 [.] / l1_j^3
+ *   [8..15]  sum_k w W o_s o_c kap1 ne_j       d ll/d lam1_j = 1/2 [.] / (d_k lam1_j^2)
+ *   [16..23] sum_k w W o_p kap2 g2 Delta_j^2   d ll/d l2_j   = 1/2 [.] / l2_j^3
+ *   [24..31] sum_k w W o_p kbar2 kap2 ne_j     d ll/d lam2_j = 1/2 [.] / (d_k lam2_j^2)
+ *   [32] sum_k w W (kbar1 + o_c kap1)  [33] sum_k w W o_s kap1  [34] sum_k w W kbar2 kap2
+ *        (d ll/d o_s, o_c, o_p = 1/2 [.])
+ *   [35] W_ii   [36] log L_ii   [37] beta_i^2   [38] alpha_i   [39] 0
+ * L, Ainv (lower part read): leading dimension ld. */
+typedef struct BoMixedMllArgs {
+  BO_STRUCT_HEADER;
+  int32_t kind, d, d_c, d_k;
+  int32_t cont_cols[BO_MIXED_MAX_DIM], cat_cols[BO_MIXED_MAX_DIM];
+  int64_t n, ld;
+  const double *X, *hyper;
+  double o_s, o_c, o_p;
+  const double *L, *Ainv, *alpha, *beta;
+  double* partial;
+} BoMixedMllArgs;
+int bo_mixed_mll_terms(const BoMixedMllArgs* a, void* stream);
+
+/* Xq: R x d query rows, R = B q (t-batch b owns rows b q .. b q + q - 1); Xt: n x d.
+ * bo_mixed_cross:      Kx[r][k] = K(zq_r, zt_k) (R x n, row-major) and
+ *                      Kxx[b][i][c] = K(zq_(b q + i), zq_(b q + c)) (B x q x q), one launch;
+ *                      kappa_direct != 0 evaluates kap by two exp per pair instead of
+ *                      the 256-entry tables (same values; kept for measurement).
+ * bo_mixed_cross_grad: dX[r] = sum_k dKx[r][k] dK(zq_r, zt_k)/dx_r
+ *                            + sum_c G[b][i][c] dK(zq_r, zq_(b q + c))/dx_r
+ *                      (R x d; G symmetric, B x q x q), dK/dx_j = -(o_s g1 / l1_j^2 +
+ *                      o_p kap2 g2 / l2_j^2) Delta_j; categorical columns are written
+ *                      as exact zeros, coincident points give 0.
+ * Any q >= 1, any B. */
+typedef struct BoMixedCrossArgs {
+  BO_STRUCT_HEADER;
+  int32_t kind, d, d_c, d_k;
+  int32_t cont_cols[BO_MIXED_MAX_DIM], cat_cols[BO_MIXED_MAX_DIM];
+  int32_t kappa_direct, _pad;
+  int64_t B, q, n;
+  const double *Xq, *Xt, *hyper;
+  double o_s, o_c, o_p;
+  double *Kx, *Kxx;       /* bo_mixed_cross: outputs */
+  const double *dKx, *G;  /* bo_mixed_cross_grad: inputs */
+  double* dX;             /* bo_mixed_cross_grad: output */
+} BoMixedCrossArgs;
+int bo_mixed_cross(const BoMixedCrossArgs* a, void* stream);
+int bo_mixed_cross_grad(const BoMixedCrossArgs* a, void* stream);
+
 /* HOST: sizeof the named record ("BoPostPartialsArgs", ...), -1 if unknown --
  * lets a binding check its declared layout once at load time. */
 int64_t bo_struct_size(const char* name);
