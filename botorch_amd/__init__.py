@@ -25,7 +25,13 @@ _EXPORTS = {"FullyBayesianAcquisitionFunction": "acquisition",
             "get_gaussian_likelihood_with_gamma_prior": "models",
             "icm_mll_terms": "fit", "icm_mll_terms_torch": "fit",
             "MixedSingleTaskGP": "models", "CategoricalKernel": "models",
-            "optimize_acqf_mixed": "optim"}
+            "optimize_acqf_mixed": "optim",
+            "SingleTaskMultiFidelityGP": "models", "LinearTruncatedFidelityKernel": "models",
+            "AffineFidelityCostModel": "models", "InverseCostWeightedUtility": "acquisition",
+            "qMultiFidelityKnowledgeGradient": "acquisition",
+            "project_to_target_fidelity": "acquisition",
+            "expand_trace_observations": "acquisition",
+            "AugmentedHartmann": "multi_fidelity"}
 __all__ = sorted(_EXPORTS)
 
 

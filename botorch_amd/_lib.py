@@ -307,6 +307,35 @@ class MixedCrossArgs(_Args):
                                      ("G", _D), ("dX", _D)]
 
 
+LTF_MAX_DIM, LTF_MLL_COLS = 16, 40  # BO_LTF_MAX_DIM, BO_LTF_MLL_COLS
+_COLS16, _COLS2 = c_int32 * LTF_MAX_DIM, c_int32 * 2
+
+
+def _ltf_head(flag):
+    return [("d", c_int32), ("d_x", c_int32), ("n_f", c_int32), (flag, c_int32),
+            ("x_cols", _COLS16), ("f_cols", _COLS2)]
+
+
+class LtfCovarArgs(_Args):
+    _fields_ = _HDR + _ltf_head("_pad") + [("n", c_int64), ("np", c_int64), ("X", _D),
+                                           ("hyper", _D), ("noise_vec", _D), ("power", c_double),
+                                           ("o", c_double), ("noise", c_double), ("A", _D)]
+
+
+class LtfMllArgs(_Args):
+    _fields_ = _HDR + _ltf_head("_pad") + [("n", c_int64), ("ld", c_int64), ("X", _D),
+                                           ("hyper", _D), ("power", c_double), ("o", c_double),
+                                           ("L", _D), ("Ainv", _D), ("alpha", _D), ("beta", _D),
+                                           ("partial", _D)]
+
+
+class LtfCrossArgs(_Args):
+    _fields_ = _HDR + _ltf_head("no_skip") + [("B", c_int64), ("q", c_int64), ("n", c_int64),
+                                              ("Xq", _D), ("Xt", _D), ("hyper", _D),
+                                              ("power", c_double), ("o", c_double), ("Kx", _D),
+                                              ("Kxx", _D), ("dKx", _D), ("G", _D), ("dX", _D)]
+
+
 class PathsArgs(_Args):
     _fields_ = _HDR + [("kind", c_int32), ("d", c_int32), ("S", c_int32), ("M", c_int32),
                        ("R", c_int64), ("n", c_int64), ("inner", c_int64), ("X", _D),
@@ -438,7 +467,13 @@ MIXED_RECORD_ENTRIES = {"bo_mixed_covar": MixedCovarArgs, "bo_mixed_mll_terms": 
                         "bo_mixed_cross": MixedCrossArgs, "bo_mixed_cross_grad": MixedCrossArgs}
 MIXED_ARG_RECORDS = {"BoMixedCovarArgs": MixedCovarArgs, "BoMixedMllArgs": MixedMllArgs,
                      "BoMixedCrossArgs": MixedCrossArgs}
-for _name, _cls in {**PLAIN_RECORD_ENTRIES, **ICM_RECORD_ENTRIES, **MIXED_RECORD_ENTRIES}.items():
+# the linear truncated fidelity kernels of ltf.hip, likewise
+LTF_RECORD_ENTRIES = {"bo_ltf_covar": LtfCovarArgs, "bo_ltf_mll_terms": LtfMllArgs,
+                      "bo_ltf_cross": LtfCrossArgs, "bo_ltf_cross_grad": LtfCrossArgs}
+LTF_ARG_RECORDS = {"BoLtfCovarArgs": LtfCovarArgs, "BoLtfMllArgs": LtfMllArgs,
+                   "BoLtfCrossArgs": LtfCrossArgs}
+for _name, _cls in {**PLAIN_RECORD_ENTRIES, **ICM_RECORD_ENTRIES, **MIXED_RECORD_ENTRIES,
+                    **LTF_RECORD_ENTRIES}.items():
     _SIGNATURES[_name] = (c_int, [POINTER(_cls), _P])
 _SIGNATURES["bo_post_backward_jobs"] = (c_int, [c_int, POINTER(POINTER(PostBackwardArgs)), _P, _P])
 ARG_RECORDS = {"BoPostPartialsArgs": PostPartialsArgs, "BoQmcFinalizeArgs": QmcFinalizeArgs,
@@ -475,7 +510,7 @@ def lib():
             raise NativeLibraryMissing(
                 f"{LIB_PATH} has ABI {handle.bo_version()}, expected {ABI_VERSION}: rebuild with `make`")
         for cname, rec in {**ARG_RECORDS, **PLAIN_ARG_RECORDS, **ICM_ARG_RECORDS,
-                           **MIXED_ARG_RECORDS}.items():  # layouts agree with the C header
+                           **MIXED_ARG_RECORDS, **LTF_ARG_RECORDS}.items():  # layouts agree with the C header
             if handle.bo_struct_size(cname.encode()) != sizeof(rec):
                 raise NativeLibraryMissing(f"{cname}: ctypes layout differs from the library's")
         _lib = handle

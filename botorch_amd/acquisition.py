@@ -61,6 +61,7 @@ class AcquisitionFunction(nn.Module):
     # whether the class's routes have been audited for a MultiTaskGP (its task view
     # carries no Cholesky factor and its caches are those of one output task)
     _admits_multitask = False
+    _admits_ltf = False  # the classes beyond those whose routes go through model.moments
 
     def __init__(self, model):
         super().__init__()
@@ -80,6 +81,15 @@ class AcquisitionFunction(nn.Module):
                 "qLogExpectedImprovement, qNoisyExpectedImprovement, "
                 "qLogNoisyExpectedImprovement, qUpperConfidenceBound, ExpectedImprovement, "
                 "LogExpectedImprovement, UpperConfidenceBound, PosteriorMean)")
+        if getattr(model, "_is_ltf", False) and not (self._admits_multitask or self._admits_ltf):
+            # and SingleTaskMultiFidelityGP, which has no prediction_cache either
+            raise UnsupportedError(
+                f"{type(self).__name__}: SingleTaskMultiFidelityGP is not on the accelerated "
+                "path of this acquisition function (admitted: qExpectedImprovement, "
+                "qLogExpectedImprovement, qNoisyExpectedImprovement, "
+                "qLogNoisyExpectedImprovement, qUpperConfidenceBound, ExpectedImprovement, "
+                "LogExpectedImprovement, UpperConfidenceBound, PosteriorMean, "
+                "qKnowledgeGradient, qMultiFidelityKnowledgeGradient)")
         self.model = model
         self.X_pending = None
 
@@ -941,7 +951,10 @@ class qKnowledgeGradient(MCAcquisitionFunction, OneShotAcquisitionFunction):
     of at most 16 rows (kernels.kg_tile_plan), the fused posterior runs once
     over all tiles and bo::kg reduces them; otherwise the generic posterior
     kernels give the joint moments and the formula runs in torch.  Both are
-    differentiable in all q + N_f points."""
+    differentiable in all q + N_f points.  A SingleTaskMultiFidelityGP takes the
+    torch formula on its own moments (``model.moments``)."""
+
+    _admits_ltf = True
 
     def __init__(self, model, num_fantasies: Optional[int] = 64, sampler=None, objective=None,
                  posterior_transform=None, inner_sampler=None, X_pending=None,
@@ -964,7 +977,8 @@ class qKnowledgeGradient(MCAcquisitionFunction, OneShotAcquisitionFunction):
         if getattr(model, "_is_ensemble", False):
             raise UnsupportedError("qKnowledgeGradient: fully Bayesian (ensemble) models are not "
                                    "on the accelerated path")
-        if model.num_outputs != 1 or not hasattr(model, "prediction_cache"):
+        if model.num_outputs != 1 or not (hasattr(model, "prediction_cache")
+                                          or getattr(model, "_is_ltf", False)):
             raise UnsupportedError("qKnowledgeGradient: multi-output models and ModelListGP are "
                                    "not on the accelerated path (single-output SingleTaskGP only)")
         if posterior_transform is not None:
@@ -989,6 +1003,8 @@ class qKnowledgeGradient(MCAcquisitionFunction, OneShotAcquisitionFunction):
         values: the likelihood's noise (fixed noise: its mean, models/model.py
         fantasize) times ystd^2."""
         ystd = self.model.outcome_stats()[1]
+        if getattr(self.model, "_is_ltf", False):
+            return self.model.fantasy_noise() * ystd * ystd
         return self.model.prediction_cache().noise * ystd * ystd
 
     def _fused(self, Xa: torch.Tensor, Xf: torch.Tensor, Z: torch.Tensor) -> torch.Tensor:
@@ -1008,15 +1024,20 @@ class qKnowledgeGradient(MCAcquisitionFunction, OneShotAcquisitionFunction):
         kernels.raise_not_psd_deferred(info, jit, type(self).__name__)
         return acq
 
-    def _generic(self, Xa: torch.Tensor, Xf: torch.Tensor, Z: torch.Tensor) -> torch.Tensor:
+    def _fantasy_values(self, Xa: torch.Tensor, Xf: torch.Tensor, Z: torch.Tensor) -> torch.Tensor:
+        """v_i (B x N_f) of the formula above from the joint moments, in torch."""
         from .posteriors import _CholJitter, posterior_moments
         B, q_a, _ = Xa.shape
-        mean, cov = posterior_moments(self.model, torch.cat([Xa, Xf], dim=-2))
+        X = torch.cat([Xa, Xf], dim=-2)
+        mean, cov = (self.model.moments(X) if getattr(self.model, "_is_ltf", False)
+                     else posterior_moments(self.model, X))
         eye = torch.eye(q_a, dtype=cov.dtype, device=cov.device)
         L = _CholJitter.apply(cov[:, :q_a, :q_a] + self._noise() * eye)
         Wt = torch.linalg.solve_triangular(L.mT, Z.T.expand(B, q_a, Z.shape[0]), upper=True)
-        values = mean[:, q_a:] + (cov[:, q_a:, :q_a] * Wt.mT).sum(dim=-1)
-        return values.mean(dim=-1)
+        return mean[:, q_a:] + (cov[:, q_a:, :q_a] * Wt.mT).sum(dim=-1)
+
+    def _generic(self, Xa: torch.Tensor, Xf: torch.Tensor, Z: torch.Tensor) -> torch.Tensor:
+        return self._fantasy_values(Xa, Xf, Z).mean(dim=-1)
 
     def forward(self, X: torch.Tensor) -> torch.Tensor:
         X = t_batch_mode(X)
@@ -1033,7 +1054,8 @@ class qKnowledgeGradient(MCAcquisitionFunction, OneShotAcquisitionFunction):
         Xa = X_actual.reshape(-1, q_a, d)
         Xf = X_fantasies.reshape(-1, self.num_fantasies, d)
         Z = self.sampler.base_samples_2d(q_a, X.device)
-        if q_a <= kernels.KG_FUSED_QMAX and d <= kernels.DP and X.is_cuda:
+        if (q_a <= kernels.KG_FUSED_QMAX and d <= kernels.DP and X.is_cuda
+                and not getattr(self.model, "_is_ltf", False)):
             acq = self._fused(Xa, Xf, Z)
         else:
             acq = self._generic(Xa, Xf, Z)
@@ -1052,6 +1074,145 @@ class qKnowledgeGradient(MCAcquisitionFunction, OneShotAcquisitionFunction):
 
     def extract_candidates(self, X_full: torch.Tensor) -> torch.Tensor:
         return X_full[..., : -self.num_fantasies, :]
+
+
+# -- multi-fidelity knowledge gradient ----------------------------------------------------
+def project_to_target_fidelity(X: torch.Tensor, target_fidelities: Optional[dict] = None,
+                               d: Optional[int] = None) -> torch.Tensor:
+    """acquisition/utils.py:352-412: set each fidelity column to its target value (the
+    last column to 1.0 without ``target_fidelities``), inserting the columns when X
+    has d - d_f of them.  Differentiable; the projected columns are constants."""
+    if target_fidelities is None:
+        target_fidelities = {-1: 1.0}
+    if d is None:
+        d = X.shape[-1]
+    tfs = {k if k >= 0 else d + k: v for k, v in target_fidelities.items()}
+    ones = torch.ones(*X.shape[:-1], device=X.device, dtype=X.dtype)
+    if X.shape[-1] == d:
+        return torch.stack([X[..., i] if i not in tfs else tfs[i] * ones for i in range(d)], dim=-1)
+    if X.shape[-1] != d - len(target_fidelities):
+        raise BotorchTensorDimensionError("X must have a last dimension with size `d` or `d-d_f`,"
+                                          f" but got {X.shape[-1]}.")
+    cols, at = [], 0
+    for i in range(d):
+        if i in tfs:
+            cols.append(tfs[i] * ones)
+        else:
+            cols.append(X[..., at])
+            at += 1
+    return torch.stack(cols, dim=-1)
+
+
+def expand_trace_observations(X: torch.Tensor, fidelity_dims: Optional[List[int]] = None,
+                              num_trace_obs: int = 0) -> torch.Tensor:
+    """acquisition/utils.py:415-465: append ``num_trace_obs`` copies of the q-batch whose
+    fidelity columns are scaled by (K - j) / (K + 1), j = 0..K-1 (batch_shape x
+    (q + K q) x d)."""
+    if num_trace_obs == 0:
+        return X
+    if fidelity_dims is None:
+        fidelity_dims = [-1]
+    q = X.size(-2)
+    X_expanded = X.repeat(*([1] * (X.ndim - 2) + [1 + num_trace_obs, 1]))
+    scale_fac = torch.ones_like(X_expanded)
+    s_pad = 1 / (num_trace_obs + 1)
+    sf = torch.linspace(1 - s_pad, s_pad, num_trace_obs, device=X.device, dtype=X.dtype)
+    sf = torch.repeat_interleave(sf, q).unsqueeze(-1).expand(num_trace_obs * q, len(fidelity_dims))
+    scale_fac[..., q:, fidelity_dims] = sf
+    return scale_fac * X_expanded
+
+
+class InverseCostWeightedUtility(nn.Module):
+    """acquisition/cost_aware.py:86-220 for a deterministic cost model and
+    ``use_mean=True``: deltas / cost where deltas > 0, deltas * cost otherwise, cost the
+    model's value clamped below by ``min_cost`` and summed over the q-batch."""
+
+    def __init__(self, cost_model, use_mean: bool = True, cost_objective=None,
+                 min_cost: float = 1e-2):
+        super().__init__()
+        from .models import GenericDeterministicModel
+        if not isinstance(cost_model, GenericDeterministicModel) or cost_model.num_outputs != 1:
+            raise UnsupportedError("InverseCostWeightedUtility: only a single-output "
+                                   "deterministic cost model is on the accelerated path")
+        if not use_mean or cost_objective is not None:
+            raise UnsupportedError("InverseCostWeightedUtility: `use_mean=False` and "
+                                   "`cost_objective` are not on the accelerated path")
+        self.cost_model = cost_model
+        self._use_mean = use_mean
+        self._min_cost = min_cost
+
+    def forward(self, X: torch.Tensor, deltas: torch.Tensor, sampler=None,
+                X_evaluation_mask=None) -> torch.Tensor:
+        cost = self.cost_model(X).squeeze(-1)  # batch_shape x q
+        cost = cost.clamp_min(self._min_cost).sum(dim=-1)
+        return torch.where(deltas > 0, deltas / cost, deltas * cost)
+
+
+class qMultiFidelityKnowledgeGradient(qKnowledgeGradient):
+    """One-shot multi-fidelity knowledge gradient
+    (acquisition/knowledge_gradient.py:308-505) with the posterior mean as inner value:
+    the fantasy observations are taken at ``expand(X_eval)``, the inner solutions are
+    evaluated at ``project(X_fantasies)``, and in the reference's order
+
+        v_i = mu(x'_i) + Sigma(x'_i, X) L^{-T} z_i - current_value
+        acq = mean_i cost_aware_utility(X=X_cand, deltas=v_i)
+
+    (the utility per fantasy, then the mean; X_cand the q candidates of X as given,
+    without ``X_pending`` and without ``expand``, which only the fantasy observations
+    X = expand([X_cand, X_pending]) see).  With identity ``project`` / ``expand``
+    and no utility a SingleTaskGP takes qKnowledgeGradient's fused tiles."""
+
+    def __init__(self, model, num_fantasies: Optional[int] = 64, sampler=None, objective=None,
+                 posterior_transform=None, inner_sampler=None, X_pending=None, current_value=None,
+                 cost_aware_utility=None, project=None, expand=None, valfunc_cls=None,
+                 valfunc_argfac=None):
+        if current_value is None and cost_aware_utility is not None:
+            raise UnsupportedError("Cost-aware KG requires current_value.")
+        if valfunc_cls is not None or valfunc_argfac is not None:
+            raise UnsupportedError("qMultiFidelityKnowledgeGradient: `valfunc_cls` / "
+                                   "`valfunc_argfac` are not on the accelerated path; the "
+                                   "inner value is the posterior mean")
+        super().__init__(model=model, num_fantasies=num_fantasies, sampler=sampler,
+                         objective=objective, posterior_transform=posterior_transform,
+                         inner_sampler=inner_sampler, X_pending=X_pending,
+                         current_value=current_value)
+        self.cost_aware_utility = cost_aware_utility
+        self.project = project
+        self.expand = expand
+
+    @property
+    def cost_sampler(self):
+        return None  # (the cost model is deterministic)
+
+    def forward(self, X: torch.Tensor) -> torch.Tensor:
+        if self.project is None and self.expand is None and self.cost_aware_utility is None:
+            return super().forward(X)
+        X = t_batch_mode(X)
+        if X.dtype != torch.float64:
+            return self.forward(X.to(torch.float64)).to(X.dtype)
+        X_cand, X_fantasies = _split_fantasy_points(X, self.num_fantasies)
+        X_eval = self._concat_pending(X_cand)  # (pending points join after the split)
+        if X_eval.shape[-2] < 1:
+            raise ValueError("qMultiFidelityKnowledgeGradient: X holds no candidate besides the "
+                             f"{self.num_fantasies} fantasy points")
+        batch, d = X.shape[:-2], X.shape[-1]
+        X_actual = X_eval if self.expand is None else self.expand(X_eval)
+        if self.project is not None:
+            X_fantasies = self.project(X_fantasies)
+        Xa = X_actual.reshape(-1, X_actual.shape[-2], d)
+        Xf = X_fantasies.reshape(-1, self.num_fantasies, d)
+        Z = self.sampler.base_samples_2d(Xa.shape[-2], X.device)
+        values = self._fantasy_values(Xa, Xf, Z)  # B x N_f
+        if self._affine is not None:
+            values = self._affine[0] * values + self._affine[1]
+        if self.current_value is not None:
+            cv = torch.as_tensor(self.current_value).to(values)
+            values = values - (cv.reshape(-1, 1) if cv.dim() else cv)
+        if self.cost_aware_utility is not None:
+            # the cost is that of the candidates alone: no pending points, no trace observations
+            values = self.cost_aware_utility(X=X_cand.reshape(-1, X_cand.shape[-2], d),
+                                             deltas=values.mT).mT
+        return values.mean(dim=-1).reshape(batch)
 
 
 # -- joint entropy search (lower bound) -------------------------------------------------

@@ -181,6 +181,8 @@ def _layout(model):
         return _ICMLayout(model)
     if getattr(model, "_is_mixed", False):
         return _MixedLayout(model)
+    if getattr(model, "_is_ltf", False):
+        return _LTFLayout(model)
     return _MultiLayout(model) if getattr(model, "_is_multi_output", False) else _Layout(model)
 
 
@@ -667,6 +669,147 @@ def mixed_mll_value_and_grad(model, x: np.ndarray, layout: "_MixedLayout"):
         ll += pv
         g[at:at + mod.ard_num_dims] += pg
         at += mod.ard_num_dims
+    return -ll / n, -g / n
+
+
+# ---- SingleTaskMultiFidelityGP: the marginal log likelihood of the fidelity kernel ------------
+def ltf_mll_terms(model, noise, const: float, hyper: np.ndarray, o: float):
+    """Data term ll = log N(y | c, K + noise) of a SingleTaskMultiFidelityGP and d ll / d
+    [noise, constant, hyper (l0, l1, power), o] on the fused route: bo_ltf_covar, the
+    optimistic (jitter-free) factorisation, A^{-1} and one bo_ltf_mll_terms pass
+    enqueued at once; the row terms are summed on the device and one device-to-host
+    transfer brings the sums and the factorisation's status (the ladder, then the sums
+    again, if it failed).  ``noise``: a float or the fixed n-vector (the first gradient
+    entry is then meaningless)."""
+    from . import ops  # noqa: F401  (registers torch.ops.bo)
+    X, y = model.train_inputs[0], model.train_targets
+    n = X.shape[0]
+    hyper = np.asarray(hyper, dtype=np.float64)
+    # (l0, l1 go to the device; the power and the outputscale travel in the record)
+    spec = model.spec(torch.as_tensor(hyper[:-1]).to(X.device), float(o), power=float(hyper[-1]))
+    dx = len(spec.xcols)
+
+    def _sums(cache, info):
+        Ainv = cache.Ainv if cache.Ainv is not None else kernels.ainv(cache)
+        part = torch.ops.bo.ltf_mll_terms(cache.Xt, spec.hyper, list(spec.xcols), list(spec.fcols),
+                                          spec.power, spec.o, cache.L, Ainv, cache.alpha, cache.beta)
+        sums = part.sum(dim=0)
+        if info is not None:
+            sums = torch.cat([sums, info.to(torch.float64)])
+        return sums.cpu().numpy()
+
+    cache, info = kernels.build_ltf_cache(X, y, spec, noise, const, optimistic=True)
+    s = _sums(cache, info)
+    status, s = int(s[-1]), s[:-1]
+    if status < 0:
+        raise RuntimeError("bo_cholesky_inverse: the Cholesky task DAG timed out")
+    if status != 0:  # not p.d. without jitter: the ladder, then the sums again
+        cache, _ = kernels.build_ltf_cache(X, y, spec, noise, const)
+        s = _sums(cache, None)
+    ll = -0.5 * s[36] - s[35] - 0.5 * n * math.log(2 * math.pi)
+    l0, l1 = hyper[:dx], hyper[dx:2 * dx]
+    g = np.concatenate([[0.5 * s[34], s[37]], 0.5 * s[0:dx] / l0 ** 3,
+                        0.5 * s[16:16 + dx] / l1 ** 3, 0.5 * s[32:34]])
+    return float(ll), g
+
+
+def ltf_mll_terms_torch(model, noise, const: float, hyper: np.ndarray, o: float):
+    """ltf_mll_terms in plain torch with autograd (the torch route: CPU tensors, any d_x,
+    several data fidelities; the comparator of tools/bench_mf.py)."""
+    from .models import _cholesky_ladder
+    X, y = model.train_inputs[0], model.train_targets
+    n = X.shape[0]
+    fixed = torch.is_tensor(noise)
+    theta = torch.as_tensor(np.concatenate([[0.0 if fixed else float(noise), const], hyper, [o]]),
+                            dtype=torch.float64).to(X.device).requires_grad_(True)
+    K = model.covar_torch(X, X, theta[2:-1], theta[-1])
+    A = K + (torch.diag(noise.to(K)) if fixed else theta[0] * torch.eye(n, dtype=K.dtype, device=K.device))
+    L = _cholesky_ladder(A)  # (cholesky_ex is differentiable: the ladder stays in the graph)
+    beta = torch.linalg.solve_triangular(L, (y - theta[1]).unsqueeze(-1), upper=False)
+    ll = -0.5 * (beta * beta).sum() - torch.log(torch.diagonal(L)).sum() - 0.5 * n * math.log(2 * math.pi)
+    (g,) = torch.autograd.grad(ll, theta)
+    return float(ll.detach()), g.cpu().numpy()
+
+
+LTF_OUTPUTSCALE_LOWER = 1e-6
+
+
+class _LTFLayout:
+    """Flat parameter vector <-> hyperparameters of a SingleTaskMultiFidelityGP, in the
+    order noise (unless fixed), constant, the model's ``hyper_params()`` (l0, l1, power
+    of every fidelity kernel; the RBF, exponential-decay and downsampling parameters
+    with ``linear_truncated=False``), then the outputscale.  The parameters are the
+    natural values, as in _Layout, each bounded below by the bound hyper_params() names,
+    the noise by the likelihood's, the outputscale by LTF_OUTPUTSCALE_LOWER (its Gamma
+    prior's log density is unbounded at 0).  Every hyperparameter is a segment of its
+    own, so a bound given for one never reaches another."""
+
+    def __init__(self, model):
+        self.model = model
+        self.fixed = isinstance(model.likelihood, FixedNoiseGaussianLikelihood)
+        self.o = 0 if self.fixed else 1
+        self.h0 = self.o + 1
+        lo = ([] if self.fixed else [model.likelihood.noise_lower]) + [-np.inf]
+        self.priors = []  # (prior, start, size) over the flat vector
+        self.params = []  # (parameter, start, size)
+        self.segments = ([] if self.fixed else [("noise", 0, 1)]) + [("constant", self.o, 1)]
+        at = self.h0
+        for name, par, prior, lower in model.hyper_params():
+            k = par.numel()
+            lo += [lower] * k
+            self.priors.append((prior, at, k))
+            self.params.append((par, at, k))
+            self.segments.append((name, at, k))
+            at += k
+        self.s0 = at
+        self.nh = self.s0 - self.h0
+        lo.append(LTF_OUTPUTSCALE_LOWER)
+        self.priors.append((model.outputscale_prior, self.s0, 1))
+        self.segments.append(("outputscale", self.s0, 1))
+        self.size = self.s0 + 1
+        self.bounds = [(None if not np.isfinite(l) else l, None) for l in lo]
+
+    def get(self) -> np.ndarray:
+        m = self.model
+        v = [] if self.fixed else [float(m.likelihood.noise.detach())]
+        v.append(float(m.mean_module.constant.detach()))
+        v += m.hyper_vector().cpu().tolist()
+        v.append(float(m.raw_outputscale.detach()))
+        return np.asarray(v, dtype=np.float64)
+
+    def set(self, x: np.ndarray) -> None:
+        m = self.model
+        if not self.fixed:
+            m.likelihood.noise = torch.tensor([float(x[0])], dtype=torch.float64)
+        m.mean_module.constant = float(x[self.o])
+        with torch.no_grad():
+            for par, at, k in self.params:
+                par.copy_(torch.as_tensor(np.asarray(x[at:at + k]), dtype=torch.float64).reshape(par.shape))
+            m.raw_outputscale.fill_(float(x[self.s0]))
+
+    def value_and_grad(self, x: np.ndarray):
+        return ltf_mll_value_and_grad(self.model, x, self)
+
+
+def ltf_mll_value_and_grad(model, x: np.ndarray, layout: "_LTFLayout"):
+    """Loss = -(log N(y | c, A) + log priors) / n of a SingleTaskMultiFidelityGP at the
+    flat vector x and its gradient: the data term from ltf_mll_terms (the fused route)
+    or ltf_mll_terms_torch, the priors on the host.  Reads x, not the module."""
+    x = np.asarray(x, dtype=np.float64)
+    o, h0, s0 = layout.o, layout.h0, layout.s0
+    n = model.train_inputs[0].shape[0]
+    noise = model.likelihood.noise if layout.fixed else float(x[0])
+    terms = ltf_mll_terms if model.fused() else ltf_mll_terms_torch
+    ll, gall = terms(model, noise, float(x[o]), x[h0:s0], float(x[s0]))
+    g = np.array(gall[1 - o:], dtype=np.float64)
+    if not layout.fixed:
+        pv, pg = _prior_terms(model.likelihood.noise_prior, np.array([x[0]]))
+        ll += pv
+        g[0] += pg[0]
+    for prior, at, size in layout.priors:
+        pv, pg = _prior_terms(prior, x[at:at + size])
+        ll += pv
+        g[at:at + size] += pg
     return -ll / n, -g / n
 
 

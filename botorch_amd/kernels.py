@@ -702,6 +702,122 @@ def mixed_cross_grad(Xq, Xt, spec: MixedSpec, dKx, G):
     return dX
 
 
+# ---- multi-fidelity GP, linear truncated fidelity kernel (ltf.hip) ------------------------------
+LTF_MAX_DIM = _lib.LTF_MAX_DIM  # bo_ltf_*: non-fidelity columns
+
+
+def ltf_fused_ok(d_x: int, n_f: int) -> bool:
+    """The route rule of the multi-fidelity kernels: 1 <= d_x <= 16 non-fidelity and
+    one or two fidelity columns take ltf.hip, anything else the torch route."""
+    return 1 <= d_x <= LTF_MAX_DIM and 1 <= n_f <= 2
+
+
+@dataclass
+class LTFSpec:
+    """What every bo_ltf_* launch needs beside its arrays: the column lists, ``hyper``
+    = [l0 (d_x), l1 (d_x)] on the device, the power and the outputscale."""
+    xcols: tuple
+    fcols: tuple
+    hyper: torch.Tensor
+    power: float
+    o: float
+
+    def head(self) -> dict:
+        dx, nf = len(self.xcols), len(self.fcols)
+        if not ltf_fused_ok(dx, nf):
+            raise ValueError(f"bo_ltf: d_x = {dx}, n_f = {nf} (d_x 1..{LTF_MAX_DIM}, n_f 1..2)")
+        return dict(d=dx + nf, d_x=dx, n_f=nf, x_cols=_lib._COLS16(*self.xcols),
+                    f_cols=_lib._COLS2(*self.fcols), hyper=self.hyper, power=float(self.power),
+                    o=float(self.o))
+
+
+def _ltf_check(spec: LTFSpec, *rows) -> None:
+    dx, d = len(spec.xcols), len(spec.xcols) + len(spec.fcols)
+    if spec.hyper.numel() != 2 * dx or not spec.hyper.is_contiguous():
+        raise ValueError("bo_ltf: hyper must hold 2 d_x contiguous values")
+    for X in rows:
+        if X.shape[-1] != d or not X.is_contiguous():
+            raise ValueError(f"bo_ltf: rows must be contiguous with {d} columns")
+
+
+def ltf_covar(X, spec: LTFSpec, noise=0.0, noise_vec=None, out=None):
+    """The multi-fidelity training covariance K(Z, Z) + diag(noise + noise_vec) as the
+    padded np x np lower Cholesky input (strict upper zero, identity pad) of
+    bo_cholesky_inverse*.  X: n x d in the model's column layout."""
+    dev = _dev(X, spec.hyper)
+    head = spec.head()
+    _ltf_check(spec, X)
+    n = X.shape[0]
+    np_ = padded_order(n)
+    A = out if out is not None else torch.empty(np_, np_, dtype=torch.float64, device=dev)
+    a = _lib.LtfCovarArgs(n=n, np=np_, X=X, noise_vec=noise_vec, noise=float(noise), A=A, **head)
+    _KEEPALIVE.append(a)
+    check(lib().bo_ltf_covar(ctypes.byref(a), _stream(dev)), "ltf_covar")
+    return A
+
+
+def build_ltf_cache(X, y, spec: LTFSpec, noise, constant, optimistic: bool = False):
+    """GPCache of the multi-fidelity model (build_icm_cache's ladder and status contract
+    with bo_ltf_covar as the covariance).  As for build_mixed_cache only L, Linv, U,
+    beta, alpha, Ainv, Xt, n, np and the constant describe the model."""
+    return build_icm_cache(X, None, y, spec.hyper, None, noise, constant, kind=_lib.MATERN52,
+                           outputscale=spec.o, optimistic=optimistic,
+                           fill=lambda s2, nv, L: ltf_covar(X, spec, s2, nv, out=L))
+
+
+def ltf_mll_partials(X, spec: LTFSpec, L, Ainv, alpha, beta):
+    """Row terms of the multi-fidelity model's marginal log likelihood
+    (bo_ltf_mll_terms): n x 40, the 34 padded kernel-hyperparameter sums, then W_ii,
+    log L_ii, beta_i^2, alpha_i (include/botorch_amd.h)."""
+    dev = _dev(X, spec.hyper, L, Ainv, alpha, beta)
+    head = spec.head()
+    _ltf_check(spec, X)
+    n = X.shape[0]
+    part = torch.empty(n, _lib.LTF_MLL_COLS, dtype=torch.float64, device=dev)
+    a = _lib.LtfMllArgs(n=n, ld=L.shape[-1], X=X, L=L, Ainv=Ainv, alpha=alpha, beta=beta,
+                        partial=part, **head)
+    _KEEPALIVE.append(a)
+    check(lib().bo_ltf_mll_terms(ctypes.byref(a), _stream(dev)), "ltf_mll_terms")
+    return part
+
+
+def ltf_cross(Xq, Xt, spec: LTFSpec, skip_target: bool = True):
+    """(K*x, K**) of B t-batches (bo_ltf_cross): Xq B x q x d, Xt n x d; returns Bq x n
+    and B x q x q.  ``skip_target=False`` sends query rows at target fidelity down
+    the general path (the same values)."""
+    dev = _dev(Xq, Xt, spec.hyper)
+    head = spec.head()
+    _ltf_check(spec, Xq, Xt)
+    B, q, _ = Xq.shape
+    n = Xt.shape[0]
+    Kx = torch.empty(B * q, n, dtype=torch.float64, device=dev)
+    Kxx = torch.empty(B, q, q, dtype=torch.float64, device=dev)
+    a = _lib.LtfCrossArgs(no_skip=int(not skip_target), B=B, q=q, n=n, Xq=Xq, Xt=Xt, Kx=Kx,
+                          Kxx=Kxx, **head)
+    _KEEPALIVE.append(a)
+    check(lib().bo_ltf_cross(ctypes.byref(a), _stream(dev)), "ltf_cross")
+    return Kx, Kxx
+
+
+def ltf_cross_grad(Xq, Xt, spec: LTFSpec, dKx, G, skip_target: bool = True):
+    """dX (B x q x d, fidelity columns included) from dK*x (Bq x n) and the symmetric G
+    (B x q x q) of each t-batch's own block (bo_ltf_cross_grad)."""
+    dev = _dev(Xq, Xt, spec.hyper, dKx, G)
+    head = spec.head()
+    _ltf_check(spec, Xq, Xt)
+    B, q, d = Xq.shape
+    n = Xt.shape[0]
+    if tuple(dKx.shape) != (B * q, n) or tuple(G.shape) != (B, q, q) or not (
+            dKx.is_contiguous() and G.is_contiguous()):
+        raise ValueError("ltf_cross_grad: dKx must be contiguous Bq x n and G B x q x q")
+    dX = torch.empty(B, q, d, dtype=torch.float64, device=dev)
+    a = _lib.LtfCrossArgs(no_skip=int(not skip_target), B=B, q=q, n=n, Xq=Xq, Xt=Xt, dKx=dKx, G=G,
+                          dX=dX, **head)
+    _KEEPALIVE.append(a)
+    check(lib().bo_ltf_cross_grad(ctypes.byref(a), _stream(dev)), "ltf_cross_grad")
+    return dX
+
+
 def build_gp_caches(specs, check_nan: bool = True):
     """GPCaches of several exact GPs whose training sets pad to one order (the
     outputs of a batched multi-output SingleTaskGP, a ModelListGP's members):

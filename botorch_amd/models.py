@@ -1095,6 +1095,25 @@ class GenericDeterministicModel(Model):
         return DeterministicPosterior(values)
 
 
+class AffineFidelityCostModel(GenericDeterministicModel):
+    """models/cost.py:24-88: the deterministic cost fixed_cost + sum_j weights[j]
+    X[..., fidelity_dims[j]] of each element of a q-batch (batch_shape x q x 1).
+    Without ``fidelity_weights`` the last column is the fidelity, with weight 1."""
+
+    def __init__(self, fidelity_weights: Optional[dict] = None, fixed_cost: float = 0.01):
+        if fidelity_weights is None:
+            fidelity_weights = {-1: 1.0}
+        super().__init__(None, num_outputs=1)
+        self.fidelity_dims = sorted(fidelity_weights)
+        self.fixed_cost = fixed_cost
+        self.register_buffer("weights", torch.tensor(
+            [float(fidelity_weights[i]) for i in self.fidelity_dims], dtype=torch.float64))
+
+    def forward(self, X: torch.Tensor) -> torch.Tensor:
+        lin_cost = (X[..., self.fidelity_dims] * self.weights.to(X)).sum(-1)
+        return self.fixed_cost + lin_cost.unsqueeze(-1)
+
+
 def sample_saas_prior(d: int, num_samples: int, seed: int = 0, dtype=torch.float64):
     """Hyperparameter sets from the SAAS prior (models/fully_bayesian.py:168-247):
     outputscale ~ Gamma(2, 0.15), mean ~ N(0, 1), noise = 1e-4 + Gamma(0.9, 10),
@@ -1881,6 +1900,419 @@ class MixedSingleTaskGP(Model):
     def fantasize(self, X, sampler, observation_noise=None, **kwargs):
         raise UnsupportedError("fantasize: MixedSingleTaskGP is not on the accelerated path "
                                "(fantasy models of mixed models)")
+
+
+LTF_POWER_LOWER = 1e-4  # floor of the fidelity kernel's power in the fit (the reference: Positive)
+
+
+class LinearTruncatedFidelityKernel(_TrackedModule):
+    """models/kernels/linear_truncated_fidelity.py: k0(x, x') + c(s, s'; power) k1(x, x')
+    over the non-fidelity columns x and one or two fidelity columns s, the parameter
+    holder: two Matern-5/2 ARD kernels (Gamma(3, 6) and Gamma(6, 2) lengthscale priors,
+    the values in the code) and the power, all starting at softplus(0) = ln 2."""
+
+    def __init__(self, fidelity_dims: List[int], dimension: int, nu: float = 2.5,
+                 power_prior=None, lengthscale_prior_unbiased=None, lengthscale_prior_biased=None):
+        super().__init__()
+        n_f = len(fidelity_dims)
+        if len(set(fidelity_dims)) != n_f:
+            raise ValueError("fidelity_dims must not have repeated elements")
+        if n_f not in {1, 2}:
+            raise UnsupportedError("LinearTruncatedFidelityKernel accepts either one or two"
+                                   "fidelity parameters.")
+        if nu not in {0.5, 1.5, 2.5}:
+            raise ValueError("nu must be one of 0.5, 1.5, or 2.5")
+        if nu != 2.5:
+            raise UnsupportedError("LinearTruncatedFidelityKernel: only nu = 2.5 is on the "
+                                   "accelerated path")
+        if dimension - n_f < 1:
+            raise RuntimeError("Input to LinearTruncatedFidelityKernel must have at least one "
+                               "non-fidelity dimension.")
+        self.fidelity_dims = [int(j) for j in fidelity_dims]
+        ln2 = math.log(2.0)
+        self.covar_module_unbiased = MaternKernel(
+            ard_num_dims=dimension - n_f, initial=ln2,
+            lengthscale_prior=lengthscale_prior_unbiased or GammaPrior(3.0, 6.0))
+        self.covar_module_biased = MaternKernel(
+            ard_num_dims=dimension - n_f, initial=ln2,
+            lengthscale_prior=lengthscale_prior_biased or GammaPrior(6.0, 2.0))
+        self.power_prior = power_prior
+        self.power_lower = LTF_POWER_LOWER
+        self.raw_power = nn.Parameter(torch.full((1,), ln2, dtype=torch.float64))
+
+    @property
+    def power(self) -> torch.Tensor:
+        return self.raw_power
+
+    @power.setter
+    def power(self, v):
+        with torch.no_grad():
+            self.raw_power.fill_(float(v))
+
+
+class _FidelityFactor(_TrackedModule):
+    """Parameter holder of one single-column fidelity kernel of the reference's
+    ``linear_truncated=False`` product: the natural values of ``NAMES``, each starting at
+    softplus(0) = ln 2 with a Gamma(3, 6) prior."""
+
+    NAMES = ()
+
+    def __init__(self, column: int):
+        super().__init__()
+        self.column = int(column)
+        for n in self.NAMES:
+            setattr(self, "raw_" + n, nn.Parameter(torch.full((1,), math.log(2.0), dtype=torch.float64)))
+            setattr(self, n + "_prior", GammaPrior(3.0, 6.0))
+
+
+class ExponentialDecayKernel(_FidelityFactor):
+    """models/kernels/exponential_decay.py: offset + ((s + s') / lengthscale + 1)^(-power)
+    over the iteration fidelity column."""
+
+    NAMES = ("lengthscale", "power", "offset")
+
+    def covar(self, X1, X2, lengthscale, power, offset):
+        dist = (X1[..., self.column].unsqueeze(-1) + X2[..., self.column].unsqueeze(-2)).abs() / lengthscale
+        return offset + (dist + 1.0).pow(-power)
+
+
+class DownsamplingKernel(_FidelityFactor):
+    """models/kernels/downsampling.py: offset + (1 - s)^(1 + power) (1 - s')^(1 + power) over
+    one data fidelity column."""
+
+    NAMES = ("power", "offset")
+
+    def covar(self, X1, X2, power, offset):
+        return offset + ((1 - X1[..., self.column]).pow(1 + power).unsqueeze(-1)
+                         * (1 - X2[..., self.column]).pow(1 + power).unsqueeze(-2))
+
+
+def ltf_covar_torch(X1, X2, xcols, fcols, l0, l1, power):
+    """One linear truncated fidelity kernel k0 + c k1 (unit outputscale) in plain torch;
+    autograd carries its gradients, the clamp's included.  X1: ... x a x d, X2: ... x b x d."""
+    diff = X1[..., xcols].unsqueeze(-2) - X2[..., xcols].unsqueeze(-3)
+
+    def matern(ls):
+        r2 = (diff / ls).pow(2).sum(-1)
+        s5r = math.sqrt(5.0) * (r2 + 1e-300).sqrt()  # (the offset keeps autograd finite at r = 0)
+        return (1.0 + s5r + (5.0 / 3.0) * r2) * torch.exp(-s5r)
+
+    s1 = [X1[..., j].clamp(0, 1).unsqueeze(-1) for j in fcols]
+    s2 = [X2[..., j].clamp(0, 1).unsqueeze(-2) for j in fcols]
+    w = [(1 - a) * (1 - b) for a, b in zip(s1, s2)]
+    c = w[0] * torch.exp(power * torch.log1p(s1[0] * s2[0]))
+    if len(fcols) == 2:
+        c = c + w[1] * torch.exp(power * torch.log1p(s1[1] * s2[1]))
+        c = c + w[1] * w[0] * torch.exp(power * torch.log1p(s1[0] * s2[0] + s1[1] * s2[1]))
+    return matern(l0) + c * matern(l1)
+
+
+class SingleTaskMultiFidelityGP(Model):
+    """Single-output exact GP over design columns and fidelity columns
+    (botorch/models/gp_regression_fidelity.py:51-180, 218-344) with the linear
+    truncated fidelity kernel: K = o prod_k [k0(l0_k) + c(s; p_k) k1(l1_k)], one factor
+    per data fidelity (each with the iteration fidelity, if any, as its first
+    fidelity column).  Priors as in the reference's code: l0 Gamma(3, 6), l1
+    Gamma(6, 2), power Gamma(3, 3), outputscale Gamma(2, 0.15); likelihood, mean and
+    the default ``Standardize(m=1)`` as SingleTaskGP's.  The parameters are the natural
+    values; the fit holds the lengthscales above this package's lower bound, the
+    power above LTF_POWER_LOWER and the outputscale above 1e-6.
+
+    One factor with 1 <= d_x <= 16 non-fidelity columns on a ROCm device takes the
+    fused kernels of ltf.hip (kernels.ltf_fused_ok); CPU tensors, d_x > 16 and
+    several data fidelities take the torch route (``_route``: None by that rule,
+    "fused" / "torch" forced), and so does ``linear_truncated=False`` (the reference's
+    product of an RBF, an exponential-decay and downsampling kernels).  There is
+    no ``prediction_cache``: acquisition functions reach the model through
+    ``posterior`` alone."""
+
+    _is_ltf = True
+
+    def __init__(self, train_X: torch.Tensor, train_Y: torch.Tensor,
+                 train_Yvar: Optional[torch.Tensor] = None,
+                 iteration_fidelity: Optional[int] = None, data_fidelities=None,
+                 data_fidelity: Optional[int] = None, linear_truncated: bool = True,
+                 nu: float = 2.5, likelihood=None, outcome_transform="DEFAULT",
+                 input_transform=None):
+        super().__init__()
+        from .exceptions import InputDataError
+        if data_fidelity is not None:
+            warnings.warn("The `data_fidelity` argument is deprecated and will be removed in "
+                          "a future release. Please use `data_fidelities` instead.",
+                          DeprecationWarning)
+            if data_fidelities is not None:
+                raise ValueError("Cannot specify both `data_fidelity` and `data_fidelities`.")
+            data_fidelities = [data_fidelity]
+        if iteration_fidelity is None and (data_fidelities is None or len(data_fidelities) == 0):
+            raise UnsupportedError(f"{self.__class__.__name__} requires at least one fidelity "
+                                   "parameter.")
+        name = type(self).__name__
+        if input_transform is not None:
+            raise UnsupportedError(f"{name}: input transforms (`input_transform`) are not on "
+                                   "the accelerated path")
+        if nu != 2.5:
+            raise UnsupportedError(f"{name}: only `nu` = 2.5 is on the accelerated path")
+        if train_X.dim() != 2 or train_Y.dim() != 2:
+            raise UnsupportedError(f"{name}: batched training data is not on the accelerated "
+                                   "path (train_X n x d, train_Y n x 1)")
+        if train_Y.shape[-1] != 1 or train_Y.shape[0] != train_X.shape[0]:
+            raise UnsupportedError(f"{name}: several outputs (m > 1) are not on the accelerated "
+                                   "path (train_Y n x 1)")
+        if train_Yvar is not None and train_Yvar.shape != train_Y.shape:
+            raise ValueError(f"train_Yvar of shape {tuple(train_Yvar.shape)} does not match "
+                             f"train_Y of shape {tuple(train_Y.shape)}")
+        d = train_X.shape[-1]
+        cols = ([iteration_fidelity] if iteration_fidelity is not None else []) + list(data_fidelities or [])
+        if any(not (-d <= int(j) < d) for j in cols):
+            raise ValueError(f"fidelity columns {cols} out of range for d = {d}")
+        if iteration_fidelity is not None:
+            iteration_fidelity = int(iteration_fidelity) % d
+        data_fidelities = [int(j) % d for j in (data_fidelities or [])]
+        lead = [iteration_fidelity] if iteration_fidelity is not None else []
+        groups = [lead + [j] for j in data_fidelities] or [lead]
+        self._init_args = {"iteration_fidelity": iteration_fidelity,
+                           "data_fidelities": data_fidelities, "linear_truncated": linear_truncated,
+                           "nu": nu}
+        train_X = train_X.to(torch.float64).contiguous()
+        train_Y = train_Y.to(torch.float64)
+        if torch.isnan(train_X).any() or torch.isnan(train_Y).any():
+            raise InputDataError("Input data contains NaN values.")
+        if train_Yvar is not None:
+            train_Yvar = train_Yvar.to(torch.float64)
+            if torch.isnan(train_Yvar).any():
+                raise InputDataError("Input data contains NaN values.")
+            if (train_Yvar < 0).any():
+                raise InputDataError("Input data contains negative variances.")
+        if outcome_transform == "DEFAULT":
+            outcome_transform = Standardize(m=1)
+        if outcome_transform is not None:
+            if not (isinstance(outcome_transform, Standardize) and outcome_transform._m == 1):
+                raise UnsupportedError(f"{name} takes Standardize(m=1) or no outcome transform here")
+            outcome_transform.train()
+            train_Y_tf, train_Yvar_tf = outcome_transform(train_Y, train_Yvar)
+            self.outcome_transform = outcome_transform
+        else:
+            train_Y_tf, train_Yvar_tf = train_Y, train_Yvar
+        SingleTaskGP._check_scaling(train_X, train_Y_tf)
+        self.train_inputs = (train_X,)
+        self.train_targets = train_Y_tf.squeeze(-1).contiguous()
+        self._raw_train_Y = train_Y
+        if likelihood is None:
+            likelihood = (get_gaussian_likelihood_with_lognormal_prior() if train_Yvar_tf is None
+                          else FixedNoiseGaussianLikelihood(train_Yvar_tf.squeeze(-1)))
+        self.likelihood = likelihood
+        self.mean_module = ConstantMean()
+        if linear_truncated:
+            self.fidelity_kernels = nn.ModuleList(
+                [LinearTruncatedFidelityKernel(g, d, nu=nu, power_prior=GammaPrior(3.0, 3.0))
+                 for g in groups])
+        else:  # RBF over the other columns x exponential decay x downsampling (torch route only)
+            self.fidelity_kernels = nn.ModuleList()
+            active = [j for j in range(d) if j not in lead + data_fidelities]
+            if not active:
+                raise UnsupportedError(f"{name}: at least one non-fidelity column is required")
+            self.design_kernel = RBFKernel(ard_num_dims=len(active), initial=math.log(2.0),
+                                           lengthscale_prior=GammaPrior(3.0, 6.0))
+            self.design_dims = active
+            self.fidelity_factors = nn.ModuleList(
+                [ExponentialDecayKernel(j) for j in lead] + [DownsamplingKernel(j) for j in data_fidelities])
+        self.outputscale_prior = GammaPrior(2.0, 0.15)
+        self.raw_outputscale = nn.Parameter(torch.tensor(math.log(2.0), dtype=torch.float64))
+        self.to(train_X.device)
+        self._route = None
+        self._cache = None
+        self._cache_key = None
+
+    # -- hyperparameters ----------------------------------------------------------------
+    @property
+    def batch_shape(self) -> torch.Size:
+        return torch.Size([])
+
+    @property
+    def outputscale(self) -> torch.Tensor:
+        return self.raw_outputscale
+
+    @staticmethod
+    def _xcols(kern, d: int) -> list:
+        return [j for j in range(d) if j not in kern.fidelity_dims]
+
+    def hyper_params(self) -> list:
+        """The kernel hyperparameters in the fit's flat order, as (name, parameter, prior,
+        lower bound): l0, l1, power of every linear truncated kernel -- or, with
+        ``linear_truncated=False``, the RBF lengthscales, then lengthscale, power, offset
+        of the exponential-decay kernel and power, offset of every downsampling kernel."""
+        out = []
+        for i, k in enumerate(self.fidelity_kernels):
+            for nm, mod in (("unbiased", k.covar_module_unbiased), ("biased", k.covar_module_biased)):
+                out.append((f"kernels.{i}.lengthscale_{nm}", mod.raw_lengthscale,
+                            mod.lengthscale_prior, mod.lengthscale_lower))
+            out.append((f"kernels.{i}.power", k.raw_power, k.power_prior, k.power_lower))
+        if not self._init_args["linear_truncated"]:
+            m = self.design_kernel
+            out.append(("kernels.0.lengthscale", m.raw_lengthscale, m.lengthscale_prior,
+                        m.lengthscale_lower))
+            lows = {"lengthscale": LENGTHSCALE_LOWER, "power": LTF_POWER_LOWER, "offset": 1e-6}
+            for i, f in enumerate(self.fidelity_factors):
+                out += [(f"kernels.{i + 1}.{n}", getattr(f, "raw_" + n), getattr(f, n + "_prior"),
+                         lows[n]) for n in f.NAMES]
+        return out
+
+    def hyper_vector(self) -> torch.Tensor:
+        """The values of hyper_params(), in order, on the model's device."""
+        return torch.cat([p.detach().reshape(-1) for _, p, _, _ in self.hyper_params()])
+
+    def fused(self) -> bool:
+        from . import kernels
+        if self._route is not None:
+            return self._route == "fused"
+        if len(self.fidelity_kernels) != 1:
+            return False
+        k = self.fidelity_kernels[0]
+        d = self.train_inputs[0].shape[-1]
+        return (self.train_inputs[0].is_cuda
+                and kernels.ltf_fused_ok(d - len(k.fidelity_dims), len(k.fidelity_dims)))
+
+    def spec(self, hyper=None, o=None, power=None):
+        """kernels.LTFSpec of the current (or the given) hyperparameters: ``hyper`` =
+        [l0, l1] of the one factor on the device (with the power appended unless
+        ``power`` gives it as a host float, which saves the read-back)."""
+        from . import kernels
+        if len(self.fidelity_kernels) != 1:
+            raise UnsupportedError(f"{type(self).__name__}: several data fidelities (a product of "
+                                   "fidelity kernels) and `linear_truncated=False` are not on "
+                                   "the fused route")
+        k = self.fidelity_kernels[0]
+        if hyper is None:
+            hyper = self.hyper_vector()
+        if o is None:
+            o = float(self.raw_outputscale.detach())
+        return kernels.LTFSpec(tuple(self._xcols(k, self.train_inputs[0].shape[-1])),
+                               tuple(k.fidelity_dims),
+                               (hyper[:-1] if power is None else hyper).contiguous(),
+                               float(hyper[-1] if power is None else power), float(o))
+
+    def covar_torch(self, X1, X2, hyper=None, o=None):
+        """K(X1, X2) in plain torch from the flat ``hyper`` (hyper_vector's order) and o."""
+        hyper = self.hyper_vector() if hyper is None else hyper
+        o = self.raw_outputscale.detach() if o is None else o
+        d, at, K = self.train_inputs[0].shape[-1], 0, None
+        for k in self.fidelity_kernels:
+            xc = self._xcols(k, d)
+            dx = len(xc)
+            Kk = ltf_covar_torch(X1, X2, xc, k.fidelity_dims, hyper[at:at + dx],
+                                 hyper[at + dx:at + 2 * dx], hyper[at + 2 * dx])
+            K = Kk if K is None else K * Kk
+            at += 2 * dx + 1
+        if K is None:  # linear_truncated=False
+            dx = len(self.design_dims)
+            diff = X1[..., self.design_dims].unsqueeze(-2) - X2[..., self.design_dims].unsqueeze(-3)
+            K = torch.exp(-0.5 * (diff / hyper[:dx]).pow(2).sum(-1))
+            at = dx
+            for f in self.fidelity_factors:
+                K = K * f.covar(X1, X2, *hyper[at:at + len(f.NAMES)])
+                at += len(f.NAMES)
+        return o * K
+
+    def train(self, mode: bool = True):
+        if mode:
+            self._cache = None
+            self._cache_key = None
+        return super().train(mode)
+
+    def _key(self):
+        d = self.__dict__
+        if d.get("_plist_gen") != _STRUCTURE[0]:
+            d["_plist"] = list(self.parameters())
+            d["_plist_gen"] = _STRUCTURE[0]
+        ps = [self.train_inputs[0], self.train_targets] + d["_plist"]
+        return tuple((p.data_ptr(), p._version) for p in ps)
+
+    def _noise(self):
+        fixed = isinstance(self.likelihood, FixedNoiseGaussianLikelihood)
+        return self.likelihood.noise.detach() if fixed else float(self.likelihood.noise.detach())
+
+    def fantasy_noise(self) -> float:
+        """The likelihood's noise (fixed noise: its mean) as a host float, read back once
+        per change of a parameter (the knowledge gradient's sigma^2 before ystd^2)."""
+        key = self._key()
+        if self.__dict__.get("_fnoise_key") != key:
+            self._fnoise = float(self.likelihood.noise.detach().mean())
+            self._fnoise_key = key
+        return self._fnoise
+
+    def _caches(self):
+        """The prediction caches, rebuilt on any change of a parameter or training
+        tensor: (spec, kernels.GPCache) from bo_ltf_covar and the Cholesky ladder on
+        the fused route, (L, alpha, constant) from torch.linalg on the torch route."""
+        from . import kernels
+        from .settings import propagate_grads
+        if propagate_grads.on() and (self.train_inputs[0].requires_grad or self.train_targets.requires_grad):
+            raise UnsupportedError(
+                "settings.propagate_grads: posterior gradients to the training data are not "
+                "supported (the prediction caches are built without a backward to them)")
+        key = (self._key(), self.fused())
+        if self._cache is None or self._cache_key != key:
+            X, y = self.train_inputs[0], self.train_targets
+            c = float(self.mean_module.constant.detach())
+            noise = self._noise()
+            if self.fused():
+                spec = self.spec()
+                cache, _ = kernels.build_ltf_cache(X, y, spec, noise, c)
+                self._cache = (spec, cache)
+            else:
+                K = self.covar_torch(X, X)
+                K = K + (torch.diag(noise) if torch.is_tensor(noise)
+                         else noise * torch.eye(X.shape[0], dtype=K.dtype, device=K.device))
+                L = _cholesky_ladder(K)
+                alpha = torch.cholesky_solve((y - c).unsqueeze(-1), L).squeeze(-1)
+                self._cache = (L, alpha, c)
+            self._cache_key = key
+        return self._cache
+
+    # -- posterior ---------------------------------------------------------------------------
+    def moments(self, X: torch.Tensor):
+        """(mean: batch x q, covariance: batch x q x q) at X (batch x q x d) in outcome
+        space, differentiable in every column of X."""
+        from .posteriors import _LTFMoments
+        d = self.train_inputs[0].shape[-1]
+        if X.shape[-1] != d:
+            raise ValueError(f"{type(self).__name__}.posterior: X has {X.shape[-1]} columns, expected {d}")
+        if X.dtype != torch.float64:
+            X = X.to(torch.float64)
+        self.eval()
+        batch, q = X.shape[:-2], X.shape[-2]
+        ymean, ystd = self.outcome_stats()
+        if self.fused():
+            mean, cov = _LTFMoments.apply(X.reshape(-1, q, d).contiguous(), self)
+            return mean.reshape(*batch, q), cov.reshape(*batch, q, q)
+        L, alpha, c = self._caches()
+        Kx = self.covar_torch(X, self.train_inputs[0])
+        V = torch.linalg.solve_triangular(L, Kx.mT, upper=False)
+        return ymean + ystd * (Kx @ alpha + c), (self.covar_torch(X, X) - V.mT @ V) * (ystd * ystd)
+
+    def posterior(self, X: torch.Tensor, output_indices=None, observation_noise=False,
+                  posterior_transform=None):
+        """models/gpytorch.py:127-199 for the fidelity kernel, computing in fp64."""
+        from .posteriors import GPyTorchPosterior, MultivariateNormal
+        if torch.is_tensor(observation_noise):
+            raise UnsupportedError(f"{type(self).__name__}.posterior: a tensor of observation "
+                                   "noise is not on the accelerated path")
+        mean, cov = self.moments(X)
+        if observation_noise is True:
+            ystd = self.outcome_stats()[1]
+            nz = self.likelihood.noise.detach().mean()
+            cov = cov + torch.diag_embed((nz * (ystd * ystd)).expand(mean.shape))
+        post = GPyTorchPosterior(MultivariateNormal(mean, cov), model=self, X=X)
+        return post if posterior_transform is None else posterior_transform(post)
+
+    # -- what stays off the accelerated path ---------------------------------------------------
+    def condition_on_observations(self, X, Y, **kwargs):
+        raise UnsupportedError("condition_on_observations: SingleTaskMultiFidelityGP is not on "
+                               "the accelerated path (conditioning of multi-fidelity models)")
+
+    def fantasize(self, X, sampler, observation_noise=None, **kwargs):
+        raise UnsupportedError("fantasize: SingleTaskMultiFidelityGP is not on the accelerated "
+                               "path (fantasy models of multi-fidelity models)")
 
 
 def _cholesky_ladder(K: torch.Tensor) -> torch.Tensor:

@@ -67,6 +67,12 @@ Ops (reference computation each replaces):
   bo::mixed_mll_terms row terms of its marginal log likelihood: 35 kernel-hyperparameter sums
   bo::mixed_cross     K*x and the t-batches' K** blocks of MixedSingleTaskGP.posterior
   bo::mixed_cross_grad  their gradient in the continuous columns of X
+  bo::ltf_covar       training covariance of the multi-fidelity GP (linear truncated fidelity
+                      kernel, models/kernels/linear_truncated_fidelity.py:183-238) as the
+                      padded Cholesky input
+  bo::ltf_mll_terms   row terms of its marginal log likelihood: 34 kernel-hyperparameter sums
+  bo::ltf_cross       K*x and the t-batches' K** blocks of SingleTaskMultiFidelityGP.posterior
+  bo::ltf_cross_grad  their gradient in every column of X, the fidelity columns included
 """
 from __future__ import annotations
 
@@ -1210,6 +1216,65 @@ def _(Xq, Xt, hyper, cont, cat, kind, o_s, o_c, o_p, dKx, G):
     return Xq.new_empty(Xq.shape, dtype=F64)
 
 
+# ---- bo::ltf_* (multi-fidelity GP, linear truncated fidelity kernel: ltf.hip) ---------------------
+def _ltf_spec(hyper, xcols, fcols, power, o):
+    return kernels.LTFSpec(tuple(xcols), tuple(fcols), hyper, power, o)
+
+
+@torch.library.custom_op("bo::ltf_covar", mutates_args=(), device_types="cuda")
+def ltf_covar(X: Tensor, hyper: Tensor, xcols: List[int], fcols: List[int], power: float, o: float,
+              noise: float, noise_vec: Optional[Tensor] = None) -> Tensor:
+    """K(Z, Z) + diag(noise + noise_vec) of the linear truncated fidelity kernel as the
+    padded np x np lower Cholesky input (identity pad)."""
+    return kernels.ltf_covar(X, _ltf_spec(hyper, xcols, fcols, power, o), noise, noise_vec)
+
+
+@ltf_covar.register_fake
+def _(X, hyper, xcols, fcols, power, o, noise, noise_vec=None):
+    np_ = _padded(X.shape[0])
+    return X.new_empty(np_, np_, dtype=F64)
+
+
+@torch.library.custom_op("bo::ltf_mll_terms", mutates_args=(), device_types="cuda")
+def ltf_mll_terms(X: Tensor, hyper: Tensor, xcols: List[int], fcols: List[int], power: float,
+                  o: float, L: Tensor, Ainv: Tensor, alpha: Tensor, beta: Tensor) -> Tensor:
+    """Row terms of the multi-fidelity model's marginal log likelihood, n x 40."""
+    return kernels.ltf_mll_partials(X, _ltf_spec(hyper, xcols, fcols, power, o), L, Ainv, alpha,
+                                    beta)
+
+
+@ltf_mll_terms.register_fake
+def _(X, hyper, xcols, fcols, power, o, L, Ainv, alpha, beta):
+    return X.new_empty(X.shape[0], _lib.LTF_MLL_COLS, dtype=F64)
+
+
+@torch.library.custom_op("bo::ltf_cross", mutates_args=(), device_types="cuda")
+def ltf_cross(Xq: Tensor, Xt: Tensor, hyper: Tensor, xcols: List[int], fcols: List[int],
+              power: float, o: float, skip_target: bool = True) -> Tuple[Tensor, Tensor]:
+    """(K*x: Bq x n, K**: B x q x q) of the linear truncated fidelity kernel for Xq B x q x d."""
+    return kernels.ltf_cross(Xq, Xt, _ltf_spec(hyper, xcols, fcols, power, o), skip_target)
+
+
+@ltf_cross.register_fake
+def _(Xq, Xt, hyper, xcols, fcols, power, o, skip_target=True):
+    B, q, _ = Xq.shape
+    return Xq.new_empty(B * q, Xt.shape[0], dtype=F64), Xq.new_empty(B, q, q, dtype=F64)
+
+
+@torch.library.custom_op("bo::ltf_cross_grad", mutates_args=(), device_types="cuda")
+def ltf_cross_grad(Xq: Tensor, Xt: Tensor, hyper: Tensor, xcols: List[int], fcols: List[int],
+                   power: float, o: float, dKx: Tensor, G: Tensor,
+                   skip_target: bool = True) -> Tensor:
+    """dX (B x q x d, fidelity columns included) from dK*x and the symmetric G."""
+    return kernels.ltf_cross_grad(Xq, Xt, _ltf_spec(hyper, xcols, fcols, power, o), dKx, G,
+                                  skip_target)
+
+
+@ltf_cross_grad.register_fake
+def _(Xq, Xt, hyper, xcols, fcols, power, o, dKx, G, skip_target=True):
+    return Xq.new_empty(Xq.shape, dtype=F64)
+
+
 OPS: List[str] = ["sobol_normal", "gp_cache", "gp_cache_extend", "chol_jitter", "chol_backward",
                   "post_partials", "qmc_finalize", "gp_posterior", "gp_posterior_backward",
                   "qmc_acq", "qmc_acq_backward", "qehvi", "qehvi_backward", "mll", "kg",
@@ -1218,4 +1283,4 @@ OPS: List[str] = ["sobol_normal", "gp_cache", "gp_cache_extend", "chol_jitter", 
                   "nipv_gram_backward", "bald", "bald_backward", "analytic", "analytic_backward",
                   "saas_potential", "fantasy_posterior", "fantasy_posterior_backward", "icm_covar",
                   "icm_mll_terms", "icm_task_view", "mixed_covar", "mixed_mll_terms", "mixed_cross",
-                  "mixed_cross_grad"]
+                  "mixed_cross_grad", "ltf_covar", "ltf_mll_terms", "ltf_cross", "ltf_cross_grad"]

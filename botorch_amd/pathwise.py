@@ -62,6 +62,10 @@ def _check_model(model) -> None:
     if getattr(model, "_is_mixed", False):
         raise UnsupportedError("Pathwise sampling: MixedSingleTaskGP is not on the accelerated "
                                "path (the paths' prior features take a single-task kernel).")
+    if getattr(model, "_is_ltf", False):
+        raise UnsupportedError("Pathwise sampling: SingleTaskMultiFidelityGP is not on the "
+                               "accelerated path (the paths' prior features take a single-task "
+                               "kernel).")
     if not isinstance(model, (SingleTaskGP, ModelListGP)):
         raise NotImplementedError(f"Pathwise sampling is not implemented for {type(model).__name__}.")
     if model.training:

@@ -197,6 +197,54 @@ class _MixedMoments(torch.autograd.Function):
         return dX, None
 
 
+class _LTFMoments(torch.autograd.Function):
+    """(mean', Sigma') of B t-batches of a SingleTaskMultiFidelityGP, differentiable
+    w.r.t. every column of X, the fidelity columns included (torch.clamp's gradient).
+    _MixedMoments with bo_ltf_cross and bo_ltf_cross_grad; the triangular and batched
+    GEMMs against the cached U are the same."""
+
+    @staticmethod
+    def forward(ctx, X3, model):
+        from . import ops  # noqa: F401  (torch.ops.bo registration)
+        spec, cache = model._caches()
+        ymean, ystd = model.outcome_stats()
+        B, q, d = X3.shape
+        n, np_ = cache.n, cache.np
+        Xq = X3.detach().contiguous()
+        Kx, Kxx = torch.ops.bo.ltf_cross(Xq, cache.Xt, spec.hyper, list(spec.xcols),
+                                         list(spec.fcols), spec.power, spec.o)
+        R = torch.empty(B * q, n, dtype=torch.float64, device=Xq.device)
+        kernels.gemm_strided(B * q, n, n, Kx, n, 0, cache.U, np_, 0, R, n, 0, 1,
+                             flags=_lib.GEMM_B_UPPER)
+        mean = kernels.gemm(Kx, cache.alpha.reshape(n, 1)).reshape(B, q)
+        RR = kernels.gemm(R.view(B, q, n), R.view(B, q, n), transB=True)
+        cov = (Kxx - RR) * (ystd * ystd)
+        mean = ymean + ystd * (mean + cache.constant)
+        if ctx.needs_input_grad[0]:
+            ctx.cache, ctx.spec, ctx.ystd, ctx.Xq, ctx.R = cache, spec, ystd, Xq, R
+        return mean, cov
+
+    @staticmethod
+    def backward(ctx, dmean, dcov):
+        cache, spec, ystd, Xq = ctx.cache, ctx.spec, ctx.ystd, ctx.Xq
+        B, q, d = Xq.shape
+        n, np_ = cache.n, cache.np
+        dev = ctx.R.device
+        if dmean is None:
+            dmean = torch.zeros(B, q, dtype=torch.float64, device=dev)
+        if dcov is None:
+            dcov = torch.zeros(B, q, q, dtype=torch.float64, device=dev)
+        G = ((ystd * ystd) * (dcov + dcov.mT)).contiguous()
+        W = torch.empty(B * q, n, dtype=torch.float64, device=dev)      # R L^{-1} = R U^T
+        kernels.gemm_strided(B * q, n, n, ctx.R, n, 0, cache.U, np_, 0, W, n, 0, 1,
+                             transB=True, flags=_lib.GEMM_B_LOWER)
+        dK = ((ystd * dmean).reshape(B * q, 1) * cache.alpha.reshape(1, n)).contiguous()
+        kernels.gemm(G, W.view(B, q, n), alpha=-1.0, beta=1.0, C=dK.view(B, q, n))
+        dX = torch.ops.bo.ltf_cross_grad(Xq, cache.Xt, spec.hyper, list(spec.xcols),
+                                         list(spec.fcols), spec.power, spec.o, dK, G)
+        return dX, None
+
+
 class _CholJitter(torch.autograd.Function):
     """psd_safe_cholesky with its gradient ([G] MultivariateNormal
     root_decomposition under autograd): forward = the jitter ladder

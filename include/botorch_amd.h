@@ -1520,6 +1520,84 @@ typedef struct BoMixedCrossArgs {
 int bo_mixed_cross(const BoMixedCrossArgs* a, void* stream);
 int bo_mixed_cross_grad(const BoMixedCrossArgs* a, void* stream);
 
+/* ---- Multi-fidelity exact GP with the linear truncated fidelity kernel
+ * (botorch/models/kernels/linear_truncated_fidelity.py:183-238,
+ * models/gp_regression_fidelity.py:218-308).  A row z = (x, s) has d = d_x + n_f
+ * columns: x_cols[0..d_x) name the ordinary ones, f_cols[0..n_f) the one or two
+ * fidelity columns (together a partition of 0..d-1; the rows stay in the caller's
+ * layout).  With s clamped to [0, 1] and u = 1 - s,
+ *   K(z, z') = o [k0(x, x'; l0) + c(s, s'; power) k1(x, x'; l1)]
+ *   c  = u1 u1' (1 + s1 s1')^power
+ *   c += u2 u2' (1 + s2 s2')^power + u1 u1' u2 u2' (1 + s1 s1' + s2 s2')^power   (n_f = 2)
+ * k0, k1 the unit-outputscale Matern-5/2 ARD kernels.  hyper: [l0 (d_x), l1 (d_x)] on
+ * the device.  1 <= d_x <= BO_LTF_MAX_DIM; fp64; no atomics, sums in a fixed order.
+ * Added within ABI 12 (plain names, as bo_mixed_covar). */
+#define BO_LTF_MAX_DIM 16
+#define BO_LTF_MLL_COLS 40
+
+/* A[i][k] = K(z_i, z_k) + (i == k)(noise + noise_vec[i]) for k <= i < n, zeros above
+ * the diagonal, the identity on rows / columns >= n: the np x np input of
+ * bo_cholesky_inverse / bo_cholesky_inverse_ainv (np = bo_padded_order(n)).
+ * noise_vec (n) is nullable. */
+typedef struct BoLtfCovarArgs {
+  BO_STRUCT_HEADER;
+  int32_t d, d_x, n_f, _pad;
+  int32_t x_cols[BO_LTF_MAX_DIM], f_cols[2];
+  int64_t n, np;
+  const double *X, *hyper, *noise_vec;
+  double power, o, noise;
+  double* A;
+} BoLtfCovarArgs;
+int bo_ltf_covar(const BoLtfCovarArgs* a, void* stream);
+
+/* One pass over the lower triangle, one workgroup per row i, W_ik = alpha_i alpha_k -
+ * A^{-1}_ik, w = 2 off the diagonal, Delta = x_i - x_k, g the radial factor of
+ * dk/dl_j = g Delta_j^2 / l_j^3.  partial: n x BO_LTF_MLL_COLS (both lengthscale
+ * groups padded to 16, padded slots exactly 0):
+ *   [0..15]  sum_k w W o g0 Delta_j^2      d ll/d l0_j = 1/2 [.] / l0_j^3
+ *   [16..31] sum_k w W o c g1 Delta_j^2    d ll/d l1_j = 1/2 [.] / l1_j^3
+ *   [32] sum_k w W o k1 dc/dpower          d ll/d power = 1/2 [.]
+ *   [33] sum_k w W (k0 + c k1)             d ll/d o = 1/2 [.]
+ *   [34] W_ii   [35] log L_ii   [36] beta_i^2   [37] alpha_i   [38] 0   [39] 0
+ * L, Ainv (lower part read): leading dimension ld. */
+typedef struct BoLtfMllArgs {
+  BO_STRUCT_HEADER;
+  int32_t d, d_x, n_f, _pad;
+  int32_t x_cols[BO_LTF_MAX_DIM], f_cols[2];
+  int64_t n, ld;
+  const double *X, *hyper;
+  double power, o;
+  const double *L, *Ainv, *alpha, *beta;
+  double* partial;
+} BoLtfMllArgs;
+int bo_ltf_mll_terms(const BoLtfMllArgs* a, void* stream);
+
+/* Xq: R x d query rows, R = B q (t-batch b owns rows b q .. b q + q - 1); Xt: n x d.
+ * bo_ltf_cross:      Kx[r][k] = K(zq_r, zt_k) (R x n, row-major) and
+ *                    Kxx[b][i][c] = K(zq_(b q + i), zq_(b q + c)) (B x q x q), one launch.
+ * bo_ltf_cross_grad: dX[r] = sum_k dKx[r][k] dK(zq_r, zt_k)/dz_r
+ *                          + sum_c G[b][i][c] dK(zq_r, zq_(b q + c))/dz_r
+ *                    (R x d; G symmetric, B x q x q) in every column: dK/dx_j =
+ *                    -o (g0 / l0_j^2 + c g1 / l1_j^2) Delta_j, dK/ds_f = o k1 dc/ds_f
+ *                    with the gradient of the clamp (dc/ds_f passes for 0 <= s_f <= 1,
+ *                    exactly 0 outside); coincident points give 0 in x.
+ * A query row with every u = 0 has c = 0 against every partner and is evaluated from
+ * k0 alone (same values, bit for bit); no_skip != 0 sends such rows down the general
+ * path (kept for that comparison and for measurement).  Any q >= 1, any B. */
+typedef struct BoLtfCrossArgs {
+  BO_STRUCT_HEADER;
+  int32_t d, d_x, n_f, no_skip;
+  int32_t x_cols[BO_LTF_MAX_DIM], f_cols[2];
+  int64_t B, q, n;
+  const double *Xq, *Xt, *hyper;
+  double power, o;
+  double *Kx, *Kxx;       /* bo_ltf_cross: outputs */
+  const double *dKx, *G;  /* bo_ltf_cross_grad: inputs */
+  double* dX;             /* bo_ltf_cross_grad: output */
+} BoLtfCrossArgs;
+int bo_ltf_cross(const BoLtfCrossArgs* a, void* stream);
+int bo_ltf_cross_grad(const BoLtfCrossArgs* a, void* stream);
+
 /* HOST: sizeof the named record ("BoPostPartialsArgs", ...), -1 if unknown --
  * lets a binding check its declared layout once at load time. */
 int64_t bo_struct_size(const char* name);
