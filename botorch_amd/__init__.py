@@ -31,7 +31,11 @@ _EXPORTS = {"FullyBayesianAcquisitionFunction": "acquisition",
             "qMultiFidelityKnowledgeGradient": "acquisition",
             "project_to_target_fidelity": "acquisition",
             "expand_trace_observations": "acquisition",
-            "AugmentedHartmann": "multi_fidelity"}
+            "AugmentedHartmann": "multi_fidelity",
+            "PairwiseGP": "pairwise", "PairwiseProbitLikelihood": "pairwise",
+            "PairwiseLaplaceMarginalLogLikelihood": "pairwise",
+            "AnalyticExpectedUtilityOfBestOption": "pairwise",
+            "qExpectedUtilityOfBestOption": "pairwise", "pairwise_laplace_torch": "pairwise"}
 __all__ = sorted(_EXPORTS)
 
 

@@ -336,6 +336,15 @@ class LtfCrossArgs(_Args):
                                               ("Kxx", _D), ("dKx", _D), ("G", _D), ("dX", _D)]
 
 
+class PairwiseLaplaceArgs(_Args):
+    _fields_ = _HDR + [("kind", c_int32), ("d", c_int32), ("maxfev", c_int32),
+                       ("want_grad", c_int32), ("n", c_int64), ("m", c_int64), ("C", c_int64),
+                       ("ldr", c_int64), ("X", _D), ("comp", _D), ("inc_ptr", _D), ("inc", _D),
+                       ("hyper", _D), ("f_init", _D), ("jitter", c_double), ("tol", c_double),
+                       ("f", _D), ("alpha", _D), ("psi", _D), ("grad", _D), ("R", _D),
+                       ("iters", _D), ("status", _D), ("work", _D), ("work_size", c_int64)]
+
+
 class PathsArgs(_Args):
     _fields_ = _HDR + [("kind", c_int32), ("d", c_int32), ("S", c_int32), ("M", c_int32),
                        ("R", c_int64), ("n", c_int64), ("inner", c_int64), ("X", _D),
@@ -472,8 +481,13 @@ LTF_RECORD_ENTRIES = {"bo_ltf_covar": LtfCovarArgs, "bo_ltf_mll_terms": LtfMllAr
                       "bo_ltf_cross": LtfCrossArgs, "bo_ltf_cross_grad": LtfCrossArgs}
 LTF_ARG_RECORDS = {"BoLtfCovarArgs": LtfCovarArgs, "BoLtfMllArgs": LtfMllArgs,
                    "BoLtfCrossArgs": LtfCrossArgs}
+# the preference GP's Laplace kernel of pairwise.hip, likewise
+PAIRWISE_RECORD_ENTRIES = {"bo_pairwise_laplace": PairwiseLaplaceArgs}
+PAIRWISE_ARG_RECORDS = {"BoPairwiseLaplaceArgs": PairwiseLaplaceArgs}
+_SIGNATURES["bo_pairwise_laplace_work"] = (c_int, [c_int64, c_int64, c_int, c_int64,
+                                                   POINTER(c_int64)])
 for _name, _cls in {**PLAIN_RECORD_ENTRIES, **ICM_RECORD_ENTRIES, **MIXED_RECORD_ENTRIES,
-                    **LTF_RECORD_ENTRIES}.items():
+                    **LTF_RECORD_ENTRIES, **PAIRWISE_RECORD_ENTRIES}.items():
     _SIGNATURES[_name] = (c_int, [POINTER(_cls), _P])
 _SIGNATURES["bo_post_backward_jobs"] = (c_int, [c_int, POINTER(POINTER(PostBackwardArgs)), _P, _P])
 ARG_RECORDS = {"BoPostPartialsArgs": PostPartialsArgs, "BoQmcFinalizeArgs": QmcFinalizeArgs,
@@ -510,7 +524,8 @@ def lib():
             raise NativeLibraryMissing(
                 f"{LIB_PATH} has ABI {handle.bo_version()}, expected {ABI_VERSION}: rebuild with `make`")
         for cname, rec in {**ARG_RECORDS, **PLAIN_ARG_RECORDS, **ICM_ARG_RECORDS,
-                           **MIXED_ARG_RECORDS, **LTF_ARG_RECORDS}.items():  # layouts agree with the C header
+                           **MIXED_ARG_RECORDS, **LTF_ARG_RECORDS,
+                           **PAIRWISE_ARG_RECORDS}.items():  # layouts agree with the C header
             if handle.bo_struct_size(cname.encode()) != sizeof(rec):
                 raise NativeLibraryMissing(f"{cname}: ctypes layout differs from the library's")
         _lib = handle

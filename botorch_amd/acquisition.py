@@ -62,6 +62,7 @@ class AcquisitionFunction(nn.Module):
     # carries no Cholesky factor and its caches are those of one output task)
     _admits_multitask = False
     _admits_ltf = False  # the classes beyond those whose routes go through model.moments
+    _admits_pairwise = False  # likewise, beyond the multi-task audit: qSimpleRegret
 
     def __init__(self, model):
         super().__init__()
@@ -90,6 +91,17 @@ class AcquisitionFunction(nn.Module):
                 "qLogNoisyExpectedImprovement, qUpperConfidenceBound, ExpectedImprovement, "
                 "LogExpectedImprovement, UpperConfidenceBound, PosteriorMean, "
                 "qKnowledgeGradient, qMultiFidelityKnowledgeGradient)")
+        if getattr(model, "_is_pairwise", False) and not (self._admits_multitask
+                                                          or self._admits_pairwise):
+            # and PairwiseGP: no prediction_cache, no Cholesky factor and no moments, so
+            # only the classes that reach a model through model.posterior alone
+            raise UnsupportedError(
+                f"{type(self).__name__}: PairwiseGP is not on the accelerated path of this "
+                "acquisition function (admitted: AnalyticExpectedUtilityOfBestOption, "
+                "qExpectedUtilityOfBestOption, qExpectedImprovement, qLogExpectedImprovement, "
+                "qNoisyExpectedImprovement, qLogNoisyExpectedImprovement, qUpperConfidenceBound, "
+                "qSimpleRegret, ExpectedImprovement, LogExpectedImprovement, "
+                "UpperConfidenceBound, PosteriorMean)")
         self.model = model
         self.X_pending = None
 
@@ -443,6 +455,7 @@ class qSimpleRegret(_PlainMaxMCAcquisitionFunction):
     qSR(X) = E[max_j Y_j].  Values may be negative, so there is no
     ``constraints`` argument (use a ConstrainedMCObjective)."""
 
+    _admits_pairwise = True
     _fused_mode = _lib.QMC_QSR
 
     def __init__(self, model, sampler=None, objective=None, posterior_transform=None,

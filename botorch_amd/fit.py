@@ -183,6 +183,8 @@ def _layout(model):
         return _MixedLayout(model)
     if getattr(model, "_is_ltf", False):
         return _LTFLayout(model)
+    if getattr(model, "_is_pairwise", False):
+        return _PairwiseLayout(model)
     return _MultiLayout(model) if getattr(model, "_is_multi_output", False) else _Layout(model)
 
 
@@ -811,6 +813,47 @@ def ltf_mll_value_and_grad(model, x: np.ndarray, layout: "_LTFLayout"):
         ll += pv
         g[at:at + size] += pg
     return -ll / n, -g / n
+
+
+class _PairwiseLayout:
+    """Flat parameter vector <-> hyperparameters of a PairwiseGP: the d lengthscales, then
+    the outputscale, natural values (as _LTFLayout), bounded by the kernel's lengthscale
+    bound and the outputscale's bounds.  The closure is one Laplace launch
+    (bo_pairwise_laplace on the fused route), warm-started from the previous closure's
+    MAP utility, plus one device-to-host transfer; the priors are added on the host."""
+
+    def __init__(self, model):
+        self.model = model
+        self.d = model.dim
+        cm = model.covar_module
+        os_lo, os_hi = getattr(cm, "outputscale_bounds", (0.0, None))
+        self.bounds = [(cm.base_kernel.lengthscale_lower, None)] * self.d + [(os_lo, os_hi)]
+        self.segments = [("lengthscale", 0, self.d), ("outputscale", self.d, 1)]
+        self.size = self.d + 1
+
+    def get(self) -> np.ndarray:
+        cm = self.model.covar_module
+        return np.asarray(cm.lengthscale.detach().reshape(-1).cpu().tolist()
+                          + [float(cm.outputscale.detach())], dtype=np.float64)
+
+    def set(self, x: np.ndarray) -> None:
+        cm = self.model.covar_module
+        cm.base_kernel.lengthscale = torch.as_tensor(np.asarray(x[:self.d])).reshape(1, -1)
+        cm.outputscale = float(x[self.d])
+
+    def value_and_grad(self, x: np.ndarray):
+        x = np.asarray(x, dtype=np.float64)
+        m, d = self.model, self.d
+        hyper = torch.as_tensor(np.concatenate([x[d:], x[:d]]), dtype=torch.float64).reshape(1, -1)
+        host = m.laplace(hyper.to(m.datapoints.device), want_grad=True)["host"]  # [psi, gradient]
+        ll, g = float(host[0]), np.concatenate([host[2:], host[1:2]])
+        for prior, at, size in ((m.covar_module.base_kernel.lengthscale_prior, 0, d),
+                                (m.covar_module.outputscale_prior, d, 1)):
+            pv, pg = prior.terms(x[at:at + size]) if hasattr(prior, "terms") else _prior_terms(
+                prior, x[at:at + size])
+            ll += pv
+            g[at:at + size] += pg
+        return -ll, -g
 
 
 class OptimizationStatus(int, Enum):

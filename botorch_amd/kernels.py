@@ -3251,6 +3251,97 @@ def saas_potential(z: torch.Tensor, X: torch.Tensor, y: torch.Tensor,
     return U, grad, status
 
 
+PAIRWISE_NMAX = 1024  # bo_pairwise_laplace: one workgroup per hyperparameter row
+PAIRWISE_DMAX = 256
+
+
+def pairwise_laplace_check(n: int, m: int, d: int, C: int = 1) -> None:
+    """The argument limits of :func:`pairwise_laplace`, raised on the host before any
+    native call."""
+    if not 2 <= n <= PAIRWISE_NMAX:
+        raise ValueError(f"pairwise_laplace: 2 <= n <= {PAIRWISE_NMAX} (got {n})")
+    if m < 1 or 2 * m >= 1 << 31:
+        raise ValueError(f"pairwise_laplace: 1 <= m with 2 m < 2^31 (got {m})")
+    if not 1 <= d <= PAIRWISE_DMAX:
+        raise ValueError(f"pairwise_laplace: 1 <= d <= {PAIRWISE_DMAX} (got {d})")
+    if C < 1 or C * n * n >= 1 << 31:
+        raise ValueError(f"pairwise_laplace: C >= 1 and C n^2 < 2^31 (got C = {C}, n = {n})")
+
+
+def pairwise_laplace_work(n: int, m: int, d: int, C: int) -> int:
+    """Doubles of workspace of a C-row :func:`pairwise_laplace` call."""
+    pairwise_laplace_check(n, m, d, C)
+    elems = ctypes.c_int64()
+    check(lib().bo_pairwise_laplace_work(n, m, d, C, ctypes.byref(elems)),
+          "pairwise_laplace_work")
+    return elems.value
+
+
+def pairwise_incidence(comp: torch.Tensor, n: int):
+    """(comp (m x 2, int32), inc_ptr (n + 1), inc (2 m)) on comp's device: the
+    comparisons per datapoint in CSR form, an entry 2 k + role (0 winner, 1 loser),
+    each datapoint's entries in ascending k.  Built on the host once per data set; it
+    also checks that every index lies in [0, n)."""
+    c = comp.detach().to("cpu", torch.int64).reshape(-1, 2)
+    if c.numel() == 0 or int(c.min()) < 0 or int(c.max()) >= n:
+        raise ValueError(f"pairwise_laplace: comparisons must be m x 2 indices in [0, {n})")
+    code = torch.arange(c.numel(), dtype=torch.int64)  # 2 k + role, row-major
+    order = torch.sort(c.reshape(-1), stable=True).indices
+    ptr = torch.zeros(n + 1, dtype=torch.int64)
+    ptr[1:] = torch.cumsum(torch.bincount(c.reshape(-1), minlength=n), 0)
+    dev = comp.device
+    return (c.to(torch.int32).contiguous().to(dev), ptr.to(torch.int32).to(dev),
+            code[order].to(torch.int32).contiguous().to(dev))
+
+
+def pairwise_laplace(X: torch.Tensor, incidence, hyper: torch.Tensor, kind: int,
+                     f_init: Optional[torch.Tensor] = None, jitter: float = 0.0,
+                     tol: float = 1e-13, maxfev: int = 50, want_grad: bool = True,
+                     work: Optional[torch.Tensor] = None, ldr: Optional[int] = None):
+    """The fused Laplace approximation of the preference GP (bo_pairwise_laplace, the
+    record's comment in include/botorch_amd.h) at the C rows of ``hyper`` =
+    [outputscale, lengthscales] over X (n x d) and ``incidence`` =
+    :func:`pairwise_incidence` (comparisons).  Returns a dict: f, alpha (C x n), psi (C),
+    grad (C x (d + 1), or None), R (C x n x ldr), iters and status (C, int32)."""
+    comp, inc_ptr, inc = incidence
+    if X.dim() != 2 or hyper.dim() != 2:
+        raise ValueError("pairwise_laplace: X must be n x d and hyper C x (d + 1)")
+    n, d = X.shape
+    m, C = comp.shape[0], hyper.shape[0]
+    pairwise_laplace_check(n, m, d, C)
+    ldr = n if ldr is None else int(ldr)
+    if hyper.shape[1] != d + 1 or inc_ptr.numel() != n + 1 or inc.numel() != 2 * m or ldr < n:
+        raise ValueError(f"pairwise_laplace: hyper must be C x {d + 1}, inc_ptr {n + 1}, inc "
+                         f"{2 * m} and ldr >= {n}")
+    if f_init is not None and tuple(f_init.shape) != (C, n):
+        raise ValueError(f"pairwise_laplace: f_init must be {C} x {n}")
+    if kind not in (_lib.RBF, _lib.MATERN52) or maxfev < 1 or tol < 0 or jitter < 0:
+        raise ValueError("pairwise_laplace: kind RBF / Matern-5/2, maxfev >= 1, tol, jitter >= 0")
+    for t in (X, hyper) + (() if f_init is None else (f_init,)):
+        if t.dtype != torch.float64:
+            raise ValueError("pairwise_laplace: every real tensor must be fp64")
+    for t in (comp, inc_ptr, inc):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError("pairwise_laplace: the incidence arrays must be contiguous int32")
+    dev = _dev(X, hyper, comp, inc_ptr, inc)
+    need = pairwise_laplace_work(n, m, d, C)
+    if work is None:
+        work = torch.empty(need, dtype=torch.float64, device=dev)
+    elif work.dtype != torch.float64 or work.numel() < need or not work.is_contiguous():
+        raise ValueError(f"pairwise_laplace: work must be {need} contiguous fp64 values")
+    _dev(work)
+    new = lambda *shape, dt=torch.float64: torch.empty(*shape, dtype=dt, device=dev)  # noqa: E731
+    out = dict(f=new(C, n), alpha=new(C, n), psi=new(C), grad=new(C, d + 1) if want_grad else None,
+               R=new(C, n, ldr), iters=new(C, dt=torch.int32), status=new(C, dt=torch.int32))
+    a = _lib.PairwiseLaplaceArgs(
+        kind=kind, d=d, maxfev=int(maxfev), want_grad=int(want_grad), n=n, m=m, C=C, ldr=ldr,
+        X=X.contiguous(), comp=comp, inc_ptr=inc_ptr, inc=inc, hyper=hyper.contiguous(),
+        f_init=None if f_init is None else f_init.contiguous(), jitter=float(jitter),
+        tol=float(tol), work=work, work_size=work.numel(), **out)
+    check(lib().bo_pairwise_laplace(ctypes.byref(a), _stream(dev)), "pairwise_laplace")
+    return out
+
+
 def kernel_grad(X: torch.Tensor, Y: torch.Tensor, dK: torch.Tensor, lengthscale: torch.Tensor,
                 kind: int, outputscale: float = 1.0, group: int = 0,
                 dX: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -90,6 +90,29 @@ class GammaPrior:
         return a * math.log(b) + (a - 1.0) * torch.log(x) - b * x - math.lgamma(a)
 
 
+class SmoothedBoxPrior:
+    """[G] SmoothedBoxPrior(a, b, sigma=0.01): flat on [a, b], Gaussian tails of width sigma."""
+
+    def __init__(self, a: float, b: float, sigma: float = 0.01):
+        self.a, self.b, self.sigma = float(a), float(b), float(sigma)
+
+    def _parts(self, x):
+        c, r = 0.5 * (self.a + self.b), 0.5 * (self.b - self.a)
+        return c, (abs(x - c) - r).clip(0.0)
+
+    def log_prob(self, x):
+        _, dist = self._parts(x)
+        M = 1.0 + (self.b - self.a) / (math.sqrt(2 * math.pi) * self.sigma)
+        return (-0.5 * (dist / self.sigma) ** 2 - math.log(self.sigma) - 0.5 * math.log(2 * math.pi)
+                - math.log(M))
+
+    def terms(self, x):
+        """(sum of log densities, gradient) at a numpy vector x (the fit's host side)."""
+        import numpy as np
+        c, dist = self._parts(x)
+        return float(np.sum(self.log_prob(x))), -dist * np.sign(x - c) / self.sigma ** 2
+
+
 class _Kernel(_TrackedModule):
     kind = _lib.RBF
 
@@ -2330,7 +2353,15 @@ def _cholesky_ladder(K: torch.Tensor) -> torch.Tensor:
     raise NotPSDError(f"Matrix not positive definite after repeatedly adding jitter up to {jitter:.1e}")
 
 
+_PAIRWISE = ("PairwiseGP", "PairwiseLaplaceMarginalLogLikelihood", "PairwiseLogitLikelihood",
+             "PairwiseProbitLikelihood", "pairwise_laplace_torch")
+
+
 def __getattr__(name):
+    # the preference GP lives in pairwise.py, which imports the kernels and priors above
+    if name in _PAIRWISE:
+        from . import pairwise
+        return getattr(pairwise, name)
     # fit_fully_bayesian_model_nuts lives in fit.py, where the reference has it
     # (fit.py imports this module, so the re-export resolves on first use)
     if name == "fit_fully_bayesian_model_nuts":

@@ -73,6 +73,10 @@ Ops (reference computation each replaces):
   bo::ltf_mll_terms   row terms of its marginal log likelihood: 34 kernel-hyperparameter sums
   bo::ltf_cross       K*x and the t-batches' K** blocks of SingleTaskMultiFidelityGP.posterior
   bo::ltf_cross_grad  their gradient in every column of X, the fidelity columns included
+  bo::pairwise_laplace  PairwiseGP._update, _util_newton_updates and
+                      PairwiseLaplaceMarginalLogLikelihood.forward (models/pairwise_gp.py): the MAP
+                      utility, the Laplace evidence, its gradient and the posterior's R, one
+                      workgroup per hyperparameter row
 """
 from __future__ import annotations
 
@@ -1275,6 +1279,29 @@ def _(Xq, Xt, hyper, xcols, fcols, power, o, dKx, G, skip_target=True):
     return Xq.new_empty(Xq.shape, dtype=F64)
 
 
+# ---- bo::pairwise_laplace (the preference GP's Laplace approximation: pairwise.hip) ---------------
+@torch.library.custom_op("bo::pairwise_laplace", mutates_args=(), device_types="cuda")
+def pairwise_laplace(X: Tensor, comp: Tensor, inc_ptr: Tensor, inc: Tensor, hyper: Tensor,
+                     kind: int, f_init: Optional[Tensor] = None, jitter: float = 0.0,
+                     tol: float = 1e-13, maxfev: int = 50, want_grad: bool = True,
+                     work: Optional[Tensor] = None) -> List[Tensor]:
+    """[f, alpha, psi, grad, R, iters, status] of kernels.pairwise_laplace (grad is empty
+    without want_grad); (comp, inc_ptr, inc) = kernels.pairwise_incidence."""
+    o = kernels.pairwise_laplace(X, (comp, inc_ptr, inc), hyper, kind, f_init, jitter, tol, maxfev,
+                                 want_grad, work)
+    grad = o["grad"] if want_grad else X.new_empty(0, dtype=F64)
+    return [o["f"], o["alpha"], o["psi"], grad, o["R"], o["iters"], o["status"]]
+
+
+@pairwise_laplace.register_fake
+def _(X, comp, inc_ptr, inc, hyper, kind, f_init=None, jitter=0.0, tol=1e-13, maxfev=50,
+      want_grad=True, work=None):
+    n, d, C = X.shape[0], X.shape[1], hyper.shape[0]
+    e = lambda *s, dt=F64: X.new_empty(*s, dtype=dt)  # noqa: E731
+    return [e(C, n), e(C, n), e(C), e(C, d + 1) if want_grad else e(0), e(C, n, n),
+            e(C, dt=torch.int32), e(C, dt=torch.int32)]
+
+
 OPS: List[str] = ["sobol_normal", "gp_cache", "gp_cache_extend", "chol_jitter", "chol_backward",
                   "post_partials", "qmc_finalize", "gp_posterior", "gp_posterior_backward",
                   "qmc_acq", "qmc_acq_backward", "qehvi", "qehvi_backward", "mll", "kg",
@@ -1283,4 +1310,5 @@ OPS: List[str] = ["sobol_normal", "gp_cache", "gp_cache_extend", "chol_jitter", 
                   "nipv_gram_backward", "bald", "bald_backward", "analytic", "analytic_backward",
                   "saas_potential", "fantasy_posterior", "fantasy_posterior_backward", "icm_covar",
                   "icm_mll_terms", "icm_task_view", "mixed_covar", "mixed_mll_terms", "mixed_cross",
-                  "mixed_cross_grad", "ltf_covar", "ltf_mll_terms", "ltf_cross", "ltf_cross_grad"]
+                  "mixed_cross_grad", "ltf_covar", "ltf_mll_terms", "ltf_cross", "ltf_cross_grad",
+                  "pairwise_laplace"]

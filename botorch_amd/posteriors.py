@@ -245,6 +245,65 @@ class _LTFMoments(torch.autograd.Function):
         return dX, None
 
 
+class _PairwiseMoments(torch.autograd.Function):
+    """(mean, Sigma) of B t-batches of a PairwiseGP on the device, differentiable w.r.t. X:
+    _GeneralMoments with the dense R = (I + C K)^{-1} C of the Laplace launch in the place
+    of the triangular U (mean = K*x alpha, Sigma = K** - K*x R K*x^T; one GEMM gives
+    K*x R, a batched one the product with K*x^T) and alpha from the same launch.
+    Backward: d K*x = d mu alpha^T - (dS + dS^T) K*x R, d K** = dS + dS^T."""
+
+    @staticmethod
+    def forward(ctx, X3, model):
+        cache, cm = model._laplace(), model.covar_module
+        ls, kind, os_ = cm.lengthscale.detach().reshape(-1), cm.kind, float(cm.outputscale)
+        B, q, d = X3.shape
+        n = model.n
+        X2 = X3.detach().reshape(B * q, d).contiguous()
+        Kx = kernels.covar_matrix(X2, model.datapoints, ls, kind, os_)
+        KR = kernels.gemm(Kx, cache["R"])
+        mean = kernels.gemm(Kx, cache["alpha"].reshape(n, 1)).reshape(B, q)
+        cov = kernels.covar_blocks(X3.detach(), ls, kind, os_) - kernels.gemm(
+            KR.view(B, q, n), Kx.view(B, q, n), transB=True)
+        if ctx.needs_input_grad[0]:
+            ctx.state = (model.datapoints, cache["alpha"], ls, kind, os_, X2, KR, (B, q, d))
+        return mean, cov
+
+    @staticmethod
+    def backward(ctx, dmean, dcov):
+        Xt, alpha, ls, kind, os_, X2, KR, (B, q, d) = ctx.state
+        n, dev = Xt.shape[0], X2.device
+        if dmean is None:
+            dmean = torch.zeros(B, q, dtype=torch.float64, device=dev)
+        if dcov is None:
+            dcov = torch.zeros(B, q, q, dtype=torch.float64, device=dev)
+        G = (dcov + dcov.mT).contiguous()
+        dK = (dmean.reshape(B * q, 1) * alpha.reshape(1, n)).contiguous()
+        kernels.gemm(G, KR.view(B, q, n), alpha=-1.0, beta=1.0, C=dK.view(B, q, n))
+        dX = kernels.kernel_grad(X2, Xt, dK, ls, kind, os_)
+        dX = kernels.kernel_grad(X2, X2, G.view(B * q, q), ls, kind, os_, group=q, dX=dX)
+        return dX.reshape(B, q, d), None
+
+
+def pairwise_moments(model, X: torch.Tensor):
+    """mean (batch x q), Sigma (batch x q x q) of a PairwiseGP at X (batch x q x d): the
+    prior without data; _PairwiseMoments on the fused route; the same formulas under
+    torch autograd on the torch route."""
+    from .pairwise import _kbar
+    batch, (q, d) = X.shape[:-2], X.shape[-2:]
+    cm = model.covar_module
+    if model._has_no_data() or not model.fused_posterior(torch.is_grad_enabled() and X.requires_grad):
+        ls = cm.lengthscale.detach().reshape(-1).to(X.device)
+        os_ = cm.outputscale.detach().to(X.device)
+        cov = os_ * _kbar(X, X, ls, cm.kind)[0]
+        if model._has_no_data():
+            return torch.zeros(*batch, q, dtype=X.dtype, device=X.device), cov
+        cache = model._laplace()
+        Kx = os_ * _kbar(X, model.datapoints, ls, cm.kind)[0]
+        return Kx @ cache["alpha"], cov - Kx @ cache["R"] @ Kx.mT
+    mean, cov = _PairwiseMoments.apply(X.reshape(-1, q, d).contiguous(), model)
+    return mean.reshape(*batch, q), cov.reshape(*batch, q, q)
+
+
 class _CholJitter(torch.autograd.Function):
     """psd_safe_cholesky with its gradient ([G] MultivariateNormal
     root_decomposition under autograd): forward = the jitter ladder

@@ -1598,6 +1598,55 @@ typedef struct BoLtfCrossArgs {
 int bo_ltf_cross(const BoLtfCrossArgs* a, void* stream);
 int bo_ltf_cross_grad(const BoLtfCrossArgs* a, void* stream);
 
+/* ---- The Laplace approximation of the preference GP (botorch/models/pairwise_gp.py,
+ * likelihoods/pairwise.py: PairwiseGP._update, _util_newton_updates,
+ * PairwiseLaplaceMarginalLogLikelihood.forward) for C hyperparameter rows
+ *   hyper[c] = [outputscale, lengthscale_1 .. lengthscale_d]   (natural values, C x (d + 1))
+ * over shared data: X (n x d) and m comparisons comp[k] = (i_k, j_k), "i_k is preferred
+ * to j_k", d_k = e_i - e_j.  inc_ptr (n + 1) / inc (2 m) is the incidence list of the
+ * comparisons per datapoint in CSR form, an entry 2 k + role (role 0: the winner, 1:
+ * the loser), each datapoint's entries in ascending k.  K = os (kbar(X, X) + jitter I),
+ * kbar the RBF or Matern-5/2 ARD kernel, zero prior mean, K = L L^T, f = L a.
+ *   z_k = clamp((f_i - f_j)/sqrt2, -3, 3), h = phi(z)/Phi(z), c = h (h + z)/2,
+ *   iota_k = [clamp inactive], b = -D^T h / sqrt2, C = sum_k c_k d_k d_k^T
+ *   root: a + L^T b(L a) = 0 by Newton on M = I + L^T C L = L_m L_m^T, the step halved
+ *   (at most 8 times) while ||a + L^T b||_2 does not fall; it stops when
+ *   ||step||_inf <= tol max(1, ||a||_inf), or after maxfev iterations (status 3)
+ *   psi = sum_k log Phi(z_k) - a^T a / 2 - sum_i log (L_m)_ii
+ *   alpha = L^{-T} a (the posterior mean is K*x alpha), f = L a
+ *   R = (I + C K)^{-1} C = L^{-T} M^{-1} L^T C, symmetrised (the posterior covariance is
+ *   K** - K*x R K*x^T); n x n at row pitch ldr
+ *   grad (want_grad != 0): d psi/d hyper, the exact derivative of psi: with
+ *   s_k = d_k^T L M^{-1} L^T d_k, c' = dc/dz,
+ *   u = -sum_k (1 - iota_k) h_k d_k/sqrt2 - sum_k iota_k c'_k s_k d_k / (2 sqrt2),
+ *   v = (I + C_iota K)^{-1} u, W = (alpha alpha^T - R + alpha v^T + v alpha^T)/2:
+ *   d psi/d theta = sum_ij W_ij dK_ij/d theta.
+ * f_init (C x n, nullable): the start value of f; otherwise (wins - mean)/std sqrt(os)
+ * of the win counts.  One workgroup per row in its slice of work
+ * (bo_pairwise_laplace_work doubles for the call); no atomics, sums in a fixed order:
+ * repeated calls are bitwise identical and row c of a C-row call equals the one-row call.
+ * status (C): 0 ok; 1 a non-finite input or result (psi = -inf, f, alpha, grad zero, R
+ * undefined); 2 a non-positive pivot of K (likewise); 3 maxfev reached (values returned).
+ * Every comp entry must lie in [0, n) (the caller checks: the arrays are on the device).
+ * 2 <= n <= 1024, 1 <= m with 2 m < 2^31, 1 <= d <= 256, C >= 1 with C n^2 < 2^31, fp64.
+ * Added within ABI 12 (a plain name, as bo_ltf_covar). */
+typedef struct BoPairwiseLaplaceArgs {
+  BO_STRUCT_HEADER;
+  int32_t kind, d, maxfev, want_grad;
+  int64_t n, m, C, ldr;
+  const double* X;
+  const int32_t *comp, *inc_ptr, *inc;
+  const double *hyper, *f_init;
+  double jitter, tol;
+  double *f, *alpha, *psi, *grad, *R; /* C x n, C x n, C, C x (d + 1), C x n x ldr */
+  int32_t *iters, *status;            /* C */
+  double* work;
+  int64_t work_size;
+} BoPairwiseLaplaceArgs;
+int bo_pairwise_laplace(const BoPairwiseLaplaceArgs* a, void* stream);
+/* HOST: doubles of work for a call of C rows. */
+int bo_pairwise_laplace_work(int64_t n, int64_t m, int d, int64_t C, int64_t* elems);
+
 /* HOST: sizeof the named record ("BoPostPartialsArgs", ...), -1 if unknown --
  * lets a binding check its declared layout once at load time. */
 int64_t bo_struct_size(const char* name);
