@@ -35,7 +35,9 @@ _EXPORTS = {"FullyBayesianAcquisitionFunction": "acquisition",
             "PairwiseGP": "pairwise", "PairwiseProbitLikelihood": "pairwise",
             "PairwiseLaplaceMarginalLogLikelihood": "pairwise",
             "AnalyticExpectedUtilityOfBestOption": "pairwise",
-            "qExpectedUtilityOfBestOption": "pairwise", "pairwise_laplace_torch": "pairwise"}
+            "qExpectedUtilityOfBestOption": "pairwise", "pairwise_laplace_torch": "pairwise",
+            "InputTransform": "transforms", "Normalize": "transforms", "Warp": "transforms",
+            "ChainedInputTransform": "transforms"}
 __all__ = sorted(_EXPORTS)
 
 

@@ -345,6 +345,24 @@ class PairwiseLaplaceArgs(_Args):
                        ("iters", _D), ("status", _D), ("work", _D), ("work_size", c_int64)]
 
 
+WARP_MAX_DIM = 64  # bo_input_warp*, bo_mll_dx: input dimensions of one launch
+
+
+class InputWarpArgs(_Args):
+    _fields_ = _HDR + [("d", c_int32), ("_pad", c_int32), ("R", c_int64),
+                       ("warped_mask", ctypes.c_uint64), ("X", _D), ("offset", _D),
+                       ("rscale", _D), ("conc1", _D), ("conc0", _D), ("eps", c_double),
+                       ("Z", _D), ("dZ", _D), ("dX", _D), ("da", _D), ("db", _D), ("work", _D),
+                       ("work_size", c_int64)]
+
+
+class MllDxArgs(_Args):
+    _fields_ = _HDR + [("kind", c_int32), ("d", c_int32), ("form", c_int32), ("_pad", c_int32),
+                       ("n", c_int64), ("ld", c_int64), ("X", _D), ("lengthscale", _D),
+                       ("outputscale", c_double), ("Ainv", _D), ("alpha", _D), ("dX", _D),
+                       ("work", _D), ("work_size", c_int64)]
+
+
 class PathsArgs(_Args):
     _fields_ = _HDR + [("kind", c_int32), ("d", c_int32), ("S", c_int32), ("M", c_int32),
                        ("R", c_int64), ("n", c_int64), ("inner", c_int64), ("X", _D),
@@ -486,8 +504,15 @@ PAIRWISE_RECORD_ENTRIES = {"bo_pairwise_laplace": PairwiseLaplaceArgs}
 PAIRWISE_ARG_RECORDS = {"BoPairwiseLaplaceArgs": PairwiseLaplaceArgs}
 _SIGNATURES["bo_pairwise_laplace_work"] = (c_int, [c_int64, c_int64, c_int, c_int64,
                                                    POINTER(c_int64)])
+# the input transforms and the MLL's input gradient of warp.hip, likewise
+WARP_RECORD_ENTRIES = {"bo_input_warp": InputWarpArgs, "bo_input_warp_bwd": InputWarpArgs,
+                       "bo_mll_dx": MllDxArgs}
+WARP_ARG_RECORDS = {"BoInputWarpArgs": InputWarpArgs, "BoMllDxArgs": MllDxArgs}
+_SIGNATURES["bo_input_warp_work"] = (c_int, [c_int64, c_int, POINTER(c_int64)])
+_SIGNATURES["bo_mll_dx_work"] = (c_int, [c_int64, c_int, POINTER(c_int64)])
 for _name, _cls in {**PLAIN_RECORD_ENTRIES, **ICM_RECORD_ENTRIES, **MIXED_RECORD_ENTRIES,
-                    **LTF_RECORD_ENTRIES, **PAIRWISE_RECORD_ENTRIES}.items():
+                    **LTF_RECORD_ENTRIES, **PAIRWISE_RECORD_ENTRIES,
+                    **WARP_RECORD_ENTRIES}.items():
     _SIGNATURES[_name] = (c_int, [POINTER(_cls), _P])
 _SIGNATURES["bo_post_backward_jobs"] = (c_int, [c_int, POINTER(POINTER(PostBackwardArgs)), _P, _P])
 ARG_RECORDS = {"BoPostPartialsArgs": PostPartialsArgs, "BoQmcFinalizeArgs": QmcFinalizeArgs,
@@ -525,7 +550,8 @@ def lib():
                 f"{LIB_PATH} has ABI {handle.bo_version()}, expected {ABI_VERSION}: rebuild with `make`")
         for cname, rec in {**ARG_RECORDS, **PLAIN_ARG_RECORDS, **ICM_ARG_RECORDS,
                            **MIXED_ARG_RECORDS, **LTF_ARG_RECORDS,
-                           **PAIRWISE_ARG_RECORDS}.items():  # layouts agree with the C header
+                           **PAIRWISE_ARG_RECORDS,
+                           **WARP_ARG_RECORDS}.items():  # layouts agree with the C header
             if handle.bo_struct_size(cname.encode()) != sizeof(rec):
                 raise NativeLibraryMissing(f"{cname}: ctypes layout differs from the library's")
         _lib = handle

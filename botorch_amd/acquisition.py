@@ -33,6 +33,7 @@ from .objective import (ConstrainedMCObjective, GenericMCObjective, IdentityMCOb
                         compute_best_feasible_objective, compute_feasibility_indicator,
                         compute_smoothed_feasibility_indicator, repeat_to_match_aug_dim, _as_etas,
                         _linear_outcome_constraints)
+from . import models as _models
 from .models import prime_prediction_caches
 from .posteriors import FUSED_QMAX
 from .sampling import (ListSampler, MCSampler, ShapeOnlyPosterior, SobolQMCNormalSampler,
@@ -55,6 +56,35 @@ def _cache_dim_ok(model, X: torch.Tensor) -> bool:
     return not model.__dict__.get("_is_multitask") or X.shape[-1] == model._d
 
 
+def _transformed_members(model) -> list:
+    """The single-output models under ``model`` that hold an input transform."""
+    out = []
+    if model is None:
+        return out
+    if getattr(model, "_modules", {}).get("input_transform") is not None:
+        out.append(model)
+    subs = getattr(model, "models", None)
+    if subs is not None:
+        for mm in subs:
+            out += _transformed_members(mm)
+    return out
+
+
+class _transform_suppressed:
+    """While open, ``posterior`` of these models takes its points as already transformed."""
+
+    def __init__(self, members):
+        self.members = members
+
+    def __enter__(self):  # a depth count: nested and concurrent uses each undo their own
+        for mm in self.members:
+            mm.__dict__["_tf_suppressed"] = mm.__dict__.get("_tf_suppressed", 0) + 1
+
+    def __exit__(self, *exc):
+        for mm in self.members:
+            mm.__dict__["_tf_suppressed"] -= 1
+
+
 class AcquisitionFunction(nn.Module):
     """acquisition/acquisition.py:33-74."""
 
@@ -63,9 +93,32 @@ class AcquisitionFunction(nn.Module):
     _admits_multitask = False
     _admits_ltf = False  # the classes beyond those whose routes go through model.moments
     _admits_pairwise = False  # likewise, beyond the multi-task audit: qSimpleRegret
+    # audited for a model with an input transform: forward touches its points only through X
+    # and X_pending, both transformed once in __call__, with posterior's own transform off
+    _admits_input_transform = False
+    _input_tf_list = False  # a ModelListGP whose members hold transforms (set in __init__)
 
     def __init__(self, model):
         super().__init__()
+        self._input_tf_models = _transformed_members(model)
+        if self._input_tf_models and not self._admits_input_transform:
+            raise UnsupportedError(
+                f"{type(self).__name__}: a model with an input_transform is not on the "
+                "accelerated path of this acquisition function (admitted: qExpectedImprovement, "
+                "qLogExpectedImprovement, qNoisyExpectedImprovement, "
+                "qLogNoisyExpectedImprovement, qUpperConfidenceBound, ExpectedImprovement, "
+                "LogExpectedImprovement, UpperConfidenceBound, PosteriorMean)")
+        # a ModelListGP's members hold transforms of their own, so X cannot be transformed
+        # once: every member's posterior transforms its input, the class keeps to its route
+        # through model.posterior, and its fused list routes stay ineligible
+        self._input_tf_list = False
+        if self._input_tf_models and not isinstance(model, _models.SingleTaskGP):
+            if not isinstance(model, _models.ModelListGP):
+                raise UnsupportedError(
+                    f"{type(self).__name__}: input transforms are admitted on a SingleTaskGP or "
+                    f"a ModelListGP of them, not inside a {type(model).__name__}")
+            self._input_tf_list = True
+            self._input_tf_models = []
         if getattr(model, "_is_multitask", False) and not self._admits_multitask:
             raise UnsupportedError(
                 f"{type(self).__name__}: MultiTaskGP is not on the accelerated path of this "
@@ -104,6 +157,31 @@ class AcquisitionFunction(nn.Module):
                 "UpperConfidenceBound, PosteriorMean)")
         self.model = model
         self.X_pending = None
+
+    def __call__(self, X, *args, **kwargs):
+        members = self.__dict__.get("_input_tf_models")
+        if not members:
+            return super().__call__(X, *args, **kwargs)
+        # every member of a multi-output SingleTaskGP shares one (Normalize-only) transform
+        tf = members[0]._modules["input_transform"]
+        pending, baseline = self.X_pending, self._buffers.get("X_baseline")
+        try:
+            if pending is not None:
+                self.X_pending = tf.eval_transform(pending.to(torch.float64)).detach()
+            if baseline is not None:
+                # transformed once per state of the transform and of the buffer
+                key = (tf.state_key(), baseline.data_ptr(), baseline._version)
+                hit = self.__dict__.get("_baseline_tf")
+                if hit is None or hit[0] != key:
+                    hit = self.__dict__["_baseline_tf"] = (
+                        key, tf.eval_transform(baseline).detach())
+                self._buffers["X_baseline"] = hit[1]
+            with _transform_suppressed(members):
+                return super().__call__(tf.eval_transform(X.to(torch.float64)), *args, **kwargs)
+        finally:
+            self.X_pending = pending
+            if baseline is not None:
+                self._buffers["X_baseline"] = baseline
 
     def set_X_pending(self, X_pending: Optional[torch.Tensor] = None) -> None:
         if X_pending is not None:
@@ -167,7 +245,7 @@ class MCAcquisitionFunction(AcquisitionFunction):
 
     def _fused_eligible(self, X: torch.Tensor) -> bool:
         m = self.model
-        return (hasattr(m, "prediction_cache") and type(self.objective) is IdentityMCObjective
+        return (not self._input_tf_list and hasattr(m, "prediction_cache") and type(self.objective) is IdentityMCObjective
                 and self.posterior_transform is None and self._constraints is None
                 and X.shape[-2] <= FUSED_QMAX and X.shape[-1] <= kernels.DP and X.is_cuda
                 and len(self.sample_shape) == 1 and _cache_dim_ok(m, X))
@@ -293,6 +371,8 @@ class qExpectedImprovement(MCAcquisitionFunction):
     """MC batch EI (acquisition/monte_carlo.py:332-414):
     qEI(X) = E[max_j max(Y_j - best_f, 0)], optionally weighted by smoothed
     outcome constraints (``constraints``, ``eta``)."""
+
+    _admits_input_transform = True
 
     _admits_multitask = True
 
@@ -473,6 +553,8 @@ class qUpperConfidenceBound(_PlainMaxMCAcquisitionFunction):
     beta' = sqrt(beta pi / 2) and mu the mean of the samples (not of the
     posterior), as the reference computes it."""
 
+    _admits_input_transform = True
+
     _admits_multitask = True
 
     _fused_mode = _lib.QMC_QUCB
@@ -529,6 +611,8 @@ class AnalyticAcquisitionFunction(AcquisitionFunction):
 class ExpectedImprovement(AnalyticAcquisitionFunction):
     """acquisition/analytic.py:298-354: sigma (phi(u) + u Phi(u)), u = (mu - best_f)/sigma."""
 
+    _admits_input_transform = True
+
     _admits_multitask = True
 
     def __init__(self, model, best_f, posterior_transform=None, maximize=True):
@@ -563,6 +647,8 @@ class ProbabilityOfImprovement(AnalyticAcquisitionFunction):
 class UpperConfidenceBound(AnalyticAcquisitionFunction):
     """acquisition/analytic.py (UCB): mu + sqrt(beta) sigma."""
 
+    _admits_input_transform = True
+
     _admits_multitask = True
 
     def __init__(self, model, beta, posterior_transform=None, maximize=True):
@@ -578,6 +664,8 @@ class UpperConfidenceBound(AnalyticAcquisitionFunction):
 
 class PosteriorMean(AnalyticAcquisitionFunction):
     """acquisition/analytic.py (PosteriorMean): mu, or -mu with ``maximize=False``."""
+
+    _admits_input_transform = True
 
     _admits_multitask = True
 
@@ -642,7 +730,7 @@ class _MomentChainAcquisition(AnalyticAcquisitionFunction):
         return []
 
     def _fused_applies(self, X3: torch.Tensor) -> bool:
-        if not X3.is_cuda or self.posterior_transform is not None:
+        if not X3.is_cuda or self.posterior_transform is not None or self._input_tf_list:
             return False
         members = _exact_members(self.model)
         if members is None:
@@ -709,6 +797,8 @@ class LogExpectedImprovement(_MomentChainAcquisition):
     """acquisition/analytic.py:356-416: log EI(x) = log_ei(u) + log sigma with
     u = (mu - best_f) / sigma; finite, with a usable gradient, where EI itself
     underflows to 0."""
+
+    _admits_input_transform = True
 
     _admits_multitask = True
 
@@ -2128,6 +2218,7 @@ class qNoisyExpectedImprovement(MCAcquisitionFunction):
     """
 
     _admits_multitask = True
+    _admits_input_transform = True  # X_baseline: see _init_baseline
 
     _fused_mode = _lib.QMC_QNEI
 
@@ -2139,6 +2230,26 @@ class qNoisyExpectedImprovement(MCAcquisitionFunction):
         self._init_baseline(model, X_baseline, prune_baseline, cache_root, marginalize_dim)
 
     def _init_baseline(self, model, X_baseline, prune_baseline, cache_root, marginalize_dim):
+        """A model with an input transform: everything cached here (the baseline root, its
+        samples, the scaled baseline rows of the fused route) is built on the transformed
+        baseline with ``posterior``'s own transform off, as every later call runs; the
+        ``X_baseline`` buffer keeps the raw (pruned) points, which ``__call__`` transforms."""
+        members = self._input_tf_models
+        if not members:
+            return self._init_baseline_on(model, X_baseline, prune_baseline, cache_root,
+                                          marginalize_dim)
+        if prune_baseline:  # on the raw points: posterior transforms them
+            X_baseline = prune_inferior_points(model, X_baseline, objective=self.objective,
+                                               posterior_transform=self.posterior_transform,
+                                               constraints=self._constraints,
+                                               marginalize_dim=marginalize_dim)
+        tf = members[0]._modules["input_transform"]
+        with _transform_suppressed(members):
+            self._init_baseline_on(model, tf.eval_transform(X_baseline.to(torch.float64)).detach(),
+                                   False, cache_root, marginalize_dim)
+        self._buffers["X_baseline"] = X_baseline
+
+    def _init_baseline_on(self, model, X_baseline, prune_baseline, cache_root, marginalize_dim):
         # outcome constraints on the fused route (per-member cached roots, _FusedSOFeas):
         # a single Sobol sampler; on a model list it must be given (without one the
         # generic route builds a ListSampler, which keeps that route)
@@ -3098,6 +3209,8 @@ def _weighted_so_plan(acqf) -> Optional[_WeightedSOPlan]:
 def _make_weighted_so_plan(acqf) -> Optional[_WeightedSOPlan]:
     cons = acqf._constraints
     if cons is None or len(cons) == 0 or acqf.posterior_transform is not None:
+        return None
+    if acqf._input_tf_list:  # members with transforms of their own: model.posterior only
         return None
     model = acqf.model
     models = getattr(model, "models", None)

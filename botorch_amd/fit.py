@@ -94,6 +94,22 @@ class _Layout:
             ("constant", self.o, 1), ("lengthscale", self.o + 1, self.d)] + (
             [("outputscale", self.o + 1 + self.d, 1)] if self.has_os else [])
         self.size = self.o + 1 + self.d + (1 if self.has_os else 0)
+        # a Warp input transform: concentration0 then concentration1 (the reference's
+        # named_parameters order), len(indices) entries each, bounded below by 1e-4
+        self.norm = self.warp = None
+        tf = model._modules.get("input_transform")
+        if tf is not None:
+            from .transforms import CONCENTRATION_LOWER, split_chain
+            self.norm, self.warp = split_chain(tf)
+        # Normalize alone: X~ is constant during a fit, formed once here
+        self.Xt_const = model.transformed_train_inputs() if (
+            self.norm is not None and self.warp is None) else None
+        if self.warp is not None:
+            k = self.warp.indices.numel()
+            self.segments += [("concentration0", self.size, k), ("concentration1", self.size + k, k)]
+            self.bounds += [(CONCENTRATION_LOWER, None)] * (2 * k)
+            self.kernel_size, self.nwarp = self.size, k
+            self.size += 2 * k
 
     def get(self) -> np.ndarray:
         m = self.model
@@ -102,6 +118,9 @@ class _Layout:
         v += self.base.lengthscale.detach().reshape(-1).cpu().tolist()
         if self.has_os:
             v.append(float(m.covar_module.outputscale.detach()))
+        if self.warp is not None:
+            v += self.warp.concentration0.detach().cpu().tolist()
+            v += self.warp.concentration1.detach().cpu().tolist()
         return np.asarray(v, dtype=np.float64)
 
     def set(self, x: np.ndarray) -> None:
@@ -112,6 +131,10 @@ class _Layout:
         self.base.lengthscale = torch.as_tensor(x[o + 1:o + 1 + self.d]).reshape(1, -1)
         if self.has_os:
             m.covar_module.outputscale = float(x[o + 1 + self.d])
+        if self.warp is not None:
+            ks, k = self.kernel_size, self.nwarp
+            self.warp.concentration0 = x[ks:ks + k]
+            self.warp.concentration1 = x[ks + k:ks + 2 * k]
 
     def value_and_grad(self, x: np.ndarray):
         # the closure reads x, not the module: the parameters are written once,
@@ -162,7 +185,8 @@ class _MultiLayout:
             for p, v in zip(self.parts, xs):
                 mm = p.model
                 noise, const, ls, os_ = _hyper_of(mm, v, p)
-                specs.append(dict(Xt=mm.train_inputs[0], y=mm.train_targets,
+                specs.append(dict(Xt=p.Xt_const if p.Xt_const is not None else mm.train_inputs[0],
+                                  y=mm.train_targets,
                                   lengthscale=torch.as_tensor(ls, dtype=torch.float64,
                                                               device=mm.train_inputs[0].device),
                                   noise=float(noise), constant=float(const), kind=int(mm.kind),
@@ -189,13 +213,16 @@ def _layout(model):
 
 
 def mll_terms(Xt: torch.Tensor, y: torch.Tensor, ls_t: torch.Tensor, noise, const: float,
-              os_: float, kind: int, cache=None):
+              os_: float, kind: int, cache=None, want_dx: bool = False):
     """Data term of [G] ExactMarginalLogLikelihood, ll = log N(y | c, K + s2 I)
     (no priors, not divided by n), and d ll / d [noise, constant,
     lengthscale_1..d, outputscale] (bo::mll's implementation).  ``noise`` may
     be an n-vector (fixed-noise likelihood: K + diag(noise); its gradient
     entry is then meaningless).  ``cache``: the caches of exactly these
-    hyperparameters, already built (the batched multi-output closure)."""
+    hyperparameters, already built (the batched multi-output closure).
+    ``want_dx``: also return d ll / d Xt (n x d, on the device; bo_mll_dx for
+    d <= 64; beyond, kernels.mll_dx raises and the caller -- _warped_value_and_grad --
+    takes its torch route instead of calling this)."""
     n, d = Xt.shape
     dev = Xt.device
     ls = ls_t.detach().cpu().numpy().astype(np.float64) if torch.is_tensor(ls_t) else np.asarray(ls_t)
@@ -212,11 +239,15 @@ def mll_terms(Xt: torch.Tensor, y: torch.Tensor, ls_t: torch.Tensor, noise, cons
         cache = kernels.build_gp_cache(Xt, y, ls_t, noise, const, kind=kind, outputscale=os_,
                                        check_nan=False)  # checked once in fit_gpytorch_mll_scipy
 
+    dx = [None]
+
     def _sums(cache, info):
         # A^{-1} = L^{-T} L^{-1}, lower tiles (n^3/3 flops on the posterior
         # kernel's MFMA tiles, stream-K over the unequal k-ranges)
         Ainv = cache.Ainv if cache.Ainv is not None else kernels.ainv(cache)
         st = kernels._stream(dev)
+        if want_dx:
+            dx[0] = kernels.mll_dx(kind, Xt, ls_t, os_, Ainv, cache.alpha)
         part = torch.empty(n, d + 5, dtype=torch.float64, device=dev)
         check(lib().bo_mll_terms(kind, kernels._p(Xt.contiguous()), n, d, kernels._p(ls_t), os_,
                                  kernels._p(cache.L), kernels._p(Ainv), cache.np,
@@ -244,6 +275,8 @@ def mll_terms(Xt: torch.Tensor, y: torch.Tensor, ls_t: torch.Tensor, noise, cons
     g[1] = sum_alpha                        # d ll / d constant
     g[2:2 + d] = 0.5 * s[:d] / ls ** 3      # d ll / d lengthscale
     g[2 + d] = 0.5 * s[d + 1]               # d ll / d outputscale
+    if want_dx:
+        return float(ll), g, dx[0]
     return float(ll), g
 
 
@@ -270,6 +303,10 @@ def mll_value_and_grad(model: SingleTaskGP, x: np.ndarray, layout: _Layout, cach
     y = model.train_targets
     n, d = Xt.shape
     o = layout.o
+    if getattr(layout, "warp", None) is not None:
+        return _warped_value_and_grad(model, x, layout)
+    if getattr(layout, "Xt_const", None) is not None:
+        Xt = layout.Xt_const
     noise = 0.0 if layout.fixed else x[0]
     nv = model.likelihood.noise if layout.fixed else None
     const = x[o]
@@ -299,6 +336,93 @@ def mll_value_and_grad(model: SingleTaskGP, x: np.ndarray, layout: _Layout, cach
     pv, pg = _prior_terms(layout.base.lengthscale_prior, ls)
     ll += pv
     g[o + 1:o + 1 + d] += pg
+    return -ll / n, -g / n
+
+
+def _mll_torch(Xt, y, ls, noise, const, os_, kind):
+    """ll = log N(y | c, K + diag(noise)) in torch (differentiable in Xt): the route of a
+    warped model beyond d = 64 and on CPU tensors, and the restatement the tests hold the
+    kernels to."""
+    D = (Xt.unsqueeze(1) - Xt.unsqueeze(0)) / ls
+    r2 = (D * D).sum(-1)
+    if kind == _lib.RBF:
+        K = torch.exp(-0.5 * r2)
+    else:
+        r = torch.sqrt(r2.clamp_min(1e-300))  # zero gradient at coincident rows, as the kernel's
+        s5r = math.sqrt(5.0) * r
+        K = (1.0 + s5r + (5.0 / 3.0) * r2) * torch.exp(-s5r)
+    n = Xt.shape[0]
+    A = os_ * K + torch.diag_embed(noise.expand(n))
+    L = torch.linalg.cholesky(A)
+    res = (y - const).unsqueeze(-1)
+    quad = (res * torch.cholesky_solve(res, L)).sum()
+    return -0.5 * quad - torch.log(torch.diagonal(L)).sum() - 0.5 * n * math.log(2 * math.pi)
+
+
+def _warped_value_and_grad(model, x: np.ndarray, layout: "_Layout"):
+    """The closure of a model whose input transform holds a Warp: bo_input_warp on the raw
+    inputs, the cache build and bo_mll_terms on X~, bo_mll_dx, and bo_input_warp_bwd, which
+    contracts d ll / d X~ into the gradients of the concentrations."""
+    Xraw = model.train_inputs[0]
+    y = model.train_targets
+    n, d = Xraw.shape
+    dev = Xraw.device
+    o, ks, k = layout.o, layout.kernel_size, layout.nwarp
+    noise = 0.0 if layout.fixed else x[0]
+    nv = model.likelihood.noise if layout.fixed else None
+    const, ls = x[o], np.asarray(x[o + 1:o + 1 + d], dtype=np.float64)
+    os_ = x[o + 1 + d] if layout.has_os else 1.0
+    b, a = x[ks:ks + k], x[ks + k:ks + 2 * k]
+    warp, norm = layout.warp, layout.norm
+    idx = warp.indices.tolist()
+    f64 = dict(dtype=torch.float64, device=dev)
+    one = np.ones(d)
+    conc1, conc0 = one.copy(), one.copy()
+    conc1[idx], conc0[idx] = a, b
+    if norm is not None:
+        offset, rscale, _, _, _ = norm.columns(d)
+    else:
+        offset, rscale = torch.zeros(d, **f64), torch.ones(d, **f64)
+    spec = kernels.WarpSpec(offset.contiguous(), rscale.contiguous(), torch.as_tensor(conc1, **f64),
+                            torch.as_tensor(conc0, **f64), warp.mask(d), warp._eps)
+    if Xraw.is_cuda and d <= kernels.WARP_MAX_DIM:
+        Xt = kernels.input_warp(Xraw, spec)
+        ll, gall, dXt = mll_terms(Xt, y, ls, nv if nv is not None else float(noise), float(const),
+                                  float(os_), int(model.kind), want_dx=True)
+        _, da, db = kernels.input_warp_bwd(dXt, Xraw, spec)
+        gab = torch.stack([da, db]).cpu().numpy()
+    else:
+        from .transforms import warp_torch
+        c1 = spec.conc1.clone().requires_grad_(True)
+        c0 = spec.conc0.clone().requires_grad_(True)
+        ls_t = torch.as_tensor(ls, **f64).requires_grad_(True)
+        sc = torch.tensor([float(noise), float(const), float(os_)], **f64).requires_grad_(True)
+        Xt = warp_torch(Xraw, spec.offset, spec.rscale, c1, c0, spec.mask, spec.eps)
+        llt = _mll_torch(Xt, y, ls_t, nv if nv is not None else sc[0], sc[1], sc[2],
+                         int(model.kind))
+        llt.backward()
+        ll = float(llt.detach())
+        gall = np.concatenate([sc.grad[:2].cpu().numpy(), ls_t.grad.cpu().numpy(),
+                               sc.grad[2:].cpu().numpy()])
+        gab = torch.stack([c1.grad, c0.grad]).cpu().numpy()
+    g = np.zeros_like(x)
+    if not layout.fixed:
+        g[0] = gall[0]
+        pv, pg = _prior_terms(model.likelihood.noise_prior, np.array([noise]))
+        ll += pv
+        g[0] += pg[0]
+    g[o:o + 1 + d] = gall[1:2 + d]
+    if layout.has_os:
+        g[o + 1 + d] = gall[2 + d]
+    pv, pg = _prior_terms(layout.base.lengthscale_prior, ls)
+    ll += pv
+    g[o + 1:o + 1 + d] += pg
+    for seg, vals, grad, prior in ((slice(ks, ks + k), b, gab[1][idx], warp.concentration0_prior),
+                                   (slice(ks + k, ks + 2 * k), a, gab[0][idx],
+                                    warp.concentration1_prior)):
+        pv, pg = _prior_terms(prior, np.asarray(vals, dtype=np.float64))
+        ll += pv
+        g[seg] = grad + pg
     return -ll / n, -g / n
 
 
@@ -907,6 +1031,8 @@ def _apply_user_bounds(layout, bounds) -> list:
     segs = {name: (start, size) for name, start, size in layout.segments}
     for pname, (lo, hi) in bounds.items():
         seg = names.get(pname)
+        if seg is None and pname.startswith("input_transform."):  # Warp's concentrations
+            seg = pname.rsplit(".", 1)[-1]
         if seg is None or seg not in segs:
             raise UnsupportedError(f"bounds for unknown parameter {pname!r}")
         start, size = segs[seg]

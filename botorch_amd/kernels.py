@@ -3392,3 +3392,91 @@ def pareto_mask(Y: torch.Tensor, maximize: bool = True, deduplicate: bool = True
         check(lib().bo_pareto_mask(_p(Y3[s0:s1]), s1 - s0, n, m, int(maximize), int(deduplicate),
                                    _p(out[s0:s1]), _stream(dev)), "pareto_mask")
     return out.bool().reshape(Y.shape[:-1])
+
+
+# ---- input transforms and the MLL's gradient to the inputs (warp.hip) ---------------------------
+WARP_MAX_DIM = _lib.WARP_MAX_DIM  # bo_input_warp*, bo_mll_dx: input dimensions of one launch
+# bo_mll_dx's contraction: 0 = v_mfma_f64_16x16x4, 1 = FMA on the differences (d < 32 only).
+# None: per instantiation, whichever won tools/bench_warp.py's alternating runs at d = 6, 15
+# and 31: FMA for d < 8 and 16 <= d < 32, MFMA for 8 <= d < 16 and,
+# where no FMA form exists, from d = 32 on
+MLL_DX_FORM = None
+
+
+@dataclass
+class WarpSpec:
+    """One affine + Kumaraswamy column map (transforms.InputTransform.warp_spec): d-vectors
+    on the device, ``mask`` bit c set where column c is warped."""
+    offset: torch.Tensor
+    rscale: torch.Tensor
+    conc1: torch.Tensor
+    conc0: torch.Tensor
+    mask: int
+    eps: float
+
+
+def _aligned_rows(X: torch.Tensor, d: int) -> torch.Tensor:
+    X2 = X.detach().reshape(-1, d).contiguous()
+    return X2 if X2.data_ptr() % 16 == 0 else X2.clone()
+
+
+def _warp_args(X2, spec: WarpSpec, **extra):
+    R, d = X2.shape
+    if not 1 <= d <= WARP_MAX_DIM:
+        raise ValueError(f"input_warp: d={d} (1..{WARP_MAX_DIM})")
+    return _lib.InputWarpArgs(d=d, R=R, warped_mask=spec.mask & ((1 << 64) - 1), X=X2, offset=spec.offset,
+                              rscale=spec.rscale, conc1=spec.conc1, conc0=spec.conc0,
+                              eps=float(spec.eps), **extra)
+
+
+def input_warp(X: torch.Tensor, spec: WarpSpec) -> torch.Tensor:
+    """Z = warp(normalize(X)) on the rows of X (... x d), bo_input_warp."""
+    dev = _dev(X, spec.offset, spec.rscale, spec.conc1, spec.conc0)
+    X2 = _aligned_rows(X, X.shape[-1])
+    Z = torch.empty_like(X2)
+    if X2.shape[0]:
+        check(lib().bo_input_warp(ctypes.byref(_warp_args(X2, spec, Z=Z)), _stream(dev)),
+              "input_warp")
+    return Z.reshape(X.shape)
+
+
+def input_warp_bwd(dZ: torch.Tensor, X: torch.Tensor, spec: WarpSpec):
+    """(dX, d conc1, d conc0) of bo_input_warp: dX like X, the others d-vectors."""
+    dev = _dev(X, dZ)
+    d = X.shape[-1]
+    X2, dZ2 = _aligned_rows(X, d), _aligned_rows(dZ, d)
+    f64 = dict(dtype=torch.float64, device=dev)
+    dX = torch.empty_like(X2)
+    da, db = torch.empty(d, **f64), torch.empty(d, **f64)
+    we = ctypes.c_int64()
+    check(lib().bo_input_warp_work(X2.shape[0], d, ctypes.byref(we)), "input_warp_work")
+    work = torch.empty(max(1, we.value), **f64)
+    if X2.shape[0] == 0:  # nothing to launch on: an empty dX and zero sums
+        return dX.reshape(X.shape), torch.zeros(d, **f64), torch.zeros(d, **f64)
+    a = _warp_args(X2, spec, dZ=dZ2, dX=dX, da=da, db=db, work=work, work_size=work.numel())
+    check(lib().bo_input_warp_bwd(ctypes.byref(a), _stream(dev)), "input_warp_bwd")
+    return dX.reshape(X.shape), da, db
+
+
+def mll_dx(kind: int, X: torch.Tensor, lengthscale: torch.Tensor, outputscale: float,
+           Ainv: torch.Tensor, alpha: torch.Tensor, form: Optional[int] = None) -> torch.Tensor:
+    """d ll / d X (n x d) of the exact MLL on bo_mll_terms' operands (Ainv: bo_ainv's lower
+    tiles, np x np), bo_mll_dx."""
+    dev = _dev(X, lengthscale, Ainv, alpha)
+    n, d = X.shape
+    if not 1 <= d <= WARP_MAX_DIM:
+        raise ValueError(f"mll_dx: d={d} (1..{WARP_MAX_DIM})")
+    if form is None:
+        form = MLL_DX_FORM if MLL_DX_FORM is not None else (
+            0 if (8 <= d < 16 or d >= 32) else 1)
+    f64 = dict(dtype=torch.float64, device=dev)
+    dX = torch.empty(n, d, **f64)
+    we = ctypes.c_int64()
+    check(lib().bo_mll_dx_work(n, d, ctypes.byref(we)), "mll_dx_work")
+    work = torch.empty(max(1, we.value), **f64)
+    a = _lib.MllDxArgs(kind=kind, d=d, form=form, n=n, ld=Ainv.shape[-1], X=X.contiguous(),
+                       lengthscale=lengthscale.reshape(-1).contiguous(),
+                       outputscale=float(outputscale), Ainv=Ainv, alpha=alpha.contiguous(), dX=dX,
+                       work=work, work_size=work.numel())
+    check(lib().bo_mll_dx(ctypes.byref(a), _stream(dev)), "mll_dx")
+    return dX

@@ -1302,6 +1302,56 @@ def _(X, comp, inc_ptr, inc, hyper, kind, f_init=None, jitter=0.0, tol=1e-13, ma
             e(C, dt=torch.int32), e(C, dt=torch.int32)]
 
 
+# ---- bo::input_warp (Normalize + Kumaraswamy Warp in one pass, warp.hip) ------------------------
+def _warp_spec(offset, rscale, conc1, conc0, mask, eps):
+    return kernels.WarpSpec(offset.detach().contiguous(), rscale.detach().contiguous(),
+                            conc1.detach().contiguous(), conc0.detach().contiguous(), mask, eps)
+
+
+@torch.library.custom_op("bo::input_warp", mutates_args=(), device_types="cuda")
+def input_warp(X: Tensor, offset: Tensor, rscale: Tensor, conc1: Tensor, conc0: Tensor, mask: int,
+               eps: float) -> Tensor:
+    """Z = warp((X - offset) rscale) on the rows of X (... x d): the Kumaraswamy CDF with
+    concentrations (conc1, conc0) on the columns whose bit of ``mask`` is set
+    (kernels.input_warp).  Differentiable in X, conc1 and conc0."""
+    return kernels.input_warp(X, _warp_spec(offset, rscale, conc1, conc0, mask, eps))
+
+
+@input_warp.register_fake
+def _(X, offset, rscale, conc1, conc0, mask, eps):
+    return X.new_empty(X.shape, dtype=F64)
+
+
+@torch.library.custom_op("bo::input_warp_backward", mutates_args=(), device_types="cuda")
+def input_warp_backward(dZ: Tensor, X: Tensor, offset: Tensor, rscale: Tensor, conc1: Tensor,
+                        conc0: Tensor, mask: int, eps: float) -> Tuple[Tensor, Tensor, Tensor]:
+    return kernels.input_warp_bwd(dZ, X, _warp_spec(offset, rscale, conc1, conc0, mask, eps))
+
+
+@input_warp_backward.register_fake
+def _(dZ, X, offset, rscale, conc1, conc0, mask, eps):
+    d = X.shape[-1]
+    return X.new_empty(X.shape, dtype=F64), X.new_empty(d, dtype=F64), X.new_empty(d, dtype=F64)
+
+
+def _warp_setup(ctx, inputs, output):
+    X, offset, rscale, conc1, conc0, mask, eps = inputs
+    ctx.save_for_backward(X, offset, rscale, conc1, conc0)
+    ctx.consts = (mask, eps)
+
+
+def _warp_bwd(ctx, dZ):
+    X, offset, rscale, conc1, conc0 = ctx.saved_tensors
+    dX, da, db = torch.ops.bo.input_warp_backward(dZ.contiguous(), X, offset, rscale, conc1, conc0,
+                                                  *ctx.consts)
+    need = ctx.needs_input_grad
+    return (dX if need[0] else None, None, None, da if need[3] else None,
+            db if need[4] else None, None, None)
+
+
+input_warp.register_autograd(_warp_bwd, setup_context=_warp_setup)
+
+
 OPS: List[str] = ["sobol_normal", "gp_cache", "gp_cache_extend", "chol_jitter", "chol_backward",
                   "post_partials", "qmc_finalize", "gp_posterior", "gp_posterior_backward",
                   "qmc_acq", "qmc_acq_backward", "qehvi", "qehvi_backward", "mll", "kg",
@@ -1311,4 +1361,4 @@ OPS: List[str] = ["sobol_normal", "gp_cache", "gp_cache_extend", "chol_jitter", 
                   "saas_potential", "fantasy_posterior", "fantasy_posterior_backward", "icm_covar",
                   "icm_mll_terms", "icm_task_view", "mixed_covar", "mixed_mll_terms", "mixed_cross",
                   "mixed_cross_grad", "ltf_covar", "ltf_mll_terms", "ltf_cross", "ltf_cross_grad",
-                  "pairwise_laplace"]
+                  "pairwise_laplace", "input_warp", "input_warp_backward"]

@@ -94,6 +94,9 @@ class _Member:
 
     def __init__(self, model):
         from .models import FixedNoiseGaussianLikelihood
+        if model._modules.get("input_transform") is not None:
+            raise UnsupportedError("pathwise sampling: a model with an input_transform is not "
+                                   "on the accelerated path (the paths read the raw inputs)")
         ls, o, noise, c = model.hyper()
         self.kind = int(model.kind)
         self.lengthscale = ls.to(F64).contiguous()

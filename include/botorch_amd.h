@@ -1647,6 +1647,59 @@ int bo_pairwise_laplace(const BoPairwiseLaplaceArgs* a, void* stream);
 /* HOST: doubles of work for a call of C rows. */
 int bo_pairwise_laplace_work(int64_t n, int64_t m, int d, int64_t C, int64_t* elems);
 
+/* ---- Input transforms (botorch/models/transforms/input.py: Normalize, Warp) on R x d rows,
+ * 1 <= d <= 64, in one pass (csrc/warp.hip):
+ *   v = (x - offset_c) rscale_c                        (identity column: offset 0, rscale 1)
+ *   bit c of warped_mask set:  u = clamp(v (1 - 2 eps) + eps, eps, 1 - eps),
+ *     t = a_c log u,  s = log(-expm1(t)),  z = -expm1(b_c s)   (= 1 - (1 - u^a)^b, the
+ *     Kumaraswamy CDF, a = conc1 = concentration1, b = conc0 = concentration0); else z = v.
+ * bo_input_warp writes Z.  bo_input_warp_bwd reads dZ and X and writes dX = dZ dz/dx
+ * (torch.clamp's gradient: 1 on the closed interval), da_c = sum_r dZ dz/da and
+ * db_c = sum_r dZ dz/db (0 on unwarped columns); the sums fold per-workgroup partials in
+ * work (bo_input_warp_work doubles) in a fixed order: no atomics, repeated calls are
+ * bitwise identical.  X, Z, dZ, dX: contiguous and 16-byte aligned.  conc1 / conc0 hold d
+ * entries (read on warped columns only; nullable when warped_mask = 0).
+ * Added within ABI 12 (plain names, as bo_ltf_covar). */
+typedef struct BoInputWarpArgs {
+  BO_STRUCT_HEADER;
+  int32_t d, _pad;
+  int64_t R;
+  uint64_t warped_mask;
+  const double *X, *offset, *rscale, *conc1, *conc0;
+  double eps;
+  double* Z;
+  const double* dZ;
+  double *dX, *da, *db, *work;
+  int64_t work_size;
+} BoInputWarpArgs;
+int bo_input_warp(const BoInputWarpArgs* a, void* stream);
+int bo_input_warp_bwd(const BoInputWarpArgs* a, void* stream);
+/* HOST: doubles of work for bo_input_warp_bwd. */
+int bo_input_warp_work(int64_t R, int d, int64_t* elems);
+
+/* The gradient of the exact marginal log likelihood with respect to the training inputs
+ * (the fit of a Warp input transform), on the operands of bo_mll_terms: with
+ * W = alpha alpha^T - A^{-1} and g_ik of bo_mll_terms (RBF: kbar; Matern-5/2:
+ * 5/3 (1 + sqrt5 r) exp(-sqrt5 r)),
+ *   dX[i][t] = d ll / d x_it = -(outputscale / l_t^2) sum_{k != i} W_ik g_ik (x_it - x_kt).
+ * Ainv: bo_ainv's lower 64 x 64 tiles (a tile above the diagonal is read as its mirror
+ * tile; the upper tiles are never touched), leading dimension ld >= 64 ceil(n / 64).
+ * form 0: the contraction G [X | 1] on v_mfma_f64_16x16x4; form 1: G_ik (x_k - x_i) by FMA
+ * (coincident rows then contribute exact zeros; d < 32).  work: bo_mll_dx_work doubles (column-range
+ * partials, folded in a fixed order: no atomics, bitwise reproducible).  1 <= d <= 64. */
+typedef struct BoMllDxArgs {
+  BO_STRUCT_HEADER;
+  int32_t kind, d, form, _pad;
+  int64_t n, ld;
+  const double *X, *lengthscale;
+  double outputscale;
+  const double *Ainv, *alpha;
+  double *dX, *work;
+  int64_t work_size;
+} BoMllDxArgs;
+int bo_mll_dx(const BoMllDxArgs* a, void* stream);
+int bo_mll_dx_work(int64_t n, int d, int64_t* elems);
+
 /* HOST: sizeof the named record ("BoPostPartialsArgs", ...), -1 if unknown --
  * lets a binding check its declared layout once at load time. */
 int64_t bo_struct_size(const char* name);
