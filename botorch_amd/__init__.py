@@ -37,7 +37,10 @@ _EXPORTS = {"FullyBayesianAcquisitionFunction": "acquisition",
             "AnalyticExpectedUtilityOfBestOption": "pairwise",
             "qExpectedUtilityOfBestOption": "pairwise", "pairwise_laplace_torch": "pairwise",
             "InputTransform": "transforms", "Normalize": "transforms", "Warp": "transforms",
-            "ChainedInputTransform": "transforms"}
+            "ChainedInputTransform": "transforms", "InputPerturbation": "transforms",
+            "RiskMeasureMCObjective": "risk_measures", "CVaR": "risk_measures",
+            "VaR": "risk_measures", "WorstCase": "risk_measures",
+            "Expectation": "risk_measures"}
 __all__ = sorted(_EXPORTS)
 
 

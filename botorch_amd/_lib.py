@@ -363,6 +363,14 @@ class MllDxArgs(_Args):
                        ("work", _D), ("work_size", c_int64)]
 
 
+class QmcRiskArgs(_Args):
+    _fields_ = _HDR + [("q", c_int32), ("n_w", c_int32), ("k", c_int32), ("kind", c_int32),
+                       ("mode", c_int32), ("fat", c_int32), ("B", c_int64), ("S", c_int64),
+                       ("mean", _D), ("L", _D), ("Z", _D), ("best_f", c_double),
+                       ("tau_relu", c_double), ("tau_max", c_double), ("acq", _D), ("dacq", _D),
+                       ("dmean", _D), ("dL", _D)]
+
+
 class PathsArgs(_Args):
     _fields_ = _HDR + [("kind", c_int32), ("d", c_int32), ("S", c_int32), ("M", c_int32),
                        ("R", c_int64), ("n", c_int64), ("inner", c_int64), ("X", _D),
@@ -510,9 +518,12 @@ WARP_RECORD_ENTRIES = {"bo_input_warp": InputWarpArgs, "bo_input_warp_bwd": Inpu
 WARP_ARG_RECORDS = {"BoInputWarpArgs": InputWarpArgs, "BoMllDxArgs": MllDxArgs}
 _SIGNATURES["bo_input_warp_work"] = (c_int, [c_int64, c_int, POINTER(c_int64)])
 _SIGNATURES["bo_mll_dx_work"] = (c_int, [c_int64, c_int, POINTER(c_int64)])
+# the risk-measure reduction over a wide t-batch of risk.hip, likewise
+RISK_RECORD_ENTRIES = {"bo_qmc_risk": QmcRiskArgs, "bo_qmc_risk_backward": QmcRiskArgs}
+RISK_ARG_RECORDS = {"BoQmcRiskArgs": QmcRiskArgs}
 for _name, _cls in {**PLAIN_RECORD_ENTRIES, **ICM_RECORD_ENTRIES, **MIXED_RECORD_ENTRIES,
                     **LTF_RECORD_ENTRIES, **PAIRWISE_RECORD_ENTRIES,
-                    **WARP_RECORD_ENTRIES}.items():
+                    **WARP_RECORD_ENTRIES, **RISK_RECORD_ENTRIES}.items():
     _SIGNATURES[_name] = (c_int, [POINTER(_cls), _P])
 _SIGNATURES["bo_post_backward_jobs"] = (c_int, [c_int, POINTER(POINTER(PostBackwardArgs)), _P, _P])
 ARG_RECORDS = {"BoPostPartialsArgs": PostPartialsArgs, "BoQmcFinalizeArgs": QmcFinalizeArgs,
@@ -551,7 +562,8 @@ def lib():
         for cname, rec in {**ARG_RECORDS, **PLAIN_ARG_RECORDS, **ICM_ARG_RECORDS,
                            **MIXED_ARG_RECORDS, **LTF_ARG_RECORDS,
                            **PAIRWISE_ARG_RECORDS,
-                           **WARP_ARG_RECORDS}.items():  # layouts agree with the C header
+                           **WARP_ARG_RECORDS,
+                           **RISK_ARG_RECORDS}.items():  # layouts agree with the C header
             if handle.bo_struct_size(cname.encode()) != sizeof(rec):
                 raise NativeLibraryMissing(f"{cname}: ctypes layout differs from the library's")
         _lib = handle

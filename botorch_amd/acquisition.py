@@ -61,12 +61,26 @@ def _transformed_members(model) -> list:
     out = []
     if model is None:
         return out
-    if getattr(model, "_modules", {}).get("input_transform") is not None:
+    tf = getattr(model, "_modules", {}).get("input_transform")
+    if tf is not None and not tf.is_one_to_many:  # (an InputPerturbation: _perturbed_members)
         out.append(model)
     subs = getattr(model, "models", None)
     if subs is not None:
         for mm in subs:
             out += _transformed_members(mm)
+    return out
+
+
+def _perturbed_members(model) -> list:
+    """The models under ``model`` that hold an InputPerturbation."""
+    out = []
+    if model is None:
+        return out
+    tf = getattr(model, "_modules", {}).get("input_transform")
+    if tf is not None and tf.is_one_to_many:
+        out.append(model)
+    for mm in getattr(model, "models", None) or []:
+        out += _perturbed_members(mm)
     return out
 
 
@@ -97,9 +111,21 @@ class AcquisitionFunction(nn.Module):
     # and X_pending, both transformed once in __call__, with posterior's own transform off
     _admits_input_transform = False
     _input_tf_list = False  # a ModelListGP whose members hold transforms (set in __init__)
+    # audited for a SingleTaskGP with an InputPerturbation: every route of the class reaches
+    # the model through model.posterior (which expands X) or through _risk_forward
+    _admits_perturbation = False
+    _perturbed = False  # the model holds an InputPerturbation (set in __init__)
 
     def __init__(self, model):
         super().__init__()
+        if _perturbed_members(model):
+            if not self._admits_perturbation or not isinstance(model, _models.SingleTaskGP):
+                raise UnsupportedError(
+                    f"{type(self).__name__}: a model with an InputPerturbation is not on the "
+                    "accelerated path of this acquisition function (admitted, on a "
+                    "single-output SingleTaskGP: qSimpleRegret, qExpectedImprovement, "
+                    "qLogExpectedImprovement)")
+            self._perturbed = True
         self._input_tf_models = _transformed_members(model)
         if self._input_tf_models and not self._admits_input_transform:
             raise UnsupportedError(
@@ -245,7 +271,7 @@ class MCAcquisitionFunction(AcquisitionFunction):
 
     def _fused_eligible(self, X: torch.Tensor) -> bool:
         m = self.model
-        return (not self._input_tf_list and hasattr(m, "prediction_cache") and type(self.objective) is IdentityMCObjective
+        return (not self._input_tf_list and not self._perturbed and hasattr(m, "prediction_cache") and type(self.objective) is IdentityMCObjective
                 and self.posterior_transform is None and self._constraints is None
                 and X.shape[-2] <= FUSED_QMAX and X.shape[-1] <= kernels.DP and X.is_cuda
                 and len(self.sample_shape) == 1 and _cache_dim_ok(m, X))
@@ -347,6 +373,77 @@ def _fused_mc(X3: torch.Tensor, acqf, mode: int, best_f: float, best_f_s, Z: tor
     kernels.raise_not_psd_deferred(info, jit, type(acqf).__name__)
     return acq
 
+class _QmcRiskFromRoots(torch.autograd.Function):
+    """The fused risk-measure reduction (bo_qmc_risk) on a caller-made root,
+    f_s = mean + L z_s over Q = q n_w points (mean B x Q, L B x Q x Q), as a
+    differentiable function of (mean, L)."""
+
+    @staticmethod
+    def forward(ctx, mean, L, Z, q, n_w, k, kind, mode, best_f, fat, tau_relu, tau_max):
+        ctx.args = (q, n_w, k, kind, mode, best_f, fat, tau_relu, tau_max)
+        acq = kernels.qmc_risk(mean, L, Z, *ctx.args)
+        ctx.save_for_backward(acq, mean, L, Z)
+        return acq
+
+    @staticmethod
+    def backward(ctx, dacq):
+        acq, mean, L, Z = ctx.saved_tensors
+        dmean, dL = kernels.qmc_risk_backward(dacq.contiguous(), acq, mean, L, Z, *ctx.args)
+        return (dmean, dL) + (None,) * 10
+
+
+def _risk_fused_ok(acqf, X: torch.Tensor, mode: int) -> bool:
+    """The fused route of a perturbed model: one of the four risk measures over the
+    transform's n_w with the identity preprocessing function, nothing else between the
+    samples and the reduction, and a t-batch bo_qmc_risk holds."""
+    from .risk_measures import RiskMeasureMCObjective
+    obj, tf = acqf.objective, acqf.model._modules["input_transform"]
+    return (isinstance(obj, RiskMeasureMCObjective) and obj.risk_kind_k() is not None
+            and type(obj.preprocessing_function) is IdentityMCObjective and obj.n_w == tf.n_w
+            and tf.transform_on_eval and acqf.posterior_transform is None
+            and acqf._constraints is None and acqf.X_pending is None and X.is_cuda
+            and len(acqf.sample_shape) == 1 and kernels.qmc_risk_ok(X.shape[-2], tf.n_w)
+            and (mode == _lib.QMC_QSR or acqf.best_f.numel() == 1))
+
+
+def _risk_forward(acqf, X: torch.Tensor, mode: int) -> torch.Tensor:
+    """qSR / qEI / qLogEI of a risk measure over a perturbed SingleTaskGP.  Fused
+    (_risk_fused_ok): X expanded to its Q = q n_w perturbed copies, the generic moment
+    kernels, the jittered root, then bo_qmc_risk on the sampler's base samples -- the
+    S x B x Q samples never reach memory.  Anything else: the generic route, whose
+    model.posterior expands X the same way.  ``acqf.risk_route`` ("auto", the default;
+    "fused"; "generic") overrides the measured default below."""
+    route = getattr(acqf, "risk_route", "auto")  # "auto" | "fused" | "generic"
+    ok = _risk_fused_ok(acqf, X, mode)
+    if route == "fused" and not ok:
+        raise UnsupportedError(f"{type(acqf).__name__}: risk_route = 'fused', but this "
+                               "configuration is not on the fused risk-measure route")
+    # measured (DESIGN.md section 29, profiles/risk/bench.json): the moments and the root
+    # dominate both routes; the fused reduction's slowest run beats the generic route's
+    # fastest only forward-only at n_w = 16, and with a gradient (one workgroup per
+    # t-batch, B = 16) it loses at every shape measured -- those calls stay generic
+    auto = acqf.model._modules["input_transform"].n_w <= 16 and not (
+        torch.is_grad_enabled() and X.requires_grad)
+    if not ok or route == "generic" or (route == "auto" and not auto):
+        return acqf._generic_forward(acqf._concat_pending(X))
+    from .posteriors import _CholJitter, posterior_moments
+    model = acqf.model
+    tf = model._modules["input_transform"]
+    batch, q, n_w = X.shape[:-2], X.shape[-2], tf.n_w
+    model.eval()
+    Xe = tf.eval_transform(X.to(torch.float64)).reshape(-1, q * n_w, X.shape[-1])
+    mean, cov = posterior_moments(model, Xe)
+    L = _CholJitter.apply(cov) if torch.is_grad_enabled() and cov.requires_grad \
+        else kernels.chol_jitter(cov)
+    Z = acqf._ensure_sampler().base_samples_2d(q * n_w, X.device)
+    kind, k = acqf.objective.risk_kind_k()
+    fat, tau_relu, tau_max = getattr(acqf, "_log_params", None) or (True, 1.0, 1.0)
+    best_f = 0.0 if mode == _lib.QMC_QSR else _host_scalar(acqf, "best_f")
+    acq = _QmcRiskFromRoots.apply(mean, L, Z, q, n_w, k, kind, mode, best_f, bool(fat),
+                                  float(tau_relu), float(tau_max))
+    return acq.reshape(batch).to(X.dtype)
+
+
 def _host_scalar(module, name: str) -> float:
     """float(module.<name>) read once per value: a best_f on the device (the
     usual ``best_f=train_Y.max()``) would otherwise be a device-to-host read,
@@ -375,6 +472,7 @@ class qExpectedImprovement(MCAcquisitionFunction):
     _admits_input_transform = True
 
     _admits_multitask = True
+    _admits_perturbation = True
 
     def __init__(self, model, best_f: Union[float, torch.Tensor], sampler=None, objective=None,
                  posterior_transform=None, X_pending=None, constraints=None, eta=1e-3):
@@ -387,6 +485,8 @@ class qExpectedImprovement(MCAcquisitionFunction):
         return (obj - self.best_f.unsqueeze(-1).to(obj)).clamp_min(0)
 
     def forward(self, X: torch.Tensor) -> torch.Tensor:
+        if self._perturbed:
+            return _risk_forward(self, t_batch_mode(X), _lib.QMC_QEI)
         X = self._concat_pending(t_batch_mode(X))
         batch = X.shape[:-2]
         q, d = X.shape[-2], X.shape[-1]
@@ -493,6 +593,8 @@ class _PlainMaxMCAcquisitionFunction(MCAcquisitionFunction):
         return 0.0, None, None
 
     def forward(self, X: torch.Tensor) -> torch.Tensor:
+        if self._perturbed:
+            return _risk_forward(self, t_batch_mode(X), self._fused_mode)
         X = self._concat_pending(t_batch_mode(X))
         if self._fused_ok(X):
             batch, q = X.shape[:-2], X.shape[-2]
@@ -536,6 +638,7 @@ class qSimpleRegret(_PlainMaxMCAcquisitionFunction):
     ``constraints`` argument (use a ConstrainedMCObjective)."""
 
     _admits_pairwise = True
+    _admits_perturbation = True
     _fused_mode = _lib.QMC_QSR
 
     def __init__(self, model, sampler=None, objective=None, posterior_transform=None,
@@ -2559,6 +2662,8 @@ class qLogExpectedImprovement(qExpectedImprovement):
         return logmeanexp(acqval, dim=tuple(range(len(self.sample_shape))))
 
     def forward(self, X: torch.Tensor) -> torch.Tensor:
+        if self._perturbed:
+            return _risk_forward(self, t_batch_mode(X), _lib.QMC_QLOGEI)
         X = self._concat_pending(t_batch_mode(X))
         batch = X.shape[:-2]
         q, d = X.shape[-2], X.shape[-1]

@@ -98,7 +98,7 @@ class _Layout:
         # named_parameters order), len(indices) entries each, bounded below by 1e-4
         self.norm = self.warp = None
         tf = model._modules.get("input_transform")
-        if tf is not None:
+        if tf is not None and not tf.is_one_to_many:  # (an InputPerturbation: prediction only)
             from .transforms import CONCENTRATION_LOWER, split_chain
             self.norm, self.warp = split_chain(tf)
         # Normalize alone: X~ is constant during a fit, formed once here

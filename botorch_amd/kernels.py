@@ -3191,6 +3191,70 @@ def bald_backward(dout: torch.Tensor, mean: torch.Tensor, L: torch.Tensor, Z: to
     return dmean, dL
 
 
+RISK_NW_MAX, RISK_QMAX, RISK_QQ_MAX = 128, 16, 128  # bo_qmc_risk: n_w, q and Q = q n_w
+RISK_CVAR, RISK_VAR = 0, 1                          # BoQmcRiskArgs.kind
+
+
+def qmc_risk_ok(q: int, n_w: int) -> bool:
+    """Whether :func:`qmc_risk` serves q points of n_w perturbations each."""
+    return 2 <= n_w <= RISK_NW_MAX and 1 <= q <= RISK_QMAX and q * n_w <= RISK_QQ_MAX
+
+
+def _risk_args(mean, L, Z, q, n_w, k, kind, mode, best_f, fat, tau_relu, tau_max, **extra):
+    """The BoQmcRiskArgs of :func:`qmc_risk` / :func:`qmc_risk_backward`: mean B x Q, L
+    B x Q x Q (lower root), Z S x Q, Q = q n_w.  The limits are the library's to refuse
+    (BO_ERR_ARG -> ValueError)."""
+    if mean.dim() != 2 or L.dim() != 3 or Z.dim() != 2:
+        raise ValueError(f"qmc_risk: mean must be B x Q, L B x Q x Q and Z S x Q, got "
+                         f"{tuple(mean.shape)}, {tuple(L.shape)} and {tuple(Z.shape)}")
+    B, Q = mean.shape
+    if Q != q * n_w or tuple(L.shape) != (B, Q, Q) or Z.shape[1] != Q:
+        raise ValueError(f"qmc_risk: q n_w = {q * n_w}, mean {tuple(mean.shape)}, L "
+                         f"{tuple(L.shape)} and Z {tuple(Z.shape)} disagree")
+    _dev(mean, L, Z)
+    return _lib.QmcRiskArgs(q=int(q), n_w=int(n_w), k=int(k), kind=int(kind), mode=int(mode),
+                            fat=int(bool(fat)), B=B, S=Z.shape[0], mean=mean.contiguous(),
+                            L=L.contiguous(), Z=Z.contiguous(), best_f=float(best_f),
+                            tau_relu=float(tau_relu), tau_max=float(tau_max), **extra)
+
+
+def qmc_risk(mean: torch.Tensor, L: torch.Tensor, Z: torch.Tensor, q: int, n_w: int, k: int,
+             kind: int, mode: int, best_f: float = 0.0, fat: bool = True, tau_relu: float = 1.0,
+             tau_max: float = 1.0) -> torch.Tensor:
+    """acq (B): the mode's reduction (QMC_QSR, QMC_QEI, QMC_QLOGEI) of the risk measure
+    (kind RISK_CVAR: the mean of the k smallest; RISK_VAR: the k-th smallest) of every
+    n_w-block of f = mean + Z L^T (bo_qmc_risk, the record's comment in
+    include/botorch_amd.h).  The S x B x Q samples never reach memory."""
+    acq = torch.empty(mean.shape[0], dtype=torch.float64, device=mean.device)
+    a = _risk_args(mean, L, Z, q, n_w, k, kind, mode, best_f, fat, tau_relu, tau_max, acq=acq)
+    if a.B == 0:
+        return acq
+    check(lib().bo_qmc_risk(ctypes.byref(a), _stream(mean.device)), "qmc_risk")
+    return acq
+
+
+def qmc_risk_backward(dacq: torch.Tensor, acq: torch.Tensor, mean: torch.Tensor, L: torch.Tensor,
+                      Z: torch.Tensor, q: int, n_w: int, k: int, kind: int, mode: int,
+                      best_f: float = 0.0, fat: bool = True, tau_relu: float = 1.0,
+                      tau_max: float = 1.0):
+    """(dmean (B x Q), dL (B x Q x Q, lower triangle; exact zeros above)) of
+    :func:`qmc_risk` from dacq (B) and the forward's acq (read in the log mode).  Every
+    entry is written, nothing to clear."""
+    B, Q = mean.shape
+    if tuple(dacq.shape) != (B,) or tuple(acq.shape) != (B,):
+        raise ValueError(f"qmc_risk_backward: dacq and acq must have shape ({B},), got "
+                         f"{tuple(dacq.shape)} and {tuple(acq.shape)}")
+    dev = _dev(dacq, acq)
+    dmean = torch.empty(B, Q, dtype=torch.float64, device=dev)
+    dL = torch.empty(B, Q, Q, dtype=torch.float64, device=dev)
+    a = _risk_args(mean, L, Z, q, n_w, k, kind, mode, best_f, fat, tau_relu, tau_max,
+                   acq=acq.contiguous(), dacq=dacq.contiguous(), dmean=dmean, dL=dL)
+    if a.B == 0:
+        return dmean, dL
+    check(lib().bo_qmc_risk_backward(ctypes.byref(a), _stream(dev)), "qmc_risk_backward")
+    return dmean, dL
+
+
 SAAS_NMAX = 1024     # bo_saas_potential: one workgroup per row of z, its panel in LDS
 SAAS_DMAX = 256
 

@@ -408,11 +408,21 @@ class SingleTaskGP(Model):
                  mean_module=None, outcome_transform="DEFAULT", input_transform=None):
         super().__init__()
         if input_transform is not None:
-            from .transforms import InputTransform, split_chain
+            from .transforms import InputPerturbation, InputTransform, split_chain
             if not isinstance(input_transform, InputTransform):
                 raise UnsupportedError("input_transform: Normalize, Warp or their chain from "
                                        "botorch_amd.transforms are on the accelerated path")
-            _, warp = split_chain(input_transform)
+            if isinstance(input_transform, InputPerturbation):
+                # prediction only: train_inputs, the fit and the caches never see it
+                if train_Y.dim() == 2 and train_Y.shape[-1] > 1:
+                    raise UnsupportedError("a multi-output SingleTaskGP with an "
+                                           "InputPerturbation is not on the accelerated path")
+                if input_transform.transform_on_train:
+                    raise UnsupportedError("InputPerturbation(transform_on_train=True) is not on "
+                                           "the accelerated path")
+                warp = None
+            else:
+                _, warp = split_chain(input_transform)
             if warp is not None and train_Y.dim() == 2 and train_Y.shape[-1] > 1:
                 raise UnsupportedError(
                     "a multi-output SingleTaskGP with a Warp input transform is not on the "
@@ -723,6 +733,9 @@ class SingleTaskGP(Model):
         if kwargs:
             raise UnsupportedError("condition_on_observations: unsupported arguments "
                                    f"{sorted(kwargs)}")
+        if getattr(self._modules.get("input_transform"), "is_one_to_many", False):
+            raise UnsupportedError("condition_on_observations: a SingleTaskGP with an "
+                                   "InputPerturbation is not on the accelerated path")
         if X.dim() > 2 or Y.dim() > 2 or (noise is not None and noise.dim() > 2):
             raise UnsupportedError("condition_on_observations takes X k x d and Y k x m here: "
                                    "batched fantasy models are not on the accelerated path")

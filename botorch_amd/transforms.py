@@ -277,6 +277,80 @@ class Warp(InputTransform):
         return torch.where(flag, x, X)
 
 
+class InputPerturbation(InputTransform):
+    """Each input with a fixed set of perturbations added (or multiplied in)
+    (input.py:1316-1441): ``batch x q x d`` becomes ``batch x (q n_w) x d``, the n_w
+    perturbed copies of input i in rows ``i n_w .. (i + 1) n_w``, clamped to ``bounds``
+    when given.  With a risk measure (``risk_measures``) as the MC objective this is
+    risk-averse optimisation under input noise.  ``perturbation_set``: an n_w x d' tensor,
+    d' = len(indices) or d; a callable set (input-dependent perturbations) is not on the
+    accelerated path.  It applies at prediction only: the training inputs stay as they are."""
+
+    is_one_to_many = True
+    transform_on_fantasize = False
+
+    def __init__(self, perturbation_set: Tensor, bounds: Optional[Tensor] = None,
+                 indices: Optional[List[int]] = None, multiplicative: bool = False,
+                 transform_on_train: bool = False, transform_on_eval: bool = True):
+        super().__init__()
+        if not isinstance(perturbation_set, Tensor):
+            raise UnsupportedError("InputPerturbation: a callable perturbation_set is not on the "
+                                   "accelerated path (pass an n_w x d tensor)")
+        if perturbation_set.dim() != 2:
+            raise ValueError("`perturbation_set` must be an `n_p x d`-dim tensor!")
+        self.register_buffer("perturbation_set", perturbation_set.to(torch.float64))
+        if bounds is not None:
+            if bounds.shape[-1] != perturbation_set.shape[-1]:
+                raise ValueError("`bounds` must have the same number of columns (last dimension) "
+                                 f"as the `perturbation_set`! Got {bounds.shape[-1]} and "
+                                 f"{perturbation_set.shape[-1]}.")
+            self.register_buffer("bounds", bounds.to(torch.float64))
+        else:
+            self.bounds = None
+        self.indices = None if indices is None else [int(i) for i in indices]
+        if self.indices is not None and len(self.indices) != perturbation_set.shape[-1]:
+            raise ValueError(f"InputPerturbation: {len(self.indices)} indices for a "
+                             f"perturbation_set of {perturbation_set.shape[-1]} columns")
+        self.multiplicative = bool(multiplicative)
+        self.transform_on_train = bool(transform_on_train)
+        self.transform_on_eval = bool(transform_on_eval)
+        self.reverse = False
+        self.batch_shape = torch.Size()
+
+    @property
+    def n_w(self) -> int:
+        return self.perturbation_set.shape[0]
+
+    def columns(self, d: int):
+        raise UnsupportedError("InputPerturbation is no per-column map")
+
+    def transform(self, X: Tensor) -> Tensor:
+        p = self.perturbation_set.to(X)
+        n_w, q, d = p.shape[0], X.shape[-2], X.shape[-1]
+        if (p.shape[1] if self.indices is None else max(self.indices) + 1) > d or (
+                self.indices is None and p.shape[1] != d):
+            raise ValueError(f"Wrong input dimension. Received {d}, the perturbation_set has "
+                             f"{p.shape[1]} columns.")
+        Xe = X.unsqueeze(-2).expand(*X.shape[:-1], n_w, d)  # ... x q x n_w x d
+        sub = Xe if self.indices is None else Xe[..., self.indices]
+        sub = sub * p if self.multiplicative else sub + p
+        if self.bounds is not None:
+            b = self.bounds.to(X)
+            sub = torch.maximum(torch.minimum(sub, b[1]), b[0])
+        if self.indices is None:
+            Y = sub
+        else:
+            idx = torch.tensor(self.indices, device=X.device)
+            Y = Xe.index_copy(-1, idx, sub)
+        return Y.reshape(*X.shape[:-2], q * n_w, d)
+
+    def eval_transform(self, X: Tensor) -> Tensor:
+        return self.transform(X) if self.transform_on_eval else X
+
+    def untransform(self, X: Tensor) -> Tensor:
+        raise UnsupportedError("InputPerturbation: a one-to-many transform has no inverse")
+
+
 class ChainedInputTransform(InputTransform):
     """input.py:158-260: the members applied in order.  Normalize followed directly by
     Warp runs as one pass of the kernel."""
@@ -285,6 +359,10 @@ class ChainedInputTransform(InputTransform):
         super().__init__()
         self._names = list(transforms)
         for name, tf in transforms.items():
+            if isinstance(tf, InputPerturbation):
+                raise UnsupportedError(f"ChainedInputTransform: member {name!r} is an "
+                                       "InputPerturbation, which is on the accelerated path "
+                                       "only as a model's sole input transform")
             if not isinstance(tf, InputTransform) or isinstance(tf, ChainedInputTransform):
                 raise UnsupportedError(f"ChainedInputTransform: member {name!r} is not a "
                                        "Normalize or Warp of this library")
@@ -358,4 +436,5 @@ def split_chain(tf: InputTransform):
         f"order are on the accelerated path, got {[k.__name__ for k in kinds]}")
 
 
-__all__ = ["InputTransform", "Normalize", "Warp", "ChainedInputTransform", "warp_torch"]
+__all__ = ["InputTransform", "Normalize", "Warp", "ChainedInputTransform", "InputPerturbation",
+           "warp_torch"]

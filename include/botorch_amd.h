@@ -1700,6 +1700,41 @@ typedef struct BoMllDxArgs {
 int bo_mll_dx(const BoMllDxArgs* a, void* stream);
 int bo_mll_dx_work(int64_t n, int d, int64_t* elems);
 
+/* ---- Risk-averse Monte-Carlo acquisition under input perturbations (botorch/acquisition/
+ * risk_measures.py: CVaR, VaR, WorstCase, Expectation behind an InputPerturbation transform,
+ * models/transforms/input.py) on a wide t-batch of Q = q n_w jointly distributed points
+ * (csrc/risk.hip).  mean (B x Q), L (B x Q x Q, the lower root, leading dimension Q; nothing
+ * above the diagonal is read), Z (S x Q, shared by all t-batches), all fp64:
+ *   f[s][j] = mean_j + sum_{i <= j} L[j][i] Z[s][i]
+ *   r[s][a] = risk of the block f[s][a n_w .. (a + 1) n_w):
+ *     kind 0: the mean of its k smallest entries (WorstCase: k = 1; Expectation: k = n_w;
+ *             CVaR(alpha): k = n_w - (ceil(n_w alpha) - 1));
+ *     kind 1: its k-th smallest entry (VaR(alpha), the same k);
+ *     among equal values the lower index counts as the smaller.
+ *   mode (the values of bo_qmc_finalize_v's modes) reduces r as that entry reduces f:
+ *     BO_QMC_QSR (6):    acq = mean_s max_a r[s][a]
+ *     BO_QMC_QEI (1):    acq = mean_s max_a relu(r[s][a] - best_f)
+ *     BO_QMC_QLOGEI (4): acq = logmeanexp_s u_s, u_s the smoothed maximum over a of
+ *                        log_soft_relu(r[s][a] - best_f) (fat, tau_relu, tau_max as there).
+ * bo_qmc_risk writes acq (B).  bo_qmc_risk_backward reads dacq (B) and, in the log mode, the
+ * forward's acq, and writes dmean (B x Q) and dL (B x Q x Q: the lower triangle, exact zeros
+ * above the diagonal); every entry is written.  One workgroup per t-batch; no atomics, every
+ * sum in a fixed order: repeated calls are bitwise identical and row b of a B-row call equals
+ * the one-row call.  2 <= n_w <= 128, 1 <= q <= 16, Q = q n_w <= 128, 1 <= k <= n_w, S >= 1.
+ * Added within ABI 12 (plain names, as bo_ltf_covar). */
+typedef struct BoQmcRiskArgs {
+  BO_STRUCT_HEADER;
+  int32_t q, n_w, k, kind, mode, fat;
+  int64_t B, S;
+  const double *mean, *L, *Z;
+  double best_f, tau_relu, tau_max;
+  double* acq;        /* bo_qmc_risk: output; bo_qmc_risk_backward: input (log mode) */
+  const double* dacq; /* bo_qmc_risk_backward */
+  double *dmean, *dL;
+} BoQmcRiskArgs;
+int bo_qmc_risk(const BoQmcRiskArgs* a, void* stream);
+int bo_qmc_risk_backward(const BoQmcRiskArgs* a, void* stream);
+
 /* HOST: sizeof the named record ("BoPostPartialsArgs", ...), -1 if unknown --
  * lets a binding check its declared layout once at load time. */
 int64_t bo_struct_size(const char* name);
