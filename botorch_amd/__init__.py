@@ -40,7 +40,9 @@ _EXPORTS = {"FullyBayesianAcquisitionFunction": "acquisition",
             "ChainedInputTransform": "transforms", "InputPerturbation": "transforms",
             "RiskMeasureMCObjective": "risk_measures", "CVaR": "risk_measures",
             "VaR": "risk_measures", "WorstCase": "risk_measures",
-            "Expectation": "risk_measures"}
+            "Expectation": "risk_measures",
+            "qLogNParEGO": "acquisition", "get_chebyshev_scalarization": "multi_objective",
+            "sample_simplex": "utils_sampling"}
 __all__ = sorted(_EXPORTS)
 
 

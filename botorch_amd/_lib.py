@@ -371,6 +371,19 @@ class QmcRiskArgs(_Args):
                        ("dmean", _D), ("dL", _D)]
 
 
+class QmcChebArgs(_Args):
+    _fields_ = _HDR + [("B", c_int32), ("q", c_int32), ("Mt", c_int32), ("S", c_int32),
+                       ("mean", _D), ("L", _D), ("Z", _D), ("F", _D), ("ldF", c_int64),
+                       ("sF", c_int64), ("Qp", c_int32), ("k", c_int32), ("best_f", c_double),
+                       ("best_f_s", _D), ("ca", c_double * 8), ("cb", c_double * 8),
+                       ("alpha", c_double), ("omask", c_int32), ("G", c_int32),
+                       ("chunk", c_int32), ("_pad", c_int32), ("A", c_double * 64),
+                       ("rhs", c_double * 8), ("eta", c_double * 8), ("feas", _D), ("dfeas", _D),
+                       ("log", c_int32), ("fat", c_int32), ("tau_relu", c_double),
+                       ("tau_max", c_double), ("acq", _D), ("dacq", _D), ("dmean", _D),
+                       ("dL", _D), ("dF", _D), ("work", _D), ("work_size", c_int64)]
+
+
 class PathsArgs(_Args):
     _fields_ = _HDR + [("kind", c_int32), ("d", c_int32), ("S", c_int32), ("M", c_int32),
                        ("R", c_int64), ("n", c_int64), ("inner", c_int64), ("X", _D),
@@ -521,9 +534,13 @@ _SIGNATURES["bo_mll_dx_work"] = (c_int, [c_int64, c_int, POINTER(c_int64)])
 # the risk-measure reduction over a wide t-batch of risk.hip, likewise
 RISK_RECORD_ENTRIES = {"bo_qmc_risk": QmcRiskArgs, "bo_qmc_risk_backward": QmcRiskArgs}
 RISK_ARG_RECORDS = {"BoQmcRiskArgs": QmcRiskArgs}
+# the Chebyshev-scalarization (ParEGO) reduction of cheb.hip, likewise
+CHEB_RECORD_ENTRIES = {"bo_qmc_cheb": QmcChebArgs, "bo_qmc_cheb_backward": QmcChebArgs}
+CHEB_ARG_RECORDS = {"BoQmcChebArgs": QmcChebArgs}
 for _name, _cls in {**PLAIN_RECORD_ENTRIES, **ICM_RECORD_ENTRIES, **MIXED_RECORD_ENTRIES,
                     **LTF_RECORD_ENTRIES, **PAIRWISE_RECORD_ENTRIES,
-                    **WARP_RECORD_ENTRIES, **RISK_RECORD_ENTRIES}.items():
+                    **WARP_RECORD_ENTRIES, **RISK_RECORD_ENTRIES,
+                    **CHEB_RECORD_ENTRIES}.items():
     _SIGNATURES[_name] = (c_int, [POINTER(_cls), _P])
 _SIGNATURES["bo_post_backward_jobs"] = (c_int, [c_int, POINTER(POINTER(PostBackwardArgs)), _P, _P])
 ARG_RECORDS = {"BoPostPartialsArgs": PostPartialsArgs, "BoQmcFinalizeArgs": QmcFinalizeArgs,
@@ -563,7 +580,8 @@ def lib():
                            **MIXED_ARG_RECORDS, **LTF_ARG_RECORDS,
                            **PAIRWISE_ARG_RECORDS,
                            **WARP_ARG_RECORDS,
-                           **RISK_ARG_RECORDS}.items():  # layouts agree with the C header
+                           **RISK_ARG_RECORDS,
+                           **CHEB_ARG_RECORDS}.items():  # layouts agree with the C header
             if handle.bo_struct_size(cname.encode()) != sizeof(rec):
                 raise NativeLibraryMissing(f"{cname}: ctypes layout differs from the library's")
         _lib = handle

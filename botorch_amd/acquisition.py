@@ -237,6 +237,9 @@ class MCAcquisitionFunction(AcquisitionFunction):
 
     _default_sample_shape = torch.Size([512])
     _log = False
+    # the Chebyshev-scalarization (ParEGO) route of qEI / qLogEI / qNEI / qLogNEI (_cheb_route):
+    cheb_route = None   # None (the measured default: fused where it applies) | "fused" | "generic"
+    cheb_groups = None  # sample groups per t-batch of bo_qmc_cheb; None: kernels.qmc_cheb_groups
 
     def __init__(self, model, sampler: Optional[MCSampler] = None, objective=None,
                  posterior_transform=None, X_pending=None, constraints=None, eta=1e-3,
@@ -507,6 +510,9 @@ class qExpectedImprovement(MCAcquisitionFunction):
             acq = _weighted_qei_forward(self, X)
             if acq is not None:
                 return acq
+        acq = _weighted_qei_forward(self, X, _cheb_route)  # a Chebyshev scalarization
+        if acq is not None:
+            return acq
         return self._generic_forward(X)
 
 
@@ -2324,6 +2330,7 @@ class qNoisyExpectedImprovement(MCAcquisitionFunction):
     _admits_input_transform = True  # X_baseline: see _init_baseline
 
     _fused_mode = _lib.QMC_QNEI
+    _cheb_default_sampler = False  # sampler=None on a model list may take the fused route
 
     def __init__(self, model, X_baseline, sampler=None, objective=None, posterior_transform=None,
                  X_pending=None, prune_baseline=True, cache_root=True, constraints=None,
@@ -2356,13 +2363,18 @@ class qNoisyExpectedImprovement(MCAcquisitionFunction):
         # outcome constraints on the fused route (per-member cached roots, _FusedSOFeas):
         # a single Sobol sampler; on a model list it must be given (without one the
         # generic route builds a ListSampler, which keeps that route)
-        wplan = _weighted_so_plan(self) if cache_root else None
+        wplan = (_weighted_so_plan(self) or _cheb_plan(self)) if cache_root else None
         if wplan is not None and not (
                 X_baseline.ndim == 2 and X_baseline.shape[-1] <= kernels.DP and X_baseline.is_cuda
                 and X_baseline.shape[-2] > 0 and len(self.sample_shape) == 1
                 and (type(self.sampler) is SobolQMCNormalSampler
-                     or (self.sampler is None and not hasattr(model, "models")))):
+                     or (self.sampler is None and (not hasattr(model, "models")
+                                                   or (self._cheb_default_sampler
+                                                       and isinstance(wplan, _ChebPlan)))))):
             wplan = None
+        if wplan is not None and self.sampler is None and hasattr(model, "models"):
+            # qLogNParEGO's default on the fused route: one Sobol sampler over all members
+            self.sampler = SobolQMCNormalSampler(sample_shape=self._default_sample_shape)
         self._roots = None
         if cache_root and wplan is None and not supports_cache_root(model, self.posterior_transform):
             warnings.warn("`cache_root` is only supported here for exact GPs (or a ModelListGP "
@@ -2520,19 +2532,53 @@ class qNoisyExpectedImprovement(MCAcquisitionFunction):
             obj_full = self.objective(samples_full, X=X_full)
             self.baseline_obj, obj = obj_full[..., :-q], obj_full[..., -q:]
             self.baseline_samples = samples_full[..., :-q, :]
+        elif self._roots is not None and hasattr(posterior, "posteriors"):
+            samples = self._member_joint_samples(posterior, q)
+            obj = self.objective(samples, X=X_full[..., -q:, :])
         else:
             self._set_sampler(q_in=q, posterior=posterior)
             samples = self._get_f_X_samples(posterior=posterior, q_in=q)
             obj = self.objective(samples, X=X_full[..., -q:, :])
         return samples, obj
 
+    def _member_joint_samples(self, posterior, q: int, cached: bool = True) -> torch.Tensor:
+        """The generic route beside the member roots (a model list under ONE Sobol sampler,
+        which no PosteriorList can be drawn from as a whole): member t's joint (r + q)
+        posterior sampled with the base samples the fused route uses -- the member root's
+        own baseline columns, then _base_samples_members' columns p Mt + t -- so the cached
+        per-sample baseline best stays consistent.  ``cached``: the q new rows from member
+        t's cached baseline root (sample_cached_cholesky, as _get_f_X_samples), standard
+        joint sampling after a failure.  -> sample_shape x batch x q x Mt."""
+        Mt = len(posterior.posteriors)
+        Zq = self._base_samples_members(q, Mt, posterior.device)
+        S = Zq.shape[0]
+        Zq = Zq.view(S, q, Mt)
+        out = []
+        for t, p in enumerate(posterior.posteriors):
+            Zt = torch.cat([self._roots[t].Z_base, Zq[:, :, t]], dim=-1)
+            Zt = Zt.reshape(S, *(1,) * len(p.batch_shape), Zt.shape[-1])
+            if cached:
+                try:
+                    out.append(sample_cached_cholesky(posterior=p, baseline_L=self._roots[t].L, q=q,
+                                                      base_samples=Zt, sample_shape=self.sample_shape))
+                    continue
+                except (NanError, NotPSDError):
+                    warnings.warn("Low-rank cholesky updates failed due NaNs or due to an "
+                                  "ill-conditioned covariance matrix. Falling back to standard "
+                                  "sampling.", BotorchWarning)
+            out.append(p.rsample_from_base_samples(self.sample_shape, Zt)[..., -q:, :])
+        return torch.cat(out, dim=-1)
+
     def _fallback_forward(self, X: torch.Tensor) -> torch.Tensor:
         """Standard joint sampling after a failed low-rank update of the fused path
         (cached_cholesky.py:147-165): the cached baseline best is kept."""
         q = X.shape[-2]
         X_full, posterior = self._joint_posterior(X)
-        self._set_sampler(q_in=q, posterior=posterior)
-        samples = self.get_posterior_samples(posterior)[..., -q:, :]
+        if self._roots is not None and hasattr(posterior, "posteriors"):
+            samples = self._member_joint_samples(posterior, q, cached=False)
+        else:
+            self._set_sampler(q_in=q, posterior=posterior)
+            samples = self.get_posterior_samples(posterior)[..., -q:, :]
         obj = self.objective(samples, X=X)
         acqval = self._apply_constraints(self._sample_forward(obj), samples)
         return _ensemble_mean(self.model, self._sample_reduction(self._q_reduction(acqval)))
@@ -2550,7 +2596,7 @@ class qNoisyExpectedImprovement(MCAcquisitionFunction):
                               "sampling.", BotorchWarning)
                 return self._fallback_forward(X)
         if self._roots is not None and self._cache_root:
-            plan = _weighted_so_route(self, X)
+            plan = _weighted_so_route(self, X) or _cheb_route(self, X)
             if plan is not None:
                 try:
                     acq = _FusedSOFeas.apply(X.reshape(-1, q, d).to(torch.float64), self, plan, None, None)
@@ -2560,6 +2606,8 @@ class qNoisyExpectedImprovement(MCAcquisitionFunction):
                                   "ill-conditioned covariance matrix. Falling back to standard "
                                   "sampling.", BotorchWarning)
                     return self._fallback_forward(X)
+        elif getattr(self, "cheb_route", None) == "fused":
+            _cheb_route(self, X)  # raises: no member roots were built
         return self._generic_forward(X)
 
     def _base_samples_members(self, q: int, Mt: int, device) -> torch.Tensor:
@@ -2677,6 +2725,9 @@ class qLogExpectedImprovement(qExpectedImprovement):
             acq = _weighted_qei_forward(self, X)
             if acq is not None:
                 return acq
+        acq = _weighted_qei_forward(self, X, _cheb_route)  # a Chebyshev scalarization
+        if acq is not None:
+            return acq
         return self._generic_forward(X)
 
 
@@ -2710,6 +2761,67 @@ class qLogNoisyExpectedImprovement(qNoisyExpectedImprovement):
 
     def _sample_reduction(self, acqval: torch.Tensor) -> torch.Tensor:
         return logmeanexp(acqval, dim=tuple(range(len(self.sample_shape))))
+
+
+class qLogNParEGO(qLogNoisyExpectedImprovement):
+    """q-LogNParEGO (acquisition/multi_objective/parego.py): qLogNEI of the augmented
+    Chebyshev scalarization of m >= 2 outcomes [Knowles2005, Daulton2020qehvi,
+    Ament2023logei].  All objectives are maximised; a negative entry of
+    ``scalarization_weights`` (default: one draw from the unit simplex) minimises that
+    outcome.  ``Y_baseline`` is the objective of the posterior mean at ``X_baseline``,
+    which fixes the scalarization's normalisation.
+
+    ``objective``: None or an IdentityMCMultiOutputObjective (optionally with
+    ``outcomes``; the other outputs then serve the constraints) is on the fused route
+    (bo_qmc_cheb); any other multi-output objective is composed
+    with the scalarization in a lambda and keeps to the generic route.  Fully Bayesian
+    (ensemble) models are refused: the ensemble mean of ``Y_baseline`` is not built here.
+
+    Unlike the reference, which builds a ListSampler for a model list, ``sampler=None``
+    on a model list builds ONE SobolQMCNormalSampler of the default sample shape over
+    all members (the convention of the fused qNEHVI) where the fused route applies
+    (2 to 8 plain SingleTaskGP members, d <= 8, X_baseline on the device, cache_root):
+    the default construction then takes the fused route, and its generic and fallback
+    paths draw each member's joint samples from that sampler's interleaved columns.
+    Anywhere else ``sampler=None`` stays None and the generic route builds the
+    reference's ListSampler.  ``cheb_route`` (None | "fused" | "generic") overrides the
+    default route."""
+
+    _cheb_default_sampler = True
+
+    def __init__(self, model, X_baseline, scalarization_weights=None, sampler=None,
+                 objective=None, constraints=None, X_pending=None, eta=1e-3, fat: bool = True,
+                 prune_baseline: bool = False, cache_root: bool = True,
+                 tau_relu: float = TAU_RELU, tau_max: float = TAU_MAX):
+        from .multi_objective import get_chebyshev_scalarization
+        from .utils_sampling import sample_simplex
+        if getattr(model, "_is_fully_bayesian", False) or getattr(model, "_is_ensemble", False) \
+                or any(getattr(mm, "_is_fully_bayesian", False) or getattr(mm, "_is_ensemble", False)
+                       for mm in getattr(model, "models", [])):
+            raise UnsupportedError("qLogNParEGO: fully Bayesian (ensemble) models are not "
+                                   "supported")
+        org_objective = objective if objective is not None else IdentityMCMultiOutputObjective()
+        with torch.no_grad():
+            Y_baseline = org_objective(model.posterior(X_baseline).mean)
+        if scalarization_weights is None:
+            scalarization_weights = sample_simplex(d=Y_baseline.shape[-1], device=X_baseline.device,
+                                                   dtype=X_baseline.dtype).view(-1)
+        scalarization = get_chebyshev_scalarization(weights=scalarization_weights, Y=Y_baseline)
+        if type(org_objective) is IdentityMCMultiOutputObjective:
+            outcomes = getattr(org_objective, "outcomes", None)
+            composite = GenericMCObjective(scalarization if outcomes is None else
+                                           scalarization.over_outcomes(outcomes.tolist()))
+        else:
+            composite = GenericMCObjective(
+                lambda samples, X=None: scalarization(org_objective(samples, X=X), X=X))
+        super().__init__(model, X_baseline, sampler=sampler, objective=composite,
+                         X_pending=X_pending, constraints=constraints, eta=eta, fat=fat,
+                         prune_baseline=prune_baseline, cache_root=cache_root, tau_max=tau_max,
+                         tau_relu=tau_relu)
+        self._org_objective = org_objective
+        self.chebyshev_scalarization = scalarization
+        self.scalarization_weights = scalarization_weights
+        self.Y_baseline = Y_baseline
 
 
 # -- qEHVI ---------------------------------------------------------------------------
@@ -3383,12 +3495,13 @@ def _weighted_so_base_samples(acqf, plan, q: int, device) -> Optional[torch.Tens
     return None
 
 
-def _weighted_qei_forward(acqf, X: torch.Tensor) -> Optional[torch.Tensor]:
-    """qEI / qLogEI with outcome constraints on the fused route (X already in
-    t-batch mode with the pending points), or None where it does not apply."""
+def _weighted_qei_forward(acqf, X: torch.Tensor, route=None) -> Optional[torch.Tensor]:
+    """qEI / qLogEI with outcome constraints (``route`` = _cheb_route: over a
+    Chebyshev scalarization) on the fused route (X already in t-batch mode with
+    the pending points), or None where it does not apply."""
     if acqf.best_f.numel() != 1:
         return None
-    plan = _weighted_so_route(acqf, X)
+    plan = (route or _weighted_so_route)(acqf, X)
     if plan is None:
         return None
     q, d = X.shape[-2], X.shape[-1]
@@ -3398,6 +3511,96 @@ def _weighted_qei_forward(acqf, X: torch.Tensor) -> Optional[torch.Tensor]:
     X3 = X.reshape(-1, q, d)
     acq = _FusedSOFeas.apply(X3.to(torch.float64), acqf, plan, Z, _host_scalar(acqf, "best_f"))
     return acq.to(X.dtype).reshape(X.shape[:-2])
+
+
+class _ChebPlan:
+    """What the fused Chebyshev-scalarization (ParEGO) route of qEI / qLogEI / qNEI /
+    qLogNEI needs, fixed at construction: the members, the affine form p_t = ca[t] f_t
+    + cb[t] of the scalarization per member (None for a member outside the objective's
+    outcomes: it enters the constraints only), alpha, and the constraints as
+    _WeightedSOPlan holds them (none: ``constraints`` empty, ``lin`` None), under the
+    names _feas_weights reads."""
+
+    def __init__(self, members, ca, cb, alpha, constraints, lin, fat):
+        self.members, self.ca, self.cb, self.alpha = members, ca, cb, alpha
+        self.constraints, self.lin, self.fat = constraints, lin, fat
+        self.eta = self.etas = None
+
+    def set_eta(self, eta) -> None:
+        if self.etas is None:
+            self.eta = _as_etas(eta, len(self.constraints)).to(torch.float64)
+            self.etas = [float(v) for v in self.eta.tolist()]
+
+
+def _cheb_plan(acqf) -> Optional[_ChebPlan]:
+    """The plan (built once), or None where the route does not apply."""
+    plan = acqf.__dict__.get("_cheb")
+    if plan is None:
+        plan = _make_cheb_plan(acqf) or False
+        acqf.__dict__["_cheb"] = plan
+    return plan or None
+
+
+def _make_cheb_plan(acqf) -> Optional[_ChebPlan]:
+    """A GenericMCObjective over a ChebyshevScalarization that covers the outputs (or
+    its ``outcomes`` of them) of 2 to 8 plain SingleTaskGP members -- a ModelListGP, or
+    a multi-output SingleTaskGP through its ``models``; no posterior transform, no
+    input transforms, no ensembles; at most 8 linear constraints in the kernel, any
+    other callable through _feas_weights."""
+    from .multi_objective import ChebyshevScalarization
+    obj = acqf.objective
+    sc = getattr(obj, "objective", None)
+    if type(obj) is not GenericMCObjective or not isinstance(sc, ChebyshevScalarization):
+        return None
+    if (acqf.posterior_transform is not None or acqf._input_tf_list or acqf._input_tf_models
+            or acqf._perturbed):
+        return None
+    models = getattr(acqf.model, "models", None)
+    if models is None or not 2 <= len(models) <= kernels.QMC_CHEB_MTMAX:
+        return None
+    members = list(models)
+    if any(type(mm) is not _models.SingleTaskGP or not hasattr(mm, "prediction_cache")
+           or hasattr(mm, "models") or getattr(mm, "_is_ensemble", False) for mm in members):
+        return None
+    Mt = len(members)
+    out = sc.outcomes if sc.outcomes is not None else list(range(Mt))
+    if (len(out) != sc.weights.numel() or len(set(out)) != len(out) or len(out) < 2
+            or any(not 0 <= i < Mt for i in out)):
+        return None
+    ca, cb = [None] * Mt, [None] * Mt
+    for i, a, b in zip(out, sc.a.tolist(), sc.b.tolist()):
+        ca[i], cb[i] = float(a), float(b)
+    if not all(math.isfinite(v) for v in ca + cb if v is not None):
+        return None
+    cons = list(acqf._constraints or [])
+    lin = _linear_outcome_constraints(cons) if cons else None
+    if lin is not None and (len(lin[0]) > kernels.QMC_CHEB_KMAX or len(lin[0][0]) != Mt):
+        lin = None
+    return _ChebPlan(members, ca, cb, sc.alpha, cons, lin, acqf._fat)
+
+
+def _cheb_route(acqf, X: torch.Tensor) -> Optional[_ChebPlan]:
+    """The plan where this call takes the fused route: the conditions of
+    _weighted_so_route, and ``acqf.cheb_route`` (None: the measured default of
+    DESIGN.md section 30; "fused": this route or an UnsupportedError; "generic")."""
+    route = getattr(acqf, "cheb_route", None)
+    if route not in (None, "fused", "generic"):
+        raise ValueError(f"cheb_route must be None, 'fused' or 'generic' (got {route!r})")
+    plan = None if route == "generic" else _cheb_plan(acqf)
+    if plan is not None and (not X.is_cuda or X.shape[-2] > kernels.QMC_CHEB_QMAX
+                             or X.shape[-1] > kernels.DP or len(acqf.sample_shape) != 1
+                             or kernels._dev_index(X.device) in kernels._CAPTURE
+                             or (hasattr(acqf, "_roots") and acqf._roots is None)):
+        plan = None
+    if plan is None:
+        if route == "fused":
+            raise UnsupportedError(f"{type(acqf).__name__}: cheb_route = 'fused', but this call "
+                                   "is not on the fused Chebyshev-scalarization route")
+        return None
+    if plan.constraints:
+        plan.set_eta(acqf._eta)
+    plan.fat = acqf._fat
+    return plan
 
 
 def _so_feas_forward(acqf, plan, mean, L, Z, F, Qp: int, best_f: float, best_f_s, need_grad: bool):
@@ -3410,17 +3613,24 @@ def _so_feas_forward(acqf, plan, mean, L, Z, F, Qp: int, best_f: float, best_f_s
     feas = None
     if plan.lin is not None:
         kw.update(A=plan.lin[0], rhs=plan.lin[1], eta=plan.etas)
-    else:
+    elif plan.constraints:
         feas = _feas_weights(plan, mean, L, Z, F, Qp, need_grad, log=acqf._log)
         kw.update(feas=feas[0].detach())
+    if isinstance(plan, _ChebPlan):
+        kw.update(G=acqf.cheb_groups)
+        return kernels.qmc_cheb(mean, L, Z, plan.ca, plan.cb, plan.alpha, **kw), (kw, feas)
     return kernels.qmc_feas(mean, L, Z, plan.c, **kw), (kw, feas)
 
 
 def _so_feas_backward(plan, state, mean, L, Z, acq, dacq):
     """bo_qmc_feas_backward, plus the constraint callables' path -> dmean, dL, dF."""
     kw, feas = state
-    dmean, dL, dF, dfeas = kernels.qmc_feas_backward(mean, L, Z, plan.c, dacq.contiguous(), acq=acq,
-                                                     **kw)
+    if isinstance(plan, _ChebPlan):
+        dmean, dL, dF, dfeas = kernels.qmc_cheb_backward(mean, L, Z, plan.ca, plan.cb, plan.alpha,
+                                                         dacq.contiguous(), acq=acq, **kw)
+    else:
+        dmean, dL, dF, dfeas = kernels.qmc_feas_backward(mean, L, Z, plan.c, dacq.contiguous(),
+                                                         acq=acq, **kw)
     if feas is not None:
         _feas_backward(feas, dfeas, dmean, dL, dF)
     return dmean, dL, dF

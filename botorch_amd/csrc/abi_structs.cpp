@@ -69,7 +69,7 @@ bool header_ok(const T* a, const char* name) {
   X(Qlogehvi) X(QmcFeas) X(Kg) X(Paths) X(Jes) X(Mes) X(Gibbon) X(MvQuantiles) X(Nipv) X(Bald) \
   X(Analytic) X(SaasPotential) X(LbfgsStep) X(Lbfgsb) X(Fantasy) X(IcmCovar) X(IcmMll)          \
   X(IcmTaskView) X(MixedCovar) X(MixedMll) X(MixedCross) X(LtfCovar) X(LtfMll) X(LtfCross) \
-  X(PairwiseLaplace) X(InputWarp) X(MllDx) X(QmcRisk)
+  X(PairwiseLaplace) X(InputWarp) X(MllDx) X(QmcRisk) X(QmcCheb)
 
 extern "C" {
 
@@ -82,7 +82,7 @@ extern "C" {
 BO_RECORD_ENTRIES(BO_ENTRY)
 #undef BO_ENTRY
 
-// fantasy.hip, icm.hip, mixed.hip, ltf.hip, pairwise.hip, warp.hip, risk.hip: record entry points added within ABI 12.  The _v names above are
+// fantasy.hip, icm.hip, mixed.hip, ltf.hip, pairwise.hip, warp.hip, risk.hip, cheb.hip: record entry points added within ABI 12.  The _v names above are
 // that version's closed set, so these carry plain names; the header check is the same.
 #define BO_ENTRY_PLAIN(entry, record)                                   \
   int bo_##entry##_impl(const Bo##record##Args* a, void* stream);       \
@@ -109,6 +109,8 @@ BO_ENTRY_PLAIN(input_warp_bwd, InputWarp)
 BO_ENTRY_PLAIN(mll_dx, MllDx)
 BO_ENTRY_PLAIN(qmc_risk, QmcRisk)
 BO_ENTRY_PLAIN(qmc_risk_backward, QmcRisk)
+BO_ENTRY_PLAIN(qmc_cheb, QmcCheb)
+BO_ENTRY_PLAIN(qmc_cheb_backward, QmcCheb)
 #undef BO_ENTRY_PLAIN
 
 // sizeof of each argument record (HOST, for bindings to verify their layouts).

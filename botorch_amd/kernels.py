@@ -2385,6 +2385,147 @@ def qmc_feas_backward(mean: torch.Tensor, L: torch.Tensor, Z: torch.Tensor, c, d
     return dmean, dL, dF, dfeas
 
 
+QMC_CHEB_QMAX = 16  # the Chebyshev-scalarization (ParEGO) kernels (bo_qmc_cheb)
+QMC_CHEB_MTMAX = 8
+QMC_CHEB_KMAX = 8
+QMC_CHEB_TILE = 16        # samples of one matrix-core tile: a group holds whole tiles
+QMC_CHEB_GROUP_MIN = 64   # samples a group should keep: one tile for each of its four waves
+_CU_COUNT = {}
+
+
+def qmc_cheb_groups(B: int, S: int, device=None, G: Optional[int] = None) -> int:
+    """G, the sample groups per t-batch of bo_qmc_cheb (its grid is B x G).  Chosen
+    (``G`` None): enough workgroups for two per CU, each keeping at least
+    QMC_CHEB_GROUP_MIN samples; 1 from B >= 2 x the CU count.  Any G is then lowered
+    until no group is empty (groups hold 16 ceil(ceil(S / G) / 16) samples)."""
+    if G is None:
+        idx = _dev_index(device if device is not None else "cuda")
+        if idx not in _CU_COUNT:
+            _CU_COUNT[idx] = torch.cuda.get_device_properties(idx).multi_processor_count
+        G = min(-(-2 * _CU_COUNT[idx] // max(B, 1)), max(S // QMC_CHEB_GROUP_MIN, 1))
+    G = max(1, min(int(G), -(-S // QMC_CHEB_TILE)))
+    Sg = -(-(-(-S // G)) // QMC_CHEB_TILE) * QMC_CHEB_TILE
+    return -(-S // Sg)
+
+
+def _qmc_cheb_args(mean, L, Z, ca, cb, alpha, best_f, best_f_s, A, rhs, eta, feas, F, Qp, log, fat,
+                   tau_relu, tau_max, G, chunk, **extra):
+    """The BoQmcChebArgs of :func:`qmc_cheb` / :func:`qmc_cheb_backward`: the layouts
+    of :func:`_qmc_feas_args`; ``ca`` / ``cb`` hold one entry per member, None for a
+    member outside the objective set (it enters the constraints only)."""
+    Mt, B, q = mean.shape
+    S = Z.shape[0]
+    if not 2 <= Mt <= QMC_CHEB_MTMAX:
+        raise ValueError(f"qmc_cheb: 2 <= Mt <= {QMC_CHEB_MTMAX} members (got {Mt})")
+    if not 1 <= q <= QMC_CHEB_QMAX:
+        raise ValueError(f"qmc_cheb: 1 <= q <= {QMC_CHEB_QMAX} (got {q})")
+    if S < 1 or L.shape != (Mt, B, q, q) or Z.numel() != S * q * Mt:
+        raise ValueError("qmc_cheb: L must be Mt x B x q x q and Z S x (q Mt), S >= 1")
+    if len(ca) != Mt or len(cb) != Mt or any((x is None) != (y is None) for x, y in zip(ca, cb)):
+        raise ValueError(f"qmc_cheb: ca and cb hold one entry per member ({Mt}), None together")
+    omask = sum(1 << t for t in range(Mt) if ca[t] is not None)
+    if bin(omask).count("1") < 2:
+        raise ValueError("qmc_cheb: the objective set needs at least two members")
+    A = [] if A is None else [[float(v) for v in row] for row in A]
+    k = len(A)
+    if k > QMC_CHEB_KMAX:
+        raise ValueError(f"qmc_cheb: at most {QMC_CHEB_KMAX} in-kernel constraints (got {k})")
+    if feas is not None and k:
+        raise ValueError("qmc_cheb: pass the constraint table or the weight tensor, not both")
+    if feas is not None and tuple(feas.shape) != (S, B, q):
+        raise ValueError(f"qmc_cheb: feas must be S x B x q = {(S, B, q)}, got {tuple(feas.shape)}")
+    rhs = [float(v) for v in (rhs if rhs is not None else [])]
+    eta = [float(v) for v in (eta if eta is not None else [])]
+    if any(len(row) != Mt for row in A) or len(rhs) != k or len(eta) != k:
+        raise ValueError("qmc_cheb: A must be k x Mt with one rhs and one eta per constraint")
+    if any(not e > 0 for e in eta):
+        raise ValueError("qmc_cheb: eta must be positive")
+    if best_f_s is not None and best_f_s.numel() != S:
+        raise ValueError(f"qmc_cheb: best_f_s holds one value per sample ({S})")
+    if chunk < 0 or chunk % QMC_CHEB_TILE:
+        raise ValueError(f"qmc_cheb: chunk must be a multiple of {QMC_CHEB_TILE} (got {chunk})")
+    Fc = F.contiguous() if F is not None else None
+    if Fc is not None and (Fc.dim() != 3 or Fc.shape[0] != Mt or Fc.shape[1] != S
+                           or Qp < q or Fc.shape[2] < B * Qp):
+        raise ValueError("qmc_cheb: F must be Mt x S x ldF with ldF >= B Qp and Qp >= q")
+    a = _lib.QmcChebArgs(B=B, q=q, Mt=Mt, S=S, mean=mean.contiguous(), L=L.contiguous(),
+                         Z=Z.reshape(S, q * Mt).contiguous(), F=Fc,
+                         ldF=Fc.shape[-1] if Fc is not None else 0,
+                         sF=Fc.shape[-1] * S if Fc is not None else 0, Qp=Qp, k=k,
+                         best_f=float(best_f),
+                         best_f_s=best_f_s.contiguous() if best_f_s is not None else None,
+                         alpha=float(alpha), omask=omask,
+                         G=qmc_cheb_groups(B, S, mean.device, G), chunk=int(chunk),
+                         feas=feas.contiguous() if feas is not None else None,
+                         log=int(bool(log)), fat=int(bool(fat)), tau_relu=float(tau_relu),
+                         tau_max=float(tau_max), **extra)
+    for t in range(Mt):
+        if ca[t] is not None:
+            a.ca[t], a.cb[t] = float(ca[t]), float(cb[t])
+    for i in range(k):
+        a.rhs[i], a.eta[i] = rhs[i], eta[i]
+        for t in range(Mt):
+            a.A[i * 8 + t] = A[i][t]
+    return a
+
+
+def qmc_cheb(mean: torch.Tensor, L: torch.Tensor, Z: torch.Tensor, ca, cb, alpha: float,
+             best_f: float = 0.0, best_f_s: Optional[torch.Tensor] = None, A=None, rhs=None,
+             eta=None, feas: Optional[torch.Tensor] = None, F: Optional[torch.Tensor] = None,
+             Qp: int = 0, log: bool = False, fat: bool = False, tau_relu: float = 1e-6,
+             tau_max: float = 1e-2, G: Optional[int] = None, chunk: int = 0) -> torch.Tensor:
+    """qEI / qNEI (``log``: qLogEI / qLogNEI) of the augmented Chebyshev scalarization
+    -(max_t p_t + alpha sum_t p_t), p_t = ca[t] f_t + cb[t], of the samples f = mean +
+    L z (+ F) of a model list's Mt members, against best_f (or best_f_s per sample),
+    weighted by the feasibility of A f - rhs <= 0 or by ``feas`` as :func:`qmc_feas`
+    (bo_qmc_cheb) -> acq (B).  ``G``: the sample groups per t-batch (None:
+    :func:`qmc_cheb_groups`); ``chunk`` caps the samples staged at a time."""
+    a = _qmc_cheb_args(mean, L, Z, ca, cb, alpha, best_f, best_f_s, A, rhs, eta, feas, F, Qp, log,
+                       fat, tau_relu, tau_max, G, chunk)
+    dev = _dev(mean, L, Z, feas, F, best_f_s)
+    acq = torch.empty(a.B, dtype=torch.float64, device=dev)
+    if a.B == 0:
+        return acq
+    work = torch.empty(2 * a.B * a.G, dtype=torch.float64, device=dev)
+    a.acq, a.work, a.work_size = acq.data_ptr(), work.data_ptr(), work.numel()
+    check(lib().bo_qmc_cheb(ctypes.byref(a), _stream(dev)), "qmc_cheb")
+    return acq
+
+
+def qmc_cheb_backward(mean: torch.Tensor, L: torch.Tensor, Z: torch.Tensor, ca, cb, alpha: float,
+                      dacq: torch.Tensor, best_f: float = 0.0,
+                      best_f_s: Optional[torch.Tensor] = None, A=None, rhs=None, eta=None,
+                      feas: Optional[torch.Tensor] = None, F: Optional[torch.Tensor] = None,
+                      Qp: int = 0, log: bool = False, fat: bool = False, tau_relu: float = 1e-6,
+                      tau_max: float = 1e-2, acq: Optional[torch.Tensor] = None,
+                      G: Optional[int] = None, chunk: int = 0):
+    """Backward of :func:`qmc_cheb` (``acq``: the forward's value, required with
+    ``log``) -> dmean (Mt x B x q), dL (Mt x B x q x q), dF (or None), dfeas
+    (S x B x q with ``feas``, else None)."""
+    Mt, B, q = mean.shape
+    S = Z.shape[0]
+    if log and (acq is None or tuple(acq.shape) != (B,)):
+        raise ValueError("qmc_cheb_backward: log mode needs the forward's acq (B)")
+    if tuple(dacq.shape) != (B,):
+        raise ValueError(f"qmc_cheb_backward: dacq must have {B} entries")
+    dev = _dev(mean, L, Z, feas, F, best_f_s, dacq, acq)
+    f64 = dict(dtype=torch.float64, device=dev)
+    dmean = torch.empty(Mt, B, q, **f64)
+    dL = torch.empty(Mt, B, q, q, **f64)
+    dF = torch.zeros(F.shape, **f64) if F is not None else None
+    dfeas = torch.empty(S, B, q, **f64) if feas is not None else None
+    a = _qmc_cheb_args(mean, L, Z, ca, cb, alpha, best_f, best_f_s, A, rhs, eta, feas, F, Qp, log,
+                       fat, tau_relu, tau_max, G, chunk,
+                       acq=acq.contiguous() if acq is not None else None, dacq=dacq.contiguous(),
+                       dmean=dmean, dL=dL, dF=dF, dfeas=dfeas)
+    if B == 0:
+        return dmean, dL, dF, dfeas
+    work = torch.empty(B * a.G * Mt * (q * q + q), **f64)
+    a.work, a.work_size = work.data_ptr(), work.numel()
+    check(lib().bo_qmc_cheb_backward(ctypes.byref(a), _stream(dev)), "qmc_cheb_backward")
+    return dmean, dL, dF, dfeas
+
+
 KG_QMAX = 16       # rows of a packed tile: q_a + slots <= 16 (bo_kg, the fused posterior)
 KG_FUSED_QMAX = 8  # largest q_a on the packed route (the X rows repeat in every tile)
 

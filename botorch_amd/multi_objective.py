@@ -98,3 +98,58 @@ class FastNondominatedPartitioning:
 
 
 NondominatedPartitioning = FastNondominatedPartitioning
+
+
+class ChebyshevScalarization:
+    """The augmented Chebyshev scalarization of :func:`get_chebyshev_scalarization` as
+    an object: ``obj(Y, X=None) = -(max_i p_i + alpha sum_i p_i)`` with the per-outcome
+    affine form ``p_i = a_i y_i + b_i`` (``a``, ``b``: what bo_qmc_cheb takes), where
+    p_i = w_i y~_i and y~ is -y normalised by ``Y_bounds`` (shifted by -1 for a negative
+    weight), or -y itself when no baseline outcomes were given.  ``outcomes`` (set by
+    :meth:`over_outcomes`): the columns of the samples it reads, None for all."""
+
+    def __init__(self, weights: torch.Tensor, Y_bounds: Optional[torch.Tensor], alpha: float,
+                 outcomes=None):
+        self.weights, self.Y_bounds, self.alpha = weights, Y_bounds, float(alpha)
+        self.outcomes = None if outcomes is None else [int(i) for i in outcomes]
+        if Y_bounds is None:
+            self.a, self.b = -weights, torch.zeros_like(weights)
+        else:
+            span = Y_bounds[1] - Y_bounds[0]
+            self.a = -weights / span
+            self.b = weights * (-Y_bounds[0] / span - (weights < 0).to(weights))
+
+    def over_outcomes(self, outcomes) -> "ChebyshevScalarization":
+        """The same scalarization reading the ``outcomes`` columns of wider samples."""
+        return ChebyshevScalarization(self.weights, self.Y_bounds, self.alpha, outcomes)
+
+    def __call__(self, Y: torch.Tensor, X: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if self.outcomes is not None:
+            Y = Y[..., self.outcomes]
+        p = self.a.to(Y) * Y + self.b.to(Y)
+        return -(p.max(dim=-1).values + self.alpha * p.sum(dim=-1))
+
+
+def get_chebyshev_scalarization(weights: torch.Tensor, Y: torch.Tensor,
+                                alpha: float = 0.05) -> ChebyshevScalarization:
+    """utils/multi_objective/scalarization.py [Knowles2005]: the augmented Chebyshev
+    scalarization g(y) = max_i w_i y_i + alpha sum_i w_i y_i, to be minimised over
+    outcomes that are to be minimised.  Outcomes here are maximised, so the returned
+    objective negates its input, normalises it with the bounds of the negated baseline
+    ``Y`` (n x m) to [0, 1] -- to [-1, 0] for a negative weight, which stands for an
+    outcome to minimise -- and returns -g.  ``Y`` with n = 0 leaves the outcomes
+    unnormalised (negative weights are then unsupported)."""
+    from .exceptions import BotorchTensorDimensionError, UnsupportedError
+    if weights.shape != Y.shape[-1:]:
+        raise BotorchTensorDimensionError(f"one weight per outcome is required: weights has shape "
+                                          f"{tuple(weights.shape)}, Y {tuple(Y.shape)}")
+    if Y.ndim > 2:
+        raise NotImplementedError(f"Y must be n x m, got {Y.ndim} dimensions")
+    if Y.shape[-2] == 0:
+        if (weights < 0).any():
+            raise UnsupportedError("a negative weight (an outcome to minimise) needs baseline "
+                                   "outcomes Y to normalise with; Y has no rows")
+        return ChebyshevScalarization(weights, None, alpha)
+    Yn = -Y
+    return ChebyshevScalarization(weights, torch.stack([Yn.min(dim=-2).values,
+                                                        Yn.max(dim=-2).values]), alpha)

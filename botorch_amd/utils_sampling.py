@@ -37,3 +37,21 @@ def draw_sobol_samples(bounds: torch.Tensor, n: int, q: int, batch_shape=None,
     if len(batch_shape):
         raw = raw.permute(-3, *range(len(batch_shape)), -2, -1)
     return lower + rng * raw
+
+
+def sample_simplex(d: int, n: int = 1, qmc: bool = False, seed: Optional[int] = None,
+                   device=None, dtype=None) -> torch.Tensor:
+    """utils/sampling.py:178-216: n uniform draws from the d-simplex (n x d, rows
+    non-negative with sum 1), as the gaps of d - 1 sorted uniforms in [0, 1]; ``qmc``
+    takes the uniforms from a scrambled Sobol sequence."""
+    if d == 1:
+        return torch.ones(n, 1, device=device, dtype=dtype)
+    if qmc:
+        u = SobolEngine(d - 1, scramble=True, seed=seed).draw(n, dtype=dtype)
+    else:
+        with manual_seed(seed=seed):
+            u = torch.rand(n, d - 1, dtype=dtype)
+    edges = torch.cat([torch.zeros(n, 1, dtype=dtype), u.sort(dim=-1).values,
+                       torch.ones(n, 1, dtype=dtype)], dim=-1)
+    gaps = edges[..., 1:] - edges[..., :-1]
+    return gaps.to(device) if device is not None else gaps

@@ -1735,6 +1735,45 @@ typedef struct BoQmcRiskArgs {
 int bo_qmc_risk(const BoQmcRiskArgs* a, void* stream);
 int bo_qmc_risk_backward(const BoQmcRiskArgs* a, void* stream);
 
+/* ---- ParEGO: the augmented Chebyshev scalarization of the Mt <= 8 single-output members of a
+ * model list under the qEI / qLogEI / qNEI / qLogNEI reductions (botorch/utils/multi_objective/
+ * scalarization.py, acquisition/multi_objective/parego.py), q <= 16 (csrc/cheb.hip).  Layouts,
+ * constraints, feas / dfeas, F / dF, best_f / best_f_s, log / fat / tau and the backward's tie
+ * rules over the points are BoQmcFeasArgs'; the objective is
+ *   p_t = ca[t] f_t + cb[t]  for the members t with bit t of omask set (2 to Mt of them),
+ *   obj = -(max_t p_t + alpha sum_t p_t),
+ * the max's cotangent goes to the lowest maximal t.  Members outside omask enter the
+ * constraints only.  The grid is B x G: workgroup (b, g) reduces the samples
+ * [g Sg, (g + 1) Sg), Sg = 16 ceil(ceil(S / G) / 16), which must leave no group empty, into
+ * work (forward: 2 B G doubles; backward: B G Mt (q q + q)), and a second launch folds the G
+ * partials of a t-batch in index order.  No atomics: repeated calls with the same G and chunk
+ * are bitwise identical; another G sums in another order.  chunk: the samples staged in LDS
+ * at a time, a multiple of 16 that caps the library's choice; 0 leaves it to the library.
+ * Added within ABI 12 (plain names, as bo_ltf_covar). */
+typedef struct BoQmcChebArgs {
+  BO_STRUCT_HEADER;
+  int32_t B, q, Mt, S;
+  const double *mean, *L, *Z, *F;
+  int64_t ldF, sF;
+  int32_t Qp, k;
+  double best_f;
+  const double* best_f_s;
+  double ca[8], cb[8], alpha;
+  int32_t omask, G, chunk, _pad;
+  double A[64], rhs[8], eta[8];
+  const double* feas;
+  double* dfeas; /* backward only, with feas */
+  int32_t log, fat;
+  double tau_relu, tau_max;
+  double* acq; /* forward: output; backward (log): the forward's value */
+  const double* dacq;
+  double *dmean, *dL, *dF;
+  double* work;
+  int64_t work_size; /* doubles */
+} BoQmcChebArgs;
+int bo_qmc_cheb(const BoQmcChebArgs* a, void* stream);
+int bo_qmc_cheb_backward(const BoQmcChebArgs* a, void* stream);
+
 /* HOST: sizeof the named record ("BoPostPartialsArgs", ...), -1 if unknown --
  * lets a binding check its declared layout once at load time. */
 int64_t bo_struct_size(const char* name);
