@@ -29,6 +29,7 @@
 // Columns are gathered through the record's column lists.  No atomics: wave shuffles,
 // then LDS, in a fixed order.
 #include "common.h"
+#include "launch_checks.h"
 
 #pragma clang fp contract(off)
 
@@ -523,14 +524,7 @@ int check_cols(const char* who, int d, int dx, int nf, const int32_t* xc, const 
   BO_CHECK_ARG(dx >= 1 && dx <= MAXD && nf >= 1 && nf <= 2 && d == dx + nf,
                "%s: d_x = %d, n_f = %d, d = %d (d_x 1..%d, n_f 1..2, d = d_x + n_f)", who, dx, nf,
                d, MAXD);
-  unsigned seen = 0;
-  for (int t = 0; t < dx + nf; ++t) {
-    const int col = t < dx ? xc[t] : fc[t - dx];
-    BO_CHECK_ARG(col >= 0 && col < d && !(seen >> col & 1u),
-                 "%s: column lists must partition 0..%d", who, d - 1);
-    seen |= 1u << col;
-  }
-  return BO_OK;
+  return check_partition(who, d, dx, xc, nf, fc);
 }
 
 }  // namespace
@@ -578,16 +572,6 @@ extern "C" int bo_ltf_mll_terms_impl(const BoLtfMllArgs* a, void* stream) {
   if (a->d_x <= 8) BO_GO(8); else BO_GO(16);
 #undef BO_GO
   BO_LAUNCH_CHECK();
-  return BO_OK;
-}
-
-static int check_cross(const char* who, const BoLtfCrossArgs* a) {
-  BO_CHECK_ARG(a->B >= 0 && a->q >= 1 && a->n >= 0 && a->B * a->q < (int64_t(1) << 31) &&
-                   a->q < (int64_t(1) << 20),
-               "%s: B = %lld, q = %lld, n = %lld", who, (long long)a->B, (long long)a->q,
-               (long long)a->n);
-  BO_CHECK_ARG(a->hyper && (a->B == 0 || a->Xq) && (a->n == 0 || a->Xt),
-               "%s: Xq, Xt and hyper are required", who);
   return BO_OK;
 }
 

@@ -23,6 +23,7 @@
 // argument record, so no packed copy of the inputs is made.  No atomics; wave
 // shuffles then LDS in a fixed order: repeated calls are bitwise identical.
 #include "common.h"
+#include "launch_checks.h"
 
 namespace {
 
@@ -393,14 +394,7 @@ int check_cols(const char* who, int kind, int d, int dc, int dk, const int32_t* 
   BO_CHECK_ARG(kind == BO_RBF || kind == BO_MATERN52, "%s: bad kind %d", who, kind);
   BO_CHECK_ARG(dc >= 1 && dc <= MD && dk >= 1 && dk <= MD && d == dc + dk,
                "%s: d_c = %d, d_k = %d, d = %d (1..%d each, d = d_c + d_k)", who, dc, dk, d, MD);
-  unsigned seen = 0;
-  for (int t = 0; t < dc + dk; ++t) {
-    const int col = t < dc ? cont[t] : cat[t - dc];
-    BO_CHECK_ARG(col >= 0 && col < d && !(seen >> col & 1u),
-                 "%s: column lists must partition 0..%d", who, d - 1);
-    seen |= 1u << col;
-  }
-  return BO_OK;
+  return check_partition(who, d, dc, cont, dk, cat);
 }
 
 }  // namespace
@@ -449,16 +443,6 @@ extern "C" int bo_mixed_mll_terms_impl(const BoMixedMllArgs* a, void* stream) {
   if (a->kind == BO_RBF) BO_GO(BO_RBF); else BO_GO(BO_MATERN52);
 #undef BO_GO
   BO_LAUNCH_CHECK();
-  return BO_OK;
-}
-
-static int check_cross(const char* who, const BoMixedCrossArgs* a) {
-  BO_CHECK_ARG(a->B >= 0 && a->q >= 1 && a->n >= 0 && a->B * a->q < (int64_t(1) << 31) &&
-                   a->q < (int64_t(1) << 20),
-               "%s: B = %lld, q = %lld, n = %lld", who, (long long)a->B, (long long)a->q,
-               (long long)a->n);
-  BO_CHECK_ARG(a->hyper && (a->B == 0 || a->Xq) && (a->n == 0 || a->Xt),
-               "%s: Xq, Xt and hyper are required", who);
   return BO_OK;
 }
 

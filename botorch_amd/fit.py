@@ -228,16 +228,13 @@ def mll_terms(Xt: torch.Tensor, y: torch.Tensor, ls_t: torch.Tensor, noise, cons
     ls = ls_t.detach().cpu().numpy().astype(np.float64) if torch.is_tensor(ls_t) else np.asarray(ls_t)
     ls_t = torch.as_tensor(ls, dtype=torch.float64, device=dev)
     fixed = torch.is_tensor(noise) and noise.numel() > 1
-    info = None
-    if cache is None and not fixed:
-        # optimistic: the jitter-free factorisation and everything after it are
-        # enqueued at once; its status comes back with the MLL sums (one
-        # device-to-host transfer per closure instead of two)
-        cache, info = kernels.build_gp_cache_optimistic(Xt, y, ls_t, float(noise), const,
-                                                        kind=kind, outputscale=os_)
-    elif cache is None:
-        cache = kernels.build_gp_cache(Xt, y, ls_t, noise, const, kind=kind, outputscale=os_,
-                                       check_nan=False)  # checked once in fit_gpytorch_mll_scipy
+
+    def _build(optimistic):
+        if optimistic:
+            return kernels.build_gp_cache_optimistic(Xt, y, ls_t, float(noise), const, kind=kind,
+                                                     outputscale=os_)
+        return kernels.build_gp_cache(Xt, y, ls_t, noise, const, kind=kind, outputscale=os_,
+                                      check_nan=False), None  # checked once in fit_gpytorch_mll_scipy
 
     dx = [None]
 
@@ -258,16 +255,13 @@ def mll_terms(Xt: torch.Tensor, y: torch.Tensor, ls_t: torch.Tensor, noise, cons
             sums = torch.cat([sums, info.to(torch.float64)])
         return sums.cpu().numpy()
 
-    s = _sums(cache, info)
-    if info is not None:
-        status = int(s[-1])
-        s = s[:-1]
-        if status < 0:
-            raise RuntimeError("bo_cholesky_inverse: the Cholesky task DAG timed out")
-        if status != 0:  # not p.d. without jitter: the ladder, then the sums again
-            cache = kernels.build_gp_cache(Xt, y, ls_t, noise, const, kind=kind, outputscale=os_,
-                                           check_nan=False)
-            s = _sums(cache, None)
+    if cache is None and not fixed:
+        # optimistic: the jitter-free factorisation and everything after it are
+        # enqueued at once; its status comes back with the MLL sums (one
+        # device-to-host transfer per closure instead of two)
+        s = _optimistic_then_ladder(_build, _sums)
+    else:
+        s = _sums(cache if cache is not None else _build(False)[0], None)
     quad, logdet_half, sum_alpha = s[d + 3], s[d + 2], s[d + 4]
     ll = -0.5 * quad - logdet_half - 0.5 * n * math.log(2 * math.pi)
     g = np.zeros(d + 3)
@@ -426,6 +420,61 @@ def _warped_value_and_grad(model, x: np.ndarray, layout: "_Layout"):
     return -ll / n, -g / n
 
 
+# ---- what the exact-GP MLL closures share (mll_terms and the dense-covariance models) -------------
+def _optimistic_then_ladder(build, sums):
+    """The host sums of an MLL closure with one device-to-host transfer where the
+    covariance is p.d. as it stands.  ``build(optimistic)`` returns (cache, info) as
+    kernels.build_dense_cache does; ``sums(cache, info)`` enqueues the row terms and
+    brings their sums to the host, with the factorisation's status appended when
+    ``info`` is given.  The optimistic (jitter-free) build and its sums go first; a
+    positive status (not p.d. without jitter) takes the ladder build, then the sums
+    again.  Returns the sums without the status."""
+    cache, info = build(True)
+    s = sums(cache, info)
+    status, s = int(s[-1]), s[:-1]
+    if status < 0:
+        raise RuntimeError("bo_cholesky_inverse: the Cholesky task DAG timed out")
+    if status != 0:
+        cache, _ = build(False)
+        s = sums(cache, None)
+    return s
+
+
+def _spec_mll_sums(spec, X, y, noise, const: float) -> np.ndarray:
+    """_optimistic_then_ladder for a model whose kernels go through a spec
+    (kernels.MixedSpec, kernels.LTFSpec): the column sums of spec.mll_row_terms."""
+
+    def sums(cache, info):
+        Ainv = cache.Ainv if cache.Ainv is not None else kernels.ainv(cache)
+        s = spec.mll_row_terms(cache.Xt, cache.L, Ainv, cache.alpha, cache.beta).sum(dim=0)
+        if info is not None:
+            s = torch.cat([s, info.to(torch.float64)])
+        return s.cpu().numpy()
+
+    return _optimistic_then_ladder(
+        lambda optimistic: spec.build_cache(X, y, noise, const, optimistic), sums)
+
+
+def _dense_mll_torch(model, noise, const: float, params, covar):
+    """ll = log N(y | c, K + noise) and d ll / d theta by autograd, theta = [noise,
+    constant, params...] on the model's device and K = ``covar(theta[2:])`` a torch
+    composition of it.  ``noise``: a float or the fixed n-vector (the first gradient
+    entry is then meaningless)."""
+    from .models import _cholesky_ladder
+    X, y = model.train_inputs[0], model.train_targets
+    n = X.shape[0]
+    fixed = torch.is_tensor(noise)
+    theta = torch.as_tensor(np.concatenate([[0.0 if fixed else float(noise), const], params]),
+                            dtype=torch.float64).to(X.device).requires_grad_(True)
+    K = covar(theta[2:])
+    A = K + (torch.diag(noise.to(K)) if fixed else theta[0] * torch.eye(n, dtype=K.dtype, device=K.device))
+    L = _cholesky_ladder(A)  # (cholesky_ex is differentiable: the ladder stays in the graph)
+    beta = torch.linalg.solve_triangular(L, (y - theta[1]).unsqueeze(-1), upper=False)
+    ll = -0.5 * (beta * beta).sum() - torch.log(torch.diagonal(L)).sum() - 0.5 * n * math.log(2 * math.pi)
+    (g,) = torch.autograd.grad(ll, theta)
+    return float(ll.detach()), g.cpu().numpy()
+
+
 # ---- MultiTaskGP: the ICM marginal log likelihood ------------------------------------------------
 # None: by kernels.icm_fused_ok (T <= 16, d <= 64 take icm.hip); "fused" / "generic": forced
 # (tests, tools/bench_mtgp.py)
@@ -482,16 +531,9 @@ def icm_mll_terms(Xd: torch.Tensor, task: torch.Tensor, y: torch.Tensor, ls, noi
                          + ([info.to(torch.float64)] if info is not None else []))
         return sums.cpu().numpy()
 
-    cache, info = kernels.build_icm_cache(Xd, task, y, ls_t, Bm, noise, const, kind=kind,
-                                          outputscale=os_, optimistic=True)
-    s = _sums(cache, info)
-    status, s = int(s[-1]), s[:-1]
-    if status < 0:
-        raise RuntimeError("bo_cholesky_inverse: the Cholesky task DAG timed out")
-    if status != 0:  # not p.d. without jitter: the ladder, then the sums again
-        cache, _ = kernels.build_icm_cache(Xd, task, y, ls_t, Bm, noise, const, kind=kind,
-                                           outputscale=os_)
-        s = _sums(cache, None)
+    s = _optimistic_then_ladder(
+        lambda optimistic: kernels.build_icm_cache(Xd, task, y, ls_t, Bm, noise, const, kind=kind,
+                                                   outputscale=os_, optimistic=optimistic), _sums)
     Gl = s[d + 5:].reshape(T, T)
     return _icm_grad(s, 0.5 * (Gl + Gl.T), d, T, ls, F, n)
 
@@ -662,31 +704,12 @@ def mixed_mll_terms(model, noise, const: float, hyper: np.ndarray, scales: np.nd
     device and one device-to-host transfer brings the sums and the factorisation's
     status (the ladder, then the sums again, if it failed).  ``noise``: a float or
     the fixed n-vector (the first gradient entry is then meaningless)."""
-    from . import ops  # noqa: F401  (registers torch.ops.bo)
     X, y = model.train_inputs[0], model.train_targets
     n = X.shape[0]
     dc, dk = len(model.cont_dims), len(model.cat_dims)
     spec = model.spec(torch.as_tensor(hyper, dtype=torch.float64).to(X.device),
                       [float(v) for v in scales])
-
-    def _sums(cache, info):
-        Ainv = cache.Ainv if cache.Ainv is not None else kernels.ainv(cache)
-        part = torch.ops.bo.mixed_mll_terms(cache.Xt, spec.hyper, list(spec.cont), list(spec.cat),
-                                            spec.kind, spec.o_s, spec.o_c, spec.o_p, cache.L, Ainv,
-                                            cache.alpha, cache.beta)
-        sums = part.sum(dim=0)
-        if info is not None:
-            sums = torch.cat([sums, info.to(torch.float64)])
-        return sums.cpu().numpy()
-
-    cache, info = kernels.build_mixed_cache(X, y, spec, noise, const, optimistic=True)
-    s = _sums(cache, info)
-    status, s = int(s[-1]), s[:-1]
-    if status < 0:
-        raise RuntimeError("bo_cholesky_inverse: the Cholesky task DAG timed out")
-    if status != 0:  # not p.d. without jitter: the ladder, then the sums again
-        cache, _ = kernels.build_mixed_cache(X, y, spec, noise, const)
-        s = _sums(cache, None)
+    s = _spec_mll_sums(spec, X, y, noise, const)
     ll = -0.5 * s[37] - s[36] - 0.5 * n * math.log(2 * math.pi)
     l1, m1, l2, m2 = np.split(np.asarray(hyper, dtype=np.float64), [dc, dc + dk, 2 * dc + dk])
     g = np.concatenate([[0.5 * s[35], s[38]], 0.5 * s[0:dc] / l1 ** 3,
@@ -698,28 +721,20 @@ def mixed_mll_terms(model, noise, const: float, hyper: np.ndarray, scales: np.nd
 def mixed_mll_terms_torch(model, noise, const: float, hyper: np.ndarray, scales: np.ndarray):
     """mixed_mll_terms in plain torch with autograd (the torch route: CPU tensors, any
     d_c and d_k, categorical columns only; the comparator of tools/bench_mixed.py)."""
-    from .models import _cholesky_ladder, mixed_covar_torch
-    X, y = model.train_inputs[0], model.train_targets
-    n = X.shape[0]
+    from .models import mixed_covar_torch
+    X = model.train_inputs[0]
     dc, dk = len(model.cont_dims), len(model.cat_dims)
-    fixed = torch.is_tensor(noise)
-    theta = torch.as_tensor(np.concatenate([[0.0 if fixed else float(noise), const], hyper, scales]),
-                            dtype=torch.float64).to(X.device).requires_grad_(True)
-    h, sc = theta[2:2 + len(hyper)], theta[2 + len(hyper):]
-    if dc:
-        l1, m1, l2, m2 = h[:dc], h[dc:dc + dk], h[dc + dk:2 * dc + dk], h[2 * dc + dk:]
-        K = mixed_covar_torch(X, X, model.cont_dims, model.cat_dims, model.kind, l1, m1, l2, m2,
-                              sc[0], sc[1], sc[2])
-    else:
-        K = mixed_covar_torch(X, X, [], model.cat_dims, model.kind, None, h, None, None, sc[0],
-                              None, None)
-    A = K + (torch.diag(noise.to(K)) if fixed else theta[0] * torch.eye(n, dtype=K.dtype, device=K.device))
-    L = _cholesky_ladder(A)  # (cholesky_ex is differentiable: the ladder stays in the graph)
-    res = (y - theta[1]).unsqueeze(-1)
-    beta = torch.linalg.solve_triangular(L, res, upper=False)
-    ll = -0.5 * (beta * beta).sum() - torch.log(torch.diagonal(L)).sum() - 0.5 * n * math.log(2 * math.pi)
-    (g,) = torch.autograd.grad(ll, theta)
-    return float(ll.detach()), g.cpu().numpy()
+
+    def covar(p):
+        h, sc = p[:len(hyper)], p[len(hyper):]
+        if dc:
+            l1, m1, l2, m2 = h[:dc], h[dc:dc + dk], h[dc + dk:2 * dc + dk], h[2 * dc + dk:]
+            return mixed_covar_torch(X, X, model.cont_dims, model.cat_dims, model.kind, l1, m1, l2,
+                                     m2, sc[0], sc[1], sc[2])
+        return mixed_covar_torch(X, X, [], model.cat_dims, model.kind, None, h, None, None, sc[0],
+                                 None, None)
+
+    return _dense_mll_torch(model, noise, const, np.concatenate([hyper, scales]), covar)
 
 
 class _MixedLayout:
@@ -741,8 +756,12 @@ class _MixedLayout:
         self.s0 = self.h0 + self.nh
         self.size = self.s0 + self.ns
         lo = ([] if self.fixed else [model.likelihood.noise_lower]) + [-np.inf]
+        self.priors = []  # (prior, start, size) over the flat vector
+        at = self.h0
         for m in self.mods:
             lo += [m.lengthscale_lower] * m.ard_num_dims
+            self.priors.append((m.lengthscale_prior, at, m.ard_num_dims))
+            at += m.ard_num_dims
         lo += [0.0] * self.ns
         self.bounds = [(None if not np.isfinite(l) else l, None) for l in lo]
         self.segments = ([] if self.fixed else [("noise", 0, 1)]) + [
@@ -769,33 +788,38 @@ class _MixedLayout:
         with torch.no_grad():
             m.raw_outputscales.copy_(torch.as_tensor(np.asarray(x[self.s0:]), dtype=torch.float64))
 
+    def data_terms(self, noise, const: float, x: np.ndarray):
+        terms = mixed_mll_terms if self.model.fused() else mixed_mll_terms_torch
+        return terms(self.model, noise, const, x[self.h0:self.s0], x[self.s0:])
+
     def value_and_grad(self, x: np.ndarray):
         return mixed_mll_value_and_grad(self.model, x, self)
 
 
-def mixed_mll_value_and_grad(model, x: np.ndarray, layout: "_MixedLayout"):
-    """Loss = -(log N(y | c, A) + log priors) / n of a MixedSingleTaskGP at the flat
-    vector x and its gradient: the data term from mixed_mll_terms (the fused route)
-    or mixed_mll_terms_torch, the noise prior (and lengthscale priors of a custom
-    continuous kernel) on the host.  Reads x, not the module."""
+def _spec_mll_value_and_grad(model, x: np.ndarray, layout):
+    """Loss = -(log N(y | c, A) + log priors) / n of a MixedSingleTaskGP or a
+    SingleTaskMultiFidelityGP at the flat vector x and its gradient: the data term from
+    ``layout.data_terms`` (the model's *_mll_terms on the fused route, *_mll_terms_torch
+    otherwise), the noise prior and ``layout.priors`` on the host.  Reads x, not the
+    module."""
     x = np.asarray(x, dtype=np.float64)
-    o, h0, s0 = layout.o, layout.h0, layout.s0
+    o = layout.o
     n = model.train_inputs[0].shape[0]
     noise = model.likelihood.noise if layout.fixed else float(x[0])
-    terms = mixed_mll_terms if model.fused() else mixed_mll_terms_torch
-    ll, gall = terms(model, noise, float(x[o]), x[h0:s0], x[s0:])
+    ll, gall = layout.data_terms(noise, float(x[o]), x)
     g = np.array(gall[1 - o:], dtype=np.float64)
     if not layout.fixed:
         pv, pg = _prior_terms(model.likelihood.noise_prior, np.array([x[0]]))
         ll += pv
         g[0] += pg[0]
-    at = h0
-    for mod in layout.mods:
-        pv, pg = _prior_terms(mod.lengthscale_prior, x[at:at + mod.ard_num_dims])
+    for prior, at, size in layout.priors:
+        pv, pg = _prior_terms(prior, x[at:at + size])
         ll += pv
-        g[at:at + mod.ard_num_dims] += pg
-        at += mod.ard_num_dims
+        g[at:at + size] += pg
     return -ll / n, -g / n
+
+
+mixed_mll_value_and_grad = ltf_mll_value_and_grad = _spec_mll_value_and_grad
 
 
 # ---- SingleTaskMultiFidelityGP: the marginal log likelihood of the fidelity kernel ------------
@@ -807,31 +831,13 @@ def ltf_mll_terms(model, noise, const: float, hyper: np.ndarray, o: float):
     transfer brings the sums and the factorisation's status (the ladder, then the sums
     again, if it failed).  ``noise``: a float or the fixed n-vector (the first gradient
     entry is then meaningless)."""
-    from . import ops  # noqa: F401  (registers torch.ops.bo)
     X, y = model.train_inputs[0], model.train_targets
     n = X.shape[0]
     hyper = np.asarray(hyper, dtype=np.float64)
     # (l0, l1 go to the device; the power and the outputscale travel in the record)
     spec = model.spec(torch.as_tensor(hyper[:-1]).to(X.device), float(o), power=float(hyper[-1]))
     dx = len(spec.xcols)
-
-    def _sums(cache, info):
-        Ainv = cache.Ainv if cache.Ainv is not None else kernels.ainv(cache)
-        part = torch.ops.bo.ltf_mll_terms(cache.Xt, spec.hyper, list(spec.xcols), list(spec.fcols),
-                                          spec.power, spec.o, cache.L, Ainv, cache.alpha, cache.beta)
-        sums = part.sum(dim=0)
-        if info is not None:
-            sums = torch.cat([sums, info.to(torch.float64)])
-        return sums.cpu().numpy()
-
-    cache, info = kernels.build_ltf_cache(X, y, spec, noise, const, optimistic=True)
-    s = _sums(cache, info)
-    status, s = int(s[-1]), s[:-1]
-    if status < 0:
-        raise RuntimeError("bo_cholesky_inverse: the Cholesky task DAG timed out")
-    if status != 0:  # not p.d. without jitter: the ladder, then the sums again
-        cache, _ = kernels.build_ltf_cache(X, y, spec, noise, const)
-        s = _sums(cache, None)
+    s = _spec_mll_sums(spec, X, y, noise, const)
     ll = -0.5 * s[36] - s[35] - 0.5 * n * math.log(2 * math.pi)
     l0, l1 = hyper[:dx], hyper[dx:2 * dx]
     g = np.concatenate([[0.5 * s[34], s[37]], 0.5 * s[0:dx] / l0 ** 3,
@@ -842,19 +848,9 @@ def ltf_mll_terms(model, noise, const: float, hyper: np.ndarray, o: float):
 def ltf_mll_terms_torch(model, noise, const: float, hyper: np.ndarray, o: float):
     """ltf_mll_terms in plain torch with autograd (the torch route: CPU tensors, any d_x,
     several data fidelities; the comparator of tools/bench_mf.py)."""
-    from .models import _cholesky_ladder
-    X, y = model.train_inputs[0], model.train_targets
-    n = X.shape[0]
-    fixed = torch.is_tensor(noise)
-    theta = torch.as_tensor(np.concatenate([[0.0 if fixed else float(noise), const], hyper, [o]]),
-                            dtype=torch.float64).to(X.device).requires_grad_(True)
-    K = model.covar_torch(X, X, theta[2:-1], theta[-1])
-    A = K + (torch.diag(noise.to(K)) if fixed else theta[0] * torch.eye(n, dtype=K.dtype, device=K.device))
-    L = _cholesky_ladder(A)  # (cholesky_ex is differentiable: the ladder stays in the graph)
-    beta = torch.linalg.solve_triangular(L, (y - theta[1]).unsqueeze(-1), upper=False)
-    ll = -0.5 * (beta * beta).sum() - torch.log(torch.diagonal(L)).sum() - 0.5 * n * math.log(2 * math.pi)
-    (g,) = torch.autograd.grad(ll, theta)
-    return float(ll.detach()), g.cpu().numpy()
+    X = model.train_inputs[0]
+    return _dense_mll_torch(model, noise, const, np.concatenate([hyper, [o]]),
+                            lambda p: model.covar_torch(X, X, p[:-1], p[-1]))
 
 
 LTF_OUTPUTSCALE_LOWER = 1e-6
@@ -913,30 +909,12 @@ class _LTFLayout:
                 par.copy_(torch.as_tensor(np.asarray(x[at:at + k]), dtype=torch.float64).reshape(par.shape))
             m.raw_outputscale.fill_(float(x[self.s0]))
 
+    def data_terms(self, noise, const: float, x: np.ndarray):
+        terms = ltf_mll_terms if self.model.fused() else ltf_mll_terms_torch
+        return terms(self.model, noise, const, x[self.h0:self.s0], float(x[self.s0]))
+
     def value_and_grad(self, x: np.ndarray):
         return ltf_mll_value_and_grad(self.model, x, self)
-
-
-def ltf_mll_value_and_grad(model, x: np.ndarray, layout: "_LTFLayout"):
-    """Loss = -(log N(y | c, A) + log priors) / n of a SingleTaskMultiFidelityGP at the
-    flat vector x and its gradient: the data term from ltf_mll_terms (the fused route)
-    or ltf_mll_terms_torch, the priors on the host.  Reads x, not the module."""
-    x = np.asarray(x, dtype=np.float64)
-    o, h0, s0 = layout.o, layout.h0, layout.s0
-    n = model.train_inputs[0].shape[0]
-    noise = model.likelihood.noise if layout.fixed else float(x[0])
-    terms = ltf_mll_terms if model.fused() else ltf_mll_terms_torch
-    ll, gall = terms(model, noise, float(x[o]), x[h0:s0], float(x[s0]))
-    g = np.array(gall[1 - o:], dtype=np.float64)
-    if not layout.fixed:
-        pv, pg = _prior_terms(model.likelihood.noise_prior, np.array([x[0]]))
-        ll += pv
-        g[0] += pg[0]
-    for prior, at, size in layout.priors:
-        pv, pg = _prior_terms(prior, x[at:at + size])
-        ll += pv
-        g[at:at + size] += pg
-    return -ll / n, -g / n
 
 
 class _PairwiseLayout:

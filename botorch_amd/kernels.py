@@ -454,27 +454,27 @@ def icm_covar(X, task, lengthscale, B, kind=_lib.RBF, outputscale=1.0, noise=0.0
     return A
 
 
-def build_icm_cache(X, task, y, lengthscale, B, noise, constant, kind=_lib.RBF, outputscale=1.0,
-                    optimistic: bool = False, max_tries=CHOLESKY_MAX_TRIES,
-                    jitter0=CHOLESKY_JITTER_F64, fill=None):
-    """GPCache of the long-format ICM model: L, L^{-1}, beta, alpha of A =
-    outputscale kbar * B[task, task] + noise (a float, or an n-vector of observed
-    variances), factorised by the existing ladder entry (bo_cholesky_inverse, or
-    its _ainv variant under AINV_IN_DAG).  ``optimistic``: the jitter-free
+def build_dense_cache(X, y, hyper, noise, constant, fill, kind, outputscale,
+                      optimistic: bool = False, max_tries=CHOLESKY_MAX_TRIES,
+                      jitter0=CHOLESKY_JITTER_F64):
+    """GPCache of an exact GP whose padded training covariance A = K + noise (a float,
+    or an n-vector of observed variances) ``fill(noise, noise_vec, out)`` writes: L,
+    L^{-1}, beta, alpha, factorised by the existing ladder entry (bo_cholesky_inverse,
+    or its _ainv variant under AINV_IN_DAG).  ``optimistic``: the jitter-free
     attempt only, enqueued without a status read-back, no U -- returns (cache,
     info) as build_gp_cache_optimistic does (the MLL closure).  Otherwise the
-    jitter ladder with U = L^{-T}, returns (cache, None).  The cache's ``Xt`` /
-    ``Xt_scaled`` hold the non-task columns.  ``fill(noise, noise_vec, out)``
-    writes another model's padded covariance in place of icm_covar
-    (build_mixed_cache: ``task`` and ``B`` are then unused, ``Xt_scaled`` is None
-    and ``lengthscale`` is stored as given)."""
-    dev = _dev(X, y, lengthscale, B)
+    jitter ladder with U = L^{-T}, returns (cache, None).  Only L, Linv, U, beta,
+    alpha, Ainv, Xt, n, np and the constant describe the model: ``lengthscale`` holds
+    ``hyper`` as given, ``kind`` and ``outputscale`` are stored for the caller, ``d``
+    counts all columns of X and ``Xt_scaled`` is None, so a single-task consumer of
+    those fields fails instead of reading something else."""
+    dev = _dev(X, y, hyper)
     X = X.contiguous()
     y = y.contiguous()
     n, d = X.shape
     np_ = padded_order(n)
     f64 = dict(dtype=torch.float64, device=dev)
-    ls = lengthscale.detach().reshape(-1).to(**f64).contiguous()
+    ls = hyper.detach().reshape(-1).to(**f64).contiguous()
     fixed = torch.is_tensor(noise) and noise.numel() > 1
     nv = noise.detach().reshape(-1).to(**f64).contiguous() if fixed else None
     if fixed and nv.numel() != n:
@@ -493,10 +493,7 @@ def build_icm_cache(X, task, y, lengthscale, B, noise, constant, kind=_lib.RBF, 
     for attempt in range(1 if optimistic else max_tries + 1):
         if attempt > 0:
             jitter = jitter0 * 10.0 ** (attempt - 1)
-        if fill is not None:
-            fill(s2 + jitter, nv, L)
-        else:
-            icm_covar(X, task, ls, B, kind, outputscale, s2 + jitter, nv, out=L)
+        fill(s2 + jitter, nv, L)
         if Ainv is not None:
             check(lib().bo_cholesky_inverse_ainv(_p(L), _p(Linv), _p(Ainv), _p(work), np_,
                                                  _p(info), st), "cholesky_inverse_ainv")
@@ -527,14 +524,31 @@ def build_icm_cache(X, task, y, lengthscale, B, noise, constant, kind=_lib.RBF, 
     else:
         U = torch.empty(np_, np_, **f64)
         check(lib().bo_transpose(_p(Linv), _p(U), np_, np_, st), "transpose")
-    Xs = torch.empty(n, DP, **f64) if fill is None else None  # (no consumer of it with ``fill``)
-    if d <= DP and fill is None:
-        check(lib().bo_scale_inputs(_p(X), n, d, _p(ls), ctypes.c_void_p(0), DP, _p(Xs), st),
-              "scale_inputs")
-    cache = GPCache(kind, n, d, np_, X, Xs, ls, float(outputscale),
+    cache = GPCache(kind, n, d, np_, X, None, ls, float(outputscale),
                     float(nv.mean()) if fixed else s2, float(constant), L, Linv, U, beta, alpha,
                     jitter, Ainv)
     return cache, (info if optimistic else None)
+
+
+def build_icm_cache(X, task, y, lengthscale, B, noise, constant, kind=_lib.RBF, outputscale=1.0,
+                    optimistic: bool = False, max_tries=CHOLESKY_MAX_TRIES,
+                    jitter0=CHOLESKY_JITTER_F64):
+    """GPCache of the long-format ICM model: build_dense_cache of A = outputscale kbar *
+    B[task, task] + noise (bo_icm_covar).  The cache's ``Xt`` / ``Xt_scaled`` hold the
+    non-task columns."""
+    dev = _dev(X, y, lengthscale, B)
+    X = X.contiguous()
+    n, d = X.shape
+    ls = lengthscale.detach().reshape(-1).to(dtype=torch.float64, device=dev).contiguous()
+    cache, info = build_dense_cache(
+        X, y, ls, noise, constant,
+        lambda s2, nv, L: icm_covar(X, task, ls, B, kind, outputscale, s2, nv, out=L),
+        kind, outputscale, optimistic, max_tries, jitter0)
+    cache.Xt_scaled = torch.empty(n, DP, dtype=torch.float64, device=dev)
+    if d <= DP:
+        check(lib().bo_scale_inputs(_p(X), n, d, _p(ls), ctypes.c_void_p(0), DP,
+                                    _p(cache.Xt_scaled), _stream(dev)), "scale_inputs")
+    return cache, info
 
 
 def icm_mll_partials(X, task, lengthscale, B, kind, outputscale, L, Ainv, alpha, beta):
@@ -616,6 +630,27 @@ class MixedSpec:
                     cont_cols=_lib._COLS8(*self.cont), cat_cols=_lib._COLS8(*self.cat),
                     hyper=self.hyper, o_s=float(self.o_s), o_p=float(self.o_p))
 
+    # The model-level calls, under the names LTFSpec gives its own: what the shared
+    # cache, MLL and posterior code reaches the kernels through.
+    def _op_args(self) -> tuple:
+        return (self.hyper, list(self.cont), list(self.cat), self.kind, self.o_s, self.o_c,
+                self.o_p)
+
+    def build_cache(self, X, y, noise, constant, optimistic: bool = False):
+        return build_mixed_cache(X, y, self, noise, constant, optimistic)
+
+    def mll_row_terms(self, X, L, Ainv, alpha, beta):
+        from . import ops  # noqa: F401  (torch.ops.bo registration)
+        return torch.ops.bo.mixed_mll_terms(X, *self._op_args(), L, Ainv, alpha, beta)
+
+    def cross(self, Xq, Xt):
+        from . import ops  # noqa: F401  (torch.ops.bo registration)
+        return torch.ops.bo.mixed_cross(Xq, Xt, *self._op_args())
+
+    def cross_grad(self, Xq, Xt, dKx, G):
+        from . import ops  # noqa: F401  (torch.ops.bo registration)
+        return torch.ops.bo.mixed_cross_grad(Xq, Xt, *self._op_args(), dKx, G)
+
 
 def _mixed_check(spec: MixedSpec, *rows) -> None:
     d = len(spec.cont) + len(spec.cat)
@@ -643,14 +678,11 @@ def mixed_covar(X, spec: MixedSpec, noise=0.0, noise_vec=None, out=None):
 
 
 def build_mixed_cache(X, y, spec: MixedSpec, noise, constant, optimistic: bool = False):
-    """GPCache of the mixed model (build_icm_cache's ladder and status contract with
-    bo_mixed_covar as the covariance).  Only L, Linv, U, beta, alpha, Ainv, Xt, n, np
-    and the constant describe the model: ``lengthscale`` holds spec.hyper (2 d values),
-    ``d`` counts all columns and ``Xt_scaled`` is None, so a single-task consumer of
-    those fields fails instead of reading something else."""
-    return build_icm_cache(X, None, y, spec.hyper, None, noise, constant, kind=spec.kind,
-                           outputscale=spec.o_s, optimistic=optimistic,
-                           fill=lambda s2, nv, L: mixed_covar(X, spec, s2, nv, out=L))
+    """GPCache of the mixed model: build_dense_cache of bo_mixed_covar's covariance
+    (``lengthscale`` holds spec.hyper, 2 d values)."""
+    return build_dense_cache(X, y, spec.hyper, noise, constant,
+                             lambda s2, nv, L: mixed_covar(X, spec, s2, nv, out=L), spec.kind,
+                             spec.o_s, optimistic)
 
 
 def mixed_mll_partials(X, spec: MixedSpec, L, Ainv, alpha, beta):
@@ -730,6 +762,25 @@ class LTFSpec:
                     f_cols=_lib._COLS2(*self.fcols), hyper=self.hyper, power=float(self.power),
                     o=float(self.o))
 
+    # the model-level calls, under MixedSpec's names
+    def _op_args(self) -> tuple:
+        return (self.hyper, list(self.xcols), list(self.fcols), self.power, self.o)
+
+    def build_cache(self, X, y, noise, constant, optimistic: bool = False):
+        return build_ltf_cache(X, y, self, noise, constant, optimistic)
+
+    def mll_row_terms(self, X, L, Ainv, alpha, beta):
+        from . import ops  # noqa: F401  (torch.ops.bo registration)
+        return torch.ops.bo.ltf_mll_terms(X, *self._op_args(), L, Ainv, alpha, beta)
+
+    def cross(self, Xq, Xt):
+        from . import ops  # noqa: F401  (torch.ops.bo registration)
+        return torch.ops.bo.ltf_cross(Xq, Xt, *self._op_args())
+
+    def cross_grad(self, Xq, Xt, dKx, G):
+        from . import ops  # noqa: F401  (torch.ops.bo registration)
+        return torch.ops.bo.ltf_cross_grad(Xq, Xt, *self._op_args(), dKx, G)
+
 
 def _ltf_check(spec: LTFSpec, *rows) -> None:
     dx, d = len(spec.xcols), len(spec.xcols) + len(spec.fcols)
@@ -757,12 +808,11 @@ def ltf_covar(X, spec: LTFSpec, noise=0.0, noise_vec=None, out=None):
 
 
 def build_ltf_cache(X, y, spec: LTFSpec, noise, constant, optimistic: bool = False):
-    """GPCache of the multi-fidelity model (build_icm_cache's ladder and status contract
-    with bo_ltf_covar as the covariance).  As for build_mixed_cache only L, Linv, U,
-    beta, alpha, Ainv, Xt, n, np and the constant describe the model."""
-    return build_icm_cache(X, None, y, spec.hyper, None, noise, constant, kind=_lib.MATERN52,
-                           outputscale=spec.o, optimistic=optimistic,
-                           fill=lambda s2, nv, L: ltf_covar(X, spec, s2, nv, out=L))
+    """GPCache of the multi-fidelity model: build_dense_cache of bo_ltf_covar's
+    covariance (``lengthscale`` holds spec.hyper, 2 d_x values)."""
+    return build_dense_cache(X, y, spec.hyper, noise, constant,
+                             lambda s2, nv, L: ltf_covar(X, spec, s2, nv, out=L), _lib.MATERN52,
+                             spec.o, optimistic)
 
 
 def ltf_mll_partials(X, spec: LTFSpec, L, Ainv, alpha, beta):

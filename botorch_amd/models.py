@@ -396,6 +396,18 @@ class Model(_TrackedModule):
         return self._ostats
 
 
+def _params_key(self):
+    """What a model's prediction caches depend on: (data_ptr, _version) of the training
+    tensors and every parameter (the list of parameters is reused until _STRUCTURE
+    changes).  The ``_key`` of MultiTaskGP and of the structured-kernel models."""
+    d = self.__dict__
+    if d.get("_plist_gen") != _STRUCTURE[0]:
+        d["_plist"] = list(self.parameters())
+        d["_plist_gen"] = _STRUCTURE[0]
+    ps = [self.train_inputs[0], self.train_targets] + d["_plist"]
+    return tuple((p.data_ptr(), p._version) for p in ps)
+
+
 class SingleTaskGP(Model):
     """Single-output exact GP (botorch/models/gp_regression.py:130-254).
 
@@ -1537,13 +1549,7 @@ class MultiTaskGP(Model):
         self._cache_key = None
         self._views = {}
 
-    def _key(self):
-        d = self.__dict__
-        if d.get("_plist_gen") != _STRUCTURE[0]:
-            d["_plist"] = list(self.parameters())
-            d["_plist_gen"] = _STRUCTURE[0]
-        ps = [self.train_inputs[0], self.train_targets] + d["_plist"]
-        return tuple((p.data_ptr(), p._version) for p in ps)
+    _key = _params_key
 
     def _base_cache(self):
         """The caches of the ICM training covariance (its L, L^{-1}, U, beta,
@@ -1729,6 +1735,102 @@ class CategoricalKernel(_TrackedModule):
     lengthscale = _Kernel.lengthscale
 
 
+class _StructuredKernelGP(Model):
+    """What MixedSingleTaskGP and SingleTaskMultiFidelityGP share: a single-output exact
+    GP whose kernel has launches of its own, reached through ``posterior`` alone.  The
+    subclass gives ``fused()`` (the route), ``spec()`` (the kernels' spec of the current
+    hyperparameters: its cache builder, ``cross`` and ``cross_grad``), ``covar_torch(X1,
+    X2)`` (the torch route) and ``_family`` (the refusals' word for its models)."""
+
+    _family = None
+
+    def train(self, mode: bool = True):
+        if mode:
+            self._cache = None
+            self._cache_key = None
+        return super().train(mode)
+
+    _key = _params_key
+
+    def _noise(self):
+        fixed = isinstance(self.likelihood, FixedNoiseGaussianLikelihood)
+        return self.likelihood.noise.detach() if fixed else float(self.likelihood.noise.detach())
+
+    def _caches(self):
+        """The prediction caches, rebuilt on any change of a parameter or training
+        tensor: (spec, kernels.GPCache) from the spec's covariance launch and the
+        Cholesky ladder on the fused route, (L, alpha, constant) from torch.linalg on
+        the torch route."""
+        from .settings import propagate_grads
+        if propagate_grads.on() and (self.train_inputs[0].requires_grad or self.train_targets.requires_grad):
+            raise UnsupportedError(
+                "settings.propagate_grads: posterior gradients to the training data are not "
+                "supported (the prediction caches are built without a backward to them)")
+        key = (self._key(), self.fused())
+        if self._cache is None or self._cache_key != key:
+            X, y = self.train_inputs[0], self.train_targets
+            c = float(self.mean_module.constant.detach())
+            noise = self._noise()
+            if self.fused():
+                spec = self.spec()
+                cache, _ = spec.build_cache(X, y, noise, c)
+                self._cache = (spec, cache)
+            else:
+                K = self.covar_torch(X, X)
+                K = K + (torch.diag(noise) if torch.is_tensor(noise)
+                         else noise * torch.eye(X.shape[0], dtype=K.dtype, device=K.device))
+                L = _cholesky_ladder(K)
+                alpha = torch.cholesky_solve((y - c).unsqueeze(-1), L).squeeze(-1)
+                self._cache = (L, alpha, c)
+            self._cache_key = key
+        return self._cache
+
+    # -- posterior ---------------------------------------------------------------------------
+    def moments(self, X: torch.Tensor):
+        """(mean: batch x q, covariance: batch x q x q) at X (batch x q x d) in outcome
+        space, differentiable in the columns of X the kernel differentiates."""
+        from .posteriors import _StructuredMoments
+        d = self.train_inputs[0].shape[-1]
+        if X.shape[-1] != d:
+            raise ValueError(f"{type(self).__name__}.posterior: X has {X.shape[-1]} columns, expected {d}")
+        if X.dtype != torch.float64:
+            X = X.to(torch.float64)
+        self.eval()
+        batch, q = X.shape[:-2], X.shape[-2]
+        ymean, ystd = self.outcome_stats()
+        if self.fused():
+            mean, cov = _StructuredMoments.apply(X.reshape(-1, q, d).contiguous(), self)
+            return mean.reshape(*batch, q), cov.reshape(*batch, q, q)
+        L, alpha, c = self._caches()
+        Kx = self.covar_torch(X, self.train_inputs[0])
+        V = torch.linalg.solve_triangular(L, Kx.mT, upper=False)
+        return ymean + ystd * (Kx @ alpha + c), (self.covar_torch(X, X) - V.mT @ V) * (ystd * ystd)
+
+    def posterior(self, X: torch.Tensor, output_indices=None, observation_noise=False,
+                  posterior_transform=None):
+        """models/gpytorch.py:127-199 for the model's kernel, computing in fp64."""
+        from .posteriors import GPyTorchPosterior, MultivariateNormal
+        if torch.is_tensor(observation_noise):
+            raise UnsupportedError(f"{type(self).__name__}.posterior: a tensor of observation "
+                                   "noise is not on the accelerated path")
+        mean, cov = self.moments(X)
+        if observation_noise is True:
+            ystd = self.outcome_stats()[1]
+            nz = self.likelihood.noise.detach().mean()
+            cov = cov + torch.diag_embed((nz * (ystd * ystd)).expand(mean.shape))
+        post = GPyTorchPosterior(MultivariateNormal(mean, cov), model=self, X=X)
+        return post if posterior_transform is None else posterior_transform(post)
+
+    # -- what stays off the accelerated path ---------------------------------------------------
+    def condition_on_observations(self, X, Y, **kwargs):
+        raise UnsupportedError(f"condition_on_observations: {type(self).__name__} is not on the "
+                               f"accelerated path (conditioning of {self._family} models)")
+
+    def fantasize(self, X, sampler, observation_noise=None, **kwargs):
+        raise UnsupportedError(f"fantasize: {type(self).__name__} is not on the accelerated path "
+                               f"(fantasy models of {self._family} models)")
+
+
 def mixed_covar_torch(X1, X2, cont, cat, kind, ls1, lam1, ls2, lam2, o_s, o_c, o_p):
     """The mixed covariance K(X1, X2) in plain torch (the torch route; autograd
     carries its gradients): o_s (kbar(l1) + o_c kap(lam1)) + o_p kbar(l2) kap(lam2),
@@ -1753,7 +1855,7 @@ def mixed_covar_torch(X1, X2, cont, cat, kind, ls1, lam1, ls2, lam2, o_s, o_c, o
     return o_s * (kbar(ls1) + o_c * kap(lam1)) + o_p * kbar(ls2) * kap(lam2)
 
 
-class MixedSingleTaskGP(Model):
+class MixedSingleTaskGP(_StructuredKernelGP):
     """Single-output exact GP over continuous and categorical columns
     (botorch/models/gp_regression_mixed.py:32-182):
       K = o_s (k_cont(l1) + o_c k_cat(lam1)) + o_p k_cont(l2) k_cat(lam2),
@@ -1771,6 +1873,7 @@ class MixedSingleTaskGP(Model):
     ``posterior`` alone."""
 
     _is_mixed = True
+    _family = "mixed"
 
     def __init__(self, train_X: torch.Tensor, train_Y: torch.Tensor, cat_dims: List[int],
                  train_Yvar: Optional[torch.Tensor] = None, cont_kernel_factory=None,
@@ -1893,7 +1996,7 @@ class MixedSingleTaskGP(Model):
         return kernels.MixedSpec(int(self.kind), tuple(self.cont_dims), tuple(self.cat_dims),
                                  hyper.contiguous(), *scales)
 
-    def _covar_torch(self, X1, X2):
+    def covar_torch(self, X1, X2):
         ls = [m.lengthscale.detach().reshape(-1) for m in self.lengthscale_modules()]
         sc = self.raw_outputscales.detach()
         if not self.cont_dims:
@@ -1901,87 +2004,6 @@ class MixedSingleTaskGP(Model):
                                      sc[0], None, None)
         return mixed_covar_torch(X1, X2, self.cont_dims, self.cat_dims, self.kind, ls[0], ls[1],
                                  ls[2], ls[3], sc[0], sc[1], sc[2])
-
-    def train(self, mode: bool = True):
-        if mode:
-            self._cache = None
-            self._cache_key = None
-        return super().train(mode)
-
-    _key = MultiTaskGP._key
-
-    def _noise(self):
-        fixed = isinstance(self.likelihood, FixedNoiseGaussianLikelihood)
-        return self.likelihood.noise.detach() if fixed else float(self.likelihood.noise.detach())
-
-    def _caches(self):
-        """The prediction caches, rebuilt on any change of a parameter or training
-        tensor: a kernels.GPCache from bo_mixed_covar and the Cholesky ladder on the
-        fused route, (L, alpha) from torch.linalg on the torch route."""
-        from . import kernels
-        from .settings import propagate_grads
-        if propagate_grads.on() and (self.train_inputs[0].requires_grad or self.train_targets.requires_grad):
-            raise UnsupportedError(
-                "settings.propagate_grads: posterior gradients to the training data are not "
-                "supported (the prediction caches are built without a backward to them)")
-        key = (self._key(), self.fused())
-        if self._cache is None or self._cache_key != key:
-            X, y = self.train_inputs[0], self.train_targets
-            c = float(self.mean_module.constant.detach())
-            if self.fused():
-                spec = self.spec()
-                cache, _ = kernels.build_mixed_cache(X, y, spec, self._noise(), c)
-                self._cache = (spec, cache)
-            else:
-                noise = self._noise()
-                K = self._covar_torch(X, X)
-                K = K + (torch.diag(noise) if torch.is_tensor(noise)
-                         else noise * torch.eye(X.shape[0], dtype=K.dtype, device=K.device))
-                L = _cholesky_ladder(K)
-                alpha = torch.cholesky_solve((y - c).unsqueeze(-1), L).squeeze(-1)
-                self._cache = (L, alpha, c)
-            self._cache_key = key
-        return self._cache
-
-    # -- posterior ---------------------------------------------------------------------------
-    def posterior(self, X: torch.Tensor, output_indices=None, observation_noise=False,
-                  posterior_transform=None):
-        """models/gpytorch.py:127-199 for the mixed kernel, computing in fp64."""
-        from .posteriors import GPyTorchPosterior, MultivariateNormal, _MixedMoments
-        if torch.is_tensor(observation_noise):
-            raise UnsupportedError("MixedSingleTaskGP.posterior: a tensor of observation noise "
-                                   "is not on the accelerated path")
-        d = self.train_inputs[0].shape[-1]
-        if X.shape[-1] != d:
-            raise ValueError(f"MixedSingleTaskGP.posterior: X has {X.shape[-1]} columns, expected {d}")
-        if X.dtype != torch.float64:
-            X = X.to(torch.float64)
-        self.eval()
-        batch, q = X.shape[:-2], X.shape[-2]
-        ymean, ystd = self.outcome_stats()
-        if self.fused():
-            mean, cov = _MixedMoments.apply(X.reshape(-1, q, d).contiguous(), self)
-            mean, cov = mean.reshape(*batch, q), cov.reshape(*batch, q, q)
-        else:
-            L, alpha, c = self._caches()
-            Kx = self._covar_torch(X, self.train_inputs[0])
-            V = torch.linalg.solve_triangular(L, Kx.mT, upper=False)
-            mean = ymean + ystd * (Kx @ alpha + c)
-            cov = (self._covar_torch(X, X) - V.mT @ V) * (ystd * ystd)
-        if observation_noise is True:
-            nz = self.likelihood.noise.detach().mean()
-            cov = cov + torch.diag_embed((nz * (ystd * ystd)).expand(*batch, q))
-        post = GPyTorchPosterior(MultivariateNormal(mean, cov), model=self, X=X)
-        return post if posterior_transform is None else posterior_transform(post)
-
-    # -- what stays off the accelerated path ---------------------------------------------------
-    def condition_on_observations(self, X, Y, **kwargs):
-        raise UnsupportedError("condition_on_observations: MixedSingleTaskGP is not on the "
-                               "accelerated path (conditioning of mixed models)")
-
-    def fantasize(self, X, sampler, observation_noise=None, **kwargs):
-        raise UnsupportedError("fantasize: MixedSingleTaskGP is not on the accelerated path "
-                               "(fantasy models of mixed models)")
 
 
 LTF_POWER_LOWER = 1e-4  # floor of the fidelity kernel's power in the fit (the reference: Positive)
@@ -2089,7 +2111,7 @@ def ltf_covar_torch(X1, X2, xcols, fcols, l0, l1, power):
     return matern(l0) + c * matern(l1)
 
 
-class SingleTaskMultiFidelityGP(Model):
+class SingleTaskMultiFidelityGP(_StructuredKernelGP):
     """Single-output exact GP over design columns and fidelity columns
     (botorch/models/gp_regression_fidelity.py:51-180, 218-344) with the linear
     truncated fidelity kernel: K = o prod_k [k0(l0_k) + c(s; p_k) k1(l1_k)], one factor
@@ -2109,6 +2131,7 @@ class SingleTaskMultiFidelityGP(Model):
     ``posterior`` alone."""
 
     _is_ltf = True
+    _family = "multi-fidelity"
 
     def __init__(self, train_X: torch.Tensor, train_Y: torch.Tensor,
                  train_Yvar: Optional[torch.Tensor] = None,
@@ -2295,24 +2318,6 @@ class SingleTaskMultiFidelityGP(Model):
                 at += len(f.NAMES)
         return o * K
 
-    def train(self, mode: bool = True):
-        if mode:
-            self._cache = None
-            self._cache_key = None
-        return super().train(mode)
-
-    def _key(self):
-        d = self.__dict__
-        if d.get("_plist_gen") != _STRUCTURE[0]:
-            d["_plist"] = list(self.parameters())
-            d["_plist_gen"] = _STRUCTURE[0]
-        ps = [self.train_inputs[0], self.train_targets] + d["_plist"]
-        return tuple((p.data_ptr(), p._version) for p in ps)
-
-    def _noise(self):
-        fixed = isinstance(self.likelihood, FixedNoiseGaussianLikelihood)
-        return self.likelihood.noise.detach() if fixed else float(self.likelihood.noise.detach())
-
     def fantasy_noise(self) -> float:
         """The likelihood's noise (fixed noise: its mean) as a host float, read back once
         per change of a parameter (the knowledge gradient's sigma^2 before ystd^2)."""
@@ -2321,80 +2326,6 @@ class SingleTaskMultiFidelityGP(Model):
             self._fnoise = float(self.likelihood.noise.detach().mean())
             self._fnoise_key = key
         return self._fnoise
-
-    def _caches(self):
-        """The prediction caches, rebuilt on any change of a parameter or training
-        tensor: (spec, kernels.GPCache) from bo_ltf_covar and the Cholesky ladder on
-        the fused route, (L, alpha, constant) from torch.linalg on the torch route."""
-        from . import kernels
-        from .settings import propagate_grads
-        if propagate_grads.on() and (self.train_inputs[0].requires_grad or self.train_targets.requires_grad):
-            raise UnsupportedError(
-                "settings.propagate_grads: posterior gradients to the training data are not "
-                "supported (the prediction caches are built without a backward to them)")
-        key = (self._key(), self.fused())
-        if self._cache is None or self._cache_key != key:
-            X, y = self.train_inputs[0], self.train_targets
-            c = float(self.mean_module.constant.detach())
-            noise = self._noise()
-            if self.fused():
-                spec = self.spec()
-                cache, _ = kernels.build_ltf_cache(X, y, spec, noise, c)
-                self._cache = (spec, cache)
-            else:
-                K = self.covar_torch(X, X)
-                K = K + (torch.diag(noise) if torch.is_tensor(noise)
-                         else noise * torch.eye(X.shape[0], dtype=K.dtype, device=K.device))
-                L = _cholesky_ladder(K)
-                alpha = torch.cholesky_solve((y - c).unsqueeze(-1), L).squeeze(-1)
-                self._cache = (L, alpha, c)
-            self._cache_key = key
-        return self._cache
-
-    # -- posterior ---------------------------------------------------------------------------
-    def moments(self, X: torch.Tensor):
-        """(mean: batch x q, covariance: batch x q x q) at X (batch x q x d) in outcome
-        space, differentiable in every column of X."""
-        from .posteriors import _LTFMoments
-        d = self.train_inputs[0].shape[-1]
-        if X.shape[-1] != d:
-            raise ValueError(f"{type(self).__name__}.posterior: X has {X.shape[-1]} columns, expected {d}")
-        if X.dtype != torch.float64:
-            X = X.to(torch.float64)
-        self.eval()
-        batch, q = X.shape[:-2], X.shape[-2]
-        ymean, ystd = self.outcome_stats()
-        if self.fused():
-            mean, cov = _LTFMoments.apply(X.reshape(-1, q, d).contiguous(), self)
-            return mean.reshape(*batch, q), cov.reshape(*batch, q, q)
-        L, alpha, c = self._caches()
-        Kx = self.covar_torch(X, self.train_inputs[0])
-        V = torch.linalg.solve_triangular(L, Kx.mT, upper=False)
-        return ymean + ystd * (Kx @ alpha + c), (self.covar_torch(X, X) - V.mT @ V) * (ystd * ystd)
-
-    def posterior(self, X: torch.Tensor, output_indices=None, observation_noise=False,
-                  posterior_transform=None):
-        """models/gpytorch.py:127-199 for the fidelity kernel, computing in fp64."""
-        from .posteriors import GPyTorchPosterior, MultivariateNormal
-        if torch.is_tensor(observation_noise):
-            raise UnsupportedError(f"{type(self).__name__}.posterior: a tensor of observation "
-                                   "noise is not on the accelerated path")
-        mean, cov = self.moments(X)
-        if observation_noise is True:
-            ystd = self.outcome_stats()[1]
-            nz = self.likelihood.noise.detach().mean()
-            cov = cov + torch.diag_embed((nz * (ystd * ystd)).expand(mean.shape))
-        post = GPyTorchPosterior(MultivariateNormal(mean, cov), model=self, X=X)
-        return post if posterior_transform is None else posterior_transform(post)
-
-    # -- what stays off the accelerated path ---------------------------------------------------
-    def condition_on_observations(self, X, Y, **kwargs):
-        raise UnsupportedError("condition_on_observations: SingleTaskMultiFidelityGP is not on "
-                               "the accelerated path (conditioning of multi-fidelity models)")
-
-    def fantasize(self, X, sampler, observation_noise=None, **kwargs):
-        raise UnsupportedError("fantasize: SingleTaskMultiFidelityGP is not on the accelerated "
-                               "path (fantasy models of multi-fidelity models)")
 
 
 def _cholesky_ladder(K: torch.Tensor) -> torch.Tensor:

@@ -35,30 +35,56 @@ def _fused_moments(X3: torch.Tensor, model):
     return mean, cov
 
 
+def _exact_forward(Kx, cache, B: int, q: int):
+    """[G] exact prediction from K*x (Bq x n) against the cached factor: R = K*x L^{-T}
+    (triangular MFMA GEMM against the cached U, leading dimension np), K*x alpha
+    (B x q) and the R_b R_b^T blocks (batched GEMM)."""
+    n, np_ = cache.n, cache.np
+    R = torch.empty(B * q, n, dtype=torch.float64, device=Kx.device)
+    kernels.gemm_strided(B * q, n, n, Kx, n, 0, cache.U, np_, 0, R, n, 0, 1,
+                         flags=_lib.GEMM_B_UPPER)
+    mean = kernels.gemm(Kx, cache.alpha.reshape(n, 1)).reshape(B, q)
+    RR = kernels.gemm(R.view(B, q, n), R.view(B, q, n), transB=True)
+    return R, mean, RR
+
+
+def _exact_backward(cache, R, ystd, dmean, dcov, B: int, q: int):
+    """The backward of _exact_forward in outcome space (s = ystd): d mu* = s d mu',
+    G = s^2 (dS + dS^T) = d K** (B x q x q) and d K*x = d mu* alpha^T - G_b W_b
+    (Bq x n) with W = R L^{-1} = K*x A^{-1} (GEMM against U^T).  A missing
+    gradient (None) counts as zero."""
+    n, np_ = cache.n, cache.np
+    dev = R.device
+    if dmean is None:
+        dmean = torch.zeros(B, q, dtype=torch.float64, device=dev)
+    if dcov is None:
+        dcov = torch.zeros(B, q, q, dtype=torch.float64, device=dev)
+    G = ((ystd * ystd) * (dcov + dcov.mT)).contiguous()
+    W = torch.empty(B * q, n, dtype=torch.float64, device=dev)      # R L^{-1} = R U^T
+    kernels.gemm_strided(B * q, n, n, R, n, 0, cache.U, np_, 0, W, n, 0, 1,
+                         transB=True, flags=_lib.GEMM_B_LOWER)
+    dK = ((ystd * dmean).reshape(B * q, 1) * cache.alpha.reshape(1, n)).contiguous()
+    kernels.gemm(G, W.view(B, q, n), alpha=-1.0, beta=1.0, C=dK.view(B, q, n))
+    return G, dK
+
+
 class _GeneralMoments(torch.autograd.Function):
     """(mean', Sigma') of B t-batches of any q and any d <= 128 through the
     generic kernels, differentiable w.r.t. X.
 
-    Forward ([G] exact prediction): K*x (bo_covar_matrix), R = K*x L^{-T}
-    (triangular MFMA GEMM against the cached U, leading dimension np), the
-    R_b R_b^T blocks (batched GEMM), K** (bo_covar_blocks), mean = c + K*x alpha.
-    Backward: d mu* = s d mu', G = s^2 (dS + dS^T); d K*x = d mu* alpha^T - G_b W_b
-    with W = R L^{-1} = K*x A^{-1} (GEMM against U^T); d K** = G through
-    bo_kernel_grad over the training points and over the t-batch's own points."""
+    Forward: K*x (bo_covar_matrix), _exact_forward, K** (bo_covar_blocks),
+    mean = c + K*x alpha.  Backward: _exact_backward, then d K*x and d K** = G
+    through bo_kernel_grad over the training points and over the t-batch's own
+    points."""
 
     @staticmethod
     def forward(ctx, X3, model):
         cache = model.prediction_cache()
         ymean, ystd = model.outcome_stats()
         B, q, d = X3.shape
-        n, np_ = cache.n, cache.np
         X2 = X3.detach().reshape(B * q, d).contiguous()
         Kx = kernels.covar_matrix(X2, cache.Xt, cache.lengthscale, cache.kind, cache.outputscale)
-        R = torch.empty(B * q, n, dtype=torch.float64, device=X2.device)
-        kernels.gemm_strided(B * q, n, n, Kx, n, 0, cache.U, np_, 0, R, n, 0, 1,
-                             flags=_lib.GEMM_B_UPPER)
-        mean = kernels.gemm(Kx, cache.alpha.reshape(n, 1)).reshape(B, q)
-        RR = kernels.gemm(R.view(B, q, n), R.view(B, q, n), transB=True)
+        R, mean, RR = _exact_forward(Kx, cache, B, q)
         Kxx = kernels.covar_blocks(X3.detach(), cache.lengthscale, cache.kind, cache.outputscale)
         cov = (Kxx - RR) * (ystd * ystd)
         mean = ymean + ystd * (mean + cache.constant)
@@ -68,20 +94,9 @@ class _GeneralMoments(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dmean, dcov):
-        cache, ystd = ctx.cache, ctx.ystd
+        cache = ctx.cache
         B, q, d = ctx.shape
-        n, np_ = cache.n, cache.np
-        dev = ctx.R.device
-        if dmean is None:
-            dmean = torch.zeros(B, q, dtype=torch.float64, device=dev)
-        if dcov is None:
-            dcov = torch.zeros(B, q, q, dtype=torch.float64, device=dev)
-        G = ((ystd * ystd) * (dcov + dcov.mT)).contiguous()
-        W = torch.empty(B * q, n, dtype=torch.float64, device=dev)      # R L^{-1} = R U^T
-        kernels.gemm_strided(B * q, n, n, ctx.R, n, 0, cache.U, np_, 0, W, n, 0, 1,
-                             transB=True, flags=_lib.GEMM_B_LOWER)
-        dK = ((ystd * dmean).reshape(B * q, 1) * cache.alpha.reshape(1, n)).contiguous()
-        kernels.gemm(G, W.view(B, q, n), alpha=-1.0, beta=1.0, C=dK.view(B, q, n))
+        G, dK = _exact_backward(cache, ctx.R, ctx.ystd, dmean, dcov, B, q)
         dX = kernels.kernel_grad(ctx.X2, cache.Xt, dK, cache.lengthscale, cache.kind,
                                  cache.outputscale)
         dX = kernels.kernel_grad(ctx.X2, ctx.X2, G.view(B * q, q), cache.lengthscale, cache.kind,
@@ -105,17 +120,12 @@ class _ICMGeneralMoments(torch.autograd.Function):
         Bm = model.task_covar_module.covar_matrix.detach()
         ymean, ystd = model.outcome_stats()
         B, q, d = X3.shape
-        n, np_ = cache.n, cache.np
         X2 = X3.detach().reshape(B * q, d).contiguous()
         Sx = Bm[tq.reshape(-1)][:, model._task_long]                       # Bq x n
         Sq = Bm[tq.unsqueeze(-1), tq.unsqueeze(-2)]                        # B x q x q
         Kx = kernels.covar_matrix(X2, cache.Xt, cache.lengthscale, cache.kind, cache.outputscale)
         Kx = (Kx * Sx).contiguous()
-        R = torch.empty(B * q, n, dtype=torch.float64, device=X2.device)
-        kernels.gemm_strided(B * q, n, n, Kx, n, 0, cache.U, np_, 0, R, n, 0, 1,
-                             flags=_lib.GEMM_B_UPPER)
-        mean = kernels.gemm(Kx, cache.alpha.reshape(n, 1)).reshape(B, q)
-        RR = kernels.gemm(R.view(B, q, n), R.view(B, q, n), transB=True)
+        R, mean, RR = _exact_forward(Kx, cache, B, q)
         Kxx = kernels.covar_blocks(X3.detach(), cache.lengthscale, cache.kind, cache.outputscale)
         cov = (Kxx * Sq - RR) * (ystd * ystd)
         mean = ymean + ystd * (mean + cache.constant)
@@ -126,20 +136,9 @@ class _ICMGeneralMoments(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dmean, dcov):
-        cache, ystd = ctx.cache, ctx.ystd
+        cache = ctx.cache
         B, q, d = ctx.shape
-        n, np_ = cache.n, cache.np
-        dev = ctx.R.device
-        if dmean is None:
-            dmean = torch.zeros(B, q, dtype=torch.float64, device=dev)
-        if dcov is None:
-            dcov = torch.zeros(B, q, q, dtype=torch.float64, device=dev)
-        G = ((ystd * ystd) * (dcov + dcov.mT)).contiguous()
-        W = torch.empty(B * q, n, dtype=torch.float64, device=dev)      # R L^{-1} = R U^T
-        kernels.gemm_strided(B * q, n, n, ctx.R, n, 0, cache.U, np_, 0, W, n, 0, 1,
-                             transB=True, flags=_lib.GEMM_B_LOWER)
-        dK = ((ystd * dmean).reshape(B * q, 1) * cache.alpha.reshape(1, n)).contiguous()
-        kernels.gemm(G, W.view(B, q, n), alpha=-1.0, beta=1.0, C=dK.view(B, q, n))
+        G, dK = _exact_backward(cache, ctx.R, ctx.ystd, dmean, dcov, B, q)
         dX = kernels.kernel_grad(ctx.X2, cache.Xt, (dK * ctx.Sx).contiguous(), cache.lengthscale,
                                  cache.kind, cache.outputscale)
         dX = kernels.kernel_grad(ctx.X2, ctx.X2, (G * ctx.Sq).reshape(B * q, q).contiguous(),
@@ -147,29 +146,23 @@ class _ICMGeneralMoments(torch.autograd.Function):
         return dX.reshape(B, q, d), None, None
 
 
-class _MixedMoments(torch.autograd.Function):
-    """(mean', Sigma') of B t-batches of a MixedSingleTaskGP, differentiable w.r.t.
-    the continuous columns of X (the categorical columns get exact zeros).
-    _GeneralMoments with bo_mixed_cross in place of bo_covar_matrix + bo_covar_blocks
-    (K*x and the K** blocks in one launch) and bo_mixed_cross_grad in place of the two
-    bo_kernel_grad calls; the triangular and batched GEMMs against the cached U
-    are the same."""
+class _StructuredMoments(torch.autograd.Function):
+    """(mean', Sigma') of B t-batches of a model whose kernel has its own launches
+    (MixedSingleTaskGP, SingleTaskMultiFidelityGP), differentiable w.r.t. X.
+    _GeneralMoments with the spec of ``model._caches()`` giving K*x and the K** blocks
+    in one launch (``spec.cross``: bo_mixed_cross, bo_ltf_cross) and dX from d K*x and
+    G in one (``spec.cross_grad``); which columns of X get a gradient is the kernel's
+    matter (mixed: exact zeros in the categorical columns; multi-fidelity: every
+    column, the fidelity columns with torch.clamp's gradient)."""
 
     @staticmethod
     def forward(ctx, X3, model):
-        from . import ops  # noqa: F401  (torch.ops.bo registration)
         spec, cache = model._caches()
         ymean, ystd = model.outcome_stats()
         B, q, d = X3.shape
-        n, np_ = cache.n, cache.np
         Xq = X3.detach().contiguous()
-        Kx, Kxx = torch.ops.bo.mixed_cross(Xq, cache.Xt, spec.hyper, list(spec.cont),
-                                           list(spec.cat), spec.kind, spec.o_s, spec.o_c, spec.o_p)
-        R = torch.empty(B * q, n, dtype=torch.float64, device=Xq.device)
-        kernels.gemm_strided(B * q, n, n, Kx, n, 0, cache.U, np_, 0, R, n, 0, 1,
-                             flags=_lib.GEMM_B_UPPER)
-        mean = kernels.gemm(Kx, cache.alpha.reshape(n, 1)).reshape(B, q)
-        RR = kernels.gemm(R.view(B, q, n), R.view(B, q, n), transB=True)
+        Kx, Kxx = spec.cross(Xq, cache.Xt)
+        R, mean, RR = _exact_forward(Kx, cache, B, q)
         cov = (Kxx - RR) * (ystd * ystd)
         mean = ymean + ystd * (mean + cache.constant)
         if ctx.needs_input_grad[0]:
@@ -178,71 +171,10 @@ class _MixedMoments(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dmean, dcov):
-        cache, spec, ystd, Xq = ctx.cache, ctx.spec, ctx.ystd, ctx.Xq
+        cache, Xq = ctx.cache, ctx.Xq
         B, q, d = Xq.shape
-        n, np_ = cache.n, cache.np
-        dev = ctx.R.device
-        if dmean is None:
-            dmean = torch.zeros(B, q, dtype=torch.float64, device=dev)
-        if dcov is None:
-            dcov = torch.zeros(B, q, q, dtype=torch.float64, device=dev)
-        G = ((ystd * ystd) * (dcov + dcov.mT)).contiguous()
-        W = torch.empty(B * q, n, dtype=torch.float64, device=dev)      # R L^{-1} = R U^T
-        kernels.gemm_strided(B * q, n, n, ctx.R, n, 0, cache.U, np_, 0, W, n, 0, 1,
-                             transB=True, flags=_lib.GEMM_B_LOWER)
-        dK = ((ystd * dmean).reshape(B * q, 1) * cache.alpha.reshape(1, n)).contiguous()
-        kernels.gemm(G, W.view(B, q, n), alpha=-1.0, beta=1.0, C=dK.view(B, q, n))
-        dX = torch.ops.bo.mixed_cross_grad(Xq, cache.Xt, spec.hyper, list(spec.cont), list(spec.cat),
-                                           spec.kind, spec.o_s, spec.o_c, spec.o_p, dK, G)
-        return dX, None
-
-
-class _LTFMoments(torch.autograd.Function):
-    """(mean', Sigma') of B t-batches of a SingleTaskMultiFidelityGP, differentiable
-    w.r.t. every column of X, the fidelity columns included (torch.clamp's gradient).
-    _MixedMoments with bo_ltf_cross and bo_ltf_cross_grad; the triangular and batched
-    GEMMs against the cached U are the same."""
-
-    @staticmethod
-    def forward(ctx, X3, model):
-        from . import ops  # noqa: F401  (torch.ops.bo registration)
-        spec, cache = model._caches()
-        ymean, ystd = model.outcome_stats()
-        B, q, d = X3.shape
-        n, np_ = cache.n, cache.np
-        Xq = X3.detach().contiguous()
-        Kx, Kxx = torch.ops.bo.ltf_cross(Xq, cache.Xt, spec.hyper, list(spec.xcols),
-                                         list(spec.fcols), spec.power, spec.o)
-        R = torch.empty(B * q, n, dtype=torch.float64, device=Xq.device)
-        kernels.gemm_strided(B * q, n, n, Kx, n, 0, cache.U, np_, 0, R, n, 0, 1,
-                             flags=_lib.GEMM_B_UPPER)
-        mean = kernels.gemm(Kx, cache.alpha.reshape(n, 1)).reshape(B, q)
-        RR = kernels.gemm(R.view(B, q, n), R.view(B, q, n), transB=True)
-        cov = (Kxx - RR) * (ystd * ystd)
-        mean = ymean + ystd * (mean + cache.constant)
-        if ctx.needs_input_grad[0]:
-            ctx.cache, ctx.spec, ctx.ystd, ctx.Xq, ctx.R = cache, spec, ystd, Xq, R
-        return mean, cov
-
-    @staticmethod
-    def backward(ctx, dmean, dcov):
-        cache, spec, ystd, Xq = ctx.cache, ctx.spec, ctx.ystd, ctx.Xq
-        B, q, d = Xq.shape
-        n, np_ = cache.n, cache.np
-        dev = ctx.R.device
-        if dmean is None:
-            dmean = torch.zeros(B, q, dtype=torch.float64, device=dev)
-        if dcov is None:
-            dcov = torch.zeros(B, q, q, dtype=torch.float64, device=dev)
-        G = ((ystd * ystd) * (dcov + dcov.mT)).contiguous()
-        W = torch.empty(B * q, n, dtype=torch.float64, device=dev)      # R L^{-1} = R U^T
-        kernels.gemm_strided(B * q, n, n, ctx.R, n, 0, cache.U, np_, 0, W, n, 0, 1,
-                             transB=True, flags=_lib.GEMM_B_LOWER)
-        dK = ((ystd * dmean).reshape(B * q, 1) * cache.alpha.reshape(1, n)).contiguous()
-        kernels.gemm(G, W.view(B, q, n), alpha=-1.0, beta=1.0, C=dK.view(B, q, n))
-        dX = torch.ops.bo.ltf_cross_grad(Xq, cache.Xt, spec.hyper, list(spec.xcols),
-                                         list(spec.fcols), spec.power, spec.o, dK, G)
-        return dX, None
+        G, dK = _exact_backward(cache, ctx.R, ctx.ystd, dmean, dcov, B, q)
+        return ctx.spec.cross_grad(Xq, cache.Xt, dK, G), None
 
 
 class _PairwiseMoments(torch.autograd.Function):

@@ -379,3 +379,34 @@ def test_icm_ops_registered_with_fake_shapes():
     for name in ("MultiTaskGP", "IndexKernel", "GammaPrior", "get_matern_kernel_with_gamma_prior",
                  "get_gaussian_likelihood_with_gamma_prior", "icm_mll_terms", "icm_mll_terms_torch"):
         assert name in botorch_amd.__all__ and getattr(botorch_amd, name) is not None
+
+
+@pytest.mark.parametrize("status", [0, 3, -1])
+def test_optimistic_then_ladder_protocol(status):
+    """fit._optimistic_then_ladder with fakes for the device: status 0 keeps the one
+    optimistic build; a positive status takes exactly one further build, the ladder's,
+    and returns its sums; a negative status raises without a second build."""
+    from botorch_amd import fit
+    builds, info = [], object()
+
+    def build(optimistic):
+        builds.append(optimistic)
+        return ("optimistic" if optimistic else "ladder"), (info if optimistic else None)
+
+    def sums(cache, given):
+        assert given is (info if cache == "optimistic" else None)
+        base = np.array([1.0, 2.0]) if cache == "optimistic" else np.array([5.0, 7.0])
+        return np.append(base, float(status)) if given is not None else base
+
+    if status < 0:
+        with pytest.raises(RuntimeError, match="the Cholesky task DAG timed out"):
+            fit._optimistic_then_ladder(build, sums)
+        assert builds == [True]
+        return
+    s = fit._optimistic_then_ladder(build, sums)
+    if status == 0:
+        assert builds == [True]
+        np.testing.assert_array_equal(s, [1.0, 2.0])
+    else:
+        assert builds == [True, False]
+        np.testing.assert_array_equal(s, [5.0, 7.0])
